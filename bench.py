@@ -9,7 +9,13 @@ A step = forward + loss + backward + gradient all-reduce (N>1, RCCL via torch.di
 batch of synthetic CALVIN-shaped windows already resident in HBM.  Workload (BASELINE.json configs[1]):
 HULC, vision goal only (use_clip_auxiliary_loss=false), B=64 windows/GPU, seq_len=32, 200x200 static + 84x84
 gripper frames, bf16 MFMA operands with fp32 accumulation / fp32 master weights, transformer dropout 0.1 (train mode).
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall-clock mean of
+the --steps timed steps).  A plain run sets up, warms up, times the steps and prints; `--full` adds everything else the benchmark
+measures: the per-class survey pass and live class timers (`roofline`, `mfma_groups`, `kernel_classes`), per-step device times
+(`step_ms`, `roofline_step`), the N > 1 bucket timeline and `cpu_baseline`.
+The last timed step starts again from the seeded initial state (restore_start, not timed), so that what it computes is the same in every
+run with the same arguments up to rounding; `--dump-outputs DIR` writes it (losses; a fixed seeded sample of the updated parameters,
+the gradients and the Adam moments) as DIR/<name>.npy, float32.
 """
 from __future__ import annotations
 
@@ -73,6 +79,22 @@ def synth_batch(B, S, dev, seed, lang=False, ingest="fp32", store_frames=0):
         mb["lang"] = (l / l.norm(dim=-1, keepdim=True)).contiguous()
         mb["aux_rows"] = np.arange(B, dtype=np.int32)
     return mb
+
+
+DUMP_SAMPLE = 1 << 21        # entries per flat buffer written by --dump-outputs: 4 buffers x 8 MB
+
+
+def dump_outputs(d, eng, paired):
+    """What the last step handed its caller, as float32 .npy files: `losses` (the loss slots [total_mod, kl, action, clip]; the paired pass:
+    vis then lang) and, of each flat fp32 buffer the step updated (`params` after Adam, the step's `grads`, Adam's `adam_m` / `adam_v`),
+    the same fixed seeded sample of DUMP_SAMPLE entries (every entry when the buffer is smaller)."""
+    os.makedirs(d, exist_ok=True)
+    n = eng.numel
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False, shuffle=False)) if n > DUMP_SAMPLE else np.arange(n)
+    idx = torch.from_numpy(idx).to(eng.flat_params.device)
+    np.save(os.path.join(d, "losses.npy"), (eng._loss_dev8 if paired else eng._loss_dev).float().cpu().numpy())
+    for name, t in (("params", eng.flat_params), ("grads", eng.flat_grads), ("adam_m", eng.adam_m), ("adam_v", eng.adam_v)):
+        np.save(os.path.join(d, name + ".npy"), t[idx].float().cpu().numpy())
 
 
 def cpu_baseline(S, budget_s=6.0, kind="hulc", rnn_type="rnn"):
@@ -180,17 +202,23 @@ def main():
                                                       "double buffer, overlapped with the previous step) — the PCIe-inclusive row SURVEY §8(d) asks for; never the headline `value`")
     ap.add_argument("--store", type=int, default=0, metavar="F", help="with --ingest u8: F > 0 = the frames live in a device-resident uint8 STORE of F frames per camera "
                                                                      "and every step draws B random windows from it by index (hulc_batch::window_start): no materialised batch, no per-step H2D")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the survey pass, live class timers, per-step device times, roofline, N > 1 bucket timeline and "
+                                                        "cpu_baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: the last step's losses and a seeded sample of the parameters, "
+                                                                       "gradients and Adam moments as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="hulc_set_option(NAME, VALUE) before the run: same-box A/B of a library switch, e.g. adam_fused_transposes=0")
-    ap.add_argument("--timer-stride", type=int, default=4, help="the live class timers record their HIP events on every N-th step of the timed region (1 = every step)")
+    ap.add_argument("--timer-stride", type=int, default=4, help="with --full: the live class timers record their HIP events on every N-th step of the timed region (1 = every step)")
     ap.add_argument("--live-timers", default="on", choices=["on", "fenced", "off"],
-                    help="A/B of the measurement itself (never a reported configuration): 'on' (default) = the dominant group's kernel classes are timed by HIP events "
+                    help="with --full, A/B of the measurement itself (never a reported configuration): 'on' (default) = the dominant group's kernel classes are timed by HIP events "
                          "inside the timed region (timing-only events, hipEventDisableSystemFence); 'fenced' = the same with default events (rounds <= 4); 'off' = no "
                          "events in the timed region, `roofline` comes from the survey pass")
     ap.add_argument("--force-comm", type=int, default=0, help="1-GPU REHEARSAL of the N > 1 code path (never a reported number): a 1-rank torch.distributed group and a "
                                                               "1-rank library RCCL communicator, so that the self-check, hulc_backward_allreduce in the timed loop and the bucket "
                                                               "timeline run before the first multi-GPU box meets them (tests/test_gpu_dp.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # --gpus N MEANS N: under a launcher it must equal WORLD_SIZE; without one, N > 1 re-launches this script with one rank per GPU.
     # A `python bench.py --gpus 8` that quietly ran one rank and printed n_gpus: 1 is the failure this guards against.
@@ -236,6 +264,20 @@ def main():
         k, v = kv.split("=")
         eng.set_option(k, int(v))
     eng.load_numpy(spec.init_all(dims, seed=0))      # identical weights on every rank (seeded init = the DDP broadcast)
+    start_params = eng.flat_params.clone()           # the seeded starting state, restored before the last timed step (restore_start)
+    start_scaler = eng.scaler_state() if args.dtype == "fp16" else None
+
+    def restore_start():
+        """The 16-bit engines sum gradients with atomics in a run-dependent order, and hundreds of Adam updates turn those last-bit
+        differences into different weights.  The last timed step therefore starts again from the seeded initial state (parameters, zero
+        Adam moments and step count, loss scaler), so that what it computes differs between runs of the same arguments by rounding only."""
+        eng.flat_params.copy_(start_params)
+        eng.adam_m.zero_()
+        eng.adam_v.zero_()
+        eng.adam_t = 0
+        if start_scaler is not None:
+            eng.scaler_load(start_scaler["scale"], start_scaler["growth_tracker"], start_scaler["taken_steps"])
+        eng.prepare_weights()                        # the compute-precision copies of the restored parameters
     # N > 1: the library's own RCCL communicator (hulc_backward_allreduce: reverse-forward buckets overlapped with the backward); the
     # torch.distributed group above only carries the ncclUniqueId, the barriers and the timing reduction.  HULC_DP_COMM=capi (the default)
     # makes a communicator that cannot be brought up an ERROR on every rank — a run that quietly measured torch.distributed all-reduces
@@ -397,45 +439,64 @@ def main():
     torch.cuda.synchronize()
     for i in range(args.warmup):
         step(i)
-    # survey pass (untimed): HIP events around every kernel class -> which class dominates the step
-    eng.timers_enable(True)
-    eng.timers_read(reset=True)
-    for i in range(2):
-        step(args.warmup + i)
-    survey = eng.timers_read(reset=True)
 
     def group_sum(tm, classes):
         rows = [tm[c] for c in classes if c in tm]
         return dict(ms=sum(r["ms"] for r in rows), flops=sum(r["flops"] for r in rows), bytes=sum(r["bytes"] for r in rows),
                     launches=sum(r["launches"] for r in rows), classes=[c for c in classes if c in tm], bounds=sorted({r["bound"] for r in rows})) if rows else None
-    groups = {g: group_sum(survey, cl) for g, cl in MFMA_GROUPS.items()}
-    groups = {g: v for g, v in groups.items() if v}
-    dom_group = max(groups.items(), key=lambda kv: kv[1]["ms"])[0] if groups else ""
-    # timed region: events only around the classes of the dominant GROUP (on the engine's stream), so the timers do not perturb the rest of the step
-    if args.live_timers == "fenced":
-        eng.set_option("timer_event_fence", 1)
-    # The live class timers are themselves a load on the stream: one timing-only event record costs ~1.8 us of stream time (a default, system-fenced event
-    # 3 us; profiles/r05_live_timer_cost.txt), 20 records per step around the dominant group's 10 launches.  They stay inside the timed region, on every
-    # `--timer-stride`-th timed step (default 4: 25 timed samples of each launch per 100 steps), so that the measurement moves the measured step by ~0.3 %.
-    tfilter = ",".join(groups[dom_group]["classes"]) if dom_group else ""
-    stride = max(1, args.timer_stride)
-    sampled = [i for i in range(args.steps) if i % stride == 0] if args.live_timers != "off" else []
-    eng.timers_enable(False)
+    sampled, stride, tfilter = [], 1, ""
+    if args.full:
+        # survey pass (untimed): HIP events around every kernel class -> which class dominates the step
+        eng.timers_enable(True)
+        eng.timers_read(reset=True)
+        for i in range(2):
+            step(args.warmup + i)
+        survey = eng.timers_read(reset=True)
+
+        groups = {g: group_sum(survey, cl) for g, cl in MFMA_GROUPS.items()}
+        groups = {g: v for g, v in groups.items() if v}
+        dom_group = max(groups.items(), key=lambda kv: kv[1]["ms"])[0] if groups else ""
+        # timed region: events only around the classes of the dominant GROUP (on the engine's stream), so the timers do not perturb the rest of the step
+        if args.live_timers == "fenced":
+            eng.set_option("timer_event_fence", 1)
+        # The live class timers are themselves a load on the stream: one timing-only event record costs ~1.8 us of stream time (a default, system-fenced event
+        # 3 us; profiles/r05_live_timer_cost.txt), 20 records per step around the dominant group's 10 launches.  They stay inside the timed region, on every
+        # `--timer-stride`-th timed step (default 4: 25 timed samples of each launch per 100 steps), so that the measurement moves the measured step by ~0.3 %.
+        tfilter = ",".join(groups[dom_group]["classes"]) if dom_group else ""
+        stride = max(1, args.timer_stride)
+        sampled = [i for i in range(args.steps) if i % stride == 0] if args.live_timers != "off" else []
+        eng.timers_enable(False)
     sc0 = eng.scaler_state() if args.dtype == "fp16" else None
-    # one event per step boundary on the engine's stream (= torch's current stream): per-step device times for median / p10 / p90 next to the
-    # wall-clock mean the contract's `ms_per_step` is (an event record costs no synchronisation and ~1 us of stream time)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    # --full: one event per step boundary on the engine's stream (= torch's current stream): per-step device times for median / p10 / p90 next to
+    # the wall-clock mean the contract's `ms_per_step` is (an event record costs no synchronisation and ~1 us of stream time)
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     barrier()
+    dt = 0.0
     t0 = time.perf_counter()
-    evs[0].record()
+    if evs is not None:
+        evs[0].record()
+    ev_last = evs[args.steps - 1] if evs is not None else None
     for i in range(args.steps):
-        if sampled and stride > 1 or i == 0:
+        last = i == args.steps - 1
+        if last:                                         # the restore is not timed: the clock and the last step's event restart after it
+            barrier()
+            dt += time.perf_counter() - t0
+            if args.full:
+                eng.timers_enable(False)
+            restore_start()
+            barrier()
+            t0 = time.perf_counter()
+            if evs is not None:
+                ev_last = torch.cuda.Event(enable_timing=True)
+                ev_last.record()
+        if args.full and (sampled and stride > 1 or i == 0 or last):
             eng.timers_enable(bool(sampled) and i % stride == 0, tfilter)      # a host-side flag + filter string: no stream work
         step(args.warmup + i)
-        evs[i + 1].record()
+        if evs is not None:
+            evs[i + 1].record()
     barrier()
-    dt = time.perf_counter() - t0
-    per_step = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)])
+    dt += time.perf_counter() - t0
+    per_step = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps - 1)] + [ev_last.elapsed_time(evs[args.steps])]) if evs is not None else None
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -444,13 +505,16 @@ def main():
     ms = dt / args.steps * 1e3
     wps = B * world / (dt / args.steps)
     loss = eng._loss_dev.cpu().numpy().tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, paired)
 
-    timers = eng.timers_read(reset=True) if args.live_timers != "off" else survey
-    eng.timers_enable(False)
+    if args.full:
+        timers = eng.timers_read(reset=True) if args.live_timers != "off" else survey
+        eng.timers_enable(False)
     # N > 1: one more (untimed) step with events around every bucket's collective: when each bucket was issued / finished relative to the END of
     # the backward on the engine stream (negative = hidden under the backward), per rank 0
     comm_tl = None
-    if lib_comm:
+    if lib_comm and args.full:
         eng.set_option("comm_timing", 1)
         step(args.warmup + args.steps)
         comm_tl = eng.comm_timeline()
@@ -537,12 +601,6 @@ def main():
     except Exception:
         pass
     if rank == 0:
-        rl = roofline(timers)
-        kernel_classes = {k: {"ms_per_step": round(v["ms"] / args.steps, 4), "launches_per_step": v["launches"] / args.steps,
-                              "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1), "gbs": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)}
-                          for k, v in sorted(survey.items(), key=lambda kv: -kv[1]["ms"])}
-        for v in kernel_classes.values():
-            v["ms_per_step"] = round(v["ms_per_step"] * args.steps / 2, 4); v["launches_per_step"] = v["launches_per_step"] * args.steps / 2
         out = {
             "metric": "trajectory-windows/sec (seq_len=%d, bs=%d/GPU)" % (S, B), "value": round(wps, 2), "unit": "windows/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
@@ -556,24 +614,33 @@ def main():
             "last_losses": {"total_mod": loss[0], "kl": loss[1], "action": loss[2], "clip": loss[3]},
             "model_flops_per_window": None if mcil else FLOP_PER_WINDOW_S32 * S / 32.0,      # SURVEY §8(d) counts the headline model only
             "step_tflops": None if mcil else round(wps / world * FLOP_PER_WINDOW_S32 * S / 32.0 / 1e12, 2),
-            # per-step device times (HIP events at the step boundaries): the mean above is wall clock incl. host stalls; SURVEY §8(d) asks for the median
-            "step_ms": {"median": round(float(np.median(per_step)), 4), "p10": round(float(np.percentile(per_step, 10)), 4), "p90": round(float(np.percentile(per_step, 90)), 4),
-                        "min": round(float(per_step.min()), 4), "max": round(float(per_step.max()), 4), "windows_per_s_at_median": round(B * world / (float(np.median(per_step)) * 1e-3), 1)},
-            "roofline_step": None if mcil else step_roofline(),
-            "roofline": rl,
-            # per GEMM group (survey pass: HIP events around every class, 2 steps): algorithmic TFLOP/s and the fraction of the dense MFMA peak
-            "mfma_groups": {g: {"ms_per_step": round(v["ms"] / 2, 4), "launches_per_step": v["launches"] / 2, "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1),
-                                "mfma_frac": round(v["flops"] / max(v["ms"], 1e-9) / 1e9 / (MFMA_BF16_PEAK_TFLOPS if args.dtype != "fp32" else 157.3), 4),
-                                "gbs": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1), "classes": v["classes"]} for g, v in sorted(groups.items(), key=lambda kv: -kv[1]["ms"])},
             "allreduce": None if (world == 1 and not lib_comm) else ({"path": "libhulc_hip RCCL (hulc_backward_allreduce)" + (" — 1-rank REHEARSAL (--force-comm)" if world == 1 else ""), "rccl_ranks": rccl_ranks, "rccl_ranks_source": "ncclCommCount of the live communicator (hulc_comm_size)", "bucket_dtype": args.bucket, "buckets": eng.comm_buckets(),
                                                   "bucket_bytes": [(hi - lo) * (4 if args.bucket == "fp32" else 2) for lo, hi in eng.comm_buckets()],
                                                   "selfcheck": selfcheck, "timeline": comm_tl, **eng.comm_stats()} if lib_comm else
                                                  {"path": "torch.distributed nccl (HULC_DP_COMM=%s)" % parallel.comm_mode(), "bucket_dtype": "fp32"}),
-            "kernel_classes": kernel_classes,
             # fp16: GradScaler state after the timed steps; skipped_in_timed_region counts optimizer steps the scaler skipped (inf/nan) inside it
             "loss_scaler": None if sc0 is None else dict(eng.scaler_state(), skipped_in_timed_region=eng.scaler_state()["skipped_steps"] - sc0["skipped_steps"]),
-            "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline(S, kind=dims.kind, rnn_type=dims.rnn_type),
         }
+        if args.full:
+            rl = roofline(timers)
+            kernel_classes = {k: {"ms_per_step": round(v["ms"] / args.steps, 4), "launches_per_step": v["launches"] / args.steps,
+                                  "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1), "gbs": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)}
+                              for k, v in sorted(survey.items(), key=lambda kv: -kv[1]["ms"])}
+            for v in kernel_classes.values():
+                v["ms_per_step"] = round(v["ms_per_step"] * args.steps / 2, 4); v["launches_per_step"] = v["launches_per_step"] * args.steps / 2
+            out.update({
+                # per-step device times (HIP events at the step boundaries): the mean above is wall clock incl. host stalls; SURVEY §8(d) asks for the median
+                "step_ms": {"median": round(float(np.median(per_step)), 4), "p10": round(float(np.percentile(per_step, 10)), 4), "p90": round(float(np.percentile(per_step, 90)), 4),
+                            "min": round(float(per_step.min()), 4), "max": round(float(per_step.max()), 4), "windows_per_s_at_median": round(B * world / (float(np.median(per_step)) * 1e-3), 1)},
+                "roofline_step": None if mcil else step_roofline(),
+                "roofline": rl,
+                # per GEMM group (survey pass: HIP events around every class, 2 steps): algorithmic TFLOP/s and the fraction of the dense MFMA peak
+                "mfma_groups": {g: {"ms_per_step": round(v["ms"] / 2, 4), "launches_per_step": v["launches"] / 2, "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1),
+                                    "mfma_frac": round(v["flops"] / max(v["ms"], 1e-9) / 1e9 / (MFMA_BF16_PEAK_TFLOPS if args.dtype != "fp32" else 157.3), 4),
+                                    "gbs": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1), "classes": v["classes"]} for g, v in sorted(groups.items(), key=lambda kv: -kv[1]["ms"])},
+                "kernel_classes": kernel_classes,
+                "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline(S, kind=dims.kind, rnn_type=dims.rnn_type),
+            })
         print(json.dumps(out), flush=True)
     if world > 1 or args.force_comm:
         import torch.distributed as dist

@@ -176,7 +176,7 @@ def test_bench_multi_gpu_code_path_rehearsal_on_one_gpu(extra):
     import json
     import subprocess
     env = dict(os.environ, MASTER_PORT=str(29700 + os.getpid() % 200))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-comm", "1", "--steps", "4", "--warmup", "1", "--preroll", "2", "--no-cpu-baseline", "--batch", "16"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-comm", "1", "--steps", "4", "--warmup", "1", "--preroll", "2", "--no-cpu-baseline", "--batch", "16"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = r.stdout.strip().splitlines()
@@ -211,3 +211,45 @@ def test_bench_gpus_flag_means_what_it_says():
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
         d = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith('{"metric"')][-1])
         assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain bench run (no --full) prints the headline only — `ms_per_step` over exactly --steps timed steps, none of the survey / roofline /
+    cpu_baseline objects — and `--dump-outputs DIR` leaves the last step's losses and the seeded sample of the flat buffers as float32 .npy files."""
+    import json
+    import subprocess
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preroll", "1", "--batch", "8",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = r.stdout.strip().splitlines()
+    assert lines[-1].startswith('{"metric"'), lines[-3:]
+    d = json.loads(lines[-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["unit"] == "windows/s"
+    assert not {"roofline", "mfma_groups", "kernel_classes", "step_ms", "cpu_baseline"} & set(d)
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["adam_m.npy", "adam_v.npy", "grads.npy", "losses.npy", "params.npy"], files
+    arrs = {f: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert np.allclose(arrs["losses.npy"], [d["last_losses"][k] for k in ("total_mod", "kl", "action", "clip")])
+    assert np.abs(arrs["grads.npy"]).max() > 0 and np.abs(arrs["params.npy"]).max() > 0
+
+
+def test_bench_dump_outputs_repeat_across_runs(tmp_path):
+    """Two bench runs with the same arguments write the same outputs up to the bf16 engine's rounding (its atomics sum in a run-dependent
+    order): the inputs are seeded and the last timed step starts from the seeded initial state, after hundreds of untimed and timed Adam updates."""
+    import subprocess
+    outs = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "5", "--preroll", "300", "--batch", "16",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        outs.append(out)
+    for f in ("losses.npy", "params.npy", "grads.npy", "adam_m.npy", "adam_v.npy"):
+        a, b = np.load(outs[0] / f).astype(np.float64), np.load(outs[1] / f).astype(np.float64)
+        rel = np.linalg.norm(a - b) / np.linalg.norm(b)
+        assert rel <= 1e-3, (f, rel)

@@ -1,7 +1,7 @@
 """Same-box comparison of bench.py's per-class HIP-event survey for two argument sets: python tools/classes_ab.py "--persist 0" "--persist 1"."""
 import json, subprocess, sys
 def run(args):
-    out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline"] + args.split(), capture_output=True, text=True).stdout.strip().splitlines()[-1]
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline"] + args.split(), capture_output=True, text=True).stdout.strip().splitlines()[-1]
     return json.loads(out)
 a, b = run(sys.argv[1]), run(sys.argv[2])
 print("ms/step", a["ms_per_step"], b["ms_per_step"], "median", a["step_ms"]["median"], b["step_ms"]["median"])

@@ -52,25 +52,25 @@ u8_store_row = ""
 if os.path.exists(P(f"{T}_bench_n1_u8_store.json")):
     us = J("_u8_store")
     u8_store_row = (f"| `{T}_bench_n1_u8_store.json` | uint8 frames from an HBM-resident frame store (`hulc_batch::window_start`: B new random windows per step gathered by index, nothing crosses PCIe, "
-                    f"no (B,S,H,W,C) tensor is materialised): {us['value']:.0f} windows/s, {us['ms_per_step']} ms/step | `python bench.py --ingest u8 --store 16384 --no-cpu-baseline` |\n")
+                    f"no (B,S,H,W,C) tensor is materialised): {us['value']:.0f} windows/s, {us['ms_per_step']} ms/step | `python bench.py --full --ingest u8 --store 16384 --no-cpu-baseline` |\n")
 files = f"""| file | what | command |
 |---|---|---|
-| `{T}_bench_n1.json` | the bench line (N=1): **{d['value']:.0f} windows/s, {d['ms_per_step']} ms/step**, `roofline` + `cpu_baseline` objects | `python bench.py` |
-| `{T}_bench_n1_fp16.json` | the same step on the fp16 engine + on-device GradScaler (the reference's `precision: 16`): {var['fp16']['value']:.0f} windows/s, {var['fp16']['ms_per_step']} ms/step | `python bench.py --dtype fp16 --no-cpu-baseline` |
-| `{T}_bench_n1_s64_fp16.json` | BASELINE config 5's shape AND precision: seq_len 64, 32 windows/GPU, fp16 + loss scaling: **{var['s64_fp16']['value']:.0f} windows/s, {var['s64_fp16']['ms_per_step']} ms/step** (scale {sc.get('scale')}, {sc.get('skipped_in_timed_region')} step(s) skipped in the timed region) | `python bench.py --seq 64 --batch 32 --dtype fp16 --no-cpu-baseline` |
+| `{T}_bench_n1.json` | the bench line (N=1): **{d['value']:.0f} windows/s, {d['ms_per_step']} ms/step**, `roofline` + `cpu_baseline` objects | `python bench.py --full` |
+| `{T}_bench_n1_fp16.json` | the same step on the fp16 engine + on-device GradScaler (the reference's `precision: 16`): {var['fp16']['value']:.0f} windows/s, {var['fp16']['ms_per_step']} ms/step | `python bench.py --full --dtype fp16 --no-cpu-baseline` |
+| `{T}_bench_n1_s64_fp16.json` | BASELINE config 5's shape AND precision: seq_len 64, 32 windows/GPU, fp16 + loss scaling: **{var['s64_fp16']['value']:.0f} windows/s, {var['s64_fp16']['ms_per_step']} ms/step** (scale {sc.get('scale')}, {sc.get('skipped_in_timed_region')} step(s) skipped in the timed region) | `python bench.py --full --seq 64 --batch 32 --dtype fp16 --no-cpu-baseline` |
 | `{T}_bench_n1_s64_fp16_vislang.json` | config 5 with 16 vis + 16 lang windows + CLIP loss (paired pass): {var['s64_fp16_vislang']['value']:.0f} windows/s, {var['s64_fp16_vislang']['ms_per_step']} ms/step | `… --seq 64 --batch 32 --dtype fp16 --lang 1` |
-| `{T}_bench_n1_s64.json` | seq_len 64, 32 windows/GPU in bf16: {var['s64']['value']:.0f} windows/s, {var['s64']['ms_per_step']} ms/step | `python bench.py --seq 64 --batch 32 --no-cpu-baseline` |
-| `{T}_bench_n1_u8.json` | uint8 (B,S,H,W,C) ingest, transforms fused into conv1 (SURVEY §8(f) row 1): {var['u8']['value']:.0f} windows/s, {var['u8']['ms_per_step']} ms/step (boxes differ by ±2 %: the same-box ratio to the fp32 boundary is in `r06_ab_fp32_vs_u8_final.txt`) | `python bench.py --ingest u8 --no-cpu-baseline` |
-{u8_store_row}| `{T}_bench_n1_vislang.json` | 32 vis + 32 lang + CLIP (BASELINE config 3 per GPU), one paired pass: {var['vislang']['value']:.0f} windows/s, {var['vislang']['ms_per_step']} ms/step | `python bench.py --lang 1 --no-cpu-baseline` |
-| `{T}_bench_n1_vislang_seq.json` | the same, one pass per modality (the reference's order): {var['vislang_seq']['value']:.0f} windows/s, {var['vislang_seq']['ms_per_step']} ms/step | `python bench.py --lang 1 --pair 0 --no-cpu-baseline` |
-| `{T}_bench_n1_mcil.json` | `model=mcil` (BiRNN plan recognition): {var['mcil']['value']:.0f} windows/s, {var['mcil']['ms_per_step']} ms/step | `python bench.py --model mcil --no-cpu-baseline` |
-| `{T}_bench_n1_mcil_gru.json` | `rnn_type=nn.GRU` (BASELINE config 4's GRU plan encoder): {var['mcil_gru']['value']:.0f} windows/s, {var['mcil_gru']['ms_per_step']} ms/step (round 1: 12.44 ms) | `python bench.py --model mcil_gru --no-cpu-baseline` |
-| `{T}_kernel_stats.csv`, `{T}_kernel_stats_summary.txt` | rocprofv3 per-kernel stats of the bench command (9 steps: 2 warm-up + 2 survey + 5 timed), top 45 per step | `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 5 --warmup 2 --preroll 0 --no-cpu-baseline`, `tools/prof_summary.py` |
+| `{T}_bench_n1_s64.json` | seq_len 64, 32 windows/GPU in bf16: {var['s64']['value']:.0f} windows/s, {var['s64']['ms_per_step']} ms/step | `python bench.py --full --seq 64 --batch 32 --no-cpu-baseline` |
+| `{T}_bench_n1_u8.json` | uint8 (B,S,H,W,C) ingest, transforms fused into conv1 (SURVEY §8(f) row 1): {var['u8']['value']:.0f} windows/s, {var['u8']['ms_per_step']} ms/step (boxes differ by ±2 %: the same-box ratio to the fp32 boundary is in `r06_ab_fp32_vs_u8_final.txt`) | `python bench.py --full --ingest u8 --no-cpu-baseline` |
+{u8_store_row}| `{T}_bench_n1_vislang.json` | 32 vis + 32 lang + CLIP (BASELINE config 3 per GPU), one paired pass: {var['vislang']['value']:.0f} windows/s, {var['vislang']['ms_per_step']} ms/step | `python bench.py --full --lang 1 --no-cpu-baseline` |
+| `{T}_bench_n1_vislang_seq.json` | the same, one pass per modality (the reference's order): {var['vislang_seq']['value']:.0f} windows/s, {var['vislang_seq']['ms_per_step']} ms/step | `python bench.py --full --lang 1 --pair 0 --no-cpu-baseline` |
+| `{T}_bench_n1_mcil.json` | `model=mcil` (BiRNN plan recognition): {var['mcil']['value']:.0f} windows/s, {var['mcil']['ms_per_step']} ms/step | `python bench.py --full --model mcil --no-cpu-baseline` |
+| `{T}_bench_n1_mcil_gru.json` | `rnn_type=nn.GRU` (BASELINE config 4's GRU plan encoder): {var['mcil_gru']['value']:.0f} windows/s, {var['mcil_gru']['ms_per_step']} ms/step (round 1: 12.44 ms) | `python bench.py --full --model mcil_gru --no-cpu-baseline` |
+| `{T}_kernel_stats.csv`, `{T}_kernel_stats_summary.txt` | rocprofv3 per-kernel stats of the bench command (9 steps: 2 warm-up + 2 survey + 5 timed), top 45 per step | `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 5 --warmup 2 --preroll 0 --no-cpu-baseline`, `tools/prof_summary.py` |
 | `{T}_pmc_hbm_per_kernel.csv`, `{T}_pmc_traffic.json` | FETCH_SIZE / WRITE_SIZE per dispatch (two separate `--pmc` passes) and the per-launch HBM bytes per kernel class, `(2 x FETCH_SIZE + WRITE_SIZE) x 1024` (MI355X_MICROARCH.md §HBM: gfx950 FETCH_SIZE reports half of a wide coalesced read; calibration: `adam` reads 5 and writes 3.5 arrays of 47.05 M fp32 = 1.41 GB algorithmic (+ 0.07 GB of transposed 16-bit copies since round 5) against {t.get('adam', 0) / 1e9:.2f} GB measured); every dispatch is counted in the FIRST class it matches, so the recurrent-step dispatches (keyed by their grid) are not in `skinny_gemm`; `bench.py` reports the dominant class's value as `roofline.traffic` | `tools/pmc_traffic.py` |
 | `{T}_mfma_util.csv`, `{T}_mfma_util_summary.txt` | per kernel: MFMA-pipe utilisation, `SQ_VALU_MFMA_BUSY_CYCLES / SQ_BUSY_CYCLES`, MFMA TFLOP/s from `SQ_INSTS_VALU_MFMA_MOPS_BF16`, LDS bank-conflict rate (`SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE`), wait breakdown — two SQ passes of 8 counters | `tools/pmc_sq.sh`, `tools/pmc_sq_summary.py` |
 | `{T}_step_sequence.txt` | every launch of ONE step in order (consecutive identical launches collapsed) from the same kernel trace: launches per step, which memsets / transposes / small kernels remain and how long each takes.  The per-step call counts of `{T}_kernel_stats_summary.txt` divide a 9-step profile that also holds the engine's one-time workspace zero-fills (≈160 `fillBufferAligned`) and bench.py's input generation; a step itself issues 3 memsets (gradient buffer, loss slots, the backward's zero arena) | `tools/step_seq.py` |
-| `{T}_bench_n1_fp32.json` | the fp32 PARITY engine (exact-fp32 MFMA, `v_mfma_f32_16x16x4_f32`: 1/16 of the bf16 matrix rate): {var['fp32']['value']:.0f} windows/s, {var['fp32']['ms_per_step']} ms/step | `python bench.py --dtype fp32 --steps 20 --no-cpu-baseline` |
-| `{T}_bench_n1_u8_h2d.json` | uint8 ingest with every step's frames copied from PINNED HOST memory (async H2D on a copy stream, double-buffered; 289 MB per step): {var['u8_h2d']['value']:.0f} windows/s, median step {(var['u8_h2d'].get('step_ms') or {{}}).get('median')} ms — PCIe-bound, SURVEY §8(d)'s H2D-inclusive row (never the headline) | `python bench.py --ingest u8 --h2d 1 --no-cpu-baseline` |
+| `{T}_bench_n1_fp32.json` | the fp32 PARITY engine (exact-fp32 MFMA, `v_mfma_f32_16x16x4_f32`: 1/16 of the bf16 matrix rate): {var['fp32']['value']:.0f} windows/s, {var['fp32']['ms_per_step']} ms/step | `python bench.py --full --dtype fp32 --steps 20 --no-cpu-baseline` |
+| `{T}_bench_n1_u8_h2d.json` | uint8 ingest with every step's frames copied from PINNED HOST memory (async H2D on a copy stream, double-buffered; 289 MB per step): {var['u8_h2d']['value']:.0f} windows/s, median step {(var['u8_h2d'].get('step_ms') or {{}}).get('median')} ms — PCIe-bound, SURVEY §8(d)'s H2D-inclusive row (never the headline) | `python bench.py --full --ingest u8 --h2d 1 --no-cpu-baseline` |
 | `{T}_conv_reg_vs_tile.txt`, `{T}_conv_reg_ablation.txt` | conv2 / conv3 forward and data gradient on 2048 frames: LDS-resident-weights kernels (conv_tile.h) against the weights-in-registers kernels (conv_reg.h); and conv_reg with phases switched off (no DMA / no multiply loop / no epilogue) | `tools/time_conv_reg.py`, `ABLATE=1 tools/time_conv_reg.py` |
 | `{T}_rnn_persist_stamps.txt` | the persistent recurrence alone (`csrc/rnn_persist.h`): every step checked against a CPU recurrence, us per step at B = 64 / 128 (S = 32) and B = 32 (S = 64), shader-clock stamps of the phases of a step (poll, payload, MFMA + LDS, barrier, epilogue, drain) | `tools/bin/rnn_persist_bench_st` (tools/rnn_persist_bench.hip, -DRP_STAMPS) |
 | `{T}_step_timeline.txt` | every launch of one step with start offset, duration, gap and queue | `tools/step_timeline.py` |

@@ -15,7 +15,7 @@ mkdir -p $O
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -- python $R/bench.py --steps 2 --warmup 1 --preroll 0 --no-cpu-baseline > $O/pmc_$c.log 2>&1 </dev/null
 done
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 5 --warmup 2 --preroll 0 --no-cpu-baseline > $O/stats.log 2>&1 </dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --full --steps 5 --warmup 2 --preroll 0 --no-cpu-baseline > $O/stats.log 2>&1 </dev/null
 cd $R
 python tools/pmc_traffic.py $O > $O/pmc_traffic.log
 mkdir -p $R/profiles && cp $O/pmc_traffic.json $R/profiles/${T}_pmc_traffic.json      # bench.py reads the newest profiles/r*_pmc_traffic.json
@@ -25,8 +25,8 @@ python tools/step_seq.py $O/stats > $O/step_sequence.txt 2>&1
 ( HULC_CT_FPB=1 python tools/time_conv_tile_gripper.py 2>/dev/null | tail -1; python tools/time_conv_tile_gripper.py 2>/dev/null | tail -1 ) > $O/conv_tile_gripper.txt
 bash tools/pmc_sq.sh $T/sq > $O/sq.log 2>&1
 cd $R
-timeout 900 python $R/bench.py > $O/bench_n1.json 2> $O/bench_n1.err </dev/null
-b() { name=$1; shift; timeout 400 python $R/bench.py --no-cpu-baseline "$@" > $O/bench_n1_$name.json 2>/dev/null </dev/null; }
+timeout 900 python $R/bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err </dev/null
+b() { name=$1; shift; timeout 400 python $R/bench.py --full --no-cpu-baseline "$@" > $O/bench_n1_$name.json 2>/dev/null </dev/null; }
 b fp16 --dtype fp16
 b s64 --seq 64 --batch 32
 b s64_fp16 --seq 64 --batch 32 --dtype fp16
