@@ -218,6 +218,14 @@ int hulc_scaler_set(hulc_ctx* ctx, float scale, int32_t growth_tracker, int64_t 
     if (!ctx) { hulc_set_error("hulc_scaler_set: null context"); return 1; }
     return ctx->e->scaler_set(scale, growth_tracker, taken_steps);
 }
+int hulc_grad_clip_set(hulc_ctx* ctx, int32_t algo, float limit, int32_t track) {
+    if (!ctx) { hulc_set_error("hulc_grad_clip_set: null context"); return 1; }
+    return ctx->e->grad_clip_set(algo, limit, track);
+}
+int hulc_grad_norm_get(hulc_ctx* ctx, float* total, float* coef, float* per_tensor_host, int64_t cap) {
+    if (!ctx) { hulc_set_error("hulc_grad_norm_get: null context"); return 1; }
+    return ctx->e->grad_norm_get(total, coef, per_tensor_host, cap);
+}
 int hulc_set_kl_beta(hulc_ctx* ctx, float b) { ctx->e->set_kl_beta(b); return 0; }
 int hulc_set_dropout(hulc_ctx* ctx, float p) {
     if (p < 0.f || p >= 1.f) { hulc_set_error("hulc_set_dropout: p must be in [0,1)"); return 1; }

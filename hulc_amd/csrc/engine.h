@@ -195,7 +195,7 @@ struct Engine : IEngine {
         KIN = dec_plan + DE + GOAL;
         maxB = cfg.max_batch; maxS = cfg.max_seq; maxN = maxB * maxS;
     }
-    ~Engine() override { for (void* p : allocs) hipFree(p); if (rp_err_host) hipHostFree((void*)rp_err_host); if (blk2desc_dev) hipFree(blk2desc_dev); if (trdesc_dev) hipFree(trdesc_dev); tr_table_free(tr_adam); tr_table_free(tr_rest); if (adam_chunk_start) hipFree(adam_chunk_start); if (adam_chunk_n) hipFree(adam_chunk_n); }
+    ~Engine() override { for (void* p : allocs) hipFree(p); if (rp_err_host) hipHostFree((void*)rp_err_host); if (blk2desc_dev) hipFree(blk2desc_dev); if (trdesc_dev) hipFree(trdesc_dev); tr_table_free(tr_adam); tr_table_free(tr_rest); if (adam_chunk_start) hipFree(adam_chunk_start); if (adam_chunk_n) hipFree(adam_chunk_n); gn_free(); if (clip_state) hipFree(clip_state); }
     int64_t workspace_bytes() const override { return ws_bytes; }
     void set_kl_beta(float b) override { cfg.kl_beta = b; }
     void set_dropout(float p) override { cfg.dropout_p = p; }
@@ -366,8 +366,10 @@ struct Engine : IEngine {
              const int64_t* numels) override {
         P = p; G = g; AM = m; AV = v; numel = n_;
         tab.clear(); trdesc.clear(); tr_blocks = 0; fragbatch = FragPackBatch{}; frag_blocks = 0; frag_linked = 0;
-        if (!std::is_same<T, float>::value && !wshadow) wshadow = alloc<T>(numel);
+        if (!std::is_same<T, float>::value && !wshadow) wshadow = alloc<T>(numel, "wshadow");      // named: hulc_get_tensor reads the 16-bit shadow back (tests)
         for (int i = 0; i < n; ++i) tab[names[i]] = Ref{offs[i], numels[i]};
+        gn_tens.clear(); gn_built = false; gn_have = false;      // the gradient-norm tables follow the tensor table (rebuilt at the end of this bind if clipping by norm / tracking is configured)
+        for (int i = 0; i < n; ++i) gn_tens.push_back(Ref{offs[i], numels[i]});
         tab_order.assign(tab.begin(), tab.end());
         std::sort(tab_order.begin(), tab_order.end(), [](const std::pair<std::string, Ref>& a, const std::pair<std::string, Ref>& b) { return a.second.off < b.second.off; });
         // data parallelism: the "this step's gradients are garbage" vote rides in an alignment-padding element of the LAST bucket (see skip_vote_put)
@@ -473,6 +475,7 @@ struct Engine : IEngine {
         else hipMemcpy(trdesc_dev, trdesc.data(), sizeof(TrDesc) * trdesc.size(), hipMemcpyHostToDevice);
         adam_tables_build();
         if (alloc_failed) { hulc_set_error("hipMalloc failed while allocating weight copies"); return 1; }
+        if ((clip_algo == HULC_CLIP_NORM || clip_track) && gn_build()) return 1;      // the norm pass's chunk table belongs to this tensor table
         bound = true;
         return prepare_weights();
     }
@@ -887,8 +890,73 @@ struct Engine : IEngine {
         return 0;
     }
 
+    // ---------------------------------------------------------------- gradient clipping / gradient norms (kernels.h: ClipState, grad_sumsq_kernel)
+    std::vector<Ref> gn_tens;               // the bound tensors in bind order
+    bool gn_built = false, gn_have = false; // tables match gn_tens / the last optimizer step computed norms
+    int gn_chunks = 0;
+    long long* gn_chunk_start = nullptr; int* gn_chunk_n = nullptr; int* gn_tfirst = nullptr; float* gn_partial = nullptr; double* gn_tsq = nullptr; float* gn_tnorm = nullptr;
+    ClipState* clip_state = nullptr;        // device
+    int clip_algo = HULC_CLIP_OFF; float clip_limit = 0.f; bool clip_track = false;
+    void gn_free() {
+        for (void* p : {(void*)gn_chunk_start, (void*)gn_chunk_n, (void*)gn_tfirst, (void*)gn_partial, (void*)gn_tsq, (void*)gn_tnorm}) if (p) hipFree(p);
+        gn_chunk_start = nullptr; gn_chunk_n = nullptr; gn_tfirst = nullptr; gn_partial = nullptr; gn_tsq = nullptr; gn_tnorm = nullptr; gn_chunks = 0; gn_built = false;
+    }
+    // chunk table of the norm pass: every bound tensor cut into GN_CHUNK pieces; only listed elements, never the padding between tensors.  Built off the
+    // step path: by hulc_bind_params when clipping by norm / tracking is already configured, else by the hulc_grad_clip_set that configures it
+    int gn_build() {
+        gn_free();
+        std::vector<long long> cs; std::vector<int> cn, tf;
+        for (const Ref& r : gn_tens) {
+            if (r.off < 0 || r.n < 0 || (r.off & 3) || r.off + r.n > numel) { hulc_set_error("gradient norm: tensor at offset %lld (%lld elements) is misaligned or outside the bound buffer", (long long)r.off, (long long)r.n); return 1; }
+            tf.push_back((int)cs.size());
+            for (int64_t x = 0; x < r.n; x += GN_CHUNK) { cs.push_back(r.off + x); cn.push_back((int)std::min<int64_t>(GN_CHUNK, r.n - x)); }
+        }
+        tf.push_back((int)cs.size());
+        if (cs.empty()) { hulc_set_error("gradient norm: no bound tensors"); return 1; }
+        const size_t nc = cs.size(), nt = gn_tens.size();
+        if (hipMalloc((void**)&gn_chunk_start, sizeof(long long) * nc) != hipSuccess || hipMalloc((void**)&gn_chunk_n, sizeof(int) * nc) != hipSuccess ||
+            hipMalloc((void**)&gn_tfirst, sizeof(int) * (nt + 1)) != hipSuccess || hipMalloc((void**)&gn_partial, sizeof(float) * nc) != hipSuccess ||
+            hipMalloc((void**)&gn_tsq, sizeof(double) * nt) != hipSuccess || hipMalloc((void**)&gn_tnorm, sizeof(float) * nt) != hipSuccess) {
+            gn_free(); hulc_set_error("gradient norm: allocation failed"); return 1;
+        }
+        HIP_CHECK(hipMemcpy(gn_chunk_start, cs.data(), sizeof(long long) * nc, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(gn_chunk_n, cn.data(), sizeof(int) * nc, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(gn_tfirst, tf.data(), sizeof(int) * (nt + 1), hipMemcpyHostToDevice));
+        gn_chunks = (int)nc; gn_built = true;
+        return 0;
+    }
+    int clip_state_write(float total, float coef) {
+        if (!clip_state && hipMalloc((void**)&clip_state, sizeof(ClipState)) != hipSuccess) { clip_state = nullptr; hulc_set_error("hulc_grad_clip_set: allocation failed"); return 1; }
+        const ClipState h{total, coef, clip_algo, clip_limit};
+        HIP_CHECK(hipMemcpyAsync(clip_state, &h, sizeof(h), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));          // `h` lives on this frame
+        return 0;
+    }
+    int grad_clip_set(int32_t algo, float limit, int32_t track) override {
+        if (algo != HULC_CLIP_OFF && algo != HULC_CLIP_NORM && algo != HULC_CLIP_VALUE) { hulc_set_error("hulc_grad_clip_set: unknown algorithm %d", (int)algo); return 1; }
+        if (!(limit > 0.f)) algo = HULC_CLIP_OFF;      // Lightning: gradient_clip_val None / 0 = no clipping
+        if ((algo == HULC_CLIP_NORM || track != 0) && bound && !gn_built && gn_build()) return 1;      // before a bind: hulc_bind_params builds the table
+        clip_algo = algo; clip_limit = algo == HULC_CLIP_OFF ? 0.f : limit; clip_track = track != 0;
+        gn_have = false;
+        if (clip_algo == HULC_CLIP_OFF && !clip_track) return 0;
+        return clip_state_write(0.f, 1.f);
+    }
+    int grad_norm_get(float* total, float* coef, float* per_tensor, int64_t cap) override {
+        if (!gn_have) { hulc_set_error("hulc_grad_norm_get: no optimizer step has computed gradient norms (hulc_grad_clip_set with HULC_CLIP_NORM or track != 0 first)"); return 1; }
+        if (per_tensor && cap < (int64_t)gn_tens.size()) { hulc_set_error("hulc_grad_norm_get: per-tensor buffer holds %lld values, %lld tensors are bound", (long long)cap, (long long)gn_tens.size()); return 1; }
+        ClipState h;
+        HIP_CHECK(hipMemcpyAsync(&h, clip_state, sizeof(h), hipMemcpyDeviceToHost, st));
+        if (per_tensor) HIP_CHECK(hipMemcpyAsync(per_tensor, gn_tnorm, sizeof(float) * gn_tens.size(), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (total) *total = h.total_norm;
+        if (coef) *coef = h.coef;
+        return 0;
+    }
+
     int optim(const hulc_optim& o) override {
         if (!bound) { hulc_set_error("hulc_optimizer_step before hulc_bind_params"); return 1; }
+        const bool want_norm = clip_algo == HULC_CLIP_NORM || clip_track;
+        if (want_norm && !gn_built) { hulc_set_error("hulc_optimizer_step: the gradient-norm tables are missing (hulc_bind_params / hulc_grad_clip_set build them)"); return 1; }      // before the step tag advances
         persist_check("hulc_optimizer_step", false);
         lazy_sweep(0, numel, st);            // an optimizer step without a backward behind hulc_zero_grads: the lazily zeroed tensors become zeros now
         bwd_since_opt = false;
@@ -899,18 +967,25 @@ struct Engine : IEngine {
         const int64_t step = o.step;
         const double bc1d = 1.0 - pow((double)b1, (double)step), bc2d = 1.0 - pow((double)b2, (double)step);
         h16_t* const shadow = std::is_same<T, float>::value ? (h16_t*)nullptr : (h16_t*)wshadow;
-        if (scaler) hipLaunchKernelGGL(nonfinite_check_kernel, dim3(2048), dim3(256), 0, st, G, (long long)numel, scaler);      // after the (host-side) all-reduce: every rank sees the same flag
+        // after the all-reduce, whoever performed it: every rank sees the same flag and derives the same clipping coefficient from the same reduced buffer
+        const ClipState* const cs = clip_algo != HULC_CLIP_OFF ? clip_state : nullptr;
+        if (want_norm) {        // one read of G: the norm pass raises found_inf itself (fp16), the separate check is skipped
+            hipLaunchKernelGGL(grad_sumsq_kernel, dim3(gn_chunks), dim3(256), 0, st, (const float*)G, (const long long*)gn_chunk_start, (const int*)gn_chunk_n, gn_partial, scaler);
+            hipLaunchKernelGGL(grad_norm_combine_kernel, dim3(1), dim3(1024), 0, st, (const float*)gn_partial, (const int*)gn_tfirst, (int)gn_tens.size(), gscale, (const ScalerState*)scaler,
+                               clip_state, gn_tsq, gn_tnorm);
+            gn_have = true;
+        } else if (scaler) hipLaunchKernelGGL(nonfinite_check_kernel, dim3(2048), dim3(256), 0, st, G, (long long)numel, scaler);
         if (o.kind == HULC_OPT_SGD)
             hipLaunchKernelGGL(sgd_kernel, dim3(2048), dim3(256), 0, st, P, G, AM, (long long)numel, lr, o.momentum, o.dampening, o.weight_decay, (int)(o.nesterov != 0),
-                               (int)(step == 1), gscale, shadow, (const ScalerState*)scaler, (const unsigned*)rp_skip, tag);
+                               (int)(step == 1), gscale, shadow, (const ScalerState*)scaler, (const unsigned*)rp_skip, tag, cs);
         else if (adam_fuse_tr && tr_adam.n && shadow) {
-            AdamArgs a{P, G, AM, AV, lr, b1, b2, eps, (float)bc1d, (float)sqrt(bc2d), gscale, o.weight_decay, (int)(o.kind == HULC_OPT_ADAMW), shadow, (const ScalerState*)scaler, (const unsigned*)rp_skip, tag};
+            AdamArgs a{P, G, AM, AV, lr, b1, b2, eps, (float)bc1d, (float)sqrt(bc2d), gscale, o.weight_decay, (int)(o.kind == HULC_OPT_ADAMW), shadow, (const ScalerState*)scaler, (const unsigned*)rp_skip, tag, cs};
             hipLaunchKernelGGL(adam_tiled_kernel, dim3(tr_adam.blocks + adam_chunks), dim3(256), 0, st, a, (const TrDesc*)tr_adam.desc, (const unsigned short*)tr_adam.b2d, tr_adam.blocks,
                                (const long long*)adam_chunk_start, (const int*)adam_chunk_n);
             tr_fresh = true;
         } else
             hipLaunchKernelGGL(adam_kernel, dim3(2048), dim3(256), 0, st, P, G, AM, AV, (long long)numel, lr, b1, b2, eps, (float)bc1d, (float)sqrt(bc2d), gscale,
-                               shadow, (const ScalerState*)scaler, o.weight_decay, (int)(o.kind == HULC_OPT_ADAMW), (const unsigned*)rp_skip, tag);
+                               shadow, (const ScalerState*)scaler, o.weight_decay, (int)(o.kind == HULC_OPT_ADAMW), (const unsigned*)rp_skip, tag, cs);
         if (scaler) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(1), 0, st, scaler, (const unsigned*)rp_skip, tag);
         if (hipGetLastError() != hipSuccess) { hulc_set_error("adam launch failed"); return 1; }
         return prepare_weights(true);

@@ -40,6 +40,9 @@ struct IEngine {
     virtual int scaler_enable(float init_scale, float growth, float backoff, int interval) = 0;
     virtual int scaler_get(float* scale, int32_t* tracker, int64_t* skipped, int32_t* last_inf, int64_t* taken) = 0;
     virtual int scaler_set(float scale, int32_t tracker, int64_t taken) = 0;
+    // ---- gradient clipping / gradient norms inside the optimizer step (engine.h: optim)
+    virtual int grad_clip_set(int32_t algo, float limit, int32_t track) = 0;
+    virtual int grad_norm_get(float* total, float* coef, float* per_tensor, int64_t cap) = 0;
     // ---- data-parallel gradient all-reduce (comm.h): whole buffer after a finished backward, or bucketed inside the backward
     virtual int allreduce_grads(int bucket_dtype) = 0;
     virtual int backward_allreduce(int bucket_dtype) = 0;

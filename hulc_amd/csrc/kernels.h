@@ -2393,8 +2393,109 @@ __global__ void scaler_update_kernel(ScalerState* __restrict__ ss, const unsigne
     ss->found_inf = 0;
 }
 
+// =========================================================================================================
+// Gradient clipping / gradient-norm logging (Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm, track_grad_norm), which the
+// reference reaches through Trainer(**cfg.trainer), hulc/training.py:57-71) folded into the optimizer pass: the L2 norm of the EFFECTIVE
+// gradient (G x grad_scale / loss scale, what the optimizer consumes) is reduced on the device, torch.nn.utils.clip_grad_norm_'s coefficient
+// lands in ClipState and the optimizer kernels multiply it into the scalar they already apply to every gradient; clip_grad_value_ is a clamp
+// of that product.  The bound gradient buffer is never rewritten.
+// =========================================================================================================
+struct ClipState {
+    float total_norm;       // of the last optimizer step's effective gradient, before clipping
+    float coef;             // min(1, limit / (total_norm + 1e-6)) for HULC_CLIP_NORM, else 1
+    int algo;               // HULC_CLIP_* (written by the host when clipping is configured)
+    float limit;
+};
+// Sum of squares over the LISTED elements of the gradient buffer (alignment padding is not gradient: it may hold the data-parallel skip vote or
+// anything the caller left there).  One block per chunk of a tensor (table built at bind time: tensors cut into GN_CHUNK pieces, starts 16-byte
+// aligned, the last piece of a tensor may end anywhere): each thread adds its <= 17 squares in order (16 + one element of a tensor's
+// 1 .. 3-element tail), 6 shuffle levels + 2 LDS levels combine the 256 threads, the chunk's sum is STORED — no float atomics, the same bits on every run.
+// Relative error of a chunk sum <= 25 u (17 sequential adds + 8 tree levels, non-negative terms).
+// ss != null (fp16 engines): the pass also raises found_inf (exponent all ones) on the words it has loaded — it replaces nonfinite_check_kernel.
+// Plain loads, not the optimizer's non-temporal ones: the optimizer reads G again right behind this pass and finds part of it in the memory-side cache
+// (A/B of the two load kinds in one process at B = 64, S = 32: plain loads make the step 8 .. 9 us shorter than non-temporal ones, bf16 and fp16 alike;
+// profiles/grad_clip_cost.txt — only that difference carries over to the cost table there, which comes from another run).
+constexpr int GN_CHUNK = 4096;
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, const long long* __restrict__ chunk_start, const int* __restrict__ chunk_n,
+                                                         float* __restrict__ partial, ScalerState* __restrict__ ss) {
+#pragma clang fp contract(off)
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const long long start = chunk_start[blockIdx.x];
+    const int n = chunk_n[blockIdx.x], n4 = n & ~3;
+    float4 q[GN_CHUNK / 1024];
+#pragma unroll
+    for (int u = 0; u < GN_CHUNK / 1024; ++u) {
+        const int i = u * 1024 + tid * 4;
+        q[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < n4) q[u] = *reinterpret_cast<const float4*>(g + start + i);
+    }
+    float s = 0.f;
+    unsigned bad = 0;
+#pragma unroll
+    for (int u = 0; u < GN_CHUNK / 1024; ++u) {
+        s += q[u].x * q[u].x; s += q[u].y * q[u].y; s += q[u].z * q[u].z; s += q[u].w * q[u].w;
+        bad |= ((__float_as_uint(q[u].x) & 0x7f800000u) == 0x7f800000u) | ((__float_as_uint(q[u].y) & 0x7f800000u) == 0x7f800000u) |
+               ((__float_as_uint(q[u].z) & 0x7f800000u) == 0x7f800000u) | ((__float_as_uint(q[u].w) & 0x7f800000u) == 0x7f800000u);
+    }
+    if (tid < n - n4) {          // the tensor's last 1 .. 3 elements (numel % 4 != 0)
+        const float x = g[start + n4 + tid];
+        s += x * x;
+        bad |= (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;
+    }
+    s = wave_sum(s);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    if (ss && __any(bad != 0) && (tid & 63) == 0) atomicOr(&ss->found_inf, 1);
+    __syncthreads();
+    if (tid == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+DEVI double wave_sum_f64(double x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+// One block: wave w combines the chunk sums of tensors w, w + 16, ... (chunks [tfirst[t], tfirst[t + 1]) of tensor t) in fp64 and a fixed order, then wave 0
+// adds the per-tensor sums the same way.  tnorm[t] = L2 norm of tensor t's effective gradient; cs->total_norm / coef as torch.nn.utils.clip_grad_norm_
+// computes them (coef = max_norm / (total_norm + 1e-6), clamped to 1; a NaN norm gives a NaN coefficient, as in torch).
+__global__ void __launch_bounds__(1024) grad_norm_combine_kernel(const float* __restrict__ partial, const int* __restrict__ tfirst, int nt, float gscale,
+                                                                 const ScalerState* __restrict__ ss, ClipState* __restrict__ cs, double* __restrict__ tsq,
+                                                                 float* __restrict__ tnorm) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (ss) gscale /= ss->scale;          // the optimizer kernels' own quotient
+    for (int t = w; t < nt; t += 16) {
+        const int a = tfirst[t], b = tfirst[t + 1];
+        double s = 0.0;
+        for (int k = a + lane; k < b; k += 64) s += (double)partial[k];
+        s = wave_sum_f64(s);
+        if (lane == 0) { tsq[t] = s; tnorm[t] = (float)(sqrt(s) * (double)gscale); }
+    }
+    __syncthreads();
+    if (w == 0) {
+        double s = 0.0;
+        for (int t = lane; t < nt; t += 64) s += tsq[t];
+        s = wave_sum_f64(s);
+        if (lane == 0) {
+            const float tn = (float)(sqrt(s) * (double)gscale);
+            float c = 1.f;
+            if (cs->algo == HULC_CLIP_NORM) { c = cs->limit / (tn + 1e-6f); c = c > 1.f ? 1.f : c; }
+            cs->total_norm = tn;
+            cs->coef = c;
+        }
+    }
+}
+
 // wd != 0: torch.optim.Adam's L2 term (g += wd p; decoupled = 0) or torch.optim.AdamW's decoupled decay (p *= 1 - lr wd before the update)
-struct AdamArgs { float* p; const float* g; float* m; float* v; float lr, b1, b2, eps, bc1, bc2_sqrt, gscale, wd; int decoupled; h16_t* shadow; const ScalerState* ss; const unsigned* skip; unsigned tag; };
+// cs (null = no clipping): HULC_CLIP_NORM multiplies cs->coef into the gradient scale, HULC_CLIP_VALUE clamps the scaled gradient to +-cs->limit (kernel-local `vclip`)
+struct AdamArgs { float* p; const float* g; float* m; float* v; float lr, b1, b2, eps, bc1, bc2_sqrt, gscale, wd; int decoupled; h16_t* shadow; const ScalerState* ss; const unsigned* skip; unsigned tag; const ClipState* cs; };
+// what a block reads of ClipState next to ss->scale: the factor for the gradient scale and the clamp bound (0 = no clamp; NaN gradients stay NaN, as under torch.clamp)
+DEVI void clip_read(const ClipState* __restrict__ cs, float& gscale, float& vclip) {
+    vclip = 0.f;
+    if (cs) {
+        const int algo = cs->algo;
+        if (algo == HULC_CLIP_NORM) gscale *= cs->coef;
+        else if (algo == HULC_CLIP_VALUE) vclip = cs->limit;
+    }
+}
 // one element quad of the Adam / AdamW step.  Floating-point contraction is OFF in here: the flat and the tiled kernel must produce the same bits, and whether
 // the compiler fuses a multiply into a following add is otherwise its choice per call site (measured: 342 k of 46 M parameters differed by one ulp after 3 steps)
 struct AdamQuad { float4 pp, gg, mm, vv; };
@@ -2405,7 +2506,7 @@ DEVI void adam_load4(const AdamArgs& a, long long i, AdamQuad& q) {
     { const f32x4nt t = __builtin_nontemporal_load(reinterpret_cast<const f32x4nt*>(a.m + i)); q.mm = make_float4(t[0], t[1], t[2], t[3]); }
     { const f32x4nt t = __builtin_nontemporal_load(reinterpret_cast<const f32x4nt*>(a.v + i)); q.vv = make_float4(t[0], t[1], t[2], t[3]); }
 }
-DEVI void adam_finish4(const AdamArgs& a, float bc1, float bc2_sqrt, float gscale, long long i, AdamQuad& q, unsigned& lo, unsigned& hi) {
+DEVI void adam_finish4(const AdamArgs& a, float bc1, float bc2_sqrt, float gscale, long long i, AdamQuad& q, unsigned& lo, unsigned& hi, float vclip = 0.f) {
 #pragma clang fp contract(off)
     typedef float f32x4nt __attribute__((ext_vector_type(4)));
     float4 &pp = q.pp, &gg = q.gg, &mm = q.mm, &vv = q.vv;
@@ -2413,6 +2514,7 @@ DEVI void adam_finish4(const AdamArgs& a, float bc1, float bc2_sqrt, float gscal
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         float gr = G[e] * gscale;
+        if (vclip > 0.f) gr = gr > vclip ? vclip : (gr < -vclip ? -vclip : gr);      // clip_grad_value_: before the L2 term, as torch clips .grad and the optimizer adds wd p
         if (a.wd != 0.f) {
             if (a.decoupled) P[e] *= 1.f - a.lr * a.wd;
             else gr += a.wd * P[e];
@@ -2427,15 +2529,15 @@ DEVI void adam_finish4(const AdamArgs& a, float bc1, float bc2_sqrt, float gscal
     __builtin_nontemporal_store(f32x4nt{mm.x, mm.y, mm.z, mm.w}, reinterpret_cast<f32x4nt*>(a.m + i));
     __builtin_nontemporal_store(f32x4nt{vv.x, vv.y, vv.z, vv.w}, reinterpret_cast<f32x4nt*>(a.v + i));
 }
-DEVI void adam_update4(const AdamArgs& a, float bc1, float bc2_sqrt, float gscale, long long i, unsigned& lo, unsigned& hi) {
+DEVI void adam_update4(const AdamArgs& a, float bc1, float bc2_sqrt, float gscale, long long i, unsigned& lo, unsigned& hi, float vclip = 0.f) {
     AdamQuad q;
     adam_load4(a, i, q);
-    adam_finish4(a, bc1, bc2_sqrt, gscale, i, q, lo, hi);
+    adam_finish4(a, bc1, bc2_sqrt, gscale, i, q, lo, hi, vclip);
 }
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n,
                             float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt, float gscale, h16_t* __restrict__ shadow,
                             const ScalerState* __restrict__ ss = nullptr, float wd = 0.f, int decoupled = 0, const unsigned* __restrict__ skip = nullptr,
-                            unsigned tag = 0) {
+                            unsigned tag = 0, const ClipState* __restrict__ cs = nullptr) {
     if (skip && *skip == tag) return;   // a persistent recurrence of this step timed out (rnn_persist.h): its gradients are garbage, the step is dropped
     if (ss) {                           // fp16 mode: unscale; a step with non-finite gradients changes nothing (GradScaler.step skips
         if (ss->found_inf) return;      // optimizer.step(), so Adam's own step count — the bias corrections — only counts the steps taken)
@@ -2444,12 +2546,14 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
         bc1 = 1.f - powf(b1, t);
         bc2_sqrt = sqrtf(1.f - powf(b2, t));
     }
+    float vclip;
+    clip_read(cs, gscale, vclip);
     // gradient and moments are touched once per step: non-temporal loads / stores keep them from displacing the parameters and their
     // 16-bit shadow (read next by the weight repacks and the forward) in the L2 / memory-side cache (same-box A/B: -0.014 ms/step)
-    const AdamArgs a{p, g, m, v, lr, b1, b2, eps, bc1, bc2_sqrt, gscale, wd, decoupled, shadow, ss, skip, tag};
+    const AdamArgs a{p, g, m, v, lr, b1, b2, eps, bc1, bc2_sqrt, gscale, wd, decoupled, shadow, ss, skip, tag, cs};
     long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const long long stride = (long long)gridDim.x * blockDim.x * 4;
-    for (; i + 3 < n; i += stride) { unsigned lo, hi; adam_update4(a, bc1, bc2_sqrt, gscale, i, lo, hi); }
+    for (; i + 3 < n; i += stride) { unsigned lo, hi; adam_update4(a, bc1, bc2_sqrt, gscale, i, lo, hi, vclip); }
 }
 
 // Adam with the TRANSPOSED 16-bit weight copies written by the same pass (16-bit engines, round 5).  The backward's data-gradient GEMMs read W^T; until round 4 a
@@ -2471,6 +2575,8 @@ __global__ void __launch_bounds__(256) adam_tiled_kernel(AdamArgs a, const TrDes
         bc1 = 1.f - powf(a.b1, t);
         bc2_sqrt = sqrtf(1.f - powf(a.b2, t));
     }
+    float vclip;
+    clip_read(a.cs, gscale, vclip);
     const int tid = threadIdx.x;
     if ((int)blockIdx.x < ntile) {
         const TrDesc D = desc[blk2desc[blockIdx.x]];
@@ -2489,7 +2595,7 @@ __global__ void __launch_bounds__(256) adam_tiled_kernel(AdamArgs a, const TrDes
         for (int ps = 0; ps < 4; ++ps) {
             const int row = ps * 16 + (tid >> 4), r = r0 + row;
             unsigned lo = 0u, hi = 0u;
-            if (r < D.R && c < D.C) adam_finish4(a, bc1, bc2_sqrt, gscale, off + (long long)r * D.C + c, q[ps], lo, hi);
+            if (r < D.R && c < D.C) adam_finish4(a, bc1, bc2_sqrt, gscale, off + (long long)r * D.C + c, q[ps], lo, hi, vclip);
             *reinterpret_cast<unsigned*>(&tile[row][cc]) = lo;
             *reinterpret_cast<unsigned*>(&tile[row][cc + 2]) = hi;
         }
@@ -2512,20 +2618,23 @@ __global__ void __launch_bounds__(256) adam_tiled_kernel(AdamArgs a, const TrDes
         const int j = blockIdx.x - ntile;
         const long long start = chunk_start[j];
         const int n = chunk_n[j];
-        for (int i = tid * 4; i + 3 < n; i += 1024) { unsigned lo, hi; adam_update4(a, bc1, bc2_sqrt, gscale, start + i, lo, hi); }
+        for (int i = tid * 4; i + 3 < n; i += 1024) { unsigned lo, hi; adam_update4(a, bc1, bc2_sqrt, gscale, start + i, lo, hi, vclip); }
     }
 }
 
 // torch.optim.SGD (conf/model/optimizer/sgd.yaml: momentum 0.9) over the flat buffer; buf = the bound first-moment buffer
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long n, float lr, float momentum,
                            float dampening, float wd, int nesterov, int first, float gscale, h16_t* __restrict__ shadow,
-                           const ScalerState* __restrict__ ss = nullptr, const unsigned* __restrict__ skip = nullptr, unsigned tag = 0) {
+                           const ScalerState* __restrict__ ss = nullptr, const unsigned* __restrict__ skip = nullptr, unsigned tag = 0,
+                           const ClipState* __restrict__ cs = nullptr) {
     if (skip && *skip == tag) return;
     if (ss) {
         if (ss->found_inf) return;
         gscale /= ss->scale;
         first = ss->steps == 0;
     }
+    float vclip;
+    clip_read(cs, gscale, vclip);
     long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const long long stride = (long long)gridDim.x * blockDim.x * 4;
     for (; i + 3 < n; i += stride) {
@@ -2535,6 +2644,7 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float gr = G[e] * gscale;
+            if (vclip > 0.f) gr = gr > vclip ? vclip : (gr < -vclip ? -vclip : gr);
             if (wd != 0.f) gr += wd * P[e];
             if (momentum != 0.f) {
                 Bf[e] = first ? gr : momentum * Bf[e] + (1.f - dampening) * gr;

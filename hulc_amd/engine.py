@@ -416,6 +416,28 @@ class StepEngine:
         """taken_steps >= 0 also restores the device-side count of optimizer steps taken (Adam's bias corrections in fp16 mode)."""
         L.check(self.lib.hulc_scaler_set(self.ctx, float(scale), int(growth_tracker), int(taken_steps)))
 
+    # ---- gradient clipping / gradient norms inside the optimizer step (include/hulc_hip.h: hulc_grad_clip_set / hulc_grad_norm_get) -------
+    def set_grad_clip(self, algo: Optional[str], limit: Optional[float], track: bool = False):
+        """Lightning's gradient_clip_algorithm / gradient_clip_val for every following adam_step / optimizer_step: algo "norm" (clip_grad_norm_),
+        "value" (clip_grad_value_) or "off" / None; limit None / <= 0 = off.  track: compute the norms on every step whatever the algorithm.
+        `flat_grads` (and the modules' .grad views) are NOT rewritten: the clipped values exist only inside the optimizer kernel."""
+        algo = "off" if algo is None else str(algo)
+        if algo not in L.CLIP:
+            raise ValueError(f"gradient clip algorithm {algo!r}: expected 'norm', 'value' or 'off'")
+        L.check(self.lib.hulc_grad_clip_set(self.ctx, L.CLIP[algo], float(limit or 0.0), int(bool(track))))
+
+    def grad_norms(self, per_tensor: bool = False) -> Dict:
+        """{"total", "coef"[, "per_tensor": {name: norm}]} of the LAST optimizer step's effective gradient (G x grad_scale / loss scale) before
+        clipping — synchronises the stream.  Raises if that step computed no norm (clipping by norm or track not enabled)."""
+        tot, coef = C.c_float(), C.c_float()
+        n = len(self.layout)
+        per = np.empty(n, np.float32) if per_tensor else None
+        L.check(self.lib.hulc_grad_norm_get(self.ctx, C.byref(tot), C.byref(coef), per.ctypes.data if per_tensor else None, n))
+        out = dict(total=tot.value, coef=coef.value)
+        if per_tensor:
+            out["per_tensor"] = {name: float(per[i]) for i, name in enumerate(self.layout.keys())}
+        return out
+
     def get_tensor(self, name: str, n: int) -> np.ndarray:
         out = np.zeros(n, np.float32)
         got = C.c_int64()

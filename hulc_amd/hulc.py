@@ -72,6 +72,11 @@ class FusedAdam:
                                               momentum=g["momentum"], dampening=g["dampening"], nesterov=g["nesterov"], grad_scale=1.0 / world)
         return loss
 
+    def grad_norm(self, per_tensor: bool = False):
+        """Norm(s) of the gradient the last step() consumed (mean over the ranks, loss scale divided out), before clipping — for callers that drive
+        the optimizer by hand; needs engine.set_grad_clip("norm", ...) or track=True (StepEngine.grad_norms)."""
+        return self.module.engine.grad_norms(per_tensor=per_tensor)
+
     def state_dict(self):
         e = self.module.engine
         sd = dict(step=e.adam_t, exp_avg=e.adam_m.clone(), exp_avg_sq=e.adam_v.clone(),

@@ -174,13 +174,33 @@ def epoch_batches(datamodule, limit_train_batches, world: int):
 class Trainer:
     def __init__(self, max_epochs: int = 1, max_steps: int = -1, log_dir: str = "./runs", callbacks: Optional[List] = None,
                  log_every: int = 10, limit_val_batches: Optional[int] = None, check_val_every_n_epoch: int = 1, limit_train_batches=None,
-                 accumulate_grad_batches: int = 1, **_unused):
+                 accumulate_grad_batches: int = 1, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: Optional[str] = "norm",
+                 track_grad_norm=-1, **_unused):
         self.max_epochs, self.max_steps, self.log_dir = int(max_epochs), int(max_steps), log_dir
         self.limit_train_batches, self.accumulate_grad_batches = limit_train_batches, max(1, int(accumulate_grad_batches or 1))
         if self.accumulate_grad_batches != 1:
             # training_step runs forward AND backward and the optimizer steps on every batch; a schedule inferred for fewer optimizer steps than
             # are taken would reach lr 0 early.  No reference configuration sets it (conf/trainer/*.yaml): rejected, not ignored
             raise NotImplementedError("accumulate_grad_batches > 1 is not supported by hulc_amd.trainer.Trainer (the reference's confs never set it)")
+        # Lightning's gradient clipping / norm tracking (reference: Trainer(**cfg.trainer), hulc/training.py:57-71), performed inside the fused
+        # optimizer step (StepEngine.set_grad_clip): None / 0 = off, algorithm "norm" (clip_grad_norm_) or "value" (clip_grad_value_)
+        algo = "norm" if gradient_clip_algorithm is None else str(gradient_clip_algorithm).lower()
+        if algo not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r} is invalid: allowed algorithms are 'norm' and 'value'")
+        if gradient_clip_val is not None and not isinstance(gradient_clip_val, (int, float)):
+            raise TypeError(f"gradient_clip_val should be an int or a float, got {gradient_clip_val!r}")
+        if gradient_clip_val is not None and float(gradient_clip_val) < 0:
+            raise ValueError(f"gradient_clip_val {gradient_clip_val!r} must not be negative")
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else None
+        self.gradient_clip_algorithm = algo
+        try:
+            tg = float(track_grad_norm)
+        except (TypeError, ValueError):
+            raise ValueError(f"track_grad_norm {track_grad_norm!r}: expected -1 (off) or a norm type")
+        if tg not in (-1.0, 2.0):
+            # only the 2-norm comes out of the fused reduction; another norm type is rejected, not silently replaced
+            raise NotImplementedError(f"track_grad_norm={track_grad_norm!r}: only the 2-norm (track_grad_norm=2) is supported by hulc_amd.trainer.Trainer")
+        self.track_grad_norm = tg
         self.datamodule = None
         self.limit_val_batches, self.check_val_every_n_epoch = limit_val_batches, max(1, int(check_val_every_n_epoch or 1))
         self.val_history: List[Dict[str, float]] = []
@@ -196,6 +216,22 @@ class Trainer:
     def _train_batches(self, datamodule) -> float:
         """Optimizer steps THIS rank takes per training epoch = epoch_batches(...)[0]: ONE arithmetic for the fit loop and Hulc.num_training_steps."""
         return epoch_batches(datamodule, self.limit_train_batches, self.world)[0]
+
+    @property
+    def clips_gradients(self) -> bool:
+        return self.gradient_clip_val is not None
+
+    def _configure_grad_clip(self, module) -> bool:
+        """Hand the clipping / tracking configuration to the module's engine (once, after configure_optimizers); returns whether the optimizer
+        step will compute gradient norms (clipping by norm, or tracking)."""
+        want_norm = self.track_grad_norm == 2.0 or (self.clips_gradients and self.gradient_clip_algorithm == "norm")
+        eng = getattr(module, "engine", None)
+        if eng is None or not hasattr(eng, "set_grad_clip"):
+            if self.clips_gradients or self.track_grad_norm == 2.0:
+                raise RuntimeError("gradient_clip_val / track_grad_norm need a module that steps through hulc_amd.engine.StepEngine")
+            return False
+        eng.set_grad_clip(self.gradient_clip_algorithm if self.clips_gradients else "off", self.gradient_clip_val, track=self.track_grad_norm == 2.0)
+        return want_norm
 
     def validate(self, module, datamodule) -> Dict[str, float]:
         """Lightning's validation loop for this module: eval mode, validation_step over the val batches, mean of every `val*` metric."""
@@ -232,6 +268,7 @@ class Trainer:
         oc = module.configure_optimizers()
         self.optimizer, sched = oc["optimizer"], oc["lr_scheduler"]["scheduler"]
         self.lr_scheduler = sched
+        log_norms = self._configure_grad_clip(module)
         if ckpt_path:
             ck = torch.load(ckpt_path, map_location="cpu", weights_only=False)
             hp = ck.get("hyper_parameters") or {}
@@ -269,6 +306,13 @@ class Trainer:
                 sched.step()
                 self.global_step += 1
                 if self.rank == 0 and self.global_step % self.log_every == 0:
+                    if log_norms:      # read back on the logged steps only (synchronises): Lightning 1.x's track_grad_norm=2 key names
+                        gn = module.engine.grad_norms(per_tensor=self.track_grad_norm == 2.0)
+                        module.logged["grad_2.0_norm_total"] = gn["total"]
+                        if self.clips_gradients and self.gradient_clip_algorithm == "norm":
+                            module.logged["grad_clip_coef"] = gn["coef"]      # not a Lightning key: the factor clip_grad_norm_ applied on this step
+                        for k, v in gn.get("per_tensor", {}).items():
+                            module.logged["grad_2.0_norm/" + k] = v
                     rec = dict(step=self.global_step, epoch=self.current_epoch, loss=float(loss), time=time.time() - t0, **module.logged)
                     self.history.append(rec)
                     print(f"[hulc_amd] epoch {self.current_epoch} step {self.global_step} loss {float(loss):.4f} "

@@ -99,6 +99,18 @@ def resolve_log_dir(log_dir: str, resume: bool, rank: int = 0, world: int = 1, f
     return choice
 
 
+def trainer_kwargs(cfg, callbacks=None) -> dict:
+    """The keywords hulc_amd.trainer.Trainer gets from a composed config.  The reference hands the whole `trainer` group to Lightning
+    (hulc/training.py:57-71: Trainer(**cfg.trainer, ...)); here the run length, the log directory and — when the group sets them — Lightning's
+    gradient_clip_val / gradient_clip_algorithm / track_grad_norm are forwarded."""
+    tc = cfg.trainer
+    kw = dict(max_epochs=tc.max_epochs, max_steps=tc.get("max_steps", -1), log_dir=cfg.log_dir, callbacks=callbacks)
+    for k in ("gradient_clip_val", "gradient_clip_algorithm", "track_grad_norm"):
+        if k in tc:
+            kw[k] = tc[k]
+    return kw
+
+
 def train(overrides=None, conf_dir: str = CONF_DIR):
     cfg = config.compose(conf_dir, "config", overrides or [])
     rank, world, local = parallel.init_from_env()
@@ -131,7 +143,7 @@ def train(overrides=None, conf_dir: str = CONF_DIR):
         from .hulc import initialize_pretrained_weights
         initialize_pretrained_weights(model, cfg)
     callbacks = [config.instantiate(c) for c in cfg.callbacks.values() if isinstance(c, dict) and "_target_" in c]
-    tr = Trainer(max_epochs=cfg.trainer.max_epochs, max_steps=cfg.trainer.get("max_steps", -1), log_dir=cfg.log_dir, callbacks=callbacks)
+    tr = Trainer(**trainer_kwargs(cfg, callbacks))
     hist = tr.fit(model, dm, ckpt_path=chk)
     return model, hist
 

@@ -212,6 +212,30 @@ int hulc_scaler_get(hulc_ctx* ctx, float* scale, int32_t* growth_tracker, int64_
  * warm moments and a zero count would shrink the first thousands of updates.  taken_steps < 0 leaves the count unchanged. */
 int hulc_scaler_set(hulc_ctx* ctx, float scale, int32_t growth_tracker, int64_t taken_steps);
 
+/* ---- Gradient clipping and gradient-norm logging inside the optimizer step (replaces Lightning's Trainer(gradient_clip_val=...,
+ * gradient_clip_algorithm=..., track_grad_norm=2), which the reference reaches through Trainer(**cfg.trainer), hulc/training.py:57-71:
+ * unscale (fp16) -> torch.nn.utils.clip_grad_norm_ / clip_grad_value_ -> optimizer.step()).  Everything refers to the EFFECTIVE gradient,
+ * what the optimizer consumes: G x grad_scale / loss scale (grad_scale = the step's argument, e.g. 1 / world after the SUM all-reduce;
+ * loss scale = the fp16 scaler's, 1 otherwise).
+ *   HULC_CLIP_NORM   total_norm = L2 norm over all bound tensors (alignment padding never counts), reduced on the device in a fixed order (same
+ *                    bits on every run and for every compute type); every gradient is multiplied by coef = min(1, limit / (total_norm + 1e-6))
+ *                    inside the optimizer's own pass.  coef == 1 leaves the step bit-identical to an unclipped one.
+ *   HULC_CLIP_VALUE  every gradient element is clamped to [-limit, +limit] before the optimizer's weight-decay term is added.
+ * The bound gradient buffer is NOT rewritten (torch leaves the clipped values in p.grad; here it keeps the unclipped — and in fp16 mode still
+ * loss-scaled — gradients).  The norm is taken inside hulc_adam_step / hulc_optimizer_step, i.e. after the all-reduce whoever performed it, so
+ * every rank derives the same coefficient and no further collective is needed.  fp16: the norm pass also performs the non-finite check (the
+ * buffer is read once); a skipped step (inf / nan, or a failed persistent recurrence) stays skipped, its reported norm is what IEEE gives.
+ * That check covers the listed tensors only: an inf / nan a caller left in alignment PADDING skips the step when the separate whole-buffer check
+ * runs (clipping by norm and track both off) and does not when the norm pass does it (padding belongs to no parameter either way).
+ * Takes effect from the next optimizer step.  limit <= 0 or HULC_CLIP_OFF: no clipping.  track != 0: the norms are computed on every step even
+ * when the algorithm is OFF / VALUE.  With clipping off and track == 0 (the default) the optimizer step launches exactly what it did before. */
+enum { HULC_CLIP_OFF = 0, HULC_CLIP_NORM = 1, HULC_CLIP_VALUE = 2 };
+int hulc_grad_clip_set(hulc_ctx* ctx, int32_t algo, float limit, int32_t track);
+/* Norms of the LAST optimizer step's effective gradient before clipping: *total (what clip_grad_norm_ returns), *coef (the factor that was
+ * applied; 1 unless HULC_CLIP_NORM) and, if per_tensor_host != NULL, one L2 norm per bound tensor in hulc_bind_params order (cap >= n_tensors).
+ * Each pointer is optional.  Synchronises the stream.  An error if the last step computed no norm. */
+int hulc_grad_norm_get(hulc_ctx* ctx, float* total, float* coef, float* per_tensor_host, int64_t cap);
+
 /* ---- Validation forward: one modality of Hulc.validation_step (hulc/models/hulc.py:770-797) = lmp_val
  * (:301-388): plan proposal and plan recognition each sample a plan (distributions.py:37-41), the decoder is run with both
  * (LogisticDecoderRNN.loss_and_act, logistic_decoder_rnn.py:85-100): NLL loss, a sampled action (_sample :234-258) mapped back to
