@@ -106,6 +106,31 @@ int hulc_rollout_act(hulc_ctx* ctx, const hulc_rollout_obs* obs, const float* u_
     if (!obs || !obs->rgb_static || !obs->rgb_gripper || !obs->robot_obs_raw || !action_out_host) { hulc_set_error("hulc_rollout_act: null argument"); return 1; }
     return ctx->e->rollout_act(obs, u_mix, u_act, action_out_host);
 }
+int hulc_rollout_envs_init(hulc_ctx* ctx, int32_t max_envs) {
+    if (!ctx) { hulc_set_error("hulc_rollout_envs_init: null context"); return 1; }
+    return ctx->e->rollout_envs_init(max_envs);
+}
+int hulc_rollout_envs_reset(hulc_ctx* ctx, int32_t n, const int32_t* slots, int32_t clear_hidden) {
+    if (!ctx) { hulc_set_error("hulc_rollout_envs_reset: null context"); return 1; }
+    return ctx->e->rollout_envs_reset(n, slots, clear_hidden);
+}
+int hulc_rollout_envs_plan(hulc_ctx* ctx, const hulc_rollout_envs_obs* obs, const float* goal_rgb_static, const float* goal_rgb_gripper, const float* goal_lang,
+                           const void* plan_inject, void* plan_out, float* latent_goal_out) {
+    if (!ctx || !obs || !obs->rgb_static || !obs->rgb_gripper) { hulc_set_error("hulc_rollout_envs_plan: null observation"); return 1; }
+    return ctx->e->rollout_envs_plan(obs, goal_rgb_static, goal_rgb_gripper, goal_lang, plan_inject, plan_out, latent_goal_out);
+}
+int hulc_rollout_envs_act(hulc_ctx* ctx, const hulc_rollout_envs_obs* obs, const float* u_mix, const float* u_act, float* actions_out_host) {
+    if (!ctx || !obs || !obs->rgb_static || !obs->rgb_gripper || !obs->robot_obs_raw || !actions_out_host) { hulc_set_error("hulc_rollout_envs_act: null argument"); return 1; }
+    return ctx->e->rollout_envs_act(obs, u_mix, u_act, actions_out_host);
+}
+int hulc_rollout_envs_get_state(hulc_ctx* ctx, int32_t n, const int32_t* slots, void* plan_out, float* latent_goal_out) {
+    if (!ctx) { hulc_set_error("hulc_rollout_envs_get_state: null context"); return 1; }
+    return ctx->e->rollout_envs_get_state(n, slots, plan_out, latent_goal_out);
+}
+int hulc_rollout_envs_set_state(hulc_ctx* ctx, int32_t n, const int32_t* slots, const void* plan, const float* latent_goal) {
+    if (!ctx || !latent_goal) { hulc_set_error("hulc_rollout_envs_set_state: null latent goal"); return 1; }
+    return ctx->e->rollout_envs_set_state(n, slots, plan, latent_goal);
+}
 int hulc_sbert_create(const hulc_sbert_config* cfg, hulc_sbert** out) {
     if (!cfg || !out) { hulc_set_error("hulc_sbert_create: null argument"); return 1; }
     int ndev = 0;

@@ -17,6 +17,7 @@
 #include "tr_fused.h"
 #include "rnn_persist.h"
 #include "enc_tail.h"
+#include "rollout_step.h"
 
 namespace HULC_NS {
 
@@ -195,7 +196,7 @@ struct Engine : IEngine {
         KIN = dec_plan + DE + GOAL;
         maxB = cfg.max_batch; maxS = cfg.max_seq; maxN = maxB * maxS;
     }
-    ~Engine() override { for (void* p : allocs) hipFree(p); if (rp_err_host) hipHostFree((void*)rp_err_host); if (blk2desc_dev) hipFree(blk2desc_dev); if (trdesc_dev) hipFree(trdesc_dev); tr_table_free(tr_adam); tr_table_free(tr_rest); if (adam_chunk_start) hipFree(adam_chunk_start); if (adam_chunk_n) hipFree(adam_chunk_n); gn_free(); if (clip_state) hipFree(clip_state); }
+    ~Engine() override { for (void* p : allocs) hipFree(p); if (rp_err_host) hipHostFree((void*)rp_err_host); if (blk2desc_dev) hipFree(blk2desc_dev); if (trdesc_dev) hipFree(trdesc_dev); tr_table_free(tr_adam); tr_table_free(tr_rest); if (adam_chunk_start) hipFree(adam_chunk_start); if (adam_chunk_n) hipFree(adam_chunk_n); gn_free(); if (clip_state) hipFree(clip_state); if (env_rows_host) hipHostFree(env_rows_host); }
     int64_t workspace_bytes() const override { return ws_bytes; }
     void set_kl_beta(float b) override { cfg.kl_beta = b; }
     void set_dropout(float p) override { cfg.dropout_p = p; }
@@ -850,6 +851,7 @@ struct Engine : IEngine {
 #include "engine_encoders.inc"      // the perceptual encoders: conv1 sources (fp32 / uint8 / frame store), conv2 / conv3 forward, data and weight gradients, spatial softmax, the fc tails
 #include "engine_forward.inc"      // MLP helper, the forward pieces shared by training / validation / rollout, hulc_forward_loss and hulc_forward_loss_pair
 #include "engine_inference.inc"      // validation forward (a20), the CLIP ground-truth metric, the stateful rollout
+#include "engine_rollout_envs.inc"      // the batched multi-environment rollout: max_envs policy slots per context (rollout_step.h)
 #include "engine_recurrent.inc"      // the 2048-wide recurrences: persistent launches (rnn_persist.h) with their probe / fallback protocol, the mcil BiRNN and BiGRU plan encoders (a12, a19)
 #include "engine_backward.inc"      // gradient all-reduce buckets + the job-wide skip vote (comm.h), hulc_backward / hulc_backward_part / hulc_backward_allreduce (a16-a17)
     // ---------------------------------------------------------------- dynamic loss scaling (kernels.h: ScalerState)

@@ -32,6 +32,14 @@ struct IEngine {
     virtual int rollout_act(const hulc_rollout_obs* obs, const float* u_mix, const float* u_act, float* action_out) = 0;
     virtual int rollout_get_goal(float* latent_goal_out) = 0;
     virtual int rollout_set_state(const void* plan, const float* latent_goal) = 0;
+    // ---- batched multi-environment rollout (engine_rollout_envs.inc, rollout_step.h)
+    virtual int rollout_envs_init(int max_envs) = 0;
+    virtual int rollout_envs_reset(int n, const int32_t* slots, int clear_hidden) = 0;
+    virtual int rollout_envs_plan(const hulc_rollout_envs_obs* obs, const float* goal_static, const float* goal_gripper, const float* goal_lang,
+                                  const void* plan_inject, void* plan_out, float* latent_goal_out) = 0;
+    virtual int rollout_envs_act(const hulc_rollout_envs_obs* obs, const float* u_mix, const float* u_act, float* actions_out) = 0;
+    virtual int rollout_envs_get_state(int n, const int32_t* slots, void* plan_out, float* latent_goal_out) = 0;
+    virtual int rollout_envs_set_state(int n, const int32_t* slots, const void* plan, const float* latent_goal) = 0;
     virtual int optim(const hulc_optim& o) = 0;
     int adam(float lr, float b1, float b2, float eps, int64_t step, float gscale) {
         hulc_optim o{}; o.kind = HULC_OPT_ADAM; o.lr = lr; o.beta1 = b1; o.beta2 = b2; o.eps = eps; o.step = step; o.grad_scale = gscale;

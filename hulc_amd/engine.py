@@ -293,6 +293,116 @@ class StepEngine:
                 raise ValueError("plan must have %d elements" % (256 if mcil else 32))
         L.check(self.lib.hulc_rollout_set_state(self.ctx, p.ctypes.data if p is not None else None, g.ctypes.data))
 
+    # ------------------------------------------------------------------ batched multi-environment rollout (hulc_rollout_envs_*)
+    def _envs_obs(self, obs: Dict, env_ids, keep, need_robot: bool):
+        """obs: rgb_static (n,[1,]3,200,200), rgb_gripper (n,[1,]3,84,84), robot_obs_raw (n,[1,]15); env_ids: the slot of every row (None = 0..n-1)."""
+        def dev(t, tail):
+            t = torch.as_tensor(t)
+            t = t.to(device=self.device, dtype=torch.float32).reshape((int(t.shape[0]),) + tail).contiguous()
+            keep.append(t)
+            return t
+        rs, rg = dev(obs["rgb_static"], (3, 200, 200)), dev(obs["rgb_gripper"], (3, 84, 84))
+        n = int(rs.shape[0])
+        if rg.shape[0] != n:
+            raise ValueError("rgb_static and rgb_gripper disagree on the number of rows")
+        ro = None
+        if need_robot:
+            ro = dev(obs["robot_obs_raw"], (15,))
+            if ro.shape[0] != n:
+                raise ValueError("robot_obs_raw must have one row per environment")
+        o = L.HulcRolloutEnvsObs(n=n, slots=self._slots_ptr(env_ids, n, keep), rgb_static=rs.data_ptr(), rgb_gripper=rg.data_ptr(),
+                                 robot_obs_raw=ro.data_ptr() if ro is not None else None)
+        return o, n
+
+    @staticmethod
+    def _slots_ptr(env_ids, n, keep):
+        if env_ids is None:
+            return None
+        s = np.ascontiguousarray(np.asarray(env_ids, np.int32).reshape(-1))
+        if n is not None and s.size != n:
+            raise ValueError(f"{s.size} env ids for {n} rows")
+        keep.append(s)
+        return s.ctypes.data
+
+    def _plan_shape(self):
+        mcil = self.dims.kind == "mcil"
+        return (256 if mcil else 32), (torch.float32 if mcil else torch.int32), (np.float32 if mcil else np.int32)
+
+    def rollout_envs_init(self, max_envs: int) -> None:
+        """Give the context `max_envs` (<= max_batch, <= 64) independent policy slots; clears every slot; may be called again."""
+        L.check(self.lib.hulc_rollout_envs_init(self.ctx, int(max_envs)))
+
+    def rollout_envs_reset(self, env_ids=None, clear_hidden: bool = False) -> None:
+        """Drop plan and goal of the slots `env_ids` (None = all); hulc / mcil also zero their hidden states, gcbc only with clear_hidden."""
+        keep = []
+        n = 0 if env_ids is None else len(env_ids)
+        L.check(self.lib.hulc_rollout_envs_reset(self.ctx, n, self._slots_ptr(env_ids, None, keep), int(bool(clear_hidden))))
+
+    def rollout_envs_plan(self, obs: Dict, goal, env_ids=None, plan=None, want_goal: bool = False):
+        """goal: dict(rgb_static (n,[1,]3,200,200), rgb_gripper) for visual goals or an (n,384) language-embedding tensor — one kind per call.
+        plan: optional injected (n,32) int / (n,256) fp32 (mcil) plans.  Returns the stored plans as a device tensor (None for gcbc), with want_goal the
+        pair (plans, (n,32) fp32 latent goals as numpy)."""
+        keep = []
+        o, n = self._envs_obs(obs, env_ids, keep, False)
+        gs = gg = gl = None
+        if isinstance(goal, dict):
+            gs = torch.as_tensor(goal["rgb_static"]).to(device=self.device, dtype=torch.float32).reshape(-1, 3, 200, 200).contiguous()
+            gg = torch.as_tensor(goal["rgb_gripper"]).to(device=self.device, dtype=torch.float32).reshape(-1, 3, 84, 84).contiguous()
+            if gs.shape[0] != n or gg.shape[0] != n:
+                raise ValueError("one goal image pair per row")
+        else:
+            gl = torch.as_tensor(goal).to(device=self.device, dtype=torch.float32).reshape(-1, 384).contiguous()
+            if gl.shape[0] != n:
+                raise ValueError("one (384,) language embedding per row")
+        width, tdt, ndt = self._plan_shape()
+        if plan is not None and int(np.prod(plan.shape)) != n * width:
+            raise ValueError(f"plan must be ({n},{width})")
+        out = torch.zeros(n, width, dtype=tdt, device=self.device) if self.dims.kind != "gcbc" else None
+        lg = np.empty((n, 32), np.float32) if want_goal else None
+        L.check(self.lib.hulc_rollout_envs_plan(self.ctx, C.byref(o), gs.data_ptr() if gs is not None else None, gg.data_ptr() if gg is not None else None,
+                                                gl.data_ptr() if gl is not None else None, self._dev_or_host_ptr(plan, keep, ndt),
+                                                out.data_ptr() if out is not None else None, lg.ctypes.data if want_goal else None))
+        return (out, lg) if want_goal else out
+
+    def rollout_envs_act(self, obs: Dict, env_ids=None, u_mix=None, u_act=None) -> np.ndarray:
+        """One decoder step for the n rows of `obs` on their slots' plans, goals and hidden states.  Returns the (n,7) world-frame actions."""
+        keep = []
+        o, n = self._envs_obs(obs, env_ids, keep, True)
+        D = 7 if self.dims.kind == "mcil" else 6
+        if u_mix is not None and int(np.prod(u_mix.shape)) != n * D * 10:
+            raise ValueError(f"u_mix must be ({n},{D},10)")
+        if u_act is not None and int(np.prod(u_act.shape)) != n * D:
+            raise ValueError(f"u_act must be ({n},{D})")
+        out = np.empty((n, 7), np.float32)
+        L.check(self.lib.hulc_rollout_envs_act(self.ctx, C.byref(o), self._dev_or_host_ptr(u_mix, keep, np.float32),
+                                               self._dev_or_host_ptr(u_act, keep, np.float32), out.ctypes.data))
+        return out
+
+    def rollout_envs_get_state(self, env_ids):
+        """(plans, latent goals) of the slots `env_ids` as numpy: (n,32) int32 | (n,256) fp32 | None (gcbc), (n,32) fp32."""
+        keep = []
+        n = len(env_ids)
+        width, _, ndt = self._plan_shape()
+        plan = np.empty((n, width), ndt) if self.dims.kind != "gcbc" else None
+        goal = np.empty((n, 32), np.float32)
+        L.check(self.lib.hulc_rollout_envs_get_state(self.ctx, n, self._slots_ptr(env_ids, n, keep), plan.ctypes.data if plan is not None else None, goal.ctypes.data))
+        return plan, goal
+
+    def rollout_envs_set_state(self, env_ids, plan, latent_goal) -> None:
+        """Install caller-held plans ((n,32) int | (n,256) fp32 for mcil | None for gcbc) and (n,32) latent goals; the hidden states are not touched."""
+        keep = []
+        n = len(env_ids)
+        width, _, ndt = self._plan_shape()
+        g = np.ascontiguousarray(np.asarray(latent_goal, np.float32).reshape(-1))
+        if g.size != n * 32:
+            raise ValueError(f"latent_goal must be ({n},32)")
+        p = None
+        if plan is not None:
+            p = np.ascontiguousarray(np.asarray(plan.cpu() if torch.is_tensor(plan) else plan, ndt).reshape(-1))
+            if p.size != n * width:
+                raise ValueError(f"plan must be ({n},{width})")
+        L.check(self.lib.hulc_rollout_envs_set_state(self.ctx, n, self._slots_ptr(env_ids, n, keep), p.ctypes.data if p is not None else None, g.ctypes.data))
+
     def set_kl_beta(self, kl_beta: float):
         L.check(self.lib.hulc_set_kl_beta(self.ctx, float(kl_beta)))
 

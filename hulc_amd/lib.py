@@ -36,6 +36,11 @@ class HulcRolloutObs(C.Structure):
     _fields_ = [("rgb_static", C.c_void_p), ("rgb_gripper", C.c_void_p), ("robot_obs_raw", C.c_void_p)]
 
 
+class HulcRolloutEnvsObs(C.Structure):
+    """hulc_rollout_envs_obs: the rows of one batched multi-environment rollout call; `slots` is a HOST int32 array (or NULL = rows 0..n-1)."""
+    _fields_ = [("n", C.c_int32), ("slots", C.c_void_p), ("rgb_static", C.c_void_p), ("rgb_gripper", C.c_void_p), ("robot_obs_raw", C.c_void_p)]
+
+
 class HulcOptim(C.Structure):
     _fields_ = [("kind", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
                 ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int32), ("step", C.c_int64), ("grad_scale", C.c_float)]
@@ -52,7 +57,7 @@ class HulcSbertConfig(C.Structure):
 
 EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_stream", "hulc_workspace_bytes",
            "hulc_bind_params", "hulc_prepare_weights", "hulc_zero_grads", "hulc_flush_grads", "hulc_forward_loss", "hulc_forward_loss_pair", "hulc_backward", "hulc_backward_part",
-           "hulc_adam_step", "hulc_optimizer_step", "hulc_comm_unique_id", "hulc_comm_prepare", "hulc_comm_init", "hulc_comm_destroy", "hulc_comm_buckets", "hulc_comm_stats", "hulc_comm_size", "hulc_comm_timeline", "hulc_allreduce_grads", "hulc_backward_allreduce", "hulc_scaler_enable", "hulc_scaler_get", "hulc_scaler_set", "hulc_grad_clip_set", "hulc_grad_norm_get", "hulc_validate", "hulc_clip_gt_encode", "hulc_clip_gt_scores", "hulc_rollout_reset", "hulc_rollout_plan", "hulc_rollout_act", "hulc_rollout_get_goal", "hulc_rollout_set_state", "hulc_sbert_create", "hulc_sbert_destroy", "hulc_sbert_set_stream", "hulc_sbert_bind", "hulc_sbert_encode", "hulc_set_kl_beta", "hulc_set_dropout", "hulc_set_option", "hulc_get_option", "hulc_timers_enable", "hulc_timers_read", "hulc_get_tensor", "hulc_get_plan_idx", "hulc_k_gemm_nt", "hulc_k_cast", "hulc_k_trread_probe", "hulc_k_conv_wgrad", "hulc_k_conv1_wgrad_u8", "hulc_k_conv1_interior_groups", "hulc_k_conv_tile", "hulc_k_skinny", "hulc_k_attention", "hulc_k_rnn_persist", "hulc_k_rnn_persist_flag_words"]
+           "hulc_adam_step", "hulc_optimizer_step", "hulc_comm_unique_id", "hulc_comm_prepare", "hulc_comm_init", "hulc_comm_destroy", "hulc_comm_buckets", "hulc_comm_stats", "hulc_comm_size", "hulc_comm_timeline", "hulc_allreduce_grads", "hulc_backward_allreduce", "hulc_scaler_enable", "hulc_scaler_get", "hulc_scaler_set", "hulc_grad_clip_set", "hulc_grad_norm_get", "hulc_validate", "hulc_clip_gt_encode", "hulc_clip_gt_scores", "hulc_rollout_reset", "hulc_rollout_plan", "hulc_rollout_act", "hulc_rollout_get_goal", "hulc_rollout_set_state", "hulc_rollout_envs_init", "hulc_rollout_envs_reset", "hulc_rollout_envs_plan", "hulc_rollout_envs_act", "hulc_rollout_envs_get_state", "hulc_rollout_envs_set_state", "hulc_sbert_create", "hulc_sbert_destroy", "hulc_sbert_set_stream", "hulc_sbert_bind", "hulc_sbert_encode", "hulc_set_kl_beta", "hulc_set_dropout", "hulc_set_option", "hulc_get_option", "hulc_timers_enable", "hulc_timers_read", "hulc_get_tensor", "hulc_get_plan_idx", "hulc_k_gemm_nt", "hulc_k_cast", "hulc_k_trread_probe", "hulc_k_conv_wgrad", "hulc_k_conv1_wgrad_u8", "hulc_k_conv1_interior_groups", "hulc_k_conv_tile", "hulc_k_skinny", "hulc_k_attention", "hulc_k_rnn_persist", "hulc_k_rnn_persist_flag_words"]
 
 _lib = None
 
@@ -117,6 +122,13 @@ def load():
     lib.hulc_rollout_act.argtypes = [C.c_void_p, C.POINTER(HulcRolloutObs), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hulc_rollout_get_goal.argtypes = [C.c_void_p, C.c_void_p]
     lib.hulc_rollout_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "hulc_rollout_envs_init") or not os.environ.get("HULC_LIB_PATH"):
+        lib.hulc_rollout_envs_init.argtypes = [C.c_void_p, C.c_int32]
+        lib.hulc_rollout_envs_reset.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        lib.hulc_rollout_envs_plan.argtypes = [C.c_void_p, C.POINTER(HulcRolloutEnvsObs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hulc_rollout_envs_act.argtypes = [C.c_void_p, C.POINTER(HulcRolloutEnvsObs), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hulc_rollout_envs_get_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hulc_rollout_envs_set_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hulc_sbert_create.argtypes = [C.POINTER(HulcSbertConfig), C.POINTER(C.c_void_p)]
     lib.hulc_sbert_destroy.argtypes = [C.c_void_p]
     lib.hulc_sbert_set_stream.argtypes = [C.c_void_p, C.c_void_p]

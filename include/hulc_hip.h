@@ -302,6 +302,46 @@ int hulc_rollout_act(hulc_ctx* ctx, const hulc_rollout_obs* obs, const float* u_
 int hulc_rollout_get_goal(hulc_ctx* ctx, float* latent_goal_out /* (32) */);
 int hulc_rollout_set_state(hulc_ctx* ctx, const void* plan, const float* latent_goal /* (32) */);
 
+/* ---- Batched multi-environment rollout: N policy slots per context (an evaluation that drives several simulator processes against one GPU policy —
+ * CALVIN's 1000 instruction chains x 5 tasks x up to 360 steps, hulc/evaluation/evaluate_policy.py — instead of one context per environment or B = 1 calls one
+ * after the other, each of which re-streams the decoder's weights for one row of work).
+ * hulc_rollout_envs_init gives the context `max_envs` (<= max_batch, <= 64) SLOTS; it allocates, clears every slot and may be called again.  A slot is one
+ * independent policy instance = what the B = 1 calls above keep per context: a plan ((32) int32 category indices, (256) fp32 for HULC_KIND_MCIL, none for
+ * HULC_KIND_GCBC), a latent goal (32), the decoder's two hidden states (2048 each), a has-plan flag and the cached time-invariant decoder input term
+ * (plan embedding gather + goal x W_ih0[:, goal cols] + b_ih0 + b_hh0; written when the slot is planned, not recomputed per step).
+ * A call names n rows (1..max_envs) and the slot of each (`slots`: HOST int32, distinct, each in [0, max_envs); NULL = rows 0..n-1); slots a call does
+ * not name are neither read nor written.  Per row each call does what its B = 1 counterpart does (hulc.py:843-957, gcbc.py:281-320):
+ *   hulc_rollout_envs_plan   encodes obs + goal of the n rows (a visual goal = an (obs, goal) 2-frame window per row; needs max_seq >= 2), samples or injects
+ *                            the plans, stores plan and goal into the rows' slots and zeroes those slots' hidden states (GCBC: stores the goal only and leaves
+ *                            the hidden state alone).  Exactly one goal kind per call: the two goal images, or goal_lang (n,384).  plan_inject / plan_out:
+ *                            (n,32) int32 | (n,256) fp32 (mcil); latent_goal_out (n,32) fp32; outputs optional, host or device.
+ *   hulc_rollout_envs_act    encodes the n current frames, runs ONE decoder step per row on its slot's plan, goal and hidden states, samples and maps tcp ->
+ *                            world; actions_out_host (n,7).  u_mix (n,D,10) / u_act (n,D), D = 6 (7 for mcil): injected uniform draws, host or device;
+ *                            NULL = drawn on the device, reproducible for a given seed and call sequence, different for every row.
+ *   hulc_rollout_envs_reset  drops plan and goal of the named slots (slots == NULL: every slot, n ignored) and zeroes their hidden states; HULC_KIND_GCBC
+ *                            zeroes them only when clear_hidden != 0 (the reference's GCBC.reset never clears the decoder state).
+ *   hulc_rollout_envs_get_state / _set_state   read / install plan and latent goal of the named slots as values ((n,32) int32 | (n,256) fp32, (n,32) fp32; host
+ *                            or device); neither touches the hidden states.  An installed category index is clamped into [0, 32).
+ * Every argument error — n out of range, a slot out of range or named twice, act / get_state on a slot without a plan (the message names the slot), both goal
+ * kinds or neither, a visual goal with max_seq < 2, any call before init — is found before the first launch and leaves all state untouched.  The slots and
+ * the B = 1 rollout state are separate: calls of either family do not disturb the other.  Every call synchronises the stream.
+ * 16-bit engines: the step from the encoder embedding to the actions is three launches and no copy whatever n is (csrc/rollout_step.h); the fp32 engine
+ * composes the generic kernels. */
+typedef struct hulc_rollout_envs_obs {
+    int32_t n;                    /* rows of this call, 1..max_envs */
+    const int32_t* slots;         /* (n) HOST: slot of each row, distinct, each in [0,max_envs); NULL = 0..n-1 */
+    const float* rgb_static;      /* (n,3,200,200) device fp32, as hulc_rollout_obs */
+    const float* rgb_gripper;     /* (n,3,84,84)   device */
+    const float* robot_obs_raw;   /* (n,15) device or host */
+} hulc_rollout_envs_obs;
+int hulc_rollout_envs_init(hulc_ctx* ctx, int32_t max_envs);
+int hulc_rollout_envs_reset(hulc_ctx* ctx, int32_t n, const int32_t* slots /* NULL = all */, int32_t clear_hidden);
+int hulc_rollout_envs_plan(hulc_ctx* ctx, const hulc_rollout_envs_obs* obs, const float* goal_rgb_static /* (n,3,200,200) */, const float* goal_rgb_gripper,
+                           const float* goal_lang /* (n,384) */, const void* plan_inject, void* plan_out, float* latent_goal_out);
+int hulc_rollout_envs_act(hulc_ctx* ctx, const hulc_rollout_envs_obs* obs, const float* u_mix, const float* u_act, float* actions_out_host /* (n,7) */);
+int hulc_rollout_envs_get_state(hulc_ctx* ctx, int32_t n, const int32_t* slots, void* plan_out, float* latent_goal_out);
+int hulc_rollout_envs_set_state(hulc_ctx* ctx, int32_t n, const int32_t* slots, const void* plan, const float* latent_goal);
+
 /* ---- MiniLM sentence encoder: the reference's SBert (hulc/models/encoders/language_network.py:8-17) =
  * sentence_transformers "all-MiniLM-L6-v2" (conf/model/sbert.yaml:2) = BERT encoder + masked mean pooling + L2 normalisation.
  * Forward only, fp32.  Weights: one flat fp32 device buffer + Hugging Face BertModel state_dict names (e.g.
