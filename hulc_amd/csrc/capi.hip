@@ -9,6 +9,7 @@
 
 #include "engine.h"
 #include "sbert.h"
+#include "store_gather.h"
 
 using namespace hulc_bf16;      // this translation unit: fp32 (parity) + bf16 engines and the per-kernel test entry points; fp16: engine_f16.hip
 
@@ -79,6 +80,19 @@ int hulc_validate(hulc_ctx* ctx, const hulc_batch* batch, const hulc_val_noise* 
                   float* pred_pp_out, float* pred_pr_out) {
     if (!batch) { hulc_set_error("hulc_validate: null batch"); return 1; }
     return ctx->e->validate(batch, noise, out_host, plan_idx_pp_out, plan_idx_pr_out, pred_pp_out, pred_pr_out);
+}
+int hulc_store_gather(hulc_ctx* ctx, const hulc_store_tables* t, const int64_t* window_start, const int32_t* window_len, const int32_t* lang_row, int32_t B, int32_t S,
+                      float* actions_out, float* robot_obs_out, float* lang_out) {
+    if (!ctx || !t || !window_start || !actions_out || !robot_obs_out) { hulc_set_error("hulc_store_gather: null argument"); return 1; }
+    if (!t->actions || !t->robot_obs || t->store_frames < 1) { hulc_set_error("hulc_store_gather: needs the actions and robot_obs tables and store_frames >= 1 (got %lld)", (long long)t->store_frames); return 1; }
+    if (B < 1 || S < 1 || (long long)B * S * 22 + (long long)B * 384 > 0x7fffffffll) { hulc_set_error("hulc_store_gather: bad shape B=%d S=%d", B, S); return 1; }
+    if (lang_out && (!t->lang || !lang_row || t->lang_rows < 1)) { hulc_set_error("hulc_store_gather: lang_out needs the lang table (lang_rows >= 1) and lang_row"); return 1; }
+    StoreGatherP p{t->actions, t->robot_obs, t->lang, reinterpret_cast<const long long*>(window_start), window_len, lang_row, actions_out, robot_obs_out, lang_out,
+                   (long long)t->store_frames, t->lang_rows, B, S, t->absolute != 0};
+    const int total = B * S * 22 + (lang_out ? B * 384 : 0);
+    hipLaunchKernelGGL(store_gather_kernel, dim3((total + 255) / 256), dim3(256), 0, ctx->e->st, p);
+    if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_store_gather: launch failed"); return 1; }
+    return 0;
 }
 int hulc_clip_gt_encode(hulc_ctx* ctx, const float* lang_emb, int32_t m, int32_t slot) {
     if (!ctx) { hulc_set_error("hulc_clip_gt_encode: null context"); return 1; }

@@ -975,6 +975,24 @@ __global__ void ingest_u8_kernel(const unsigned char* __restrict__ in, const int
     out[idx] = u8_to_unit(in[((src.frame(f) * IH + sy) * IW + sx) * 3 + c]);       // src: only its frame-store fields are used (frame(f) = f without a store)
 }
 
+// variable-length windows (include/hulc_hip.h hulc_batch::window_len): window b holds L = clamp(wlen[b], 1, S) real frames starting at
+// clamp(wstart[b], 0, nstore - L) and is padded to S by REPEATING its last real frame, store index and RandomShiftsAug shift both (the reference pads after the
+// image transform: an exact duplicate).  The engine expands this ONCE per forward into a per-frame start table and the effective per-frame shifts; the conv1
+// kernels then read the batch as a frame store of ONE-frame windows (Conv1Src: wstart = the table, S = 1) — the code they run is the fixed-window code, untouched.
+__global__ void __launch_bounds__(256) window_expand_kernel(const long long* __restrict__ wstart, const int* __restrict__ wlen, int B, int S, long long nstore,
+                                                            const int* __restrict__ sh_s, const int* __restrict__ sh_g, long long* __restrict__ frame_out,
+                                                            int* __restrict__ sh_s_out, int* __restrict__ sh_g_out) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= B * S) return;
+    const int b = idx / S, t = idx - b * S;
+    const int L = min(max(wlen[b], 1), (int)min((long long)S, nstore));      // a store shorter than S bounds L too: never an out-of-bounds read
+    const long long s0 = min(max(wstart[b], 0ll), nstore - (long long)L);
+    const int te = min(t, L - 1), fe = b * S + te;
+    frame_out[idx] = s0 + te;
+    if (sh_s) { sh_s_out[2 * idx] = sh_s[2 * fe]; sh_s_out[2 * idx + 1] = sh_s[2 * fe + 1]; }
+    if (sh_g) { sh_g_out[2 * idx] = sh_g[2 * fe]; sh_g_out[2 * idx + 1] = sh_g[2 * fe + 1]; }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // conv1 (8x8 stride 4, 3 -> 32 channels) weight gradient straight from the fp32 NCHW boundary frames.
 //   dW[co][(c,kh,kw)] = sum dY[n][oh][ow][co] * X[n][c][oh*4+kh][ow*4+kw]

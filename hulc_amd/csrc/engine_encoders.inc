@@ -15,7 +15,34 @@
         // exactly like the reference (ingest_u8_kernel)
         s.fold = (s.u8 && std::is_same<T, h16_t>::value && u8_fold_mode) ? 1 : 0;
         if (s.u8 && b.window_start) { s.wstart = reinterpret_cast<const long long*>(b.window_start); s.S = b.S; s.nstore = b.store_frames; }      // windows gathered from the frame store
+        if (s.wstart && b.window_len) {      // variable-length padded windows: the per-frame table of window_len_expand, read as one-frame windows
+            const int set = &b == &cur2 ? 1 : 0;
+            s.wstart = wl_frame[set]; s.S = 1;
+            if (s.shift) s.shift = wl_shift[set][gripper ? 1 : 0];
+        }
         return s;
+    }
+    // hulc_batch::window_len, expanded once per forward / validation (conv_wgrad.h window_expand_kernel); set 0 = the batch of the pass, 1 = the paired pass's lang batch (cur2)
+    long long* wl_frame[2] = {nullptr, nullptr};
+    int* wl_shift[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    int window_len_expand(const hulc_batch& b, int nB, int set) {
+        if (!b.window_len) return 0;
+        if (!wl_frame[set]) {
+            wl_frame[set] = alloc<long long>((int64_t)maxN); wl_shift[set][0] = alloc<int>((int64_t)maxN * 2); wl_shift[set][1] = alloc<int>((int64_t)maxN * 2);
+            if (alloc_failed) { hulc_set_error("window_len: workspace allocation failed"); return 1; }
+        }
+        hipLaunchKernelGGL(window_expand_kernel, dim3(cdiv(nB * b.S, 256)), dim3(256), 0, st, reinterpret_cast<const long long*>(b.window_start), b.window_len, nB, b.S,
+                           (long long)b.store_frames, b.shift_static, b.shift_gripper, wl_frame[set], wl_shift[set][0], wl_shift[set][1]);
+        return 0;
+    }
+    // argument check of the frame-store fields, before any launch (hulc_forward_loss / _pair, hulc_validate): true = error set
+    static bool store_args_bad(const hulc_batch* b) {
+        if (b->window_len && !b->window_start) { hulc_set_error("window_len (variable-length windows) needs window_start (the frame store)"); return true; }
+        if (!b->window_start) return false;
+        if (b->store_frames < 1) { hulc_set_error("window_start (frame store) needs store_frames >= 1 (got %lld)", (long long)b->store_frames); return true; }
+        // fixed windows need S frames in the store; with window_len a window may be as short as one frame
+        if (!b->frames_u8 || (!b->window_len && b->store_frames < b->S)) { hulc_set_error("window_start (frame store) needs frames_u8 and store_frames >= S (got frames_u8=%d, store_frames=%lld, S=%d)", b->frames_u8, (long long)b->store_frames, b->S); return true; }
+        return false;
     }
     // b - sum_k W16 of the two conv1 layers (Conv1Src::fold), recomputed after every weight refresh, only when a uint8 batch asks for it
     float* c1_bias_fold[2] = {nullptr, nullptr};

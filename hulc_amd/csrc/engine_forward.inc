@@ -222,7 +222,7 @@
         if (vb->is_lang || !lb->is_lang || !lb->lang) { hulc_set_error("hulc_forward_loss_pair: first batch must be the vis modality, second the lang modality with embeddings"); return 1; }
         if (vb->B != lb->B || vb->S != lb->S) { hulc_set_error("hulc_forward_loss_pair: both modalities need the same B and S (got %dx%d and %dx%d)", vb->B, vb->S, lb->B, lb->S); return 1; }
         for (const hulc_batch* b : {vb, lb}) {
-            if (b->window_start && (!b->frames_u8 || b->store_frames < b->S)) { hulc_set_error("window_start (frame store) needs frames_u8 and store_frames >= S (got frames_u8=%d, store_frames=%lld, S=%d)", b->frames_u8, (long long)b->store_frames, b->S); return 1; }
+            if (store_args_bad(b)) return 1;
             if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
         }
         if (vb->frames_u8 != lb->frames_u8 || vb->actions_absolute != lb->actions_absolute || vb->max_rel_pos != lb->max_rel_pos || vb->max_rel_orn != lb->max_rel_orn) {
@@ -271,9 +271,10 @@
         }
         if (b->is_lang && !b->lang) { hulc_set_error("lang modality batch without language embeddings (hulc.py:440 KeyError 'lang')"); return 1; }
         if (b->actions_absolute && !(b->max_rel_pos > 0.f && b->max_rel_orn > 0.f)) { hulc_set_error("actions_absolute needs max_rel_pos > 0 and max_rel_orn > 0 (RelativeActions, transforms.py:35-37)"); return 1; }
-        if (b->window_start && (!b->frames_u8 || b->store_frames < b->S)) { hulc_set_error("window_start (frame store) needs frames_u8 and store_frames >= S (got frames_u8=%d, store_frames=%lld, S=%d)", b->frames_u8, (long long)b->store_frames, b->S); return 1; }
+        if (store_args_bad(b)) return 1;
         if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
         cur = *b; cur_lw = lw; cur_cw = cw; have_fwd = false; val_clip_n = 0;
+        if (window_len_expand(*b, pair ? pairBv : b->B, 0) || (pair && window_len_expand(cur2, cur2.B, 1))) return 1;
         const int B = b->B, S = b->S, N = B * S, SB = S * B;
         const bool hulc = cfg.kind == HULC_KIND_HULC;
         const float dp = cfg.dropout_p;

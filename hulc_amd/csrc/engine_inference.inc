@@ -41,11 +41,12 @@
         if (b->actions_absolute && !(b->max_rel_pos > 0.f && b->max_rel_orn > 0.f)) { hulc_set_error("actions_absolute needs max_rel_pos > 0 and max_rel_orn > 0 (RelativeActions, transforms.py:35-37)"); return 1; }
         val_alloc();
         if (alloc_failed) { hulc_set_error("hulc_validate: workspace allocation failed"); return 1; }
-        if (b->window_start && (!b->frames_u8 || b->store_frames < b->S)) { hulc_set_error("window_start (frame store) needs frames_u8 and store_frames >= S"); return 1; }
+        if (store_args_bad(b)) return 1;
         if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
         static const hulc_val_noise none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         if (!nz) nz = &none;
         cur = *b; have_fwd = false; pair = false; val_clip_n = 0;
+        if (window_len_expand(*b, b->B, 0)) return 1;
         const int B = b->B, S = b->S, SB = S * B;
         HIP_CHECK(hipMemsetAsync(valm, 0, 32 * sizeof(float), st));
         trunk_fwd(b, 0.f);

@@ -88,11 +88,15 @@ class StepEngine:
         """uint8 (B,S,H,W,C) frames select the fused ingest path (include/hulc_hip.h: frames_u8); optional per-frame RandomShiftsAug
         shifts `shift_static` / `shift_gripper` (B*S,2) int32 in [0, 2*pad] with pads `pad_static` (10) / `pad_gripper` (4).
         `window_start` (B,) int64 selects the FRAME STORE form (hulc_batch::window_start): rgb_static / rgb_gripper are then the device-resident
-        stores (F,H,W,3) uint8 and window b = store frames [window_start[b], window_start[b] + S) — nothing is materialised per step."""
+        stores (F,H,W,3) uint8 and window b = store frames [window_start[b], window_start[b] + S) — nothing is materialised per step.
+        `window_len` (B,) int32 on the device next to it: window b holds that many real frames and is padded to S by repeating its last one
+        (hulc_batch::window_len)."""
         rel = {}
         if mb.get("actions_absolute"):        # RelativeActions (transforms.py:32-56) applied on the device
             rel = dict(actions_absolute=1, max_rel_pos=float(mb.get("max_rel_pos", 0.02)), max_rel_orn=float(mb.get("max_rel_orn", 0.05)))
         if mb["rgb_static"].dtype != torch.uint8:
+            if mb.get("window_len") is not None:
+                raise ValueError("window_len needs the frame store form: uint8 stores and window_start")
             return rel
         if mb["rgb_gripper"].dtype != torch.uint8 or mb["rgb_static"].shape[-1] != 3 or mb["rgb_gripper"].shape[-1] != 3:
             raise ValueError("uint8 ingest expects both cameras as uint8 (B,S,H,W,3) tensors")
@@ -108,6 +112,11 @@ class StepEngine:
                 raise ValueError("frame store: window_start must live on the device")
             f["window_start"] = ptr(ws.to(torch.int64))
             f["store_frames"] = int(mb["rgb_static"].shape[0])
+        if mb.get("window_len") is not None:      # without window_start the library reports the error (hulc_last_error)
+            wl = mb["window_len"]
+            if not torch.is_tensor(wl) or not wl.is_cuda or wl.dtype != torch.int32 or wl.dim() != 1 or wl.shape[0] != mb["actions"].shape[0]:
+                raise ValueError("frame store: window_len must be a (B,) int32 tensor on the device")
+            f["window_len"] = ptr(wl)
         return f
 
     def _batch_struct(self, mb: Dict, is_lang: bool, step: int, keep: list):
@@ -163,6 +172,41 @@ class StepEngine:
             self._loss_dev = torch.zeros(4, dtype=torch.float32, device=self.device)
         L.check(self.lib.hulc_forward_loss(self.ctx, C.byref(b), loss_weight, clip_weight, self._loss_dev.data_ptr(), 0))
         return self._loss_dev
+
+    def store_gather(self, actions: torch.Tensor, robot_obs: torch.Tensor, window_start: torch.Tensor, S: int, window_len: Optional[torch.Tensor] = None,
+                     lang: Optional[torch.Tensor] = None, lang_row: Optional[torch.Tensor] = None, absolute: bool = False):
+        """hulc_store_gather: the non-image half of a frame-store batch from the per-frame tables actions (F,7) / robot_obs (F,15) and, optionally, the
+        language table lang (A,384) with one row index per window — all fp32 / int on the device.  Same window arithmetic and padding as the frames
+        (window_len); padded relative actions are zero in dims 0..5 and repeat the gripper, `absolute` repeats all seven.  One asynchronous launch on
+        the context's stream.  Returns (actions (B,S,7), robot_obs (B,S,15), lang (B,384) or None)."""
+        def dev(t, dtype, shape_tail, name):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape[1:]) != shape_tail or not t.is_contiguous():
+                raise ValueError(f"store_gather: {name} must be a contiguous {dtype} device tensor of shape (n,{','.join(map(str, shape_tail))})")
+            return t
+        actions, robot_obs = dev(actions, torch.float32, (7,), "actions"), dev(robot_obs, torch.float32, (15,), "robot_obs")
+        if actions.shape[0] != robot_obs.shape[0] or actions.shape[0] < 1:
+            raise ValueError("store_gather: actions and robot_obs must hold the same F >= 1 rows")
+        ws = dev(window_start, torch.int64, (), "window_start")
+        B = int(ws.shape[0])
+        wl = None if window_len is None else dev(window_len, torch.int32, (), "window_len")
+        if wl is not None and wl.shape[0] != B:
+            raise ValueError("store_gather: window_len must be (B,)")
+        lang_out = None
+        if lang is not None:
+            lang = dev(lang, torch.float32, (384,), "lang")
+            if lang_row is None:
+                raise ValueError("store_gather: a lang table needs lang_row (B,)")
+            lang_row = dev(lang_row, torch.int32, (), "lang_row")
+            if lang_row.shape[0] != B:
+                raise ValueError("store_gather: lang_row must be (B,)")
+            lang_out = torch.empty(B, 384, dtype=torch.float32, device=self.device)
+        a_out = torch.empty(B, int(S), 7, dtype=torch.float32, device=self.device)
+        r_out = torch.empty(B, int(S), 15, dtype=torch.float32, device=self.device)
+        t = L.HulcStoreTables(actions=actions.data_ptr(), robot_obs=robot_obs.data_ptr(), lang=None if lang is None else lang.data_ptr(),
+                              store_frames=int(actions.shape[0]), lang_rows=0 if lang is None else int(lang.shape[0]), absolute=int(bool(absolute)))
+        L.check(self.lib.hulc_store_gather(self.ctx, C.byref(t), ws.data_ptr(), None if wl is None else wl.data_ptr(), None if lang is None else lang_row.data_ptr(),
+                                           B, int(S), a_out.data_ptr(), r_out.data_ptr(), None if lang_out is None else lang_out.data_ptr()))
+        return a_out, r_out, lang_out
 
     # ------------------------------------------------------------------ validation / rollout (forward only)
     @staticmethod

@@ -24,7 +24,12 @@ class HulcBatch(C.Structure):
                 ("plan_idx", C.c_void_p), ("aux_rows", C.c_void_p), ("n_aux", C.c_int32), ("step", C.c_uint64),
                 ("frames_u8", C.c_int32), ("pad_static", C.c_int32), ("pad_gripper", C.c_int32), ("shift_static", C.c_void_p),
                 ("shift_gripper", C.c_void_p), ("plan_eps", C.c_void_p), ("actions_absolute", C.c_int32), ("max_rel_pos", C.c_float),
-                ("max_rel_orn", C.c_float), ("window_start", C.c_void_p), ("store_frames", C.c_int64)]
+                ("max_rel_orn", C.c_float), ("window_start", C.c_void_p), ("store_frames", C.c_int64), ("window_len", C.c_void_p)]
+
+
+class HulcStoreTables(C.Structure):
+    """hulc_store_tables: the per-frame tables next to a frame store (hulc_store_gather)."""
+    _fields_ = [("actions", C.c_void_p), ("robot_obs", C.c_void_p), ("lang", C.c_void_p), ("store_frames", C.c_int64), ("lang_rows", C.c_int32), ("absolute", C.c_int32)]
 
 
 class HulcValNoise(C.Structure):
@@ -57,7 +62,7 @@ class HulcSbertConfig(C.Structure):
 
 EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_stream", "hulc_workspace_bytes",
            "hulc_bind_params", "hulc_prepare_weights", "hulc_zero_grads", "hulc_flush_grads", "hulc_forward_loss", "hulc_forward_loss_pair", "hulc_backward", "hulc_backward_part",
-           "hulc_adam_step", "hulc_optimizer_step", "hulc_comm_unique_id", "hulc_comm_prepare", "hulc_comm_init", "hulc_comm_destroy", "hulc_comm_buckets", "hulc_comm_stats", "hulc_comm_size", "hulc_comm_timeline", "hulc_allreduce_grads", "hulc_backward_allreduce", "hulc_scaler_enable", "hulc_scaler_get", "hulc_scaler_set", "hulc_grad_clip_set", "hulc_grad_norm_get", "hulc_validate", "hulc_clip_gt_encode", "hulc_clip_gt_scores", "hulc_rollout_reset", "hulc_rollout_plan", "hulc_rollout_act", "hulc_rollout_get_goal", "hulc_rollout_set_state", "hulc_rollout_envs_init", "hulc_rollout_envs_reset", "hulc_rollout_envs_plan", "hulc_rollout_envs_act", "hulc_rollout_envs_get_state", "hulc_rollout_envs_set_state", "hulc_sbert_create", "hulc_sbert_destroy", "hulc_sbert_set_stream", "hulc_sbert_bind", "hulc_sbert_encode", "hulc_set_kl_beta", "hulc_set_dropout", "hulc_set_option", "hulc_get_option", "hulc_timers_enable", "hulc_timers_read", "hulc_get_tensor", "hulc_get_plan_idx", "hulc_k_gemm_nt", "hulc_k_cast", "hulc_k_trread_probe", "hulc_k_conv_wgrad", "hulc_k_conv1_wgrad_u8", "hulc_k_conv1_interior_groups", "hulc_k_conv_tile", "hulc_k_skinny", "hulc_k_attention", "hulc_k_rnn_persist", "hulc_k_rnn_persist_flag_words"]
+           "hulc_adam_step", "hulc_optimizer_step", "hulc_comm_unique_id", "hulc_comm_prepare", "hulc_comm_init", "hulc_comm_destroy", "hulc_comm_buckets", "hulc_comm_stats", "hulc_comm_size", "hulc_comm_timeline", "hulc_allreduce_grads", "hulc_backward_allreduce", "hulc_scaler_enable", "hulc_scaler_get", "hulc_scaler_set", "hulc_grad_clip_set", "hulc_grad_norm_get", "hulc_validate", "hulc_store_gather", "hulc_clip_gt_encode", "hulc_clip_gt_scores", "hulc_rollout_reset", "hulc_rollout_plan", "hulc_rollout_act", "hulc_rollout_get_goal", "hulc_rollout_set_state", "hulc_rollout_envs_init", "hulc_rollout_envs_reset", "hulc_rollout_envs_plan", "hulc_rollout_envs_act", "hulc_rollout_envs_get_state", "hulc_rollout_envs_set_state", "hulc_sbert_create", "hulc_sbert_destroy", "hulc_sbert_set_stream", "hulc_sbert_bind", "hulc_sbert_encode", "hulc_set_kl_beta", "hulc_set_dropout", "hulc_set_option", "hulc_get_option", "hulc_timers_enable", "hulc_timers_read", "hulc_get_tensor", "hulc_get_plan_idx", "hulc_k_gemm_nt", "hulc_k_cast", "hulc_k_trread_probe", "hulc_k_conv_wgrad", "hulc_k_conv1_wgrad_u8", "hulc_k_conv1_interior_groups", "hulc_k_conv_tile", "hulc_k_skinny", "hulc_k_attention", "hulc_k_rnn_persist", "hulc_k_rnn_persist_flag_words"]
 
 _lib = None
 
@@ -117,6 +122,8 @@ def load():
     lib.hulc_clip_gt_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     lib.hulc_clip_gt_scores.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.hulc_validate.argtypes = [C.c_void_p, C.POINTER(HulcBatch), C.POINTER(HulcValNoise), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "hulc_store_gather") or not os.environ.get("HULC_LIB_PATH"):
+        lib.hulc_store_gather.argtypes = [C.c_void_p, C.POINTER(HulcStoreTables), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hulc_rollout_reset.argtypes = [C.c_void_p]
     lib.hulc_rollout_plan.argtypes = [C.c_void_p, C.POINTER(HulcRolloutObs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hulc_rollout_act.argtypes = [C.c_void_p, C.POINTER(HulcRolloutObs), C.c_void_p, C.c_void_p, C.c_void_p]

@@ -264,6 +264,8 @@ class Trainer:
     def fit(self, module, datamodule, ckpt_path: Optional[str] = None):
         self.rank, self.world, self.local = parallel.init_from_env()
         self.datamodule = datamodule
+        if hasattr(datamodule, "attach") and getattr(module, "engine", None) is not None:
+            datamodule.attach(module.engine)       # store-backed datamodules gather their tables on the engine's stream (hulc_store_gather)
         module.trainer = self                      # Lightning attaches the trainer before configure_optimizers (Hulc.num_training_steps reads it)
         oc = module.configure_optimizers()
         self.optimizer, sched = oc["optimizer"], oc["lr_scheduler"]["scheduler"]

@@ -111,14 +111,20 @@ def trainer_kwargs(cfg, callbacks=None) -> dict:
     return kw
 
 
+def make_datamodule(cfg, device: str):
+    """The datamodule of a composed config.  The keys the model tree only interpolates (action_*) are not constructor arguments; `root_data_dir`
+    is handed to datamodules that read a dataset (conf/datamodule/calvin_store.yaml), the synthetic one has none."""
+    drop = ("action_space", "action_max", "action_min") + (() if cfg.datamodule.get("root_data_dir") else ("root_data_dir",))
+    return config.instantiate({k: v for k, v in cfg.datamodule.items() if k not in drop}, device=device, seed=cfg.seed)
+
+
 def train(overrides=None, conf_dir: str = CONF_DIR):
     cfg = config.compose(conf_dir, "config", overrides or [])
     rank, world, local = parallel.init_from_env()
     torch.manual_seed(cfg.seed)                        # seed_everything(cfg.seed) (training.py:36)
     np.random.seed(cfg.seed)
     device = f"cuda:{local}"
-    dm = config.instantiate({k: v for k, v in cfg.datamodule.items() if k not in ("root_data_dir", "action_space", "action_max", "action_min")},
-                            device=device, seed=cfg.seed)
+    dm = make_datamodule(cfg, device)
     # The reference runs inside a fresh timestamped Hydra directory (conf/config.yaml hydra.run.dir) and resumes from the newest
     # checkpoint found THERE (training.py:38-46), i.e. only when the same run directory is re-entered.  Here: log_dir may contain
     # "{now}" (expanded once on rank 0, then shared); the default conf writes runs/<date>/<time>; `resume=true` re-enters the newest run

@@ -93,6 +93,15 @@ typedef struct hulc_batch {
      * shift_* stay (B*S,2) per batch frame.  The step is bit-identical to the same windows passed as a materialised uint8 batch. */
     const int64_t* window_start;
     int64_t store_frames;
+    /* ---- variable-length padded windows (the reference's datasets draw a window of min_window_size..max_window_size frames and pad it to the
+     * maximum: conf/datamodule/datasets/vision_dataset/vision.yaml, lang_dataset/lang.yaml: min_window_size 20, max_window_size 32, pad true).
+     * window_len: (B) int32 on the DEVICE, requires window_start; NULL = every window has S frames (bit-identical to the fields above alone).
+     * With L = clamp(window_len[b], 1, S) and s0 = clamp(window_start[b], 0, store_frames - L), batch frame (b, t) is store frame
+     * s0 + min(t, L - 1): the window is padded to S by REPEATING its last real frame, and the RandomShiftsAug offsets of frame (b, t) are
+     * shift[b * S + min(t, L - 1)] (the reference pads after the image transform, so a padded frame is an exact duplicate; shift entries with
+     * t >= L are ignored).  A short window may therefore start closer to the end of the store than S frames; store_frames >= 1 is all it needs.
+     * Nothing downstream changes: the model sees S frames, the visual goal emb[:, -1] is the last real frame, nothing is masked (as in the reference). */
+    const int32_t* window_len;
 } hulc_batch;
 
 /* out_losses (device or host pointer, see `losses_on_host`): [total_mod, kl_scaled, action, clip] of this modality,
@@ -260,6 +269,25 @@ typedef struct hulc_val_noise {
 #define HULC_N_VAL 18
 int hulc_validate(hulc_ctx* ctx, const hulc_batch* batch, const hulc_val_noise* noise, float* out_host, int32_t* plan_idx_pp_out,
                   int32_t* plan_idx_pr_out, float* pred_pp_out, float* pred_pr_out);
+
+/* ---- The non-image half of a frame-store batch, gathered on the device (replaces the per-sample numpy slicing and padding of the reference's disk
+ * datasets: calvin_agent's _pad_sequence behind conf/datamodule/datasets/vision_dataset/vision.yaml `pad: true`; restated here, its source is not part
+ * of the reference tree).  The per-frame tables live next to the frame store; one launch on the context's stream, asynchronous.  Window arithmetic as
+ * hulc_batch::window_len: L = clamp(window_len[b], 1, S) (window_len NULL: L = S), s0 = clamp(window_start[b], 0, store_frames - L), row (b, t) =
+ * table row s0 + min(t, L - 1).  Padding rows t >= L: robot_obs repeats the last real row; relative actions (absolute == 0) pad dims 0..5 with ZEROS
+ * and repeat dim 6, the gripper; absolute != 0 repeats all seven dims (hulc_batch::actions_absolute then sees consistent rows).  lang_out[b] =
+ * lang[lang_row[b]] (row index clamped into the table); lang_out NULL skips it.  Outputs are caller-owned device buffers. */
+typedef struct hulc_store_tables {
+    const float* actions;        /* (store_frames,7) */
+    const float* robot_obs;      /* (store_frames,15) */
+    const float* lang;           /* (lang_rows,384) or NULL */
+    int64_t store_frames;
+    int32_t lang_rows;
+    int32_t absolute;            /* actions hold absolute targets: padding repeats all seven dims */
+} hulc_store_tables;
+int hulc_store_gather(hulc_ctx* ctx, const hulc_store_tables* tables, const int64_t* window_start /* (B) device */, const int32_t* window_len /* (B) device or NULL */,
+                      const int32_t* lang_row /* (B) device, with lang_out */, int32_t B, int32_t S, float* actions_out /* (B,S,7) */,
+                      float* robot_obs_out /* (B,S,15) */, float* lang_out /* (B,384) or NULL */);
 
 /* ---- CLIP ground-truth validation metric (Hulc.on_validation_epoch_start, hulc/models/hulc.py:967-974, and the device part of
  * Hulc._clip_groundtruth_loss, :1024-1029).  hulc_clip_gt_encode runs language_goal (goal_encoders.py:64-69) and proj_vis_lang.mlp_lang
