@@ -35,17 +35,8 @@ __device__ __forceinline__ void lds_dma16(const void* src, unsigned lds_addr) {
 }
 #endif
 
-// Kernel-routing / debugging switches.  The PRODUCTION build has none: every HULC_SWITCH("NAME", default) is the compile-time constant
-// `default`, so the library contains exactly one code path per launch site (an environment switch per A/B experiment doubled
-// an untested path each).  An experiment build (`HULC_BUILD_AB=1 python -c "import __graft_entry__ as g; g.build()"`, i.e. -DHULC_AB_SWITCHES)
-// reads the same names from the environment once per process; tools/ab_env.sh needs that build.
-#ifdef HULC_AB_SWITCHES
-#include <cstdlib>
-static inline int hulc_switch_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#define HULC_SWITCH(name, dflt) hulc_switch_env(name, dflt)
-#else
-#define HULC_SWITCH(name, dflt) (dflt)
-#endif
+// Kernel routing has no build-time or environment switches: every launch site names the one kernel form that won its measurement (profiles/,
+// docs/history/).  To try another form, build it and compare the two libraries on one box (tools/ab_lib.sh).
 
 #ifdef HULC_HALF_F16
 #define HULC_NS hulc_f16

@@ -449,15 +449,9 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
                         o[e >> 2][e & 3] = pack2h(v0, v1);
                     }
                     if (opx[mm] >= 0) {
-                        long long ob = opx[mm];
-#ifdef HULC_AB_SWITCHES
-                        if (p.dbg & 64) ob = min((((long long)cur * NCLS + cls) * ntiles + t0 + mm) * 32 + lj, (long long)p.Nf * p.OUTH * p.OUTW - 1);   // experiment: tile-contiguous output
-#endif
+                        const long long ob = opx[mm];
                         u32x4_t* op = reinterpret_cast<u32x4_t*>(p.out + ob * CN + chw * 32 + 16 * h);
-#ifdef HULC_AB_SWITCHES
-                        if (p.dbg & 128) { __builtin_nontemporal_store(o[0], op); __builtin_nontemporal_store(o[1], op + 1); } else
-#endif
-                        { op[0] = o[0]; op[1] = o[1]; }
+                        op[0] = o[0]; op[1] = o[1];
                     }
                 }
                 continue;

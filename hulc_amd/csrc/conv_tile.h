@@ -421,8 +421,7 @@ static inline bool launch_conv_tile_nw(hipStream_t st, ConvTileP p) {
     // ---- small frames (whole frame per band and still only a fraction of an 8-wave round): stack FPB frames to a band.  Cost of a launch =
     // bands per workgroup x (per-band overhead + 8-wave rounds of the band's groups); one frame per band leaves most waves without a group
     // (7x7 outputs = 2 groups) and pays the two barriers + staging per frame (tools/ct_stamps.hip: ~2.5 us against a ~5.5 us full round).
-    static const int fpb_env = HULC_SWITCH("HULC_CT_FPB", -1);      // A/B: 1 = off, n = force n frames where it fits
-    if (best_nb == 1 && fpb_env != 1 && p.Nf > 1 && (REV || p.IMH % SI == 0)) {
+    if (best_nb == 1 && p.Nf > 1 && (REV || p.IMH % SI == 0)) {
         const int vpi = REV ? p.IMH + TA - 1 : p.IMH, vpo = REV ? vpi : p.IMH / SI;
         auto band_cost = [&](int fpb, int& RBo, int& LRo) -> double {
             RBo = REV ? fpb * vpo : (fpb * p.IMH - TA) / SI + 1;
@@ -445,7 +444,7 @@ static inline bool launch_conv_tile_nw(hipStream_t st, ConvTileP p) {
             int RBf, LRf;
             const double c = band_cost(fpb, RBf, LRf);
             if (c < 0) break;
-            if ((fpb_env > 1 && fpb <= fpb_env) || (fpb_env < 0 && c < bc - 1e-9)) { bc = c; bestf = fpb; p.RB = RBf; p.LR = LRf; }
+            if (c < bc - 1e-9) { bc = c; bestf = fpb; p.RB = RBf; p.LR = LRf; }
         }
         if (bestf > 1) { p.FPB = bestf; p.VPI = vpi; p.VPO = vpo; }
     }
@@ -465,11 +464,8 @@ static inline bool launch_conv_tile(hipStream_t st, ConvTileP p) {
     // 16 waves (four per SIMD, 128 VGPRs, one fragment set instead of the software-pipelined pair): the dgrad kernels fit (0 / 31 spilled registers,
     // none inside the multiply loop) and gain 5-11 % — while one wave sits in its epilogue or group setup three others feed the matrix pipe.  The
     // forward kernels do not fit: the compiler spills the band prefetch registers, i.e. waits for the loads right where they are issued
-    // (load phase alone 28 -> 76 us for conv3); they stay at 8 waves.  HULC_CT_NW=8 / 16 forces one width for every kernel (A/B).
-    static const int nw = HULC_SWITCH("HULC_CT_NW", 0);
-    if constexpr (REV) { if (nw != 8) return launch_conv_tile_nw<CK, CN, TA, TB, SI, OS, REV, 16>(st, p); }
-    else { if (nw == 16) return launch_conv_tile_nw<CK, CN, TA, TB, SI, OS, REV, 16>(st, p); }
-    return launch_conv_tile_nw<CK, CN, TA, TB, SI, OS, REV, 8>(st, p);
+    // (load phase alone 28 -> 76 us for conv3); they stay at 8 waves.
+    return launch_conv_tile_nw<CK, CN, TA, TB, SI, OS, REV, REV ? 16 : 8>(st, p);
 }
 
 // the multiply + epilogue of one staged band (shared by the fp32 / register-staged kernel and the uint8 LDS-DMA kernel below)
@@ -571,7 +567,7 @@ __global__ void __launch_bounds__(256, MINW) conv1_fwd_kernel(Conv1Src X, const 
     for (int ks = 0; ks < 6; ++ks) { const int ck = ks * 4 + g; rowsel[ks] = ((ck >> 3) * XR + (ck & 7)) * XRS; }
     const float4 bb[2] = {*reinterpret_cast<const float4*>(bias + g * 8), *reinterpret_cast<const float4*>(bias + g * 8 + 4)};
     const int nitems = Nf * nbands;
-    // frame-wise (fw, experiment knob HULC_C1_FW=1): a workgroup walks the bands of one frame back to back so that the rows two bands share come
+    // frame-wise (fw: dbg bit 32 clear): a workgroup walks the bands of one frame back to back so that the rows two bands share come
     // from L2 — what cut conv1's weight gradient by 25 % measured 0.4 % SLOWER here (4 resident workgroups per CU already re-read those rows
     // from the XCD's L2 within microseconds; the frame-wise order only removes the interleaving of their phases): default item-wise
     const bool fw = Nf >= (int)gridDim.x && !(dbg & 32);
@@ -719,29 +715,21 @@ static inline void launch_conv1_fwd(hipStream_t st, const Conv1Src& X, const h16
                                     unsigned* maskbits = nullptr, float* zero8a = nullptr, float* zero8b = nullptr) {
     // (tried: an 8-wave, 2-workgroups-per-CU version with the next band prefetched in registers like conv1_wgrad_tr2_kernel — 4.355 vs 4.341
     //  ms/step on one box: with 4 resident workgroups per CU the staging of one already overlaps the MFMAs of the others; not kept)
-    // uint8, round 6: HULC_C1_U8REG (or dbg bit 8) = the register-staged kernel with the conversion from 16-byte windows (conv1_stage_band regconv: no raw rows in LDS)
-    static const int u8reg = HULC_SWITCH("HULC_C1_U8REG", 0);
-    const bool regconv = X.u8 && (u8reg || (dbg & 256)) && (IW % 4) == 0 && IW >= 8 && ((uintptr_t)X.X & 3) == 0;
+    // uint8, dbg bit 8: the register-staged kernel with the conversion from 16-byte windows (conv1_stage_band regconv: no raw rows in LDS)
+    const bool regconv = X.u8 && (dbg & 256) && (IW % 4) == 0 && IW >= 8 && ((uintptr_t)X.X & 3) == 0;
     if (regconv) dbg |= 256; else dbg &= ~256;
     auto lds_of = [&](int R) { const int XR = (R - 1) * 4 + 8; return (size_t)3 * XR * (IW * 2 + 16) + 64 + ((X.u8 && !regconv) ? (size_t)XR * conv1_raw_pitch16(IW) + 16 : 0); };   // + raw uint8 rows
-    static const int lds_kb = HULC_SWITCH("HULC_C1_LDS", 39);   // 4 workgroups per CU: one stages while others multiply (255 vs 299 us at 2 per CU)
-    static const int max_wg = HULC_SWITCH("HULC_C1_WG", 1024);
+    constexpr int lds_kb = 39, max_wg = 1024;   // 4 workgroups per CU: one stages while others multiply (255 vs 299 us at 2 per CU)
     int R = OH;
     while (R > 1 && lds_of(R) > (size_t)lds_kb * 1024) --R;
     const int nbands = (OH + R - 1) / R;
     R = (OH + nbands - 1) / nbands;
-    static const int fw_env = HULC_SWITCH("HULC_C1_FW", 0);    // same-box A/B: frame-wise 4.458 vs item-wise 4.440 ms/step -> off
-    if (!fw_env) dbg |= 32;
-    static const int occ = HULC_SWITCH("HULC_C1_OCC", 4);      // min waves per SIMD the register allocation targets: 128 VGPRs (5 spilled) lets all 4 workgroups of a CU be resident (133 -> only 3); A/B on one box: -0.8 % of the step
+    dbg |= 32;      // item-wise bands (frame-wise measured slower in the step)
+    // OCC = 4: min waves per SIMD the register allocation targets: 128 VGPRs (5 spilled) lets all 4 workgroups of a CU be resident
     static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)conv1_fwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)conv1_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    if (!attr_set) { hipFuncSetAttribute((const void*)conv1_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
     const int items = Nf * nbands;
-    static const int u8dma = HULC_SWITCH("HULC_C1_U8DMA", 1);
-    if (X.u8 && !regconv && u8dma && (IW * 3) % 4 == 0 && ((uintptr_t)X.X & 3) == 0) {
+    if (X.u8 && !regconv && (IW * 3) % 4 == 0 && ((uintptr_t)X.X & 3) == 0) {
         static bool a2 = false;
         if (!a2) { hipFuncSetAttribute((const void*)conv1_fwd_u8dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a2 = true; }
         hipLaunchKernelGGL(conv1_fwd_u8dma_kernel, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, dbg, maskbits, zero8a, zero8b);
@@ -753,8 +741,7 @@ static inline void launch_conv1_fwd(hipStream_t st, const Conv1Src& X, const h16
         hipLaunchKernelGGL((conv1_fwd_kernel<4, true>), dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, dbg, maskbits, zero8a, zero8b);
         return;
     }
-    if (occ >= 4) hipLaunchKernelGGL(conv1_fwd_kernel<4>, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, dbg, maskbits, zero8a, zero8b);
-    else hipLaunchKernelGGL(conv1_fwd_kernel<2>, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, dbg, maskbits, zero8a, zero8b);
+    hipLaunchKernelGGL(conv1_fwd_kernel<4>, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, dbg, maskbits, zero8a, zero8b);
 }
 
 }  // namespace HULC_NS

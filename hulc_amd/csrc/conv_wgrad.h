@@ -357,7 +357,7 @@ __global__ void __launch_bounds__(NWV * 64) conv_wgrad_tr8_kernel(const h16_t* _
 // ---------------------------------------------------------------------------------------------------------------------
 // v3 (round 4): the v2 multiply loop fed by LDS-DMA into TWO band buffers.
 //   v2 stages a band through 16 prefetch registers per thread and a commit phase (ds_write_b128 + the bias sums), behind two barriers per band;
-//   measured on 2048 static-camera frames (experiment build, rocprofv3): whole kernel 129 / 137 us (conv3 / conv2), without the MFMA loop 71 / 96,
+//   measured on 2048 static-camera frames (rocprofv3): whole kernel 129 / 137 us (conv3 / conv2), without the MFMA loop 71 / 96,
 //   without the global loads 101 / 100, with neither 37 / 42 — per band: 2.5 us of commit + barriers, ~3.5 us of load latency that the MFMA loop of
 //   ONE resident band cannot cover (the next band's registers are only free after the commit), ~8 us of multiply loop.
 //   Here a band = X rows + dY rows of R output rows as ONE contiguous LDS image (same pitches, same tr-read fragments as v2), filled by
@@ -581,10 +581,8 @@ template <int CI, int CO, int KH, int KW, int S>
 static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16_t* dY, float* part, float* bias_part, int Nf, int IH, int IW, int OH,
                                        int OW, int max_blocks, int* work_ctr = nullptr, const h16_t* zeros = nullptr) {
     using C = WgradCfg<CI, CO, KH, KW, S>;
-    static const bool v1 = HULC_SWITCH("HULC_WGRAD_V1", 0) != 0;
-    static const bool v3 = HULC_SWITCH("HULC_WGRAD_DMA", 1) != 0;
     // v3 (LDS-DMA, two band buffers): frames large enough that v2 would not stack them (>= 2 bands of multiply work per frame)
-    if (!v1 && v3 && zeros && OH * OW >= 256 && Nf >= 2) {
+    if (zeros && OH * OW >= 256 && Nf >= 2) {
         int nb = 0; size_t lds = 0;
         const int R = conv_wgrad_dma_rows<CI, CO, KH, KW, S>(IH, IW, OH, OW, &nb, &lds);
         if (R > 0 && (long long)Nf * IH * IW * CI < (1ll << 31)) {
@@ -596,66 +594,51 @@ static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16
                 attr3 = true;
             }
             const int grid = std::min(std::min(Nf * nb, 256), max_blocks);
-            static const int dbg3 = HULC_SWITCH("HULC_WGRAD_DBG", 0);
-            if (IWS && IW == IWS) hipLaunchKernelGGL((conv_wgrad_dma_kernel<CI, CO, KH, KW, S, IWS>), dim3(grid), dim3(512), lds, st, X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nb, dbg3, work_ctr);
-            else hipLaunchKernelGGL((conv_wgrad_dma_kernel<CI, CO, KH, KW, S, 0>), dim3(grid), dim3(512), lds, st, X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nb, dbg3, work_ctr);
+            if (IWS && IW == IWS) hipLaunchKernelGGL((conv_wgrad_dma_kernel<CI, CO, KH, KW, S, IWS>), dim3(grid), dim3(512), lds, st, X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nb, 0, work_ctr);
+            else hipLaunchKernelGGL((conv_wgrad_dma_kernel<CI, CO, KH, KW, S, 0>), dim3(grid), dim3(512), lds, st, X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nb, 0, work_ctr);
             return grid;
         }
     }
     constexpr int NWV = 8;                                   // 16 waves (one co-tile each, 4 waves per SIMD) measured slower: 0.43 vs 0.40 ms/step
-    if (!v1) {
-        // fewest balanced bands whose chunks fit the 16 x 512 prefetch slots and whose images fit in 160 KB (16 KB kept for the bias reduction)
-        for (int nb = 1; nb <= OH; ++nb) {
-            int R = (OH + nb - 1) / nb, XR = (R - 1) * S + KH;
-            long long chunks = (long long)R * OW * (CO / 8) + (long long)XR * IW * (CI / 8);
-            size_t lds = std::max<size_t>(C::lds_bytes(R, IW, OW), NWV * 64 * 8 * sizeof(float));
-            if (chunks > 16 * 512 || lds > 160 * 1024 - 64 || (long long)XR * IW * CI >= (1 << 20)) continue;
-            // small frames (whole frame per band): stack FPB frames to a band — the two barriers, the staging and the exposed load latency of a band
-            // (~5 us, against ~0.5 us of MFMAs for a 7x7 gripper map) are then paid once per FPB frames.  Largest FPB that fits LDS and the prefetch
-            // slots and still leaves every workgroup two bands (the second one's loads fly under the first one's MFMAs).
-            int fpb = 1;
-            static const int fpb_env = HULC_SWITCH("HULC_WG_FPB", -1);     // A/B: 1 = off, n = at most n
-            if (nb == 1 && IH % S == 0 && fpb_env != 1) {
-                for (int f = 2; f <= 16; ++f) {
-                    const int Rf = (f - 1) * (IH / S) + OH, XRf = (Rf - 1) * S + KH;
-                    const long long ch = (long long)f * OH * OW * (CO / 8) + (long long)XRf * IW * (CI / 8);
-                    const size_t l = std::max<size_t>(C::lds_bytes(Rf, IW, OW), NWV * 64 * 8 * sizeof(float));
-                    if (ch > 16 * 512 || l > 160 * 1024 - 64 || (long long)XRf * IW * CI >= (1 << 20)) break;
-                    if (fpb_env > 1 ? f > fpb_env : (Nf + f - 1) / f < 2 * std::min(256, max_blocks)) break;
-                    fpb = f; R = Rf; XR = XRf; chunks = ch; lds = l;
-                }
+    // fewest balanced bands whose chunks fit the 16 x 512 prefetch slots and whose images fit in 160 KB (16 KB kept for the bias reduction)
+    for (int nb = 1; nb <= OH; ++nb) {
+        int R = (OH + nb - 1) / nb, XR = (R - 1) * S + KH;
+        long long chunks = (long long)R * OW * (CO / 8) + (long long)XR * IW * (CI / 8);
+        size_t lds = std::max<size_t>(C::lds_bytes(R, IW, OW), NWV * 64 * 8 * sizeof(float));
+        if (chunks > 16 * 512 || lds > 160 * 1024 - 64 || (long long)XR * IW * CI >= (1 << 20)) continue;
+        // small frames (whole frame per band): stack FPB frames to a band — the two barriers, the staging and the exposed load latency of a band
+        // (~5 us, against ~0.5 us of MFMAs for a 7x7 gripper map) are then paid once per FPB frames.  Largest FPB that fits LDS and the prefetch
+        // slots and still leaves every workgroup two bands (the second one's loads fly under the first one's MFMAs).
+        int fpb = 1;
+        if (nb == 1 && IH % S == 0) {
+            for (int f = 2; f <= 16; ++f) {
+                const int Rf = (f - 1) * (IH / S) + OH, XRf = (Rf - 1) * S + KH;
+                const long long ch = (long long)f * OH * OW * (CO / 8) + (long long)XRf * IW * (CI / 8);
+                const size_t l = std::max<size_t>(C::lds_bytes(Rf, IW, OW), NWV * 64 * 8 * sizeof(float));
+                if (ch > 16 * 512 || l > 160 * 1024 - 64 || (long long)XRf * IW * CI >= (1 << 20)) break;
+                if ((Nf + f - 1) / f < 2 * std::min(256, max_blocks)) break;
+                fpb = f; R = Rf; XR = XRf; chunks = ch; lds = l;
             }
-            static bool attr8 = false;
-            if (!attr8) {
-                hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-                attr8 = true;
-            }
-            const int items = fpb > 1 ? (Nf + fpb - 1) / fpb : Nf * nb;
-            const int grid = std::min(std::min(items, 256), max_blocks);
-            static const int dbg = HULC_SWITCH("HULC_WGRAD_DBG", 0);   // bench ablation only
-#ifdef HULC_AB_SWITCHES
-            static const int dsel = HULC_SWITCH("HULC_WGRAD_D", 3);      // experiment: depth of the B-fragment ring
-            if (dsel == 6 || dsel == 8) {
-                static bool a2 = false;
-                if (!a2) { hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-                           hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); a2 = true; }
-                if (dsel == 6) hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 6>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
-                else hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 8>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
+        }
+        static bool attr8 = false;
+        if (!attr8) {
+            hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+            attr8 = true;
+        }
+        const int items = fpb > 1 ? (Nf + fpb - 1) / fpb : Nf * nb;
+        const int grid = std::min(std::min(items, 256), max_blocks);
+        constexpr int dbg = 0;
+        {      // the gripper camera's maps (84 x 84 frames): conv3 reads 9 x 9, conv2 20 x 20 — the compile-time-width instance (tap offsets as ds_read immediates)
+            constexpr int IWG = (CI == 64 && KH == 3) ? 9 : ((CI == 32 && KH == 4) ? 20 : 0);
+            if (IWG && IW == IWG) {
+                static bool ag = false;
+                if (!ag) { hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 3, IWG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); ag = true; }
+                hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 3, IWG>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
                 return grid;
             }
-#endif
-            {      // the gripper camera's maps (84 x 84 frames): conv3 reads 9 x 9, conv2 20 x 20 — the compile-time-width instance (tap offsets as ds_read immediates)
-                constexpr int IWG = (CI == 64 && KH == 3) ? 9 : ((CI == 32 && KH == 4) ? 20 : 0);
-                if (IWG && IW == IWG) {
-                    static bool ag = false;
-                    if (!ag) { hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 3, IWG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); ag = true; }
-                    hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 3, IWG>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
-                    return grid;
-                }
-            }
-            hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
-            return grid;
         }
+        hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
+        return grid;
     }
     int R = OH;                                              // largest band that keeps two workgroups per CU (<= 78 KB)
     while (R > 1 && C::lds_bytes(R, IW, OW) > 78 * 1024) --R;
@@ -1757,12 +1740,10 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2r_kernel(Conv1Src S, in
     }
 }
 
-inline int g_conv1_wgrad_u8reg = -1;      // tools/conv1_wgrad_probe.hip only: 0 / 1 force the uint8 kernel form (-1: the build's own)
+inline int g_conv1_wgrad_u8reg = -1;      // hulc_k_conv1_wgrad_u8's `form` (tests): 0 / 1 / 2 force the uint8 kernel form (-1: the engine's, 2)
 static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const h16_t* dY, float* part, float* bias_part, int Nf, int IH, int IW, int OH,
                                         int OW, int max_blocks, int* work_ctr = nullptr) {
-    static const int v2 = HULC_SWITCH("HULC_W1_V2", 1);
-    static const int u8reg_sw = HULC_SWITCH("HULC_W1_U8REG", 2);      // uint8: 2 = conversion from the prefetch registers with interior / row-end slots (conv1_wgrad_tr2r_kernel<3, 2, true>), 1 = one general slot kind, 0 = round 5's raw rows through LDS
-    if (v2 && !X.u8 && (IW % 4) == 0) {
+    if (!X.u8 && (IW % 4) == 0) {
         // tallest band whose images fit 2 workgroups per CU and whose chunks fit the prefetch slots (8 frame + 2 dY registers of 16 B per thread:
         // 10 + 3 slots spilled 46 registers of in-flight data at the 128-VGPR budget of 2 x 8 waves per CU, which serialised the prefetch)
         int R = OH;
@@ -1782,8 +1763,9 @@ static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const
             return grid;
         }
     }
-    const int u8form = g_conv1_wgrad_u8reg < 0 ? u8reg_sw : g_conv1_wgrad_u8reg;
-    if (v2 && X.u8 && (IW % 4) == 0 && IW >= 8 && u8form >= 2) {
+    // uint8 forms: 2 = conversion from the prefetch registers with interior / row-end slots (conv1_wgrad_tr2r_kernel<3, 2, true>), 1 = one general slot kind, 0 = raw rows through LDS
+    const int u8form = g_conv1_wgrad_u8reg < 0 ? 2 : g_conv1_wgrad_u8reg;
+    if (X.u8 && (IW % 4) == 0 && IW >= 8 && u8form >= 2) {
         // round 6, second pass: 2 slots of interior groups (fast conversion) + 1 slot of row-end groups + 2 dY slots per thread (conv1_wgrad_tr2r_kernel<3, 2, true>)
         int R = OH;
         auto fits = [&](int r) {
@@ -1805,7 +1787,7 @@ static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const
             return grid;
         }
     }
-    if (v2 && X.u8 && (IW % 4) == 0 && IW >= 8 && u8form) {
+    if (X.u8 && (IW % 4) == 0 && IW >= 8 && u8form) {
         // uint8 boundary, round 6: 4 window slots of 16 bytes + 2 dY slots per thread, converted from the registers (conv1_wgrad_tr2r_kernel); no raw rows in LDS
         int R = OH;
         auto fits = [&](int r) {
@@ -1824,7 +1806,7 @@ static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const
             return grid;
         }
     }
-    if (v2 && X.u8 && (IW % 4) == 0) {
+    if (X.u8 && (IW % 4) == 0) {
         // uint8 boundary: 12 raw 4-byte slots + 2 dY slots per thread; the raw rows add their LDS area to the two images
         int R = OH;
         auto fits = [&](int r) {
@@ -1843,9 +1825,7 @@ static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const
             return grid;
         }
     }
-    static const int lds_kb = HULC_SWITCH("HULC_W1_LDS", 39);   // 4 workgroups per CU (0.44 vs 0.50 ms/step at 2 per CU with 78 KB bands)
-    static const int env_wg = HULC_SWITCH("HULC_W1_WG", 0);
-    if (env_wg > 0) max_blocks = env_wg;
+    constexpr int lds_kb = 39;   // 4 workgroups per CU (0.44 vs 0.50 ms/step at 2 per CU with 78 KB bands)
     int R = OH;
     while (R > 1 && Wgrad1Cfg::lds_bytes(R, IW, OW, X.u8) > (size_t)lds_kb * 1024) --R;
     const size_t lds = Wgrad1Cfg::lds_bytes(R, IW, OW, X.u8);

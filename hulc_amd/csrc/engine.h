@@ -22,9 +22,6 @@
 namespace HULC_NS {
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-// HULC_DEBUG_SYNC=1: synchronise after every stage and trace its name to stderr (bring-up / fault localisation)
-static inline bool hulc_dbg() { static const bool v = HULC_SWITCH("HULC_DEBUG_SYNC", 0) != 0; return v; }
-#define STAGE(name) do { if (hulc_dbg()) { hipError_t e_ = hipStreamSynchronize(st); fprintf(stderr, "[hulc] stage %s -> %s\n", name, hipGetErrorString(e_)); fflush(stderr); } } while (0)
 #define HIP_CHECK_VOID(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { hulc_set_error("%s:%d %s", __FILE__, __LINE__, hipGetErrorString(e_)); } } while (0)
 
 template <typename T>
@@ -211,10 +208,9 @@ struct Engine : IEngine {
         const int H1 = (IH - 8) / 4 + 1, H2 = (H1 - 4) / 2 + 1, H3 = H2 - 2;
         std::string s(pre);
         a.a1 = alloc<T>((int64_t)maxN * H1 * H1 * 32, (s + "a1").c_str());
-        static const bool use_bits = HULC_SWITCH("HULC_MASKBITS", 1) != 0;
-        a.m1bits = (use_bits && std::is_same<T, h16_t>::value) ? alloc<unsigned>((int64_t)maxN * H1 * H1) : nullptr;   // ReLU bitmask of a1 (conv2 dgrad)
+        a.m1bits = std::is_same<T, h16_t>::value ? alloc<unsigned>((int64_t)maxN * H1 * H1) : nullptr;   // ReLU bitmask of a1 (conv2 dgrad)
         a.a2 = alloc<T>((int64_t)maxN * H2 * H2 * 64, (s + "a2").c_str());
-        a.m2bits = (use_bits && std::is_same<T, h16_t>::value) ? alloc<unsigned>((int64_t)maxN * H2 * H2 * 2) : nullptr;   // ReLU bitmask of a2 (conv3 dgrad), emitted by conv2's forward
+        a.m2bits = std::is_same<T, h16_t>::value ? alloc<unsigned>((int64_t)maxN * H2 * H2 * 2) : nullptr;   // ReLU bitmask of a2 (conv3 dgrad), emitted by conv2's forward
         a.a3 = alloc<T>((int64_t)maxN * H3 * H3 * 64, (s + "a3").c_str());
         a.ss = gripper ? nullptr : alloc<T>((int64_t)maxN * 128, (s + "ss").c_str());
         a.ssstats = gripper ? nullptr : alloc<float>((int64_t)maxN * 64 * 4);
@@ -327,7 +323,9 @@ struct Engine : IEngine {
         }
     }
     int frag_linked = 0;                    // weights whose fragment-ordered copies ride on their transpose descriptor (2 frag jobs each)
-    static bool frag_weights() { static const bool on = HULC_SWITCH("HULC_FRAG_W", 1) != 0; return on; }
+    // unfused attention: two lanes per query row in the 16-bit engines; the fp32 (parity) engine keeps the one-lane kernel's summation order: the hulc_visonly
+    // fixture has an FFN pre-activation within fp32 epsilon of zero, and an epsilon-level change upstream flips its ReLU (1e-3 gradient gate)
+    static constexpr bool att_wide = !std::is_same<T, float>::value;
     static constexpr int TRT = std::is_same<T, float>::value ? 32 : 64;     // transpose tile (bf16: 64x64, 16-byte accesses)
     void add_tr(const float* w32, const T* w, T* wt, int R, int C) {
         TrDesc d; d.src = std::is_same<T, float>::value ? (const void*)w32 : (const void*)w; d.dst = wt; d.lds = C; d.ldt = R; d.R = R; d.C = C;
@@ -405,7 +403,7 @@ struct Engine : IEngine {
                         const std::string bp = pr + "birnn_model.";
                         bind_lin(bw_ih[l][d], bp + "weight_ih" + sfx, (gru ? 3 : 1) * HID, l ? 2 * HID : EMB, false);
                         bind_lin(bw_hh[l][d], bp + "weight_hh" + sfx, (gru ? 3 : 1) * HID, HID, false);
-                        if (gru && frag_weights()) add_frag(bw_hh[l][d]);
+                        if (gru) add_frag(bw_hh[l][d]);
                         bb_ih[l][d] = pw(bp + "bias_ih" + sfx); bb_hh[l][d] = pw(bp + "bias_hh" + sfx);
                         dbb_ih[l][d] = gw(bp + "bias_ih" + sfx); dbb_hh[l][d] = gw(bp + "bias_hh" + sfx);
                     }
@@ -547,7 +545,7 @@ struct Engine : IEngine {
     // collected and issued as one grid; anything else that arrives in between flushes the queue first, so program order is kept.  The caller vouches for the
     // independence of what it brackets (no queued product reads another's output).
     GemmGroupP gq{}; bool gq_open = false; double gq_fl = 0, gq_by = 0;
-    void gemm_group_begin() { static const int sw = HULC_SWITCH("HULC_GEMM_GROUP", 1); gq_open = sw != 0 && gemm_group_mode; gq.n = 0; gq_fl = gq_by = 0; }
+    void gemm_group_begin() { gq_open = gemm_group_mode; gq.n = 0; gq_fl = gq_by = 0; }
     void gemm_group_flush() {
         if constexpr (std::is_same<T, h16_t>::value) {
             if (gq.n == 1) { TimerScope ts(this, "gemm_128x128", "mfma", gq_fl, gq_by); launch_gemm_glds(st, gq.a[0], gq.b[0], gq.om[0], gq.ep[0], gq.M[0], gq.N[0], gq.K[0]); }
@@ -557,7 +555,6 @@ struct Engine : IEngine {
     }
     void gemm_group_end() { gemm_group_flush(); gq_open = false; }
     void gemm(const DenseLoader<T>& a, const DenseLoader<T>& b, const DenseOut& om, const EpiP& ep, int M, int N, int K) {
-        static const bool trace = HULC_SWITCH("HULC_TRACE_GEMM", 0) != 0;
         if constexpr (std::is_same<T, h16_t>::value) {
             if (gq_open) {
                 const long long w128g = (long long)cdiv(M, 128) * cdiv(N, 128);
@@ -572,7 +569,6 @@ struct Engine : IEngine {
                 gemm_group_flush();
             }
         }
-        if (trace) fprintf(stderr, "[gemm] M=%d N=%d K=%d lda=%lld ldb=%lld f32out=%d acc=%d atomic=%d\n", M, N, K, a.s1, b.s1, ep.out_f32, ep.accumulate, ep.atomic);
         const double fl = 2.0 * M * N * K, by = ((double)M * K + (double)N * K + (double)M * N) * sizeof(T);
         if constexpr (std::is_same<T, h16_t>::value) {
             if (a.R1 == 0x7fffffff && b.R1 == 0x7fffffff && ep.z_stride == 0 && skinny_ok(M, N, K, a.s1, b.s1, a.p, b.p)) {
@@ -595,17 +591,11 @@ struct Engine : IEngine {
         }
         else {
             // small-N / short-K GEMMs (transformer, encoder heads) are bound by the exposed L2 latency of each k-step: a deeper BK means fewer of them
-            static const int small_bk = HULC_SWITCH("HULC_SMALL_BK", 128);     // A/B on one box: 4.764 (32) / 4.739 (64) / 4.728 ms per step (128)
             const bool t64 = w64 >= 128 || (M <= 64 && N <= 64);
             if constexpr (std::is_same<T, h16_t>::value) {
-                if (small_bk == 128 && K >= 128) {
+                if (K >= 128) {        // BK = 128 (the default 32 only for K < 128)
                     if (t64) launch_gemm<T, 64, 64, DenseLoader<T>, DenseLoader<T>, DenseOut, 128>(st, a, b, om, ep, M, N, K);
                     else launch_gemm<T, 32, 32, DenseLoader<T>, DenseLoader<T>, DenseOut, 128>(st, a, b, om, ep, M, N, K);
-                    return;
-                }
-                if (small_bk == 64 && K >= 64) {
-                    if (t64) launch_gemm<T, 64, 64, DenseLoader<T>, DenseLoader<T>, DenseOut, 64>(st, a, b, om, ep, M, N, K);
-                    else launch_gemm<T, 32, 32, DenseLoader<T>, DenseLoader<T>, DenseOut, 64>(st, a, b, om, ep, M, N, K);
                     return;
                 }
             }
@@ -645,16 +635,6 @@ struct Engine : IEngine {
                 return;
             }
             grad_ensure_zero(dW);      // the paths below accumulate
-            static const bool fused_largem = HULC_SWITCH("HULC_LINBWD_LARGEM", 0) != 0;   // measured 0.25 ms/step SLOWER than transposes + NT GEMM (A/B, same box): off
-            if (fused_largem && (long long)N * K <= 2048ll * 512) {
-                // token-major layers (M = B*S): the same kernel, rows split over blockIdx.z (~256 workgroups), partials by atomics
-                const int tiles = cdiv(N, 64) * cdiv(K, 128);
-                const int z = std::max(1, std::min(cdiv(M, 64), cdiv(256, tiles)));
-                const int mchunk = cdiv(cdiv(M, z), 64) * 64;
-                hipLaunchKernelGGL(lin_bwd_smallm_kernel, dim3(cdiv(N, 64), cdiv(K, 128), cdiv(M, mchunk)), dim3(256), 0, st, dY, (long long)N, X, ldx, M, N, K, dW, lddw,
-                                   db, db2, mchunk);
-                return;
-            }
         }
         const int mp = ldpad(M);
         constexpr bool fuse_cs = std::is_same<T, h16_t>::value;     // bf16 (bench) mode: the dY transpose also adds its column sums into db (atomics)
@@ -676,27 +656,20 @@ struct Engine : IEngine {
                 long long ldd, int acc, T* dxt, long long ldt, float* dg, float* db, float drop_p = 0.f, unsigned long long drop_seed = 0,
                 int bcast_rows = 0, float bcast_div = 1.f, int dy_parts = 1, long long dy_part_stride = 0) {
         if constexpr (std::is_same<T, h16_t>::value) {
-            static const bool fused = HULC_SWITCH("HULC_LN_FUSED", 1) != 0;
-            if (fused || bcast_rows > 0 || dy_parts > 1) {
-                const int rpb = rows >= 1024 ? 16 : 4;
-                hipLaunchKernelGGL((layernorm_bwd_fused_kernel<T>), dim3(cdiv(rows, rpb)), dim3(rpb == 16 ? 1024 : 256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt,
-                                   drop_p, drop_seed, rpb, dg, db, bcast_rows, bcast_div, dy_parts, dy_part_stride);
-                return;
-            }
+            const int rpb = rows >= 1024 ? 16 : 4;
+            hipLaunchKernelGGL((layernorm_bwd_fused_kernel<T>), dim3(cdiv(rows, rpb)), dim3(rpb == 16 ? 1024 : 256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt,
+                               drop_p, drop_seed, rpb, dg, db, bcast_rows, bcast_div, dy_parts, dy_part_stride);
+        } else {        // fp32 (parity) mode: unfused and deterministic
+            if ((drop_p > 0.f || drop_seed != 0) && dxt && dxf) {       // dx first, its copy through the dropout mask in a second launch
+                hipLaunchKernelGGL((layernorm_bwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, (T*)nullptr, 0);
+                hipLaunchKernelGGL((dropout_apply_kernel<T>), dim3(cdiv((long long)rows * n, 256)), dim3(256), 0, st, dxf, (float*)nullptr, dxt, (long long)rows * n, drop_p, drop_seed);
+            } else
+                hipLaunchKernelGGL((layernorm_bwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt);
+            const int nsplit = std::max(1, std::min(64, cdiv(rows, 64)));
+            hipLaunchKernelGGL(layernorm_param_grad_kernel, dim3(cdiv(n, 64), nsplit), dim3(256), 0, st, dy, lddy, x, ldx, stats, rows, n, cdiv(rows, nsplit), cspart, (float*)nullptr, (float*)nullptr);
+            hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, cspart, nsplit, n, dg, (float*)nullptr, 1.f);
+            hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, cspart + (long long)nsplit * n, nsplit, n, db, (float*)nullptr, 1.f);
         }
-        if ((drop_p > 0.f || drop_seed != 0) && dxt && dxf) {       // unfused: dx first, its 16-bit copy through the dropout mask in a second launch
-            hipLaunchKernelGGL((layernorm_bwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, (T*)nullptr, 0);
-            hipLaunchKernelGGL((dropout_apply_kernel<T>), dim3(cdiv((long long)rows * n, 256)), dim3(256), 0, st, dxf, (float*)nullptr, dxt, (long long)rows * n, drop_p, drop_seed);
-        } else
-        hipLaunchKernelGGL((layernorm_bwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt);
-        const int nsplit = std::max(1, std::min(64, cdiv(rows, 64)));
-        if constexpr (std::is_same<T, h16_t>::value) {
-            hipLaunchKernelGGL(layernorm_param_grad_kernel, dim3(cdiv(n, 64), nsplit), dim3(256), 0, st, dy, lddy, x, ldx, stats, rows, n, cdiv(rows, nsplit), cspart, dg, db);
-            return;
-        }
-        hipLaunchKernelGGL(layernorm_param_grad_kernel, dim3(cdiv(n, 64), nsplit), dim3(256), 0, st, dy, lddy, x, ldx, stats, rows, n, cdiv(rows, nsplit), cspart, (float*)nullptr, (float*)nullptr);
-        hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, cspart, nsplit, n, dg, (float*)nullptr, 1.f);
-        hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, cspart + (long long)nsplit * n, nsplit, n, db, (float*)nullptr, 1.f);
     }
 
     // ---------------------------------------------------------------- weight preparation
@@ -739,7 +712,6 @@ struct Engine : IEngine {
             // (the optimizer's tile pass wrote them when every frag job is linked to a tiled descriptor: frag_by_adam)
             if (fragbatch.n && !(was_fresh && frag_by_adam)) hipLaunchKernelGGL(frag_pack_kernel, dim3(frag_blocks), dim3(256), 0, st, fragbatch);
         }
-        STAGE("prepare_weights");
         if (hipGetLastError() != hipSuccess) { hulc_set_error("kernel launch failed in prepare_weights"); return 1; }
         return 0;
     }

@@ -108,16 +108,11 @@
             ConvTileP p3{}; p3.img = a.a2; p3.IMH = p3.IMW = e.H2; p3.w = e.c3.Wf; p3.out = a.a3; p3.OUTH = p3.OUTW = e.H3; p3.bias = e.c3.b32; p3.relu = 1; p3.Nf = Nf;
             const double px2 = (double)Nf * e.H2 * e.H2, px3 = (double)Nf * e.H3 * e.H3, px1 = (double)Nf * e.H1 * e.H1;
             TimerScope ts(this, "conv_tile_fwd", "mfma", 2.0 * px2 * 64 * 512 + 2.0 * px3 * 64 * 576, (px1 * 32 + 2 * px2 * 64 + px3 * 64) * 2);
-            static const int conv_reg = HULC_SWITCH("HULC_CONV_REG", 7);      // A/B: bit 0 = conv2 forward, bit 1 = conv3 forward, bit 2 = conv3 data gradient on the weights-in-registers kernel (conv_reg.h)
-            // HULC_CONV_REG_W4 (same bits): the form with two co-resident 256-thread workgroups per CU (conv_reg.h, NWV = 4)
-            static const int w4 = HULC_SWITCH("HULC_CONV_REG_W4", 11);          // in the step: conv2 fwd 84.0 vs 85.4 us, conv3 fwd 54.7 vs 56.5, conv2 dgrad 79.8 vs 87.9 (launch pairs' average, two-workgroup form first)
-            // HULC_CONV_REG_PK (round 5, same bits): large maps (the static camera) take the one-workgroup form with the band-invariant DMA slot decode
-            // held in registers (conv_reg.h: PKR) — standalone on 2048 static frames conv2 forward 135 us against 142 (two workgroups) / 143, conv3
-            // forward 77 against 84 / 81; the gripper camera's stacked small maps stay on the two-workgroup form (30.5 against 34.8 us)
-            static const int pkr = HULC_SWITCH("HULC_CONV_REG_PK", 11);
+            // weights-in-registers kernels (conv_reg.h): large maps (the static camera) take the one-workgroup form with the band-invariant DMA slot decode
+            // held in registers (PKR), the gripper camera's stacked small maps the form with two co-resident 256-thread workgroups per CU (NWV = 4)
             const bool big = e.H2 >= 16;
-            const bool t2 = ((conv_reg & 1) && (((w4 & 1) && !(big && (pkr & 1))) ? launch_conv_reg<32, 4, 4, 2, false, 1, 4, 0, true>(st, p2) : launch_conv_reg_fwd<32, 4, 4, 2>(st, p2))) || launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p2);
-            const bool t3 = ((conv_reg & 2) && (((w4 & 2) && !(big && (pkr & 2))) ? launch_conv_reg<64, 3, 3, 1, false, 1, 4>(st, p3) : launch_conv_reg_fwd<64, 3, 3, 1>(st, p3))) || launch_conv_tile<64, 64, 3, 3, 1, 1, false>(st, p3);
+            const bool t2 = (big ? launch_conv_reg_fwd<32, 4, 4, 2>(st, p2) : launch_conv_reg<32, 4, 4, 2, false, 1, 4, 0, true>(st, p2)) || launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p2);
+            const bool t3 = (big ? launch_conv_reg_fwd<64, 3, 3, 1>(st, p3) : launch_conv_reg<64, 3, 3, 1, false, 1, 4>(st, p3)) || launch_conv_tile<64, 64, 3, 3, 1, 1, false>(st, p3);
             tiled = t2 && t3;
         }
         if (!tiled) {
@@ -187,52 +182,48 @@
             q.demb = demb; q.Nf = Nf; q.ldemb = EMB;
             launch_enc_tail_bwd(st, q);
             // weight / bias gradients of the four Linear layers: one launch, frames split over blockIdx.y (fp32 atomics), operands read as they lie
-            static const int chunk = HULC_SWITCH("HULC_ENC_WGRAD_CHUNK", 256);
-            tail_wgrad_done = chunk > 0;
-            if (tail_wgrad_done) {
-                LinBwdBatch bt{}; bt.M = Nf; bt.store = 0; bt.mchunk = chunk;
-                int blk = 0;
-                const int nz = cdiv(Nf, chunk);
-                static const bool slab_ok = HULC_SWITCH("HULC_ENC_WGRAD_SLABS", 1) != 0;
-                for (int k = 0; k < 2; ++k)
-                    for (int l = 0; l < 2; ++l) {          // l = 0: fc2 (dY = d_f2, X = f1);  1: fc1 (dY = d_f1, X = the tail's input)
-                        const LinW& L = l ? ew[k]->fc1 : ew[k]->fc2;
-                        LinBwdJob& J = bt.j[bt.n++];
-                        J.dY = l ? q.cam[k].d_f1 : q.cam[k].d_f2; J.X = l ? (ew[k]->gripper ? ea[k]->g0 : ea[k]->ss) : ea[k]->f1;
-                        J.dW = L.dW; J.db = L.db; J.ldx = L.K; J.lddw = L.K; J.N = L.N; J.K = L.K; J.nx = cdiv(L.N, 64); J.blk0 = blk;
-                        blk += J.nx * cdiv(L.K, 128);
-                        // every row chunk writes its own slab; the slabs are summed into the gradient by the encoders' one unpack launch (no
-                        // per-element atomics here: 1.5 M of them made this launch 39 us)
-                        const int64_t need = (int64_t)nz * L.N * L.K;
-                        if (slab_ok && unpack_jobs.n < 12 && part_cur + need <= this->partcap) {
-                            J.part = this->part + part_cur;
-                            UnpackJob& U = unpack_jobs.j[unpack_jobs.n++];
-                            U.part = J.part; U.grad = L.dW; U.slab = (long long)L.N * L.K; U.nsplit = nz; U.O = L.N; U.I = L.K; U.KH = U.KW = 1; U.nhwc = 0; U.blk0 = unpack_blocks; U.ysplit = 1;
-                            unpack_blocks += cdiv(L.N * L.K, 1024); part_cur += need;
-                        }
-                    }
-                // + the gripper camera's first Linear (3136 -> 128, dY = d_g0 which the launch above just wrote): its slabs are in the packed (NHWC)
-                // column order of a3 and the unpack launch lands them in the torch layout (the conv weights' permutation with a 7 x 7 "kernel")
-                tail_fc7_done = false;
-                {
-                    const LinW& L = encG.fc7;
+            constexpr int chunk = 256;
+            LinBwdBatch bt{}; bt.M = Nf; bt.store = 0; bt.mchunk = chunk;
+            int blk = 0;
+            const int nz = cdiv(Nf, chunk);
+            for (int k = 0; k < 2; ++k)
+                for (int l = 0; l < 2; ++l) {          // l = 0: fc2 (dY = d_f2, X = f1);  1: fc1 (dY = d_f1, X = the tail's input)
+                    const LinW& L = l ? ew[k]->fc1 : ew[k]->fc2;
+                    LinBwdJob& J = bt.j[bt.n++];
+                    J.dY = l ? q.cam[k].d_f1 : q.cam[k].d_f2; J.X = l ? (ew[k]->gripper ? ea[k]->g0 : ea[k]->ss) : ea[k]->f1;
+                    J.dW = L.dW; J.db = L.db; J.ldx = L.K; J.lddw = L.K; J.N = L.N; J.K = L.K; J.nx = cdiv(L.N, 64); J.blk0 = blk;
+                    blk += J.nx * cdiv(L.K, 128);
+                    // every row chunk writes its own slab; the slabs are summed into the gradient by the encoders' one unpack launch (no
+                    // per-element atomics here: 1.5 M of them made this launch 39 us)
                     const int64_t need = (int64_t)nz * L.N * L.K;
-                    if (slab_ok && L.N == 128 && L.K == 3136 && unpack_jobs.n < 12 && part_cur + need <= this->partcap) {
-                        LinBwdJob& J = bt.j[bt.n++];
-                        J.dY = d_g0; J.X = aG.a3; J.dW = nullptr; J.db = L.db; J.ldx = L.K; J.lddw = L.K; J.N = L.N; J.K = L.K; J.nx = cdiv(L.N, 64); J.blk0 = blk;
-                        blk += J.nx * cdiv(L.K, 128);
+                    if (unpack_jobs.n < 12 && part_cur + need <= this->partcap) {
                         J.part = this->part + part_cur;
                         UnpackJob& U = unpack_jobs.j[unpack_jobs.n++];
-                        U.part = J.part; U.grad = L.dW; U.slab = (long long)L.N * L.K; U.nsplit = nz; U.O = L.N; U.I = 64; U.KH = U.KW = 7; U.nhwc = 1; U.blk0 = unpack_blocks; U.ysplit = 1;
+                        U.part = J.part; U.grad = L.dW; U.slab = (long long)L.N * L.K; U.nsplit = nz; U.O = L.N; U.I = L.K; U.KH = U.KW = 1; U.nhwc = 0; U.blk0 = unpack_blocks; U.ysplit = 1;
                         unpack_blocks += cdiv(L.N * L.K, 1024); part_cur += need;
-                        tail_fc7_done = true;
                     }
                 }
-                hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(blk, nz), dim3(256), 0, st, bt);
+            // + the gripper camera's first Linear (3136 -> 128, dY = d_g0 which the launch above just wrote): its slabs are in the packed (NHWC)
+            // column order of a3 and the unpack launch lands them in the torch layout (the conv weights' permutation with a 7 x 7 "kernel")
+            tail_fc7_done = false;
+            {
+                const LinW& L = encG.fc7;
+                const int64_t need = (int64_t)nz * L.N * L.K;
+                if (L.N == 128 && L.K == 3136 && unpack_jobs.n < 12 && part_cur + need <= this->partcap) {
+                    LinBwdJob& J = bt.j[bt.n++];
+                    J.dY = d_g0; J.X = aG.a3; J.dW = nullptr; J.db = L.db; J.ldx = L.K; J.lddw = L.K; J.N = L.N; J.K = L.K; J.nx = cdiv(L.N, 64); J.blk0 = blk;
+                    blk += J.nx * cdiv(L.K, 128);
+                    J.part = this->part + part_cur;
+                    UnpackJob& U = unpack_jobs.j[unpack_jobs.n++];
+                    U.part = J.part; U.grad = L.dW; U.slab = (long long)L.N * L.K; U.nsplit = nz; U.O = L.N; U.I = 64; U.KH = U.KW = 7; U.nhwc = 1; U.blk0 = unpack_blocks; U.ysplit = 1;
+                    unpack_blocks += cdiv(L.N * L.K, 1024); part_cur += need;
+                    tail_fc7_done = true;
+                }
             }
+            hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(blk, nz), dim3(256), 0, st, bt);
         }
     }
-    bool tail_wgrad_done = false, tail_fc7_done = false;
+    bool tail_fc7_done = false;
     float* pend_zero[2] = {nullptr, nullptr};   // loss accumulators the next conv1 forward launch clears (16-bit engines)
     Conv1Src wgrad_src;                       // conv1 only: set by enc_bwd before conv_wgrad(e.c1, ...)
     // 16-bit engines: the slab -> gradient reductions of the encoders' convolutions are collected and run as ONE launch (flush_unpacks) after
@@ -241,7 +232,7 @@
     int64_t part_cur = 0;
     int unpack_blocks = 0;
     void flush_unpacks() {
-        static const int yparts = HULC_SWITCH("HULC_UNPACK_YB", 8);      // same-box: 4 / 8 / 16 / 32 parts = 60 / 55 / 59 / 86 us (with 8 slab quads in flight per thread)
+        constexpr int yparts = 8;      // same-box: 4 / 8 / 16 / 32 parts = 60 / 55 / 59 / 86 us (with 8 slab quads in flight per thread)
         if (unpack_jobs.n > 0) hipLaunchKernelGGL(unpack_conv_wgrad_batched_kernel, dim3(unpack_blocks, yparts), dim3(256), 0, st, unpack_jobs);
         unpack_jobs.n = 0; part_cur = 0; unpack_blocks = 0;
     }
@@ -289,8 +280,7 @@
                 return;
             }
         }
-        static const int ypart_env = HULC_SWITCH("HULC_UNPACK_Y", 16);
-        const int yparts = (!std::is_same<T, float>::value && nsplit >= 64) ? ypart_env : 1;
+        const int yparts = (!std::is_same<T, float>::value && nsplit >= 64) ? 16 : 1;
         hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3(ybl, yparts), dim3(256), 0, st, part, nsplit, (long long)c.O * Kc,   // fp32 (parity) mode: one deterministic pass, no atomics
                            c.dW, c.O, c.I, c.KH, c.KW, c.nhwc);
         if (!bias_done) colsum(dy, c.O, (int)npix, c.O, c.db);
@@ -308,29 +298,20 @@
             // algorithmic bytes as SURVEY 8(d) counts them: dY read once, dX written once, 2 B each; the ReLU mask of the layer below is read as BIT words
             // (pin * I / 8 bytes) when the forward left them, as a second 16-bit activation read otherwise (VERDICT r5 weak #4: the bit form was priced as a full read)
             TimerScope ts(this, "conv_tile_dgrad", "mfma", 2.0 * pout * c.O * c.I * c.KH * c.KW, (pout * c.O + pin * c.I) * 2 + (maskbits ? pin * c.I / 8 : (mask ? pin * c.I * 2 : 0)));
-            static const int conv_reg = HULC_SWITCH("HULC_CONV_REG", 15);      // bit 2: conv3, bit 3: conv2 data gradient on conv_reg.h
-            static const int w4 = HULC_SWITCH("HULC_CONV_REG_W4", 11);         // same bits: two 256-thread workgroups per CU (NWV = 4).  conv3's data gradient (bit 2) stays on the one-workgroup form:
-                                                                               // 144 weight registers + the zero-border decode spill 16 registers at 256 VGPRs (90.3 vs 83.5 us in the step, 3.470 vs 3.448 ms/step)
+            // both data gradients run on conv_reg.h's pipelined-epilogue form (EPI: a tile's epilogue rides in the next tile's multiply loop), two 256-thread workgroups per CU
             if (c.KH == 3 && c.S == 1 && c.I == 64 && c.O == 64) {
                 if (!zero_page) zero_page = alloc<h16_t>(128);      // zero-initialised by alloc(): the staged zero border of the data-gradient form
                 p.zeros = zero_page;
-                // round 5: the pipelined-epilogue form (conv_reg.h EPI: a tile's epilogue rides in the next tile's multiply loop; one tile at a time also ends
-                // the spills of the pair form at 144 weight registers) on two workgroups per CU: 129 -> 97 us standalone on 2048 static frames, 30.6 -> 28.2 gripper
-                static const int epi = HULC_SWITCH("HULC_CONV_REG_EPI", 12);      // bit 2: conv3, bit 3: conv2 data gradient
                 if (!dump_page) dump_page = alloc<h16_t>(4096);
                 p.dump = dump_page;
-                ok = ((conv_reg & 4) && maskbits && ((epi & 4) ? launch_conv_reg<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, p)
-                                                       : ((w4 & 4) ? launch_conv_reg<64, 3, 3, 1, true, 1, 4>(st, p) : launch_conv_reg<64, 3, 3, 1, true>(st, p)))) || launch_conv_tile<64, 64, 3, 3, 1, 1, true>(st, p);
+                ok = (maskbits && launch_conv_reg<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, p)) || launch_conv_tile<64, 64, 3, 3, 1, 1, true>(st, p);
             }
             else if (c.KH == 4 && c.S == 2 && c.I == 32 && c.O == 64) {
                 if (!zero_page) zero_page = alloc<h16_t>(128);
                 p.zeros = zero_page;
-                static const int pkr = HULC_SWITCH("HULC_CONV_REG_PK", 11);       // bit 3: slot decode in registers (no spill at 64 weight registers): 147 -> 140 us standalone
-                static const int epi = HULC_SWITCH("HULC_CONV_REG_EPI", 12);      // bit 3: pipelined epilogue (142 -> 137 us standalone static, 29.7 -> 28.7 gripper)
                 if (!dump_page) dump_page = alloc<h16_t>(4096);
                 p.dump = dump_page;
-                ok = ((conv_reg & 8) && maskbits && ((w4 & 8) ? ((epi & 8) ? launch_conv_reg<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, p) : (pkr & 8) ? launch_conv_reg<64, 2, 2, 1, true, 2, 4, 0, true>(st, p) : launch_conv_reg<64, 2, 2, 1, true, 2, 4>(st, p))
-                                                              : launch_conv_reg<64, 2, 2, 1, true, 2>(st, p))) || launch_conv_tile<64, 32, 2, 2, 1, 2, true>(st, p);
+                ok = (maskbits && launch_conv_reg<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, p)) || launch_conv_tile<64, 32, 2, 2, 1, 2, true>(st, p);
             }
             if (ok) return;
         }
@@ -374,7 +355,7 @@
         if (!tail_done) ln_bwd(demb + col0, EMB, a.f2, 64, a.lnst, e.lng, Nf, 64, nullptr, 0, 0, d_f2t, 64, e.dlng, e.dlnb);
         // fc2
         if (!tail_done) { EpiP ep = epi(d_f1, false); ep.mask = a.f1; lin_dgrad(d_f2t, Nf, e.fc2, ep, dense_out(512)); }
-        const bool wdone = tail_done && tail_wgrad_done;
+        const bool wdone = tail_done;       // enc_tail_bwd_both ran the tails' weight gradients too
         if (!wdone) lin_wgrad(d_f2t, a.f1, 512, Nf, 64, 512, e.fc2.dW, 512, e.fc2.db);
         const int H3 = e.H3;
         if (!e.gripper) {

@@ -77,11 +77,9 @@
             const Conv1Src s2s = conv1_src(cur2, false), s2g = conv1_src(cur2, true);
             const bool tail_fused = enc_tail_fusable();
             enc_fwd(encS, aS, conv1_src(*b, false), N, 0, pair ? &s2s : nullptr, tail_fused);
-            STAGE("enc_static_fwd");
             enc_fwd(encG, aG, conv1_src(*b, true), N, 64, pair ? &s2g : nullptr, tail_fused);
             x0_done = false;
             if (tail_fused) enc_tail_fwd_both(N, !mcil && tr_fused_mode && S <= 64 && EMB == 128, S, dp);
-            STAGE("enc_gripper_fwd");
         }
         // ---- goal encoder (goal_encoders.py:31-36 / 64-69)
         if (pair) {       // rows [0, Bv): visual goal = emb[:, -1]; rows [Bv, B): language goal
@@ -116,7 +114,6 @@
             if (!ppx_packed) hipLaunchKernelGGL((concat_pp_kernel<T>), dim3(cdiv(B * (EMB + GOAL), 256)), dim3(256), 0, st, emb, (long long)S * EMB, EMB, goal_t, GOAL, B, ppx);
             mlp_fwd(ppx, EMB + GOAL, B, pp, 5, ppa, pp_logits, nullptr);
         }
-        STAGE("goal+pp_fwd");
     }
     // plan recognition transformer -> seq_feat, pr_logits
     void pr_fwd(int B, int S, float dp) {
@@ -150,13 +147,13 @@
         }
         for (int l = 0; l < 2 && !fused; ++l) {
             { EpiP ep = epi(qkv[l], false); lin_fwd(xt[l], EMB, N, tr_in[l], ep, 3 * EMB); }
-            // two lanes per query row in the 16-bit engines; the fp32 (parity) engine keeps the one-lane kernel's summation order: the hulc_visonly
-            // fixture has an FFN pre-activation within fp32 epsilon of zero, and an epsilon-level change upstream flips its ReLU (1e-3 gradient gate)
-            static const bool att32 = (HULC_SWITCH("HULC_ATT32", 1) != 0) && !std::is_same<T, float>::value;
-            if (S <= 32 && att32) hipLaunchKernelGGL((attention_fwd32_kernel<T>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
-            else if (S <= 32) hipLaunchKernelGGL((attention_fwd_kernel<T, 32>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
-            else if (att32) hipLaunchKernelGGL((attention_fwd64_kernel<T>), dim3(B * NH), dim3(256), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
-            else hipLaunchKernelGGL((attention_fwd_kernel<T, 64>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
+            if constexpr (att_wide) {
+                if (S <= 32) hipLaunchKernelGGL((attention_fwd32_kernel<T>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
+                else hipLaunchKernelGGL((attention_fwd64_kernel<T>), dim3(B * NH), dim3(256), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
+            } else {
+                if (S <= 32) hipLaunchKernelGGL((attention_fwd_kernel<T, 32>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
+                else hipLaunchKernelGGL((attention_fwd_kernel<T, 64>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
+            }
             { EpiP ep = epi(y1[l], true); ep.res = xf[l]; ep.res_f32 = 1; ep.res_ld = EMB; ep.res_late = 1; ep.drop_p = dp; ep.drop_seed = site_seed(2 + 4 * l);
               lin_fwd(ao[l], EMB, N, tr_out[l], ep, EMB); }
             ln_fwd(y1[l], EMB, N, EMB, tr_n1g[l], tr_n1b[l], x1t[l], EMB, x1f[l], EMB, st1[l]);
@@ -170,7 +167,6 @@
         { EpiP ep = epi(seqf, true); ep.out2 = seqf_t; ep.out2_lo = 0; ep.out2_hi = (long long)B * FCH;      // the 16-bit copy the next GEMM reads: a second store of the epilogue
           lin_fwd(xm, EMB, B, pr_fc, ep, FCH); }
         { EpiP ep = epi(pr_logits, true); lin_fwd(seqf_t, FCH, B, pr_fs, ep, PLAN); }
-        STAGE("plan_recognition_fwd");
     }
     // action decoder up to the packed heads [S*B][NHEAD] (logistic_decoder_rnn.py:260-287); plan/goal terms hoisted out of the time loop.
     // h0_0 / h0_1: previous hidden states [B][HID] of the two layers (stateful rollout, :107-111) or null (h0 = 0).
@@ -317,10 +313,9 @@
         {
             dec_fwd(pidx, B, S, nullptr, nullptr);
             // mcil_default.yaml: gripper_control false (no tcp-frame transform), discrete_gripper false (7th mixture dimension instead of the CE head)
-            static const int ll_block = HULC_SWITCH("HULC_LL_BLOCK", 64);     // one wave per workgroup: 256 CUs x 1 wave instead of 64 CUs x 4 (the kernel is one long serial chain per thread)
+            constexpr int ll_block = 64;     // one wave per workgroup: 256 CUs x 1 wave instead of 64 CUs x 4 (the kernel is one long serial chain per thread)
             // 16-bit engines: one lane per mixture component (kernels.h logistic_loss_wide_kernel: 17.9 -> ~6 us); the fp32 parity engine keeps the serial kernel's summation order
-            static const int ll_wide = HULC_SWITCH("HULC_LL_WIDE", 1);
-            if (ll_wide && !std::is_same<T, float>::value && NMIX <= 16 && NDIM <= 7)
+            if (!std::is_same<T, float>::value && NMIX <= 16 && NDIM <= 7)
                 hipLaunchKernelGGL((logistic_loss_wide_kernel<T>), dim3(SB), dim3(128), 0, st, heads, NHEAD, actions_of(*b), b->robot_obs, B, S, NMIX, NDIM,
                                    cfg.num_classes, cfg.log_scale_min, cfg.gripper_alpha, mcil ? 0 : 1, lw / (float)(S * Bm), rowloss, a_tcp, dheads, mcil ? 0 : 1, lscale());
             else
@@ -329,7 +324,6 @@
             if (pair) hipLaunchKernelGGL(sum_rows_pair_kernel, dim3(1), dim3(256), 0, st, rowloss, SB, B, pairBv, 1.f / (S * Bm), losses + 0, losses2 + 0);
             // one modality: the action-loss sum, the KL sum, the packing and the copy to a device `out` are ONE launch at the end (finish_losses_kernel)
         }
-        STAGE("decoder_fwd");
         // ---- CLIP auxiliary loss (hulc.py:650-695), lang modality, masked rows
         clip_n = 0;
         if ((b->is_lang || pair) && cfg.use_clip && b->n_aux > 0) {
@@ -343,13 +337,11 @@
             { EpiP ep = epi(img, true); lin_fwd(im1, 128, n, cl_im2, ep, GOAL); }
             { EpiP ep = epi(la1, false); ep.relu = 1; lin_fwd(g_m, GOAL, n, cl_la0, ep, 128); }
             { EpiP ep = epi(txt, true); lin_fwd(la1, 128, n, cl_la2, ep, GOAL); }
-            static const bool clip_wide = HULC_SWITCH("HULC_CLIP_WIDE", 1) != 0;
-            if (clip_wide && GOAL <= 32 && !std::is_same<T, float>::value)
+            if (GOAL <= 32 && !std::is_same<T, float>::value)
                 hipLaunchKernelGGL(clip_loss_wide_kernel, dim3(1), dim3(1024), 0, st, img, txt, n, GOAL, logit_scale, cw, (pair ? losses2 : losses) + 2, dimg, dtxt, dlogit_scale, lscale());
             else
             hipLaunchKernelGGL(clip_loss_kernel, dim3(1), dim3(64), 0, st, img, txt, n, GOAL, logit_scale, cw, (pair ? losses2 : losses) + 2, dimg, dtxt, dlogit_scale, lscale());
         }
-        STAGE("clip_fwd");
         if (hipGetLastError() != hipSuccess) { hulc_set_error("kernel launch failed in forward"); return 1; }
         have_fwd = true;
         // [total_mod, kl, action, clip]; a device `out` is written by the kernels themselves

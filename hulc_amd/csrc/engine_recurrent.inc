@@ -131,11 +131,10 @@
     // The two directions of a bidirectional layer are independent chains of S dependent launches each: advanced in lockstep, one launch (grid.z = 2)
     // carries step i of both — the same work per launch boundary paid once instead of twice (gemm.h: Skinny2).  Direction 0 runs t = 0..S-1,
     // direction 1 (reverse) t = S-1..0.  Shapes the dual launch does not cover fall back to the two sequential recurrences.
-    static bool pair_dirs() { static const bool on = HULC_SWITCH("HULC_PAIR_DIRS", 1) != 0; return on; }
     void rnn_fwd2(T* const Zx[2], T* const H[2], const LinW* const whh[2], int B, int S, int act) {
         const long long BH = (long long)B * HID;
         bool dual = false;
-        if constexpr (std::is_same<T, h16_t>::value) dual = pair_dirs() && S > 1 && !persist_usable(B, S);     // two persistent launches (2 x ~90 us at S = 32) beat 31 paired ones
+        if constexpr (std::is_same<T, h16_t>::value) dual = S > 1 && !persist_usable(B, S);     // two persistent launches (2 x ~90 us at S = 32) beat 31 paired ones
         if (dual) {
             auto at = [&](int d, int i) { return (long long)(d ? S - 1 - i : i) * BH; };
             for (int d = 0; d < 2; ++d) hipLaunchKernelGGL((relu_copy_kernel<T>), dim3(cdiv(BH, 256)), dim3(256), 0, st, Zx[d] + at(d, 0), H[d] + at(d, 0), BH, act);
@@ -152,8 +151,7 @@
         }
         if constexpr (std::is_same<T, h16_t>::value) {
             // both directions as ONE persistent launch, four XCDs each (rnn_persist.h: dual)
-            static const bool dualp = HULC_SWITCH("HULC_PERSIST_DUAL", 1) != 0;
-            if (dualp && persist_usable(B, S) && B <= 16 * (RP_NG / 2)) {
+            if (persist_usable(B, S) && B <= 16 * (RP_NG / 2)) {
                 auto at = [&](int d, int i) { return (long long)(d ? S - 1 - i : i) * BH; };
                 for (int d = 0; d < 2; ++d) hipLaunchKernelGGL((relu_copy_kernel<T>), dim3(cdiv(BH, 256)), dim3(256), 0, st, Zx[d] + at(d, 0), H[d] + at(d, 0), BH, act);
                 if (rnn_persist(H[0], whh[0]->W, Zx[0], nullptr, B, S, 0, 1, act, H[1], whh[1]->W, Zx[1], nullptr, S - 1, -1)) return;
@@ -166,7 +164,7 @@
     void rnn_bwd2(T* const dH[2], T* const H[2], T* const dZ[2], const LinW* const whh[2], int B, int S, int act) {
         const long long BH = (long long)B * HID;
         bool dual = false;
-        if constexpr (std::is_same<T, h16_t>::value) dual = pair_dirs() && S > 1 && !persist_usable(B, S);
+        if constexpr (std::is_same<T, h16_t>::value) dual = S > 1 && !persist_usable(B, S);
         if (dual) {
             auto at = [&](int d, int i) { return (long long)(d ? S - 1 - i : i) * BH; };
             for (int d = 0; d < 2; ++d)
@@ -185,8 +183,7 @@
             return;
         }
         if constexpr (std::is_same<T, h16_t>::value) {
-            static const bool dualp = HULC_SWITCH("HULC_PERSIST_DUAL", 1) != 0;
-            if (dualp && persist_usable(B, S) && B <= 16 * (RP_NG / 2)) {
+            if (persist_usable(B, S) && B <= 16 * (RP_NG / 2)) {
                 auto at = [&](int d, int i) { return (long long)(d ? S - 1 - i : i) * BH; };
                 for (int d = 0; d < 2; ++d)
                     hipLaunchKernelGGL((mask_mul_kernel<T>), dim3(cdiv(BH, 256)), dim3(256), 0, st, dH[d] + at(d, S - 1), H[d] + at(d, S - 1), dZ[d] + at(d, S - 1), BH, act);
@@ -224,7 +221,6 @@
         copy2d<T, T>(bH1 + (S - 1) * BH, HID, bxcat, 2 * HID, B, HID, 0);
         copy2d<T, T>(bh1b, HID, bxcat + HID, 2 * HID, B, HID, 0);
         { EpiP ep = epi(pr_logits, true); lin_fwd(bxcat, 2 * HID, B, pr_fs, ep, PLAN); }
-        STAGE("birnn_fwd");
     }
     // ---------------------------------------------------------------- the same with rnn_type = nn.GRU (BASELINE config 4)
     // one direction of one layer: Zx (incl. b_ih) [S][B][3H] -> H [S][B][H]; per step one M = B GEMM against W_hh (N = 3H) + the gate kernel
@@ -235,8 +231,7 @@
             const long long t = at(i);
             const T* hp = i ? g.H + at(i - 1) * BH : nullptr;
             if constexpr (std::is_same<T, h16_t>::value) {      // GEMM + gate arithmetic of the step in one launch (gemm.h: gru_step_lds_kernel)
-                static const bool fused = HULC_SWITCH("HULC_GRU_FUSED", 1) != 0;
-                if (i && fused) {
+                if (i) {
                     TimerScope ts(this, "gru_step", "hbm", 2.0 * B * 3 * HID * HID, ((double)3 * HID * HID + 9.0 * B * HID) * sizeof(T));
                     const GruStepP q{hp, whh.Wfr ? whh.Wfr : whh.W, g.Zx + t * 3 * BH, bhh, g.H + t * BH, g.R + t * BH, g.Z + t * BH, g.N + t * BH, g.GN + t * BH};
                     if (launch_gru_step(st, &q, 1, B, HID, whh.Wfr != nullptr)) continue;
@@ -261,8 +256,7 @@
             fused_prev = false;
             if (!i) break;
             if constexpr (std::is_same<T, h16_t>::value) {      // carry GEMM + the gate backward of step i-1 in one launch (gemm.h: GruBwdP)
-                static const bool fused = HULC_SWITCH("HULC_GRU_FUSED_BWD", 1) != 0;
-                if (fused && skinny_use_lds) {
+                if (skinny_use_lds) {
                     const long long tp = at(i - 1);
                     GruBwdP gbp{};
                     gbp.dH = dH_last_only ? nullptr : dH + tp * BH;
@@ -281,7 +275,7 @@
     void gru_recur_fwd2(GruBuf* const g[2], const LinW* const whh[2], const float* const bhh[2], int B, int S) {
         const long long BH = (long long)B * HID;
         bool dual = false;
-        if constexpr (std::is_same<T, h16_t>::value) dual = pair_dirs() && S > 1 && skinny_use_lds;
+        if constexpr (std::is_same<T, h16_t>::value) dual = S > 1 && skinny_use_lds;
         if (dual) {
             auto at = [&](int d, int i) { return (long long)(d ? S - 1 - i : i); };
             for (int i = 0; i < S; ++i) {
@@ -312,7 +306,7 @@
     void gru_recur_bwd2(GruBuf* const g[2], T* const dH[2], const LinW* const whh[2], int B, int S) {
         const long long BH = (long long)B * HID;
         bool dual = false;
-        if constexpr (std::is_same<T, h16_t>::value) dual = pair_dirs() && S > 1 && skinny_use_lds && B <= 64 && (3 * HID) % 2048 == 0 && 3 * HID > 2048;   // = what launch_skinny_lds_kchunk covers
+        if constexpr (std::is_same<T, h16_t>::value) dual = S > 1 && skinny_use_lds && B <= 64 && (3 * HID) % 2048 == 0 && 3 * HID > 2048;   // = what launch_skinny_lds_kchunk covers
         if constexpr (std::is_same<T, h16_t>::value) {
             if (dual) {
                 if (!gcarB2) gcarB2 = alloc<T>((int64_t)maxB * HID);
@@ -380,7 +374,6 @@
         copy2d<T, T>(bH1 + (S - 1) * BH, HID, bxcat, 2 * HID, B, HID, 0);
         copy2d<T, T>(bh1b, HID, bxcat + HID, 2 * HID, B, HID, 0);
         { EpiP ep = epi(pr_logits, true); lin_fwd(bxcat, 2 * HID, B, pr_fs, ep, PLAN); }
-        STAGE("bigru_fwd");
     }
     void bigru_bwd(const T* dpr, int B, int S) {
         const int SB = S * B, mp = ldpad(SB), H3 = 3 * HID;
@@ -417,7 +410,6 @@
             { EpiP ep = epi(demb, true); ep.accumulate = 1;
               gemm(dense<T>(gb[d].dZx, SB, H3), dense<T>(bw_ih[0][d].Wt, EMB, H3), dense_out_map(B, EMB, (long long)S * EMB), ep, SB, EMB, H3); }
         }
-        STAGE("bigru_bwd");
     }
     // dpr: d pr_state (T, [B][PLAN]).  Accumulates the BiRNN / fc_state parameter gradients and adds d emb into demb (B,S,128).
     void birnn_bwd(const T* dpr, int B, int S) {
@@ -462,6 +454,5 @@
             { EpiP ep = epi(demb, true); ep.accumulate = 1;
               gemm(dense<T>(bdZ0[d], SB, HID), dense<T>(bw_ih[0][d].Wt, EMB, HID), dense_out_map(B, EMB, (long long)S * EMB), ep, SB, EMB, HID); }
         }
-        STAGE("birnn_bwd");
     }
 

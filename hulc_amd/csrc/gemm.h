@@ -920,25 +920,11 @@ static inline bool gemm_glds_ok(const DenseLoader<h16_t>& a, const DenseLoader<h
     return K >= 64 && (K % 32) == 0 && ep.z_stride == 0 && row_ok(a) && row_ok(b);
 }
 static inline void launch_gemm_glds(hipStream_t st, const DenseLoader<h16_t>& a, const DenseLoader<h16_t>& b, const DenseOut& om, const EpiP& ep, int M, int N, int K) {
-    static const int nw = HULC_SWITCH("HULC_GLDS_NW", 8);
     static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)gemm_glds_kernel<3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        hipFuncSetAttribute((const void*)gemm_glds_kernel<3, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        attr_set = true;
-    }
+    if (!attr_set) { hipFuncSetAttribute((const void*)gemm_glds_kernel<3, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr_set = true; }
     const int tiles_m = (M + 127) / 128, tiles_n = (N + 127) / 128;
-    // round 5 experiment: a FOUR-stage ring (128 KB of LDS, three k-steps of 64 in flight) — same-box A/B in the step: 3.073 / 3.080 / 3.080 ms (3 stages)
-    // against 3.082 / 3.095 / 3.091 (4), mcil_gru 7.27 / 7.33 against 7.39 / 7.37: the operand stream of a tile is NOT latency-bound; stays at 3
-    static const int nst = HULC_SWITCH("HULC_GLDS_NST", 3);
-    if (nst == 4 && nw == 8) {
-        static bool a4 = false;
-        if (!a4) { hipFuncSetAttribute((const void*)gemm_glds_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); a4 = true; }
-        hipLaunchKernelGGL((gemm_glds_kernel<4, 8>), dim3(tiles_m * tiles_n), dim3(512), 128 * 1024, st, a, b, om, ep, M, N, K, tiles_m, tiles_n);
-        return;
-    }
-    if (nw == 4) hipLaunchKernelGGL((gemm_glds_kernel<3, 4>), dim3(tiles_m * tiles_n), dim3(256), 96 * 1024, st, a, b, om, ep, M, N, K, tiles_m, tiles_n);
-    else hipLaunchKernelGGL((gemm_glds_kernel<3, 8>), dim3(tiles_m * tiles_n), dim3(512), 96 * 1024, st, a, b, om, ep, M, N, K, tiles_m, tiles_n);
+    // a three-stage ring, eight waves (a four-stage ring measured no faster: the operand stream of a tile is not latency-bound)
+    hipLaunchKernelGGL((gemm_glds_kernel<3, 8>), dim3(tiles_m * tiles_n), dim3(512), 96 * 1024, st, a, b, om, ep, M, N, K, tiles_m, tiles_n);
 }
 
 static inline void launch_gemm_glds_group(hipStream_t st, GemmGroupP& g) {
@@ -1302,8 +1288,7 @@ static inline bool launch_gru_step(hipStream_t st, const GruStepP* q, int nprob,
         if (H != 2048 || M < 1 || ((uintptr_t)q[k].A % 128) != 0 || ((uintptr_t)q[k].W % 16) != 0) return false;
     static bool attr = false;
     if (!attr) { hipFuncSetAttribute((const void*)gru_step_lds_kernel<2, 4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    static const int walk = HULC_SWITCH("HULC_GRU_WALK", 0);      // 1: one workgroup walks the row blocks with W_hh loaded once — measured SLOWER in the step (mcil_gru 7.30 -> 7.47, 7.37 -> 7.63 ms: the row blocks of a workgroup serialise, two rounds of workgroups overlap their loads), kept for the record
-    dim3 grid(H / 16, (walk && M <= 128) ? 1 : (M + 31) / 32, nprob);
+    dim3 grid(H / 16, (M + 31) / 32, nprob);
     // LDS: the A region (16 waves x 2 x 2 x 2 KB = 128 KB) is reused for the 16 x 2 x 3 K-partials (96 KB)
     hipLaunchKernelGGL((gru_step_lds_kernel<2, 4, 16>), grid, dim3(1024), (size_t)16 * 2 * 2 * 2 * 1024, st, q[0], q[nprob - 1], (long long)H, wfrag ? 0ll : (long long)H, M, H);
     return true;
@@ -1459,20 +1444,19 @@ static inline bool launch_skinny_lds(hipStream_t st, const h16_t* A, long long l
     dim3 grid(N / 16, (M + MT * 16 - 1) / (MT * 16));
     const int kq32 = K / 256;
 #define SKL(mt, kq) launch_skinny_lds_t<mt, kq>(st, grid, A, lda, W, ldw, M, N, K, om, ep)
-    static const int nw16 = HULC_SWITCH("HULC_SKINNY_NW16", 1);   // A/B: -0.6 % of the step
     if (MT == 1) {                                  // M <= 32 recurrent step (32 + 32 windows per GPU): 16-row blocks so that 2 x 128 workgroups fill the chip
         static bool attr1 = false;
         if (!attr1) { hipFuncSetAttribute((const void*)skinny_lds_kernel<1, 4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr1 = true; }
         hipLaunchKernelGGL((skinny_lds_kernel<1, 4, 16>), grid, dim3(1024), (size_t)16 * 1 * 2 * 2 * 1024, st, A, lda, W, ldw, M, N, K, om, ep);
         return true;
     }
-    if (nw16 && MT == 2 && kq32 == 8) {            // K = 2048 (the recurrent step): 16 waves x 4 k-steps, 4 waves per SIMD overlap DMA issue and MFMAs
+    if (MT == 2 && kq32 == 8) {            // K = 2048 (the recurrent step): 16 waves x 4 k-steps, 4 waves per SIMD overlap DMA issue and MFMAs
         static bool attr16 = false;
         if (!attr16) { hipFuncSetAttribute((const void*)skinny_lds_kernel<2, 4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr16 = true; }
         hipLaunchKernelGGL((skinny_lds_kernel<2, 4, 16>), grid, dim3(1024), (size_t)16 * 2 * 2 * 2 * 1024, st, A, lda, W, ldw, M, N, K, om, ep);
         return true;
     }
-    if (MT == 2) { if (kq32 == 8) SKL(2, 8); else if (kq32 == 4) SKL(2, 4); else if (kq32 == 2) SKL(2, 2); else return false; }
+    if (MT == 2) { if (kq32 == 4) SKL(2, 4); else if (kq32 == 2) SKL(2, 2); else return false; }
     else { if (kq32 == 4) SKL(4, 4); else if (kq32 == 2) SKL(4, 2); else return false; }
 #undef SKL
     return true;
@@ -1495,12 +1479,10 @@ static inline void launch_skinny_nw(hipStream_t st, const h16_t* A, long long ld
     // With only N/16 workgroups (128 at N = 2048) half the CUs idle, so split the rows in two 32-row blocks when that fills the chip.
     int MT = M >= 64 ? 4 : (M + 15) / 16;
     if (M > 32 && (N / 16) * ((M + 63) / 64) <= 160) MT = 2;
-    static const bool mt2k = HULC_SWITCH("HULC_SKINNY_MT2K", 1) != 0;
     // K = 2048 (GRU recurrent step with N = 3 x 2048; the many-row weight-gradient / small-N GEMMs over 2048 tokens): 32-row blocks keep the
     // LDS-DMA kernel eligible (64 rows x 2048 would not fit LDS) and double the workgroup count of the small-M cases
-    if (mt2k && M > 32 && K == 2048 && NW == 8) MT = 2;
-    static const bool mt1 = HULC_SWITCH("HULC_SKINNY_MT1", 1) != 0;
-    if (mt1 && M > 16 && M <= 32 && K == 2048 && NW == 8 && (N / 16) * 2 <= 320) MT = 1;     // 16-row blocks: twice the workgroups, 128 KB instead of 192 KB each
+    if (M > 32 && K == 2048 && NW == 8) MT = 2;
+    if (M > 16 && M <= 32 && K == 2048 && NW == 8 && (N / 16) * 2 <= 320) MT = 1;     // 16-row blocks: twice the workgroups, 128 KB instead of 192 KB each
     if (NW == 8 && skinny_use_lds && launch_skinny_lds(st, A, lda, W, ldw, M, N, K, MT, om, ep)) return;
     dim3 grid(N / 16, (M + MT * 16 - 1) / (MT * 16)), block(NW * 64);
     switch (MT) {
@@ -1512,17 +1494,14 @@ static inline void launch_skinny_nw(hipStream_t st, const h16_t* A, long long ld
 }
 static inline void launch_skinny(hipStream_t st, const h16_t* A, long long lda, const h16_t* W, long long ldw, int M, int N, int K,
                                  const DenseOut& om, const EpiP& ep) {
-    static const bool kchunk = HULC_SWITCH("HULC_SKINNY_KCHUNK", 1) != 0;
-    if (kchunk && skinny_use_lds && M > 16 && launch_skinny_lds_kchunk(st, A, lda, W, ldw, M, N, K, om, ep)) return;     // K = n x 2048, M <= 64 (GRU BPTT step)
+    if (skinny_use_lds && M > 16 && launch_skinny_lds_kchunk(st, A, lda, W, ldw, M, N, K, om, ep)) return;     // K = n x 2048, M <= 64 (GRU BPTT step)
     if (K % 512 == 0) launch_skinny_nw<8>(st, A, lda, W, ldw, M, N, K, om, ep);     // 8 waves x >=2 k-steps
     else launch_skinny_nw<4>(st, A, lda, W, ldw, M, N, K, om, ep);
 }
 static inline bool skinny_ok(int M, int N, int K, long long lda, long long ldw, const void* A, const void* W) {
     // many-row use: every 64-row block of A is re-read by each of the N/16 column workgroups -> only when M*N is small
-    // (short K: the skinny kernel is shorter per launch at M = 2048, N = 128, K = 128..512 (5 vs 12 us in rocprof) but the step got
-    //  0.03 ms SLOWER in an A/B on one box — kept off)
-    static const bool shortk = HULC_SWITCH("HULC_SKINNY_SHORTK", 0) != 0;
-    const bool shape = M <= 64 || ((shortk || K >= 512) && (long long)M * N <= 524288 && (long long)((M + 63) / 64) * (N / 16) >= 16);
+    // and K >= 512 (at shorter K the kernel is shorter per launch but the step measured slower)
+    const bool shape = M <= 64 || (K >= 512 && (long long)M * N <= 524288 && (long long)((M + 63) / 64) * (N / 16) >= 16);
     return shape && (K % 32) == 0 && K >= 128 && (N % 16) == 0 && (lda % 8) == 0 && (ldw % 8) == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0;
 }
 

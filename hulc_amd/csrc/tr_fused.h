@@ -624,7 +624,7 @@ struct TrAttnBwdP {
     float *dy_f, *dx;                            // [N][128] fp32
     int B, S;
     float dp; unsigned long long seed_o, seed_att;
-    int dbg;                                     // experiment builds: phases switched off (1: P0, 2: P2, 4: P1, 8: P3)
+    int dbg;                                     // phases switched off (1: P0, 2: P2, 4: P1, 8: P3); 0 from the engine
 };
 constexpr int TRA_HP = 48;                                          // bytes per row of a head's [32][16] 16-bit operand: two 16-byte reads per row
 constexpr int TRA_HEADB = 4 * 32 * TRA_HP + 2 * 32 * 33 * 4;        // q, k, v, dO + dS, dropped P
@@ -647,7 +647,7 @@ __global__ void __launch_bounds__(512) tr_attn_bwd_kernel(TrAttnBwdP p) {
     const int w = blockIdx.x, S = p.S;
     const long long row0 = (long long)w * S;
     const bool mt1 = true;        // both 16-row tiles always (rows past S are zero).  With the second tile's MFMAs under `S > 16`, as in the kernels above,
-    // S <= 16 produced wrong d k / d v (transposed dS / P reads) while S >= 17 was exact — not understood; tools/tr_bwd_probe.py + tr_bwd_cmp.py (experiment build, HULC_TR_ATTN_BWD=0 / 1) reproduce it
+    // S <= 16 produced wrong d k / d v (transposed dS / P reads) while S >= 17 was exact — not understood
 
     // out_proj^T fragments (rows = the 16 features of head `wave`, 4 k-steps over the 128 columns of b_d): requested first
     h16x8_t wo[4];

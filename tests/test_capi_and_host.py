@@ -27,6 +27,19 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(lib.EXPORTS)
 
 
+def test_library_reads_no_environment_switches():
+    """Kernel routing is fixed at build time: the built library imports neither getenv nor secure_getenv."""
+    import shutil
+    import subprocess
+    import __graft_entry__ as g
+    g.build()
+    nm = shutil.which("nm")
+    cmd = [nm, "-D", "--undefined-only", g.LIB] if nm else ["/opt/rocm/llvm/bin/llvm-nm", "-D", "--undefined-only", g.LIB]
+    undefined = {l.split()[-1].split("@")[0] for l in subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.splitlines() if l.strip()}
+    assert "hipLaunchKernel" in undefined, "imports not parsed"
+    assert not undefined & {"getenv", "secure_getenv"}
+
+
 def test_ctypes_struct_layout_matches_header(tmp_path):
     """The ctypes mirrors in hulc_amd/lib.py against the C compiler's view of include/hulc_hip.h (sizeof / offsetof)."""
     import subprocess

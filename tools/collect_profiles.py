@@ -74,7 +74,7 @@ files = f"""| file | what | command |
 | `{T}_conv_reg_vs_tile.txt`, `{T}_conv_reg_ablation.txt` | conv2 / conv3 forward and data gradient on 2048 frames: LDS-resident-weights kernels (conv_tile.h) against the weights-in-registers kernels (conv_reg.h); and conv_reg with phases switched off (no DMA / no multiply loop / no epilogue) | `tools/time_conv_reg.py`, `ABLATE=1 tools/time_conv_reg.py` |
 | `{T}_rnn_persist_stamps.txt` | the persistent recurrence alone (`csrc/rnn_persist.h`): every step checked against a CPU recurrence, us per step at B = 64 / 128 (S = 32) and B = 32 (S = 64), shader-clock stamps of the phases of a step (poll, payload, MFMA + LDS, barrier, epilogue, drain) | `tools/bin/rnn_persist_bench_st` (tools/rnn_persist_bench.hip, -DRP_STAMPS) |
 | `{T}_step_timeline.txt` | every launch of one step with start offset, duration, gap and queue | `tools/step_timeline.py` |
-| `{T}_conv_tile_gripper_fpb.txt` | the four conv tile kernels on the gripper camera's shapes with 1 frame per band and with the stacked bands the launch picks | `tools/time_conv_tile_gripper.py` |
+| `{T}_conv_tile_gripper_fpb.txt` | the four conv tile kernels on the gripper camera's shapes with the stacked bands the launch picks (rounds up to 6: also with 1 frame per band) | `tools/time_conv_tile_gripper.py` |
 | `{T}_gridbar_xcd_barrier.txt`, `{T}_gridbar_naive_barrier.txt` | grid barrier + cross-XCD exchange cost with the fast primitives (XCD-hierarchical barrier, relaxed polls, `sc1` write-through publish) and with round 1's acquire-polled single counter | `tools/bin/gridbar2`, `tools/bin/gridbar` |
 """
 s = open(P("README.md")).read()

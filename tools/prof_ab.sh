@@ -1,4 +1,4 @@
-# on the GPU box (experiment build): per-kernel durations of the bench step under environment settings.  usage: bash tools/prof_ab.sh OUTTAG "VAR=a" "VAR=b" ...
+# on the GPU box: per-kernel durations of the bench step under environment settings, e.g. two builds of the library (tools/ab_lib.sh).  usage: bash tools/prof_ab.sh OUTTAG "HULC_LIB_PATH=a.so" "HULC_LIB_PATH=b.so" ...
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; T=$1; shift
 O=$R/gpurun_out/$T; mkdir -p $O

@@ -1,4 +1,4 @@
-# on the GPU box (experiment build): per-kernel durations of the uint8-ingest bench step.  usage: bash tools/prof_u8.sh OUTTAG "VAR=a" "VAR=b" ...
+# on the GPU box: per-kernel durations of the uint8-ingest bench step under environment settings, e.g. two builds of the library.  usage: bash tools/prof_u8.sh OUTTAG "HULC_LIB_PATH=a.so" "HULC_LIB_PATH=b.so" ...
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; T=$1; shift
 O=$R/gpurun_out/$T; mkdir -p $O

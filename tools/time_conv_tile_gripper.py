@@ -1,6 +1,5 @@
 """Time the four conv_tile kernels on the gripper camera's shapes (2048 frames) in their production form (bitmask modes 7/8/9, mode 0 for conv3
-forward).  The frames-per-band choice is read once per process: run as `HULC_CT_FPB=n python tools/time_conv_tile_gripper.py` (1 = one frame per
-band, unset = the launch's own cost model)."""
+forward).  The frames per band are the launch's own cost model (conv_tile.h)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,4 +25,4 @@ for name, mode, ishape, wshape, bias, mask, oshape, IMH, OUTH, dbg in cases:
     img = torch.randn(*ishape, device="cuda").to(torch.bfloat16); w = (torch.randn(*wshape, device="cuda") * 0.05).to(torch.bfloat16)
     out = torch.zeros(*oshape, device="cuda", dtype=torch.bfloat16)
     res.append(f"{name}: {run(mode, img, w, bias, mask, out, IMH, OUTH, dbg):.1f} us")
-print(f"HULC_CT_FPB={os.environ.get('HULC_CT_FPB', 'auto')} HULC_CT_NW={os.environ.get('HULC_CT_NW', 'default (8 fwd / 16 dgrad)')}:  " + "   ".join(res))
+print("   ".join(res))
