@@ -458,6 +458,110 @@ int hulc_k_conv_tile(int32_t mode, const void* img, const void* w, const float* 
     return 0;
 }
 
+// host arithmetic only (no device needed): the division of a launch's persistent workgroups between the two cameras' jobs (conv_wgrad.h::camera_split)
+int hulc_k_camera_split(int32_t grid, double work_static, double work_gripper, int32_t* wg_static, int32_t* wg_gripper) {
+    int a = 0, b = 0;
+    camera_split(grid, work_static, work_gripper, a, b);
+    *wg_static = a; *wg_gripper = b;
+    return 0;
+}
+
+// One stage of both encoders as ONE launch (conv_reg.h launch_conv_reg_jobs, conv_wgrad.h launch_conv_wgrad_pair /
+// launch_conv1_wgrad_jobs) in the forms the engine runs, dynamic claiming on (one zeroed counter per job, as the engine's next_ctr()); b == NULL: job a alone through the same entry
+int hulc_k_conv_pair(int32_t stage, const hulc_conv_job* a, const hulc_conv_job* b, int32_t wg_a, int32_t wg_b, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const bool fwd = stage == HULC_PAIR_CONV2_FWD || stage == HULC_PAIR_CONV3_FWD, dgr = stage == HULC_PAIR_CONV3_DGRAD || stage == HULC_PAIR_CONV2_DGRAD;
+    const bool wgr = stage == HULC_PAIR_CONV3_WGRAD || stage == HULC_PAIR_CONV2_WGRAD || stage == HULC_PAIR_CONV1_WGRAD;
+    // every argument is checked before anything is allocated or written
+    if (!fwd && !dgr && !wgr) { hulc_set_error("hulc_k_conv_pair: unknown stage %d", (int)stage); return 1; }
+    if (!a) { hulc_set_error("hulc_k_conv_pair: job a is required"); return 1; }
+    if (wg_a < 1 || (b && wg_b < 1)) { hulc_set_error("hulc_k_conv_pair: every job needs at least one workgroup"); return 1; }
+    if (wgr && !b) { hulc_set_error("hulc_k_conv_pair: the weight-gradient stages need both jobs"); return 1; }
+    {
+        const hulc_conv_job* src[2] = {a, b};
+        for (int k = 0; k < (b ? 2 : 1); ++k)
+            if (!src[k]->in || !src[k]->w || !src[k]->out || src[k]->frames < 1 || src[k]->in_side < 1 || src[k]->out_side < 1 || (wgr && !src[k]->bits)) { hulc_set_error("hulc_k_conv_pair: incomplete job"); return 1; }
+    }
+    if (wgr) {
+        const int KH = stage == HULC_PAIR_CONV1_WGRAD ? 8 : (stage == HULC_PAIR_CONV3_WGRAD ? 3 : 4), S = stage == HULC_PAIR_CONV1_WGRAD ? 4 : (stage == HULC_PAIR_CONV3_WGRAD ? 1 : 2);
+        if (a->in_side < KH || b->in_side < KH || a->out_side != (a->in_side - KH) / S + 1 || b->out_side != (b->in_side - KH) / S + 1) { hulc_set_error("hulc_k_conv_pair: out_side does not belong to in_side"); return 1; }
+    }
+    static void *dp = nullptr, *zp = nullptr;
+    static int* ctr = nullptr;
+    if (!dp && hipMalloc(&dp, 8192) != hipSuccess) { hulc_set_error("hulc_k_conv_pair: hipMalloc failed"); return 1; }
+    if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_pair: hipMalloc failed"); return 1; } hipMemset(zp, 0, 256); }
+    if (!ctr && hipMalloc(&ctr, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_pair: hipMalloc failed"); return 1; }
+    hipMemsetAsync(ctr, 0, 256, st);      // job k claims through ctr + 16 k
+    if (wgr) {
+        // weight gradients: the launch writes one slab per workgroup, each job's slabs are then summed into its own output as hulc_k_conv_wgrad does.  Synchronises
+        const bool c1 = stage == HULC_PAIR_CONV1_WGRAD, c3 = stage == HULC_PAIR_CONV3_WGRAD;
+        const int KC = c1 ? 192 : (c3 ? 576 : 512), CO = c1 ? 32 : 64;
+        float* part = nullptr;
+        if (hipMalloc(&part, sizeof(float) * (size_t)(wg_a + wg_b) * CO * KC) != hipSuccess) { hulc_set_error("hulc_k_conv_pair: hipMalloc failed"); return 1; }
+        const hulc_conv_job* src[2] = {a, b};
+        const int wg[2] = {wg_a, wg_b};
+        int ns[2] = {0, 0};
+        bool okw = false;
+        if (c1) {      // fp32 NCHW frames (the headline boundary): both jobs on conv1_wgrad_tr2_kernel<6, 2>
+            Wgrad1Job J[2];
+            for (int k = 0; k < 2; ++k) {
+                Wgrad1Job q{}; q.S = Conv1Src{src[k]->in, nullptr, 0, 0}; q.work_ctr = ctr + 16 * k; q.dY = (const h16_t*)src[k]->w; q.bias_part = (float*)src[k]->bits;
+                q.Nf = src[k]->frames; q.IH = q.IW = src[k]->in_side; q.OH = q.OW = src[k]->out_side;
+                J[k] = q;
+            }
+            J[0].part = part;
+            size_t l0 = 0, l1 = 0; int r, nb;
+            okw = conv1_wgrad_plan(J[0].S, J[0].IH, J[0].IW, J[0].OH, J[0].OW, r, nb, l0) == conv1_wgrad_plan(J[1].S, J[1].IH, J[1].IW, J[1].OH, J[1].OW, r, nb, l1);
+            if (okw) {
+                for (int k = 0; k < 2; ++k) { hipMemsetAsync(src[k]->bits, 0, sizeof(float) * CO, st); hipMemsetAsync(src[k]->out, 0, sizeof(float) * CO * KC, st); }
+                okw = launch_conv1_wgrad_jobs(st, J, 2, 1024, wg, ns);
+            }
+        } else {
+            WgradJob J[2];
+            for (int k = 0; k < 2; ++k) {
+                WgradJob q{}; q.X = (const h16_t*)src[k]->in; q.dY = (const h16_t*)src[k]->w; q.bias_part = (float*)src[k]->bits; q.zeros = (const h16_t*)zp; q.work_ctr = ctr + 16 * k;
+                q.Nf = src[k]->frames; q.IH = q.IW = src[k]->in_side; q.OH = q.OW = src[k]->out_side; q.FPB = 1;
+                J[k] = q;
+            }
+            J[0].part = part;
+            using W3 = WgradCamW<64, 3>; using W2 = WgradCamW<32, 4>;
+            okw = c3 ? (a->in_side == W3::stat && b->in_side == W3::gripper) : (a->in_side == W2::stat && b->in_side == W2::gripper);      // the shapes the launch takes: nothing is written otherwise
+            if (okw) {
+                for (int k = 0; k < 2; ++k) { hipMemsetAsync(src[k]->bits, 0, sizeof(float) * CO, st); hipMemsetAsync(src[k]->out, 0, sizeof(float) * CO * KC, st); }
+                okw = c3 ? launch_conv_wgrad_pair<64, 64, 3, 3, 1>(st, J[0], J[1], 512, wg, ns) : launch_conv_wgrad_pair<32, 64, 4, 4, 2>(st, J[0], J[1], 512, wg, ns);
+            }
+        }
+        if (okw) {
+            hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((CO * KC + 1023) / 1024), dim3(256), 0, st, part, ns[0], (long long)CO * KC, (float*)a->out, CO, KC, 1, 1, 0);
+            hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((CO * KC + 1023) / 1024), dim3(256), 0, st, part + (long long)ns[0] * CO * KC, ns[1], (long long)CO * KC, (float*)b->out, CO, KC, 1, 1, 0);
+        }
+        const hipError_t e = hipStreamSynchronize(st);
+        hipFree(part);
+        if (!okw) { hulc_set_error("hulc_k_conv_pair: unsupported shape (the two cameras' maps only)"); return 1; }
+        if (e != hipSuccess) { hulc_set_error("hulc_k_conv_pair: %s", hipGetErrorString(e)); return 1; }
+        return 0;
+    }
+    ConvTileP j[2]; int wg[2] = {wg_a, wg_b};
+    const hulc_conv_job* src[2] = {a, b};
+    const int n = b ? 2 : 1;
+    for (int k = 0; k < n; ++k) {
+        ConvTileP p{}; p.img = (const h16_t*)src[k]->in; p.IMH = p.IMW = src[k]->in_side; p.w = (const h16_t*)src[k]->w; p.out = (h16_t*)src[k]->out; p.OUTH = p.OUTW = src[k]->out_side;
+        p.Nf = src[k]->frames; p.dump = (h16_t*)dp;
+        if (fwd) { p.bias = src[k]->bias; p.relu = 1; p.bits_out = (unsigned*)src[k]->bits; }
+        else { p.maskbits = (const unsigned*)src[k]->bits; p.zeros = (const h16_t*)zp; }
+        p.work_ctr = ctr + 16 * k;
+        j[k] = p;
+    }
+    bool ok = false;
+    if (stage == HULC_PAIR_CONV2_FWD) ok = launch_conv_reg_fwd_jobs<32, 4, 4, 2>(st, j, n, wg);
+    else if (stage == HULC_PAIR_CONV3_FWD) ok = launch_conv_reg_fwd_jobs<64, 3, 3, 1>(st, j, n, wg);
+    else if (stage == HULC_PAIR_CONV3_DGRAD) ok = launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, j, n, wg);
+    else ok = launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, j, n, wg);
+    if (!ok) { hulc_set_error("hulc_k_conv_pair: unsupported shape"); return 1; }
+    if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_conv_pair: launch failed"); return 1; }
+    return 0;
+}
+
 // skinny GEMM alone (bf16): out[M][N] (bf16) = A[M][K] W[N][K]^T ; variant = NW*10 + MT (e.g. 82 = 8 waves, 32-row blocks)
 int hulc_k_skinny(const void* A, const void* W, void* out, int32_t M, int32_t N, int32_t K, int32_t variant, void* stream) {
     hipStream_t st = (hipStream_t)stream;

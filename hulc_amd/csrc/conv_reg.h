@@ -35,10 +35,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #ifdef HULC_CR_STAMPS     // tools/cr_stamps.hip only: shader-clock stamps of a band's phases, every wave of workgroups 0..15 (never defined in the library build)
 __device__ unsigned long long g_cr_stamps[16 * 8 * 32 * 8];      // [workgroup][wave][band iteration][stamp]
-#define CRSTAMP(n) do { if (lane == 0 && blockIdx.x < 16 && crit < 32) g_cr_stamps[((blockIdx.x * 8 + wave) * 32 + crit) * 8 + (n)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define CRSTAMP(n) do { if (lane == 0 && bid < 16 && crit < 32) g_cr_stamps[((bid * 8 + wave) * 32 + crit) * 8 + (n)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define CRSTAMP(n)
 #endif
+
+// Up to four jobs in one launch: job k owns the workgroups [blk0[k], blk0[k+1]) for their whole life
+struct ConvRegBatch { ConvTileP j[4]; int n; int blk0[5]; };
 
 template <int CK, int TA, int TB, int SI>
 struct ConvRegCfg {
@@ -102,8 +105,16 @@ struct ConvRegCfg {
 //   two-workgroup EPI form — all forms of conv2's forward converge at ~1.4 x the mixed read / write streaming time of its 500 MB, so the blocked
 //   issue was not the whole story.  Kept selectable, not the production form.
 template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, int NBUF_ = 0, bool PKR = false, int EPI = 0, int LDR = 0>
-__global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(ConvTileP p) {
+__global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(ConvRegBatch bt) {
     using C = ConvRegCfg<CK, TA, TB, SI>;
+    // the job of this workgroup (wave-uniform: kernel arguments and blockIdx only, its fields are scalar loads; copied by value — through a reference the
+    // conv3 data-gradient form spilled 4 more registers, profiles/camera_merge_resources.txt); bid / nwg = the index and the count
+    // of workgroups WITHIN the job, which are what blockIdx.x / gridDim.x were to the one-job kernel
+    int jb = 0;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (k < bt.n && (int)blockIdx.x >= bt.blk0[k]) jb = k;
+    const ConvTileP p = bt.j[jb];
+    const int bid = (int)blockIdx.x - bt.blk0[jb], nwg = bt.blk0[jb + 1] - bt.blk0[jb];
     static_assert(!REV || SI == 1, "the data-gradient forms are stride-1 correlations (per parity class for OS = 2)");
     static_assert(OS == 1 || REV, "output parity classes only exist in the data-gradient form");
     static_assert(NWV == 8 || NWV == 4, "8 waves (one workgroup per CU, two band buffers) or 4 (two workgroups per CU, one buffer each)");
@@ -215,7 +226,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
         toff[t] = ((((ta % SI) * SI + tb % SI) * PLR + ta / SI) * PLC + tb / SI) * C::XS;
     }
     const float invPLC = 1.f / (float)PLC, invVPO = 1.f / (float)max(p.VPO, 1);
-    int item = blockIdx.x, nb = 0;
+    int item = bid, nb = 0;
     if (NBUF == 2 && (!LDR || wave >= NCW)) {
         if (item < nitems) dma(item, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -225,7 +236,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
         int it = item, b = 0;
         while (it < nitems) {
             __syncthreads();                                    // band `it` has landed (this wave waited for its pieces); the compute waves are done with the other buffer
-            it += (int)gridDim.x; b ^= 1;
+            it += nwg; b ^= 1;
             if (it < nitems) { dma(it, b); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         }
         return;
@@ -256,7 +267,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
         const int cur = item;
         if (NBUF == 1) dma(cur, 0);                             // one buffer: every wave is done with the previous band -> load this one (the CU's
                                                                 // OTHER workgroup multiplies meanwhile)
-        item += (int)gridDim.x;
+        item += nwg;
         lds_char* const xb = lbase + nb * bbytes;
         if (NBUF == 2) nb ^= 1;
         const int f = multi ? cur * p.FPB : cur / p.nbands, b = multi ? 0 : cur % p.nbands;
@@ -536,10 +547,9 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
 
 // host side: band height for two resident bands (fewest bands), stacked frames for the gripper camera's small maps
 inline int g_conv_reg_wgpc = 0;      // tools/cr_bench.hip only: workgroups per CU the band geometry is sized for (0 = the form's own: 1 for 8 waves, 2 for 4)
+// band / stack geometry of ONE job that will run on `wgs` workgroups: fills p, its dynamic LDS bytes, its items and its multiply work (items x (0.35 + wave passes per item))
 template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, int NBUF_ = 0, bool PKR = false, int EPI = 0, int LDR = 0>
-static inline bool launch_conv_reg(hipStream_t st, ConvTileP p) {
-    if (EPI && (!p.dump || (REV && (!p.maskbits || p.relu || p.mask))))       // the pipelined epilogue covers the production forms only
-        return launch_conv_reg<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, 0, LDR>(st, p);
+static inline bool plan_conv_reg(ConvTileP& p, int wgs_job, size_t& lds, int& items_out, double& work) {
     using C = ConvRegCfg<CK, TA, TB, SI>;
     constexpr int NBUF = NBUF_ ? NBUF_ : (NWV == 8 ? 2 : 1);                                  // band buffers per workgroup
     const int WGPC = g_conv_reg_wgpc ? g_conv_reg_wgpc : (NWV == 8 ? 1 : 2);                  // workgroups per CU
@@ -564,15 +574,15 @@ static inline bool launch_conv_reg(hipStream_t st, ConvTileP p) {
     p.nbands = (NI + p.RB - 1) / p.RB;
     p.LR = REV ? p.RB + TA - 1 : (p.RB - 1) * SI + TA;
     p.VPI = (p.LR + SI - 1) / SI;
+    constexpr int per = 2 * (OS == 1 ? (NWV - LDR) / 2 : NWV / 4);                                                        // a wave pass = 2 tiles x the pixel parts
     if (p.nbands == 1 && p.Nf > 1 && (REV ? p.OUTH == OS * (p.IMH + TA - 1) : p.IMH % SI == 0)) {   // stack FPB frames to a band: a band should feed the 8 waves' 16 tile slots
         const int vpo = REV ? p.IMH + TA - 1 : p.IMH / SI;
         int bestf = 1; double bc = 1e30;
         for (int fpb = 1; fpb <= 32; ++fpb) {
             const int LR = REV ? fpb * vpo + TA - 1 : fpb * p.IMH, PLR = (LR + SI - 1) / SI, RB = REV ? fpb * vpo : (LR - TA) / SI + 1;
             if (!fits(LR, PLR, fpb * p.OUTH)) break;
-            constexpr int per = 2 * (OS == 1 ? (NWV - LDR) / 2 : NWV / 4);                                                // a wave pass = 2 tiles x the pixel parts
             const int tiles = (RB * p.LP + 31) / 32, rounds = (tiles + per - 1) / per;
-            const int items = (p.Nf + fpb - 1) / fpb, wgs = std::min(items, 256 * WGPC);
+            const int items = (p.Nf + fpb - 1) / fpb, wgs = std::min(items, wgs_job);      // the workgroups of THIS job, not of the launch
             const double c = (double)((items + wgs - 1) / wgs) * (0.35 + rounds);
             if (c < bc - 1e-9) { bc = c; bestf = fpb; }
         }
@@ -582,17 +592,52 @@ static inline bool launch_conv_reg(hipStream_t st, ConvTileP p) {
         }
     }
     p.MB = (int)maskb(p.FPB > 1 ? p.FPB * p.OUTH : std::min(p.RB * OS, p.OUTH));
-    const size_t lds = C::lds_bytes(p.VPI, p.LP, NBUF, (size_t)p.MB);
+    lds = C::lds_bytes(p.VPI, p.LP, NBUF, (size_t)p.MB);
+    items_out = p.FPB > 1 ? (p.Nf + p.FPB - 1) / p.FPB : p.Nf * p.nbands;
+    const int tiles = (p.RB * p.LP + 31) / 32;
+    work = (double)items_out * (0.35 + (tiles + per - 1) / per);
+    return true;
+}
+// n <= 4 jobs of one stage in ONE launch.  wg == nullptr: one job takes the grid it always took (min(items, 256 x workgroups per CU)); two jobs share
+// that grid by camera_split over their work, every job's stack geometry sized for its own share.  wg != nullptr: the workgroups of each job, as given (tests).
+template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, int NBUF_ = 0, bool PKR = false, int EPI = 0, int LDR = 0>
+static inline bool launch_conv_reg_jobs(hipStream_t st, const ConvTileP* jobs, int n, const int* wg = nullptr) {
+    if (n < 1 || n > 4 || (!wg && n > 2)) return false;
+    for (int k = 0; k < n; ++k) {
+        const ConvTileP& p = jobs[k];
+        if (EPI && (!p.dump || (REV && (!p.maskbits || p.relu || p.mask))))       // the pipelined epilogue covers the production forms only
+            return launch_conv_reg_jobs<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, 0, LDR>(st, jobs, n, wg);
+    }
+    const int WGPC = g_conv_reg_wgpc ? g_conv_reg_wgpc : (NWV == 8 ? 1 : 2);
+    const int grid_max = 256 * WGPC;
+    ConvRegBatch bt{}; bt.n = n;
+    size_t lds[4] = {0, 0, 0, 0}; int items[4] = {0, 0, 0, 0}, nw[4] = {0, 0, 0, 0}; double work[4] = {0, 0, 0, 0};
+    auto plan = [&](int k, int wgs) { bt.j[k] = jobs[k]; return bt.j[k].Nf >= 1 && plan_conv_reg<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>(bt.j[k], wgs, lds[k], items[k], work[k]); };
+    for (int k = 0; k < n; ++k) if (!plan(k, wg ? std::max(wg[k], 1) : grid_max)) return false;
+    if (wg) { for (int k = 0; k < n; ++k) nw[k] = std::min(std::max(wg[k], 1), items[k]); }
+    else if (n == 1) nw[0] = std::min(items[0], grid_max);
+    else if (items[0] + items[1] <= grid_max) { nw[0] = items[0]; nw[1] = items[1]; }      // (small calls) one item per workgroup, as in two launches
+    else {
+        camera_split(grid_max, work[0], work[1], nw[0], nw[1]);
+        for (int k = 0; k < 2; ++k) if (nw[k] > items[k]) { nw[1 - k] = std::min(items[1 - k], nw[1 - k] + nw[k] - items[k]); nw[k] = items[k]; }
+        // stacked frames: the stack that suited the whole grid may not suit the share (fewer workgroups -> more items each -> taller stacks pay)
+        for (int k = 0; k < 2; ++k) { if (!plan(k, nw[k])) return false; nw[k] = std::min(nw[k], items[k]); }
+    }
+    size_t ldsmax = 0;
+    for (int k = 0; k < n; ++k) { bt.blk0[k + 1] = bt.blk0[k] + nw[k]; ldsmax = std::max(ldsmax, lds[k]); }
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute((const void*)conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / (NWV == 8 ? 1 : 2) - 64);
         attr_set = true;
     }
-    const int items = p.FPB > 1 ? (p.Nf + p.FPB - 1) / p.FPB : p.Nf * p.nbands;
-    hipLaunchKernelGGL((conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>), dim3(items < 256 * WGPC ? items : 256 * WGPC), dim3(NWV * 64), lds, st, p);
+    hipLaunchKernelGGL((conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>), dim3(bt.blk0[n]), dim3(NWV * 64), ldsmax, st, bt);
     return true;
 }
+template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, int NBUF_ = 0, bool PKR = false, int EPI = 0, int LDR = 0>
+static inline bool launch_conv_reg(hipStream_t st, ConvTileP p) { return launch_conv_reg_jobs<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>(st, &p, 1); }
 template <int CK, int TA, int TB, int SI>
 static inline bool launch_conv_reg_fwd(hipStream_t st, const ConvTileP& p) { return launch_conv_reg<CK, TA, TB, SI, false, 1, 8, 0, true>(st, p); }
+template <int CK, int TA, int TB, int SI>
+static inline bool launch_conv_reg_fwd_jobs(hipStream_t st, const ConvTileP* jobs, int n, const int* wg = nullptr) { return launch_conv_reg_jobs<CK, TA, TB, SI, false, 1, 8, 0, true>(st, jobs, n, wg); }
 
 }  // namespace HULC_NS

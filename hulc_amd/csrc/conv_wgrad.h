@@ -179,10 +179,31 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_tr_kernel(const h16_t* __re
 //   * whole-frame bands where the frame fits (conv3: 152 KB of LDS), balanced bands otherwise (no 1-row tail band).
 // Chunk k of a thread is (dY or X, LDS offset, global offset) packed in one register; loads are unconditional (clamped).
 // ---------------------------------------------------------------------------------------------------------------------
+// host side: how a launch's persistent workgroups are divided between two independent jobs (the two cameras' copies of one stage): job B gets
+// round(grid * wB / (wA + wB)) of them, both jobs at least one; wA / wB = the jobs' multiply work in the units of the launchers' cost models
+// (items x rounds per item).  wB <= 0 (one job): the whole grid is job A's.  hulc_k_camera_split exposes it to the host tests.
+static inline void camera_split(int grid, double wA, double wB, int& nA, int& nB) {
+    if (grid < 1) grid = 1;
+    if (!(wB > 0.0)) { nA = grid; nB = 0; return; }
+    if (!(wA > 0.0)) { nA = 0; nB = grid; return; }
+    if (grid < 2) { nA = nB = 1; return; }      // (callers never ask: two jobs need two workgroups)
+    int b = (int)(grid * (wB / (wA + wB)) + 0.5);
+    b = std::min(std::max(b, 1), grid - 1);
+    nA = grid - b; nB = b;
+}
+
+// One weight-gradient job of a launch (conv_wgrad_tr8_body / conv_wgrad_dma_body): the operands and band geometry the kernels used to take as separate arguments.
+// part = the job's OWN slab area (slab index = the workgroup's index within the job), work_ctr its own claim counter.
+struct WgradJob {
+    const h16_t* X; const h16_t* dY; float* part; float* bias_part; const h16_t* zeros;
+    int Nf, IH, IW, OH, OW, R, nbands, dbg; int* work_ctr; int FPB;
+};
+// bid / nwg: index of this workgroup within its job and the job's workgroup count (blockIdx.x / gridDim.x of a one-job launch)
 template <int CI, int CO, int KH, int KW, int S, int NWV, int D = 3, int IWC = 0>      // IWC: compile-time image width (0: run time), see conv_wgrad_dma_kernel
-__global__ void __launch_bounds__(NWV * 64) conv_wgrad_tr8_kernel(const h16_t* __restrict__ X, const h16_t* __restrict__ dY, float* __restrict__ part,
-                                                            float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands, int dbg,
-                                                            int* __restrict__ work_ctr, int FPB) {
+DEVI void conv_wgrad_tr8_body(const WgradJob& J, const int bid, const int nwg) {
+    const h16_t* __restrict__ const X = J.X; const h16_t* __restrict__ const dY = J.dY; float* __restrict__ const part = J.part; float* __restrict__ const bias_part = J.bias_part;
+    const int Nf = J.Nf, IH = J.IH, IW = J.IW, OH = J.OH, OW = J.OW, R = J.R, nbands = J.nbands, dbg = J.dbg, FPB = J.FPB;
+    int* __restrict__ const work_ctr = J.work_ctr;
     // FPB > 1 (small frames, nbands == 1): FPB frames are stacked to one band.  X rows of consecutive frames are contiguous in memory; dY is staged
     // with a pitch of VP = IH / S rows per frame, its OH real rows followed by rows that stay zero from the initial LDS fill, so that dY row v still
     // sits over X row v * S and the pixel runs that cross into the next frame multiply zeros.  R = (FPB - 1) * VP + OH virtual rows.
@@ -261,10 +282,10 @@ __global__ void __launch_bounds__(NWV * 64) conv_wgrad_tr8_kernel(const h16_t* _
         }
     };
     __shared__ int s_next[2];
-    int item = blockIdx.x, iter = 0;
+    int item = bid, iter = 0;
     if (item < nitems) prefetch(item);
     while (item < nitems) {
-        if (work_ctr && tid == 0) s_next[iter & 1] = (int)gridDim.x + atomicAdd(work_ctr, 1);   // dynamic claim (see ConvTileP::work_ctr)
+        if (work_ctr && tid == 0) s_next[iter & 1] = nwg + atomicAdd(work_ctr, 1);   // dynamic claim (see ConvTileP::work_ctr)
         __syncthreads();                               // previous band fully consumed (first pass: zero fill visible)
         zmask_cur = zmask;
 #pragma unroll
@@ -279,7 +300,7 @@ __global__ void __launch_bounds__(NWV * 64) conv_wgrad_tr8_kernel(const h16_t* _
             }
         }
         __syncthreads();
-        item = work_ctr ? s_next[iter & 1] : item + (int)gridDim.x;
+        item = work_ctr ? s_next[iter & 1] : item + nwg;
         ++iter;
         if (item < nitems) prefetch(item);             // in flight during the MFMAs below
         const int units = (dbg & 1) ? 0 : R * U;
@@ -333,7 +354,7 @@ __global__ void __launch_bounds__(NWV * 64) conv_wgrad_tr8_kernel(const h16_t* _
         }
     }
     constexpr int KC = KH * KW * CI;
-    float* out = part + (long long)blockIdx.x * CO * KC;
+    float* out = part + (long long)bid * CO * KC;
     if (!(dbg & 4) || acc[0][0][0] == 12345.678f)
 #pragma unroll
     for (int j = 0; j < C::NTW; ++j)
@@ -352,6 +373,13 @@ __global__ void __launch_bounds__(NWV * 64) conv_wgrad_tr8_kernel(const h16_t* _
         for (int t = cgrp; t < NTH; t += CHY) s += red[t * 8 + e];
         unsafeAtomicAdd(bias_part + tid, s);
     }
+}
+template <int CI, int CO, int KH, int KW, int S, int NWV, int D = 3, int IWC = 0>
+__global__ void __launch_bounds__(NWV * 64) conv_wgrad_tr8_kernel(const h16_t* __restrict__ X, const h16_t* __restrict__ dY, float* __restrict__ part,
+                                                            float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands, int dbg,
+                                                            int* __restrict__ work_ctr, int FPB) {
+    const WgradJob J{X, dY, part, bias_part, nullptr, Nf, IH, IW, OH, OW, R, nbands, dbg, work_ctr, FPB};
+    conv_wgrad_tr8_body<CI, CO, KH, KW, S, NWV, D, IWC>(J, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -379,9 +407,11 @@ DEVI void wg_lds_dma16(const void* src, lds_char* dst) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(a) : "memory", "m0");
 }
 template <int CI, int CO, int KH, int KW, int S, int IWC = 0>      // IWC: the image width at compile time (0: run time) — the tap offsets of the B fragments become ds_read immediates
-__global__ void __launch_bounds__(512) conv_wgrad_dma_kernel(const h16_t* __restrict__ X, const h16_t* __restrict__ dY, float* __restrict__ part,
-                                                             float* __restrict__ bias_part, const h16_t* __restrict__ zeros, int Nf, int IH, int IW, int OH, int OW,
-                                                             int R, int nbands, int dbg, int* __restrict__ work_ctr) {
+DEVI void conv_wgrad_dma_body(const WgradJob& J, const int bid, const int nwg) {
+    const h16_t* __restrict__ const X = J.X; const h16_t* __restrict__ const dY = J.dY; float* __restrict__ const part = J.part; float* __restrict__ const bias_part = J.bias_part;
+    const h16_t* __restrict__ const zeros = J.zeros;
+    const int Nf = J.Nf, IH = J.IH, IW = J.IW, OH = J.OH, OW = J.OW, R = J.R, nbands = J.nbands, dbg = J.dbg;
+    int* __restrict__ const work_ctr = J.work_ctr;
     using C = WgradCfg<CI, CO, KH, KW, S>;
     constexpr int NWV = 8, NTH = NWV * 64, CTH = C::CT / (NWV / 4), CHY = CO / 8, CHX = CI / 8, XSS = C::XS / 16, YSS = C::DYS / 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -458,17 +488,17 @@ __global__ void __launch_bounds__(512) conv_wgrad_dma_kernel(const h16_t* __rest
     for (int j = 0; j < C::NTW; ++j) toff[j] = ((j / KW) * IWk + j % KW) * C::XS;
     float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     __shared__ int s_next[2];
-    int item = blockIdx.x, iter = 0, nb = 0;
+    int item = bid, iter = 0, nb = 0;
     if (item < nitems) dma(item, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const int px = (g & 1) * 4 + prow;
     const int q4 = 4 / U, r4 = 4 - q4 * U;
     const int step4 = (q4 * S * IW + r4 * 8 * S) * C::XS, wrapd = (S * IW - U * 8 * S) * C::XS;
     while (item < nitems) {
-        if (work_ctr && tid == 0) s_next[iter & 1] = (int)gridDim.x + atomicAdd(work_ctr, 1);   // dynamic claim (see ConvTileP::work_ctr)
+        if (work_ctr && tid == 0) s_next[iter & 1] = nwg + atomicAdd(work_ctr, 1);   // dynamic claim (see ConvTileP::work_ctr)
         __syncthreads();                               // this band has landed (every wave waited for its own pieces) and nobody reads the other buffer any more
         const int cur = item;
-        item = work_ctr ? s_next[iter & 1] : item + (int)gridDim.x;
+        item = work_ctr ? s_next[iter & 1] : item + nwg;
         ++iter;
         lds_char* const ximg0 = lbase + nb * bbytes;
         lds_char* const dyimg = ximg0 + xslots * 16;
@@ -537,7 +567,7 @@ __global__ void __launch_bounds__(512) conv_wgrad_dma_kernel(const h16_t* __rest
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of the next band have landed
     }
     constexpr int KC = KH * KW * CI;
-    float* out = part + (long long)blockIdx.x * CO * KC;
+    float* out = part + (long long)bid * CO * KC;
     if (!(dbg & 4) || acc[0][0][0] == 12345.678f)
 #pragma unroll
     for (int j = 0; j < C::NTW; ++j)
@@ -556,6 +586,20 @@ __global__ void __launch_bounds__(512) conv_wgrad_dma_kernel(const h16_t* __rest
         for (int t = cgrp; t < NTH; t += CHY) s += red[t * 8 + e];
         unsafeAtomicAdd(bias_part + tid, s);
     }
+}
+template <int CI, int CO, int KH, int KW, int S, int IWC = 0>
+__global__ void __launch_bounds__(512) conv_wgrad_dma_kernel(const h16_t* __restrict__ X, const h16_t* __restrict__ dY, float* __restrict__ part,
+                                                             float* __restrict__ bias_part, const h16_t* __restrict__ zeros, int Nf, int IH, int IW, int OH, int OW,
+                                                             int R, int nbands, int dbg, int* __restrict__ work_ctr) {
+    const WgradJob J{X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nbands, dbg, work_ctr, 1};
+    conv_wgrad_dma_body<CI, CO, KH, KW, S, IWC>(J, (int)blockIdx.x, (int)gridDim.x);
+}
+// The weight gradient of one stage for BOTH cameras in one launch: the static camera's job on the LDS-DMA body (IWS = its map width), the gripper camera's on the
+// stacked-band body (IWG).  A workgroup belongs to one job for its life: blockIdx.x < wgA -> job A.  Neither multiply loop changes; both bodies are 512 threads.
+template <int CI, int CO, int KH, int KW, int S, int IWS, int IWG>
+__global__ void __launch_bounds__(512) conv_wgrad_pair_kernel(WgradJob A, WgradJob B, int wgA) {
+    if ((int)blockIdx.x < wgA) conv_wgrad_dma_body<CI, CO, KH, KW, S, IWS>(A, (int)blockIdx.x, wgA);
+    else conv_wgrad_tr8_body<CI, CO, KH, KW, S, 8, 3, IWG>(B, (int)blockIdx.x - wgA, (int)gridDim.x - wgA);
 }
 // band height for v3: among the heights of which two bands fit the LDS, the one with the fewest multiply steps per frame — a band of r rows is
 // ceil(r U / 4) steps of four 8-pixel runs (U = OWp / 8 runs per row; a partially filled last step multiplies zeros) plus about one step's worth of
@@ -577,6 +621,42 @@ static inline int conv_wgrad_dma_rows(int IH, int IW, int OH, int OW, int* nband
     return bestR;
 }
 
+// the map widths of the two cameras at conv3 / conv2 (200 x 200 and 84 x 84 frames): the compile-time-width instances of the kernels
+template <int CI, int KH> struct WgradCamW {
+    static constexpr int fixed = (CI == 64 && KH == 3) ? 1 : ((CI == 32 && KH == 4) ? 2 : 0);
+    static constexpr int stat = fixed == 1 ? 23 : (fixed == 2 ? 49 : 0), gripper = fixed == 1 ? 9 : (fixed == 2 ? 20 : 0);
+};
+// band / stack geometry of the stacked-band kernel (conv_wgrad_tr8_kernel) for a job that runs on `wgs` workgroups; false = shape not covered
+template <int CI, int CO, int KH, int KW, int S>
+static inline bool conv_wgrad_tr8_plan(int Nf, int IH, int IW, int OH, int OW, int wgs, int& R_out, int& nb_out, int& fpb_out, size_t& lds_out) {
+    using C = WgradCfg<CI, CO, KH, KW, S>;
+    constexpr int NWV = 8;
+    // fewest balanced bands whose chunks fit the 16 x 512 prefetch slots and whose images fit in 160 KB (16 KB kept for the bias reduction)
+    for (int nb = 1; nb <= OH; ++nb) {
+        int R = (OH + nb - 1) / nb, XR = (R - 1) * S + KH;
+        long long chunks = (long long)R * OW * (CO / 8) + (long long)XR * IW * (CI / 8);
+        size_t lds = std::max<size_t>(C::lds_bytes(R, IW, OW), NWV * 64 * 8 * sizeof(float));
+        if (chunks > 16 * 512 || lds > 160 * 1024 - 64 || (long long)XR * IW * CI >= (1 << 20)) continue;
+        // small frames (whole frame per band): stack FPB frames to a band — the two barriers, the staging and the exposed load latency of a band
+        // (~5 us, against ~0.5 us of MFMAs for a 7x7 gripper map) are then paid once per FPB frames.  Largest FPB that fits LDS and the prefetch
+        // slots and still leaves every workgroup OF THIS JOB two bands (the second one's loads fly under the first one's MFMAs).
+        int fpb = 1;
+        if (nb == 1 && IH % S == 0) {
+            for (int f = 2; f <= 16; ++f) {
+                const int Rf = (f - 1) * (IH / S) + OH, XRf = (Rf - 1) * S + KH;
+                const long long ch = (long long)f * OH * OW * (CO / 8) + (long long)XRf * IW * (CI / 8);
+                const size_t l = std::max<size_t>(C::lds_bytes(Rf, IW, OW), NWV * 64 * 8 * sizeof(float));
+                if (ch > 16 * 512 || l > 160 * 1024 - 64 || (long long)XRf * IW * CI >= (1 << 20)) break;
+                if ((Nf + f - 1) / f < 2 * wgs) break;
+                fpb = f; R = Rf; XR = XRf; chunks = ch; lds = l;
+            }
+        }
+        R_out = R; nb_out = nb; fpb_out = fpb; lds_out = lds;
+        return true;
+    }
+    return false;
+}
+
 template <int CI, int CO, int KH, int KW, int S>
 static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16_t* dY, float* part, float* bias_part, int Nf, int IH, int IW, int OH,
                                        int OW, int max_blocks, int* work_ctr = nullptr, const h16_t* zeros = nullptr) {
@@ -586,7 +666,7 @@ static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16
         int nb = 0; size_t lds = 0;
         const int R = conv_wgrad_dma_rows<CI, CO, KH, KW, S>(IH, IW, OH, OW, &nb, &lds);
         if (R > 0 && (long long)Nf * IH * IW * CI < (1ll << 31)) {
-            constexpr int IWS = (CI == 64 && KH == 3) ? 23 : ((CI == 32 && KH == 4) ? 49 : 0);      // the static camera's maps (200 x 200 frames): conv3 reads 23 x 23, conv2 49 x 49
+            constexpr int IWS = WgradCamW<CI, KH>::stat;      // the static camera's maps (200 x 200 frames): conv3 reads 23 x 23, conv2 49 x 49
             static bool attr3 = false;
             if (!attr3) {
                 hipFuncSetAttribute((const void*)conv_wgrad_dma_kernel<CI, CO, KH, KW, S, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
@@ -600,26 +680,9 @@ static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16
         }
     }
     constexpr int NWV = 8;                                   // 16 waves (one co-tile each, 4 waves per SIMD) measured slower: 0.43 vs 0.40 ms/step
-    // fewest balanced bands whose chunks fit the 16 x 512 prefetch slots and whose images fit in 160 KB (16 KB kept for the bias reduction)
-    for (int nb = 1; nb <= OH; ++nb) {
-        int R = (OH + nb - 1) / nb, XR = (R - 1) * S + KH;
-        long long chunks = (long long)R * OW * (CO / 8) + (long long)XR * IW * (CI / 8);
-        size_t lds = std::max<size_t>(C::lds_bytes(R, IW, OW), NWV * 64 * 8 * sizeof(float));
-        if (chunks > 16 * 512 || lds > 160 * 1024 - 64 || (long long)XR * IW * CI >= (1 << 20)) continue;
-        // small frames (whole frame per band): stack FPB frames to a band — the two barriers, the staging and the exposed load latency of a band
-        // (~5 us, against ~0.5 us of MFMAs for a 7x7 gripper map) are then paid once per FPB frames.  Largest FPB that fits LDS and the prefetch
-        // slots and still leaves every workgroup two bands (the second one's loads fly under the first one's MFMAs).
-        int fpb = 1;
-        if (nb == 1 && IH % S == 0) {
-            for (int f = 2; f <= 16; ++f) {
-                const int Rf = (f - 1) * (IH / S) + OH, XRf = (Rf - 1) * S + KH;
-                const long long ch = (long long)f * OH * OW * (CO / 8) + (long long)XRf * IW * (CI / 8);
-                const size_t l = std::max<size_t>(C::lds_bytes(Rf, IW, OW), NWV * 64 * 8 * sizeof(float));
-                if (ch > 16 * 512 || l > 160 * 1024 - 64 || (long long)XRf * IW * CI >= (1 << 20)) break;
-                if ((Nf + f - 1) / f < 2 * std::min(256, max_blocks)) break;
-                fpb = f; R = Rf; XR = XRf; chunks = ch; lds = l;
-            }
-        }
+    {
+        int R = 0, nb = 0, fpb = 1; size_t lds = 0;
+        if (conv_wgrad_tr8_plan<CI, CO, KH, KW, S>(Nf, IH, IW, OH, OW, std::min(256, max_blocks), R, nb, fpb, lds)) {
         static bool attr8 = false;
         if (!attr8) {
             hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
@@ -629,7 +692,7 @@ static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16
         const int grid = std::min(std::min(items, 256), max_blocks);
         constexpr int dbg = 0;
         {      // the gripper camera's maps (84 x 84 frames): conv3 reads 9 x 9, conv2 20 x 20 — the compile-time-width instance (tap offsets as ds_read immediates)
-            constexpr int IWG = (CI == 64 && KH == 3) ? 9 : ((CI == 32 && KH == 4) ? 20 : 0);
+            constexpr int IWG = WgradCamW<CI, KH>::gripper;
             if (IWG && IW == IWG) {
                 static bool ag = false;
                 if (!ag) { hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 3, IWG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); ag = true; }
@@ -639,6 +702,7 @@ static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16
         }
         hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
         return grid;
+        }
     }
     int R = OH;                                              // largest band that keeps two workgroups per CU (<= 78 KB)
     while (R > 1 && C::lds_bytes(R, IW, OW) > 78 * 1024) --R;
@@ -653,6 +717,55 @@ static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16
     const int grid = Nf < max_blocks ? Nf : max_blocks;
     hipLaunchKernelGGL((conv_wgrad_tr_kernel<CI, CO, KH, KW, S>), dim3(grid), dim3(256), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R);
     return grid;                                             // = number of partial slabs written
+}
+
+// Both cameras' weight gradient of conv3 or conv2 as ONE launch (conv_wgrad_pair_kernel): A = the static camera's job (LDS-DMA body), B = the gripper camera's
+// (stacked-band body, its stack sized for its own workgroups).  The launch's min(256, max_blocks) workgroups are divided by camera_split over the jobs' multiply
+// steps (bands x (steps of four 8-pixel runs + 1), the cost model of conv_wgrad_dma_rows); wg != nullptr: the two counts as given (tests).  A.part = the slab area:
+// A's slabs first, B's right behind them (B.part is set here).  Returns false (nothing launched) for shapes that are not the two cameras' maps; ns = slabs per job.
+template <int CI, int CO, int KH, int KW, int S>
+static inline bool launch_conv_wgrad_pair(hipStream_t st, WgradJob A, WgradJob B, int max_blocks, const int* wg, int ns[2]) {
+    using W = WgradCamW<CI, KH>;
+    if constexpr (W::fixed == 0) return false;
+    else {
+        constexpr int IWS = W::stat, IWG = W::gripper;
+        if (A.IW != IWS || A.IH != IWS || B.IW != IWG || B.IH != IWG || !A.zeros || A.OH * A.OW < 256 || A.Nf < 1 || B.Nf < 1) return false;
+        if ((long long)A.Nf * A.IH * A.IW * CI >= (1ll << 31)) return false;
+        int nbA = 0; size_t ldsA = 0;
+        A.R = conv_wgrad_dma_rows<CI, CO, KH, KW, S>(A.IH, A.IW, A.OH, A.OW, &nbA, &ldsA);
+        if (A.R <= 0) return false;
+        A.nbands = nbA; A.FPB = 1;
+        const int grid = std::min(256, max_blocks);
+        if (grid < 2) return false;
+        auto steps = [](int rows, int OW) { return (rows * ((OW + 7) / 8) + 3) / 4 + 1; };
+        const int itemsA = A.Nf * nbA;
+        const double wA = (double)A.Nf * ((nbA - 1) * steps(A.R, A.OW) + steps(A.OH - (nbA - 1) * A.R, A.OW));
+        size_t ldsB = 0; int itemsB = 0;
+        auto planB = [&](int wgs) {
+            if (!conv_wgrad_tr8_plan<CI, CO, KH, KW, S>(B.Nf, B.IH, B.IW, B.OH, B.OW, wgs, B.R, B.nbands, B.FPB, ldsB)) return false;
+            itemsB = B.FPB > 1 ? (B.Nf + B.FPB - 1) / B.FPB : B.Nf * B.nbands;
+            return true;
+        };
+        int nA, nB;
+        if (wg) { nA = std::max(wg[0], 1); nB = std::max(wg[1], 1); if (!planB(nB)) return false; }
+        else {
+            if (!planB(grid)) return false;
+            if (itemsA + itemsB <= grid) { nA = itemsA; nB = itemsB; }      // (small calls) one item per workgroup, as in two launches
+            else {
+                camera_split(grid, wA, (double)itemsB * steps(B.R, B.OW), nA, nB);
+                if (nA > itemsA) { nB = std::min(itemsB, nB + nA - itemsA); nA = itemsA; }
+                if (nB > itemsB) { nA = std::min(itemsA, nA + nB - itemsB); nB = itemsB; }
+                if (!planB(nB)) return false;
+            }
+        }
+        nA = std::min(nA, itemsA); nB = std::min(nB, itemsB);
+        B.part = A.part + (long long)nA * CO * (KH * KW * CI);
+        static bool attrp = false;
+        if (!attrp) { hipFuncSetAttribute((const void*)conv_wgrad_pair_kernel<CI, CO, KH, KW, S, IWS, IWG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attrp = true; }
+        hipLaunchKernelGGL((conv_wgrad_pair_kernel<CI, CO, KH, KW, S, IWS, IWG>), dim3(nA + nB), dim3(512), std::max(ldsA, ldsB), st, A, B, nA);
+        ns[0] = nA; ns[1] = nB;
+        return true;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -992,8 +1105,19 @@ struct Wgrad1Cfg {
     }
 };
 
-__global__ void __launch_bounds__(256, 2) conv1_wgrad_tr_kernel(Conv1Src X, int* __restrict__ work_ctr, const h16_t* __restrict__ dY, float* __restrict__ part,
-                                                                float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R) {
+// One conv1 weight-gradient job of a launch (the two cameras' frames, or the two frame sources of a camera in the paired pass): the arguments the kernels below took
+// one by one.  A workgroup belongs to ONE job for its life: the job whose block range [blk0, next blk0) holds blockIdx.x; the body sees its index within the job (bid)
+// and the job's workgroup count (nwg) where a one-job launch has blockIdx.x and gridDim.x.  part = the job's own slab area, work_ctr its own claim counter.
+struct Wgrad1Job { Conv1Src S; int* work_ctr; const h16_t* dY; float* part; float* bias_part; int Nf, IH, IW, OH, OW, R, nbands, blk0; };
+struct Wgrad1Batch { Wgrad1Job j[4]; int n; };
+#define WGRAD1_PICK_JOB(bt)                                                                       \
+    int jk = 0;                                                                                   \
+    while (jk + 1 < bt.n && (int)blockIdx.x >= bt.j[jk + 1].blk0) ++jk;                           \
+    const Wgrad1Job& J = bt.j[jk];                                                                \
+    const int bid = (int)blockIdx.x - J.blk0, nwg = (jk + 1 < bt.n ? bt.j[jk + 1].blk0 : (int)gridDim.x) - J.blk0;
+
+DEVI void conv1_wgrad_tr_body(const Conv1Src& X, int* __restrict__ work_ctr, const h16_t* __restrict__ dY, float* __restrict__ part,
+                              float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, const int bid, const int nwg) {
     using C = Wgrad1Cfg;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1021,8 +1145,8 @@ __global__ void __launch_bounds__(256, 2) conv1_wgrad_tr_kernel(Conv1Src X, int*
 
     __shared__ int s_nextf[2];
     int fiter = 0;
-    for (int f = blockIdx.x; f < Nf;) {
-        if (work_ctr && tid == 0) s_nextf[fiter & 1] = (int)gridDim.x + atomicAdd(work_ctr, 1);   // next frame claimed dynamically (see ConvTileP::work_ctr)
+    for (int f = bid; f < Nf;) {
+        if (work_ctr && tid == 0) s_nextf[fiter & 1] = nwg + atomicAdd(work_ctr, 1);   // next frame claimed dynamically (see ConvTileP::work_ctr)
         for (int oh0 = 0; oh0 < OH; oh0 += R) {
             __syncthreads();
             {   // dY band, one row per wave pass
@@ -1064,10 +1188,10 @@ __global__ void __launch_bounds__(256, 2) conv1_wgrad_tr_kernel(Conv1Src X, int*
                 }
             }
         }
-        f = work_ctr ? s_nextf[fiter & 1] : f + (int)gridDim.x;   // written >= 2 barriers ago; the other slot is the one tid 0 writes next
+        f = work_ctr ? s_nextf[fiter & 1] : f + nwg;   // written >= 2 barriers ago; the other slot is the one tid 0 writes next
         ++fiter;
     }
-    float* out = part + (long long)blockIdx.x * C::CO * 192;
+    float* out = part + (long long)bid * C::CO * 192;
 #pragma unroll
     for (int j = 0; j < 3; ++j)
 #pragma unroll
@@ -1085,6 +1209,10 @@ __global__ void __launch_bounds__(256, 2) conv1_wgrad_tr_kernel(Conv1Src X, int*
         for (int t = cgrp; t < 256; t += 4) s += red[t * 8 + e];
         unsafeAtomicAdd(bias_part + tid, s);
     }
+}
+__global__ void __launch_bounds__(256, 2) conv1_wgrad_tr_kernel(Wgrad1Batch bt) {
+    WGRAD1_PICK_JOB(bt)
+    conv1_wgrad_tr_body(J.S, J.work_ctr, J.dY, J.part, J.bias_part, J.Nf, J.IH, J.IW, J.OH, J.OW, J.R, bid, nwg);
 }
 
 // phase ablation of the two v2 kernels below, compiled in only by tools/conv1_wgrad_probe.hip (-DHULC_W1_PROBE): bit 0 = no multiply loop, bit 1 = no prefetch of the next band,
@@ -1107,8 +1235,8 @@ __device__ int g_w1_probe = 0;
 //   units and are summed through LDS at the end.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int PFX, int PFY>
-__global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2_kernel(const float* __restrict__ X, int* __restrict__ work_ctr, const h16_t* __restrict__ dY, float* __restrict__ part,
-                                                                 float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands) {
+DEVI void conv1_wgrad_tr2_body(const float* __restrict__ X, int* __restrict__ work_ctr, const h16_t* __restrict__ dY, float* __restrict__ part,
+                               float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands, const int bid, const int nwg) {
     using C = Wgrad1Cfg;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
@@ -1172,11 +1300,11 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2_kernel(const float* __
     // consecutive bands share are then re-read by the same CU a few microseconds later and come from L2 instead of HBM (with the bands of
     // a frame dealt to different workgroups the PMC counters showed 27 % more HBM bytes than the frames hold).
     __shared__ int s_next[2];
-    int frame = blockIdx.x, fiter = 0, band = 0;
+    int frame = bid, fiter = 0, band = 0;
     int item = frame * nbands;
     if (frame < Nf) prefetch(item);
     while (frame < Nf) {
-        if (band == 0 && work_ctr && tid == 0) s_next[fiter & 1] = (int)gridDim.x + atomicAdd(work_ctr, 1);
+        if (band == 0 && work_ctr && tid == 0) s_next[fiter & 1] = nwg + atomicAdd(work_ctr, 1);
         __syncthreads();                                          // previous band consumed (first pass: zero fill visible)
         const int cxr = xrows, cyr = yrows;
 #pragma unroll
@@ -1201,7 +1329,7 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2_kernel(const float* __
         __syncthreads();
         if (++band == nbands) {                                   // next frame (its claim was written at the frame's first band: >= 1 barrier ago)
             band = 0;
-            frame = work_ctr ? s_next[fiter & 1] : frame + (int)gridDim.x;
+            frame = work_ctr ? s_next[fiter & 1] : frame + nwg;
             ++fiter;
         }
         item = frame * nbands + band;
@@ -1246,7 +1374,7 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2_kernel(const float* __
     }
     __syncthreads();
     if (uh == 0) {
-        float* out = part + (long long)blockIdx.x * C::CO * 192;
+        float* out = part + (long long)bid * C::CO * 192;
 #pragma unroll
         for (int j = 0; j < 3; ++j)
 #pragma unroll
@@ -1267,6 +1395,11 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2_kernel(const float* __
         for (int t = cgrp; t < 512; t += 4) sacc += redf[t * 8 + e];
         unsafeAtomicAdd(bias_part + tid, sacc);
     }
+}
+template <int PFX, int PFY>
+__global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2_kernel(Wgrad1Batch bt) {
+    WGRAD1_PICK_JOB(bt)
+    conv1_wgrad_tr2_body<PFX, PFY>(reinterpret_cast<const float*>(J.S.X), J.work_ctr, J.dY, J.part, J.bias_part, J.Nf, J.IH, J.IW, J.OH, J.OW, J.R, J.nbands, bid, nwg);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1498,8 +1631,8 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2u_kernel(Conv1Src S, in
 // slot PFX - 1 the few groups next to the row ends (threads [0, XR * edge groups per row)) with the general conversion — the slot index is an unrolled compile-time
 // constant, so no wave pays the slow path for its interior lanes.  Same LDS image, same slabs.
 template <int PFX, int PFY, bool SPLIT = false>
-__global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2r_kernel(Conv1Src S, int* __restrict__ work_ctr, const h16_t* __restrict__ dY, float* __restrict__ part,
-                                                                  float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands) {
+DEVI void conv1_wgrad_tr2r_body(const Conv1Src& S, int* __restrict__ work_ctr, const h16_t* __restrict__ dY, float* __restrict__ part,
+                                float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands, const int bid, const int nwg) {
     using C = Wgrad1Cfg;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
@@ -1587,11 +1720,11 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2r_kernel(Conv1Src S, in
         }
     };
     __shared__ int s_next[2];
-    int frame = blockIdx.x, fiter = 0, band = 0;
+    int frame = bid, fiter = 0, band = 0;
     int item = frame * nbands;
     if (frame < Nf) prefetch(item);
     while (frame < Nf) {
-        if (band == 0 && work_ctr && tid == 0) s_next[fiter & 1] = (int)gridDim.x + atomicAdd(work_ctr, 1);
+        if (band == 0 && work_ctr && tid == 0) s_next[fiter & 1] = nwg + atomicAdd(work_ctr, 1);
         __syncthreads();                                          // previous band consumed (first pass: zero fill visible)
         const int cxr = xrows, cyr = yrows, dx = pdx;
         if (!W1_PROBE_SKIP(8)) {
@@ -1665,7 +1798,7 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2r_kernel(Conv1Src S, in
         __syncthreads();
         if (++band == nbands) {
             band = 0;
-            frame = work_ctr ? s_next[fiter & 1] : frame + (int)gridDim.x;
+            frame = work_ctr ? s_next[fiter & 1] : frame + nwg;
             ++fiter;
         }
         item = frame * nbands + band;
@@ -1724,7 +1857,7 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2r_kernel(Conv1Src S, in
     }
     __syncthreads();
     if (uh == 0) {
-        float* out = part + (long long)blockIdx.x * C::CO * 192;
+        float* out = part + (long long)bid * C::CO * 192;
         const float fsc = S.fold ? CONV1_FOLD_SCALE : 1.f;
 #pragma unroll
         for (int j = 0; j < 3; ++j)
@@ -1739,10 +1872,17 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2r_kernel(Conv1Src S, in
             }
     }
 }
+template <int PFX, int PFY, bool SPLIT = false>
+__global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2r_kernel(Wgrad1Batch bt) {
+    WGRAD1_PICK_JOB(bt)
+    conv1_wgrad_tr2r_body<PFX, PFY, SPLIT>(J.S, J.work_ctr, J.dY, J.part, J.bias_part, J.Nf, J.IH, J.IW, J.OH, J.OW, J.R, J.nbands, bid, nwg);
+}
 
 inline int g_conv1_wgrad_u8reg = -1;      // hulc_k_conv1_wgrad_u8's `form` (tests): 0 / 1 / 2 force the uint8 kernel form (-1: the engine's, 2)
-static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const h16_t* dY, float* part, float* bias_part, int Nf, int IH, int IW, int OH,
-                                        int OW, int max_blocks, int* work_ctr = nullptr) {
+// Kernel form and band height of one conv1 weight-gradient job: 1 = conv1_wgrad_tr2_kernel<6, 2> (fp32 frames), 2 = conv1_wgrad_tr2r_kernel<3, 2, true>,
+// 3 = conv1_wgrad_tr2r_kernel<4, 2>, 4 = conv1_wgrad_tr2u_kernel<12, 2> (uint8 frames), 5 = conv1_wgrad_tr_kernel (any shape)
+static inline int conv1_wgrad_plan(const Conv1Src& X, int IH, int IW, int OH, int OW, int& R_out, int& nb_out, size_t& lds_out) {
+    auto balanced = [&](int R) { const int nb = (OH + R - 1) / R; nb_out = nb; R_out = (OH + nb - 1) / nb; };
     if (!X.u8 && (IW % 4) == 0) {
         // tallest band whose images fit 2 workgroups per CU and whose chunks fit the prefetch slots (8 frame + 2 dY registers of 16 B per thread:
         // 10 + 3 slots spilled 46 registers of in-flight data at the 128-VGPR budget of 2 x 8 waves per CU, which serialised the prefetch)
@@ -1753,14 +1893,9 @@ static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const
         };
         while (R > 1 && !fits(R)) --R;
         if (fits(R)) {
-            const int nb = (OH + R - 1) / R;
-            R = (OH + nb - 1) / nb;
-            const size_t lds = std::max<size_t>(Wgrad1Cfg::lds_bytes(R, IW, OW), 512 * 8 * sizeof(float));
-            static bool attr2 = false;
-            if (!attr2) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2_kernel<6, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2 = true; }
-            const int grid = std::min(std::min(Nf, 512), max_blocks);
-            hipLaunchKernelGGL((conv1_wgrad_tr2_kernel<6, 2>), dim3(grid), dim3(512), lds, st, reinterpret_cast<const float*>(X.X), work_ctr, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb);
-            return grid;
+            balanced(R);
+            lds_out = std::max<size_t>(Wgrad1Cfg::lds_bytes(R_out, IW, OW), 512 * 8 * sizeof(float));
+            return 1;
         }
     }
     // uint8 forms: 2 = conversion from the prefetch registers with interior / row-end slots (conv1_wgrad_tr2r_kernel<3, 2, true>), 1 = one general slot kind, 0 = raw rows through LDS
@@ -1777,14 +1912,9 @@ static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const
         };
         while (R > 1 && !fits(R)) --R;
         if (fits(R)) {
-            const int nb = (OH + R - 1) / R;
-            R = (OH + nb - 1) / nb;
-            const size_t lds = std::max<size_t>(Wgrad1Cfg::lds_bytes(R, IW, OW, false), 32 * 1024);
-            static bool attr2s = false;
-            if (!attr2s) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2r_kernel<3, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2s = true; }
-            const int grid = std::min(std::min(Nf, 512), max_blocks);
-            hipLaunchKernelGGL((conv1_wgrad_tr2r_kernel<3, 2, true>), dim3(grid), dim3(512), lds, st, X, work_ctr, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb);
-            return grid;
+            balanced(R);
+            lds_out = std::max<size_t>(Wgrad1Cfg::lds_bytes(R_out, IW, OW, false), 32 * 1024);
+            return 2;
         }
     }
     if (X.u8 && (IW % 4) == 0 && IW >= 8 && u8form) {
@@ -1796,14 +1926,9 @@ static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const
         };
         while (R > 1 && !fits(R)) --R;
         if (fits(R)) {
-            const int nb = (OH + R - 1) / R;
-            R = (OH + nb - 1) / nb;
-            const size_t lds = std::max<size_t>(Wgrad1Cfg::lds_bytes(R, IW, OW, false), 32 * 1024);      // (>= the epilogue's reduction areas: 24.6 KB)
-            static bool attr2r = false;
-            if (!attr2r) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2r_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2r = true; }
-            const int grid = std::min(std::min(Nf, 512), max_blocks);
-            hipLaunchKernelGGL((conv1_wgrad_tr2r_kernel<4, 2>), dim3(grid), dim3(512), lds, st, X, work_ctr, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb);
-            return grid;
+            balanced(R);
+            lds_out = std::max<size_t>(Wgrad1Cfg::lds_bytes(R_out, IW, OW, false), 32 * 1024);      // (>= the epilogue's reduction areas: 24.6 KB)
+            return 3;
         }
     }
     if (X.u8 && (IW % 4) == 0) {
@@ -1815,29 +1940,91 @@ static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const
         };
         while (R > 1 && !fits(R)) --R;
         if (fits(R)) {
-            const int nb = (OH + R - 1) / R;
-            R = (OH + nb - 1) / nb;
-            const size_t lds = std::max<size_t>(Wgrad1Cfg::lds_bytes(R, IW, OW, true), 512 * 8 * sizeof(float));
-            static bool attr2u = false;
-            if (!attr2u) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2u_kernel<12, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2u = true; }
-            const int grid = std::min(std::min(Nf, 512), max_blocks);
-            hipLaunchKernelGGL((conv1_wgrad_tr2u_kernel<12, 2>), dim3(grid), dim3(512), lds, st, X, work_ctr, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb);
-            return grid;
+            balanced(R);
+            lds_out = std::max<size_t>(Wgrad1Cfg::lds_bytes(R_out, IW, OW, true), 512 * 8 * sizeof(float));
+            return 4;
         }
     }
     constexpr int lds_kb = 39;   // 4 workgroups per CU (0.44 vs 0.50 ms/step at 2 per CU with 78 KB bands)
     int R = OH;
     while (R > 1 && Wgrad1Cfg::lds_bytes(R, IW, OW, X.u8) > (size_t)lds_kb * 1024) --R;
-    const size_t lds = Wgrad1Cfg::lds_bytes(R, IW, OW, X.u8);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)conv1_wgrad_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-        attr_set = true;
+    R_out = R; nb_out = (OH + R - 1) / R;
+    lds_out = Wgrad1Cfg::lds_bytes(R, IW, OW, X.u8);
+    return 5;
+}
+// conv1's weight gradient for up to four jobs as ONE launch: the two cameras' frames (and, in the paired pass, each camera's two frame sources).  Every job must
+// take the same kernel form (else false: nothing launched); each job's band height is its own, the dynamic LDS the largest.  The launch's workgroups — as many as
+// one launch of the largest job would start — are divided over the jobs by camera_split on frames x bands x (multiply steps of 8 eight-pixel runs + 1), no job
+// more than its frames (work unit = frame); wg != nullptr: the counts as given (tests).  j[0].part = the slab area: job k's slabs lie behind job k - 1's
+// (part of the later jobs is set here).  ns[k] = slabs (= workgroups) of job k.
+static inline bool launch_conv1_wgrad_jobs(hipStream_t st, Wgrad1Job* j, int n, int max_blocks, const int* wg, int* ns) {
+    if (n < 1 || n > 4) return false;
+    int form = 0; size_t lds = 0; double w[4]; int cap = 0;
+    for (int k = 0; k < n; ++k) {
+        size_t l = 0;
+        const int f = conv1_wgrad_plan(j[k].S, j[k].IH, j[k].IW, j[k].OH, j[k].OW, j[k].R, j[k].nbands, l);
+        if (k && f != form) return false;
+        if (j[k].Nf < 1 || (f == 4 && n > 1)) return false;      // (the raw-row uint8 form takes one job)
+        form = f; lds = std::max(lds, l);
+        const int U = (j[k].OW + 7) / 8;
+        w[k] = (double)j[k].Nf * j[k].nbands * ((j[k].R * U + 7) / 8 + 1);
+        cap = std::max(cap, j[k].Nf);
     }
-    const int grid = Nf < max_blocks ? Nf : max_blocks;
-    Conv1Src X1 = X; X1.fold = 0;      // this (fallback) kernel writes the plain slab: it stages x itself
-    hipLaunchKernelGGL(conv1_wgrad_tr_kernel, dim3(grid), dim3(256), lds, st, X1, work_ctr, dY, part, bias_part, Nf, IH, IW, OH, OW, R);
-    return grid;
+    const int grid = std::min(form == 5 ? cap : std::min(cap, 512), max_blocks);
+    long long total = 0;
+    for (int k = 0; k < n; ++k) total += j[k].Nf;
+    if (wg) { for (int k = 0; k < n; ++k) ns[k] = std::min(std::max(wg[k], 1), j[k].Nf); }
+    else if (n == 1) ns[0] = grid;
+    else if (total <= std::min(form == 5 ? (int)total : 512, max_blocks)) { for (int k = 0; k < n; ++k) ns[k] = j[k].Nf; }      // (small calls) one frame per workgroup, as in separate launches
+    else {
+        if (grid < n) return false;
+        int left = grid; double wl = 0;
+        for (int k = 0; k < n; ++k) wl += w[k];
+        for (int k = n - 1; k > 0; --k) {          // job k against the jobs before it; those keep at least one workgroup each
+            int a, b;
+            camera_split(left, wl - w[k], w[k], a, b);
+            b = std::min(std::min(b, left - k), j[k].Nf);
+            ns[k] = b; left -= b; wl -= w[k];
+        }
+        ns[0] = std::min(left, j[0].Nf);
+    }
+    Wgrad1Batch bt{}; bt.n = n;
+    int blk = 0;
+    for (int k = 0; k < n; ++k) {
+        if (k) j[k].part = j[k - 1].part + (long long)ns[k - 1] * Wgrad1Cfg::CO * 192;
+        j[k].blk0 = blk; blk += ns[k];
+        bt.j[k] = j[k];
+    }
+    if (form == 1) {
+        static bool attr2 = false;
+        if (!attr2) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2_kernel<6, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2 = true; }
+        hipLaunchKernelGGL((conv1_wgrad_tr2_kernel<6, 2>), dim3(blk), dim3(512), lds, st, bt);
+    } else if (form == 2) {
+        static bool attr2s = false;
+        if (!attr2s) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2r_kernel<3, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2s = true; }
+        hipLaunchKernelGGL((conv1_wgrad_tr2r_kernel<3, 2, true>), dim3(blk), dim3(512), lds, st, bt);
+    } else if (form == 3) {
+        static bool attr2r = false;
+        if (!attr2r) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2r_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2r = true; }
+        hipLaunchKernelGGL((conv1_wgrad_tr2r_kernel<4, 2>), dim3(blk), dim3(512), lds, st, bt);
+    } else if (form == 4) {
+        static bool attr2u = false;
+        if (!attr2u) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2u_kernel<12, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2u = true; }
+        const Wgrad1Job& q = j[0];
+        hipLaunchKernelGGL((conv1_wgrad_tr2u_kernel<12, 2>), dim3(blk), dim3(512), lds, st, q.S, q.work_ctr, q.dY, q.part, q.bias_part, q.Nf, q.IH, q.IW, q.OH, q.OW, q.R, q.nbands);
+    } else {
+        static bool attr_set = false;
+        if (!attr_set) { hipFuncSetAttribute((const void*)conv1_wgrad_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr_set = true; }
+        for (int k = 0; k < n; ++k) bt.j[k].S.fold = 0;      // this (fallback) kernel writes the plain slab: it stages x itself
+        hipLaunchKernelGGL(conv1_wgrad_tr_kernel, dim3(blk), dim3(256), lds, st, bt);
+    }
+    return true;
+}
+static inline int launch_conv1_wgrad_tr(hipStream_t st, const Conv1Src& X, const h16_t* dY, float* part, float* bias_part, int Nf, int IH, int IW, int OH,
+                                        int OW, int max_blocks, int* work_ctr = nullptr) {
+    Wgrad1Job q{}; q.S = X; q.work_ctr = work_ctr; q.dY = dY; q.part = part; q.bias_part = bias_part; q.Nf = Nf; q.IH = IH; q.IW = IW; q.OH = OH; q.OW = OW;
+    int ns = 0;
+    return launch_conv1_wgrad_jobs(st, &q, 1, max_blocks, nullptr, &ns) ? ns : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -83,9 +83,10 @@
     bool pair = false; int pairBv = 0; hulc_batch cur2;
     float *act_j = nullptr, *ro_j = nullptr, *eps_j = nullptr, *losses2 = nullptr; int* aux_j = nullptr;
     // src2 (paired pass): frames [0, Nf/2) come from src, [Nf/2, Nf) from src2 — conv1 runs once per source, the rest on all Nf frames
-    void enc_fwd(const EncW& e, EncA& a, const Conv1Src& src, int Nf, int col0, const Conv1Src* src2 = nullptr, bool defer_tail = false) {
+    // phases: 1 = conv1, 2 = conv2, 4 = conv3, 8 = what follows conv3 (enc_fwd_both runs conv2 / conv3 of both cameras itself)
+    void enc_fwd(const EncW& e, EncA& a, const Conv1Src& src, int Nf, int col0, const Conv1Src* src2 = nullptr, bool defer_tail = false, int phases = 15) {
         ConvGeom g1 = geom(Nf, e.IH, 3, 8, 4), g2 = geom(Nf, e.H1, 32, 4, 2), g3 = geom(Nf, e.H2, 64, 3, 1);
-        for (int h = 0; h < (src2 ? 2 : 1); ++h) {
+        for (int h = 0; h < ((phases & 1) ? (src2 ? 2 : 1) : 0); ++h) {
             const Conv1Src& sh = h ? *src2 : src;
             const int nf = src2 ? Nf / 2 : Nf;
             const long long foff = h ? Nf / 2 : 0, poff = foff * g1.OH * g1.OW;
@@ -102,31 +103,31 @@
                 launch_gemm<T, 128, 32>(st, l, dense<T>(e.c1.Wf, 32, 192), dense_out(32), ep, nf * g1.OH * g1.OW, 32, 192);
             }
         }
-        bool tiled = false;
-        if constexpr (std::is_same<T, h16_t>::value) {   // raw-tile kernels (conv_tile.h): weights resident in LDS, bands streamed once
-            ConvTileP p2{}; p2.img = a.a1; p2.IMH = p2.IMW = e.H1; p2.w = e.c2.Wf; p2.out = a.a2; p2.OUTH = p2.OUTW = e.H2; p2.bias = e.c2.b32; p2.relu = 1; p2.Nf = Nf; p2.bits_out = a.m2bits;
-            ConvTileP p3{}; p3.img = a.a2; p3.IMH = p3.IMW = e.H2; p3.w = e.c3.Wf; p3.out = a.a3; p3.OUTH = p3.OUTW = e.H3; p3.bias = e.c3.b32; p3.relu = 1; p3.Nf = Nf;
-            const double px2 = (double)Nf * e.H2 * e.H2, px3 = (double)Nf * e.H3 * e.H3, px1 = (double)Nf * e.H1 * e.H1;
-            TimerScope ts(this, "conv_tile_fwd", "mfma", 2.0 * px2 * 64 * 512 + 2.0 * px3 * 64 * 576, (px1 * 32 + 2 * px2 * 64 + px3 * 64) * 2);
+        const bool do2 = (phases & 2) != 0, do3 = (phases & 4) != 0;
+        bool tiled = !do2 && !do3;
+        if constexpr (std::is_same<T, h16_t>::value) if (do2 || do3) {   // raw-tile kernels (conv_tile.h): weights resident in LDS, bands streamed once
+            const ConvTileP p2 = conv2_fwd_job(e, a, Nf), p3 = conv3_fwd_job(e, a, Nf);
+            TimerScope ts(this, "conv_tile_fwd", "mfma", conv_fwd_flops(e, Nf, do2, do3), conv_fwd_bytes(e, Nf, do2, do3));
             // weights-in-registers kernels (conv_reg.h): large maps (the static camera) take the one-workgroup form with the band-invariant DMA slot decode
             // held in registers (PKR), the gripper camera's stacked small maps the form with two co-resident 256-thread workgroups per CU (NWV = 4)
             const bool big = e.H2 >= 16;
-            const bool t2 = (big ? launch_conv_reg_fwd<32, 4, 4, 2>(st, p2) : launch_conv_reg<32, 4, 4, 2, false, 1, 4, 0, true>(st, p2)) || launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p2);
-            const bool t3 = (big ? launch_conv_reg_fwd<64, 3, 3, 1>(st, p3) : launch_conv_reg<64, 3, 3, 1, false, 1, 4>(st, p3)) || launch_conv_tile<64, 64, 3, 3, 1, 1, false>(st, p3);
+            const bool t2 = !do2 || (big ? launch_conv_reg_fwd<32, 4, 4, 2>(st, p2) : launch_conv_reg<32, 4, 4, 2, false, 1, 4, 0, true>(st, p2)) || launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p2);
+            const bool t3 = !do3 || (big ? launch_conv_reg_fwd<64, 3, 3, 1>(st, p3) : launch_conv_reg<64, 3, 3, 1, false, 1, 4>(st, p3)) || launch_conv_tile<64, 64, 3, 3, 1, 1, false>(st, p3);
             tiled = t2 && t3;
         }
         if (!tiled) {
-            {
+            if (do2) {
                 ConvNHWCLoader<T> l{a.a1, g2};
                 EpiP ep = epi(a.a2, false); ep.bias = e.c2.b32; ep.relu = 1;
                 launch_gemm<T, 128, 64>(st, l, dense<T>(e.c2.Wf, 64, 512), dense_out(64), ep, Nf * g2.OH * g2.OW, 64, 512);
             }
-            {
+            if (do3) {
                 ConvNHWCLoader<T> l{a.a2, g3};
                 EpiP ep = epi(a.a3, false); ep.bias = e.c3.b32; ep.relu = 1;
                 launch_gemm<T, 128, 64>(st, l, dense<T>(e.c3.Wf, 64, 576), dense_out(64), ep, Nf * g3.OH * g3.OW, 64, 576);
             }
         }
+        if (!(phases & 8)) return;
         const T* fin; int fk;
         if (!e.gripper) {
             if constexpr (std::is_same<T, h16_t>::value) hipLaunchKernelGGL(spatial_softmax_fwd64_kernel, dim3(Nf), dim3(256), 0, st, a.a3, e.H3, e.H3, a.ss, a.ssstats);
@@ -141,6 +142,43 @@
         { EpiP ep = epi(a.f1, false); ep.relu = 1; lin_fwd(fin, fk, Nf, e.fc1, ep, 512); }
         { EpiP ep = epi(a.f2, true); lin_fwd(a.f1, 512, Nf, e.fc2, ep, 64); }
         ln_fwd(a.f2, 64, Nf, 64, e.lng, e.lnb, emb + col0, EMB, nullptr, 0, a.lnst);
+    }
+    ConvTileP conv2_fwd_job(const EncW& e, EncA& a, int Nf) const {
+        ConvTileP p2{}; p2.img = a.a1; p2.IMH = p2.IMW = e.H1; p2.w = e.c2.Wf; p2.out = a.a2; p2.OUTH = p2.OUTW = e.H2; p2.bias = e.c2.b32; p2.relu = 1; p2.Nf = Nf; p2.bits_out = a.m2bits;
+        return p2;
+    }
+    ConvTileP conv3_fwd_job(const EncW& e, EncA& a, int Nf) const {
+        ConvTileP p3{}; p3.img = a.a2; p3.IMH = p3.IMW = e.H2; p3.w = e.c3.Wf; p3.out = a.a3; p3.OUTH = p3.OUTW = e.H3; p3.bias = e.c3.b32; p3.relu = 1; p3.Nf = Nf;
+        return p3;
+    }
+    static double conv_fwd_flops(const EncW& e, int Nf, bool c2, bool c3) { return (c2 ? 2.0 * Nf * e.H2 * e.H2 * 64 * 512 : 0.0) + (c3 ? 2.0 * Nf * e.H3 * e.H3 * 64 * 576 : 0.0); }
+    static double conv_fwd_bytes(const EncW& e, int Nf, bool c2, bool c3) {
+        const double px2 = (double)Nf * e.H2 * e.H2, px3 = (double)Nf * e.H3 * e.H3, px1 = (double)Nf * e.H1 * e.H1;
+        return ((c2 ? px1 * 32 + px2 * 64 : 0.0) + (c3 ? px2 * 64 + px3 * 64 : 0.0)) * 2;
+    }
+    // Both encoders' forward.  The two networks are independent, so in the 16-bit engines conv2 and conv3 of BOTH cameras are one launch per stage
+    // (conv_reg.h launch_conv_reg_jobs): the gripper camera's job runs in the static camera's 8-wave form on its share of the persistent workgroups,
+    // its prologue and tail under the static job's throughput.  A shape the merged launch does not take goes the per-camera way (shape-decided).
+    void enc_fwd_both(const Conv1Src& srcS, const Conv1Src& srcG, int Nf, const Conv1Src* src2s, const Conv1Src* src2g, bool defer_tail) {
+        if constexpr (std::is_same<T, h16_t>::value) {
+            enc_fwd(encS, aS, srcS, Nf, 0, src2s, defer_tail, 1);
+            enc_fwd(encG, aG, srcG, Nf, 64, src2g, defer_tail, 1);
+            bool m2, m3 = false;
+            {
+                const ConvTileP j2[2] = {conv2_fwd_job(encS, aS, Nf), conv2_fwd_job(encG, aG, Nf)}, j3[2] = {conv3_fwd_job(encS, aS, Nf), conv3_fwd_job(encG, aG, Nf)};
+                TimerScope ts(this, "conv_tile_fwd", "mfma", 0, 0, 0);      // accounted per launch that was taken: what falls back accounts for itself
+                m2 = launch_conv_reg_fwd_jobs<32, 4, 4, 2>(st, j2, 2);
+                if (m2) ts.add(conv_fwd_flops(encS, Nf, true, false) + conv_fwd_flops(encG, Nf, true, false), conv_fwd_bytes(encS, Nf, true, false) + conv_fwd_bytes(encG, Nf, true, false));
+                if (m2) m3 = launch_conv_reg_fwd_jobs<64, 3, 3, 1>(st, j3, 2);
+                if (m3) ts.add(conv_fwd_flops(encS, Nf, false, true) + conv_fwd_flops(encG, Nf, false, true), conv_fwd_bytes(encS, Nf, false, true) + conv_fwd_bytes(encG, Nf, false, true));
+            }
+            const int rest = (m2 ? 0 : 2) | (m3 ? 0 : 4) | 8;
+            enc_fwd(encS, aS, srcS, Nf, 0, src2s, defer_tail, rest);
+            enc_fwd(encG, aG, srcG, Nf, 64, src2g, defer_tail, rest);
+        } else {
+            enc_fwd(encS, aS, srcS, Nf, 0, src2s, defer_tail);
+            enc_fwd(encG, aG, srcG, Nf, 64, src2g, defer_tail);
+        }
     }
     // enc_tail.h is written for the reference's tail widths (128 -> 512 -> 64, vision_network.py:46-52 / vision_network_gripper.py:18-27) and EMB = 2 x 64
     bool enc_tail_fusable() const {
@@ -285,32 +323,132 @@
                            c.dW, c.O, c.I, c.KH, c.KW, c.nhwc);
         if (!bias_done) colsum(dy, c.O, (int)npix, c.O, c.db);
     }
+    // conv3's or conv2's weight gradient for BOTH cameras as one launch (conv_wgrad.h launch_conv_wgrad_pair); both jobs' slabs go into the one batched
+    // unpack launch whatever their number (the gripper job has fewer than the 64 that send a single launch's slabs there).  false = nothing launched
+    bool conv_wgrad_both(const ConvW& cS, const ConvW& cG, const T* dyS, const T* dyG, const T* xS, const T* xG, const ConvGeom& gS, const ConvGeom& gG) {
+        if constexpr (std::is_same<T, h16_t>::value) {
+            const int Kc = cS.I * cS.KH * cS.KW;
+            const int64_t slab = (int64_t)cS.O * Kc;
+            if (cG.I != cS.I || cG.KH != cS.KH || cG.O != cS.O || cS.O != 64 || unpack_jobs.n + 2 > 12 || part_cur + 256 * slab > this->partcap) return false;
+            auto job = [&](const ConvW& c, const T* dy, const T* x, const ConvGeom& g) {
+                WgradJob J{}; J.X = x; J.dY = dy; J.bias_part = c.db; J.zeros = wgrad_zero_page(); J.Nf = g.Nf; J.IH = g.IH; J.IW = g.IW; J.OH = g.OH; J.OW = g.OW; J.work_ctr = next_ctr(); J.FPB = 1;
+                return J;
+            };
+            WgradJob A = job(cS, dyS, xS, gS), B = job(cG, dyG, xG, gG);
+            A.part = this->part + part_cur;
+            auto fl = [&](const ConvGeom& g) { return 2.0 * g.Nf * g.OH * g.OW * cS.O * Kc; };
+            auto by = [&](const ConvGeom& g) { return (double)g.Nf * g.IH * g.IW * cS.I * 2 + (double)g.Nf * g.OH * g.OW * cS.O * 2; };
+            int ns[2] = {0, 0};
+            bool ok = false;
+            {
+                TimerScope ts(this, "conv_wgrad_tr", "mfma", 0, 0, 0);
+                if (cS.I == 64 && cS.KH == 3) ok = launch_conv_wgrad_pair<64, 64, 3, 3, 1>(st, A, B, 512, nullptr, ns);
+                else if (cS.I == 32 && cS.KH == 4) ok = launch_conv_wgrad_pair<32, 64, 4, 4, 2>(st, A, B, 512, nullptr, ns);
+                if (ok) ts.add(fl(gS) + fl(gG), by(gS) + by(gG));
+            }
+            if (!ok) return false;
+            const ConvW* cw[2] = {&cS, &cG};
+            for (int k = 0; k < 2; ++k) {
+                UnpackJob& J = unpack_jobs.j[unpack_jobs.n++];
+                J.part = this->part + part_cur; J.grad = cw[k]->dW; J.slab = slab; J.nsplit = ns[k]; J.O = cS.O; J.I = cS.I; J.KH = cS.KH; J.KW = cS.KW; J.nhwc = cw[k]->nhwc; J.blk0 = unpack_blocks; J.ysplit = 0;
+                unpack_blocks += cdiv(cS.O * Kc, 1024); part_cur += (int64_t)ns[k] * slab;
+            }
+            return true;
+        }
+        return false;
+    }
+    // conv1's weight gradient for BOTH cameras (and, in the paired pass, both frame sources of each) as one launch (conv_wgrad.h launch_conv1_wgrad_jobs):
+    // the jobs are [static: source, second source | gripper: source, second source], so a camera's slabs lie together and are one job of the batched unpack.
+    // false = nothing launched (the cameras' frames take different kernel forms, or no room for the slabs): the caller runs conv_wgrad per camera
+    bool conv1_wgrad_both(const Conv1Src& srcS, const Conv1Src& srcG, int Nf, const Conv1Src* src2s, const Conv1Src* src2g) {
+        if constexpr (std::is_same<T, h16_t>::value) {
+            const ConvW &cS = encS.c1, &cG = encG.c1;
+            const int Kc = cS.I * cS.KH * cS.KW;
+            const int64_t slab = (int64_t)cS.O * Kc;
+            if (cS.O != 32 || cG.O != 32 || Kc != 192 || cG.I * cG.KH * cG.KW != 192 || (src2s == nullptr) != (src2g == nullptr)) return false;
+            if (unpack_jobs.n + 2 > 12 || part_cur + 1024 * slab > this->partcap) return false;      // (at most max_blocks = 1024 slabs)
+            const int ns_src = src2s ? 2 : 1, nf = src2s ? Nf / 2 : Nf;
+            Wgrad1Job J[4]; int nj = 0;
+            double fl = 0, by = 0;
+            for (int cam = 0; cam < 2; ++cam) {
+                const EncW& e = cam ? encG : encS;
+                const ConvGeom g = geom(nf, e.IH, 3, 8, 4);
+                for (int h = 0; h < ns_src; ++h) {
+                    const Conv1Src& sh = h ? (cam ? *src2g : *src2s) : (cam ? srcG : srcS);
+                    Wgrad1Job q{}; q.S = sh; q.work_ctr = next_ctr(); q.dY = (cam ? dact1g : this->dact1) + (long long)h * nf * g.OH * g.OW * 32; q.bias_part = (cam ? cG : cS).db;
+                    q.Nf = nf; q.IH = g.IH; q.IW = g.IW; q.OH = g.OH; q.OW = g.OW;
+                    J[nj++] = q;
+                    fl += 2.0 * nf * g.OH * g.OW * 32 * Kc; by += (double)nf * 3 * g.IH * g.IW * (sh.u8 ? 1 : 4) + (double)nf * g.OH * g.OW * 32 * 2;
+                }
+            }
+            J[0].part = this->part + part_cur;
+            int ns[4] = {0, 0, 0, 0};
+            {
+                TimerScope ts(this, "conv1_wgrad", "hbm", 0, 0, 0);
+                if (!launch_conv1_wgrad_jobs(st, J, nj, 1024, nullptr, ns)) return false;
+                ts.add(fl, by);
+            }
+            for (int cam = 0; cam < 2; ++cam) {
+                const ConvW& c = cam ? cG : cS;
+                int nsl = 0;
+                for (int h = 0; h < ns_src; ++h) nsl += ns[cam * ns_src + h];
+                UnpackJob& U = unpack_jobs.j[unpack_jobs.n++];
+                U.part = this->part + part_cur; U.grad = c.dW; U.slab = slab; U.nsplit = nsl; U.O = c.O; U.I = c.I; U.KH = c.KH; U.KW = c.KW; U.nhwc = c.nhwc; U.blk0 = unpack_blocks; U.ysplit = 0;
+                unpack_blocks += cdiv(c.O * Kc, 1024); part_cur += (int64_t)nsl * slab;
+            }
+            return true;
+        }
+        return false;
+    }
     h16_t* zero_page = nullptr;
     const h16_t* wgrad_zero_page() {
         if constexpr (std::is_same<T, h16_t>::value) { if (!zero_page) zero_page = alloc<h16_t>(128); }     // zero-initialised by alloc()
         return zero_page;
     }
+    ConvTileP conv_dgrad_job(const ConvW& c, const T* dy, const ConvGeom& g, T* dx, const T* mask, const unsigned* maskbits) {
+        ConvTileP p{};
+        if constexpr (std::is_same<T, h16_t>::value) {
+            p.img = dy; p.IMH = g.OH; p.IMW = g.OW; p.w = c.Wd; p.out = dx; p.OUTH = g.IH; p.OUTW = g.IW; p.mask = maskbits ? nullptr : mask; p.maskbits = maskbits; p.Nf = g.Nf; p.work_ctr = next_ctr();
+            if (!zero_page) zero_page = alloc<h16_t>(128);      // zero-initialised by alloc(): the staged zero border of the data-gradient form
+            p.zeros = zero_page;
+            if (!dump_page) dump_page = alloc<h16_t>(4096);
+            p.dump = dump_page;
+        }
+        return p;
+    }
+    // algorithmic bytes as SURVEY 8(d) counts them: dY read once, dX written once, 2 B each; the ReLU mask of the layer below is read as BIT words
+    // (pin * I / 8 bytes) when the forward left them, as a second 16-bit activation read otherwise (VERDICT r5 weak #4: the bit form was priced as a full read)
+    static double conv_dgrad_flops(const ConvW& c, const ConvGeom& g) { return 2.0 * g.Nf * g.OH * g.OW * c.O * c.I * c.KH * c.KW; }
+    static double conv_dgrad_bytes(const ConvW& c, const ConvGeom& g, bool bits, bool mask) {
+        const double pin = (double)g.Nf * g.IH * g.IW, pout = (double)g.Nf * g.OH * g.OW;
+        return (pout * c.O + pin * c.I) * 2 + (bits ? pin * c.I / 8 : (mask ? pin * c.I * 2 : 0));
+    }
+    // the data gradient of one stage (conv3 or conv2) for BOTH cameras as one launch: the production bitmask form, both jobs on the same instantiation.
+    // false = nothing launched (a shape / mask form the merged launch does not take): the caller runs conv_dgrad per camera
+    bool conv_dgrad_both(const ConvW& cS, const ConvW& cG, const T* dyS, const T* dyG, const ConvGeom& gS, const ConvGeom& gG, T* dxS, T* dxG, const unsigned* bitsS, const unsigned* bitsG) {
+        if constexpr (std::is_same<T, h16_t>::value) {
+            if (!bitsS || !bitsG) return false;
+            const bool k3 = cS.KH == 3 && cS.S == 1 && cS.I == 64 && cS.O == 64 && cG.KH == 3 && cG.S == 1 && cG.I == 64 && cG.O == 64;
+            const bool k2 = cS.KH == 4 && cS.S == 2 && cS.I == 32 && cS.O == 64 && cG.KH == 4 && cG.S == 2 && cG.I == 32 && cG.O == 64;
+            if (!k3 && !k2) return false;
+            const ConvTileP j[2] = {conv_dgrad_job(cS, dyS, gS, dxS, nullptr, bitsS), conv_dgrad_job(cG, dyG, gG, dxG, nullptr, bitsG)};
+            TimerScope ts(this, "conv_tile_dgrad", "mfma", 0, 0, 0);
+            const bool ok = k3 ? launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, j, 2) : launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, j, 2);
+            if (ok) ts.add(conv_dgrad_flops(cS, gS) + conv_dgrad_flops(cG, gG), conv_dgrad_bytes(cS, gS, true, false) + conv_dgrad_bytes(cG, gG, true, false));
+            return ok;
+        }
+        return false;
+    }
     void conv_dgrad(const ConvW& c, const T* dy, const ConvGeom& g, T* dx, const T* mask, const unsigned* maskbits = nullptr) {
         if constexpr (std::is_same<T, h16_t>::value) {
-            ConvTileP p{}; p.img = dy; p.IMH = g.OH; p.IMW = g.OW; p.w = c.Wd; p.out = dx; p.OUTH = g.IH; p.OUTW = g.IW; p.mask = maskbits ? nullptr : mask; p.maskbits = maskbits; p.Nf = g.Nf; p.work_ctr = next_ctr();
+            ConvTileP p = conv_dgrad_job(c, dy, g, dx, mask, maskbits);
             bool ok = false;
-            const double pin = (double)g.Nf * g.IH * g.IW, pout = (double)g.Nf * g.OH * g.OW;
-            // algorithmic bytes as SURVEY 8(d) counts them: dY read once, dX written once, 2 B each; the ReLU mask of the layer below is read as BIT words
-            // (pin * I / 8 bytes) when the forward left them, as a second 16-bit activation read otherwise (VERDICT r5 weak #4: the bit form was priced as a full read)
-            TimerScope ts(this, "conv_tile_dgrad", "mfma", 2.0 * pout * c.O * c.I * c.KH * c.KW, (pout * c.O + pin * c.I) * 2 + (maskbits ? pin * c.I / 8 : (mask ? pin * c.I * 2 : 0)));
+            TimerScope ts(this, "conv_tile_dgrad", "mfma", conv_dgrad_flops(c, g), conv_dgrad_bytes(c, g, maskbits != nullptr, mask != nullptr));
             // both data gradients run on conv_reg.h's pipelined-epilogue form (EPI: a tile's epilogue rides in the next tile's multiply loop), two 256-thread workgroups per CU
             if (c.KH == 3 && c.S == 1 && c.I == 64 && c.O == 64) {
-                if (!zero_page) zero_page = alloc<h16_t>(128);      // zero-initialised by alloc(): the staged zero border of the data-gradient form
-                p.zeros = zero_page;
-                if (!dump_page) dump_page = alloc<h16_t>(4096);
-                p.dump = dump_page;
                 ok = (maskbits && launch_conv_reg<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, p)) || launch_conv_tile<64, 64, 3, 3, 1, 1, true>(st, p);
             }
             else if (c.KH == 4 && c.S == 2 && c.I == 32 && c.O == 64) {
-                if (!zero_page) zero_page = alloc<h16_t>(128);
-                p.zeros = zero_page;
-                if (!dump_page) dump_page = alloc<h16_t>(4096);
-                p.dump = dump_page;
                 ok = (maskbits && launch_conv_reg<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, p)) || launch_conv_tile<64, 32, 2, 2, 1, 2, true>(st, p);
             }
             if (ok) return;
@@ -344,39 +482,48 @@
         O o; int zc;
         DEVI long long offset(int r, int) const { return o.offset(r, zc); }
     };
-    void enc_bwd(const EncW& e, EncA& a, const Conv1Src& src, int Nf, int col0, const Conv1Src* src2 = nullptr, bool tail_done = false) {
+    // phases: 1 = everything down to the gradient of a3, 2 / 8 / 32 = the weight gradients of conv3 / conv2 / conv1, 4 / 16 = the data gradients of conv3 / conv2
+    // (enc_bwd_both runs the data gradients of both cameras itself).  The gripper camera has its own gradient buffers in the 16-bit engines: both
+    // cameras' gradients of a stage are alive at once there.
+    void enc_bwd(const EncW& e, EncA& a, const Conv1Src& src, int Nf, int col0, const Conv1Src* src2 = nullptr, bool tail_done = false, int phases = 63) {
         wgrad_src = src;
+        T* const dact1 = e.gripper && dact1g ? dact1g : this->dact1;
+        T* const dact2 = e.gripper && dact2g ? dact2g : this->dact2;
+        T* const dact3 = e.gripper && dact3g ? dact3g : this->dact3;
         const float* x = nullptr;
         if constexpr (std::is_same<T, float>::value) x = src.u8 ? x32[e.gripper ? 1 : 0] : reinterpret_cast<const float*>(src.X);   // materialised by the forward
         ConvGeom g1 = geom(Nf, e.IH, 3, 8, 4), g2 = geom(Nf, e.H1, 32, 4, 2), g3 = geom(Nf, e.H2, 64, 3, 1);
         T* const d_f1 = tail_done && e.gripper ? d_f1g : this->d_f1;
         T* const d_f2t = tail_done && e.gripper ? d_f2tg : this->d_f2t;
-        // LN bwd on demb[:, col0:col0+64]
-        if (!tail_done) ln_bwd(demb + col0, EMB, a.f2, 64, a.lnst, e.lng, Nf, 64, nullptr, 0, 0, d_f2t, 64, e.dlng, e.dlnb);
-        // fc2
-        if (!tail_done) { EpiP ep = epi(d_f1, false); ep.mask = a.f1; lin_dgrad(d_f2t, Nf, e.fc2, ep, dense_out(512)); }
-        const bool wdone = tail_done;       // enc_tail_bwd_both ran the tails' weight gradients too
-        if (!wdone) lin_wgrad(d_f2t, a.f1, 512, Nf, 64, 512, e.fc2.dW, 512, e.fc2.db);
-        const int H3 = e.H3;
-        if (!e.gripper) {
-            if (!tail_done) { EpiP ep = epi(d_ss, true); lin_dgrad(d_f1, Nf, e.fc1, ep, dense_out(128)); }
-            if (!wdone) lin_wgrad(d_f1, a.ss, 128, Nf, 512, 128, e.fc1.dW, 128, e.fc1.db);
-            if constexpr (std::is_same<T, h16_t>::value) hipLaunchKernelGGL(spatial_softmax_bwd64_kernel, dim3(Nf), dim3(256), 0, st, a.a3, a.ssstats, d_ss, H3, H3, dact3);
-            else hipLaunchKernelGGL((spatial_softmax_bwd_kernel<T>), dim3(Nf), dim3(256), 0, st, a.a3, a.ssstats, d_ss, H3, H3, 64, dact3);
-        } else {
-            if (!tail_done) { EpiP ep = epi(d_g0, false); ep.mask = a.g0; lin_dgrad(d_f1, Nf, e.fc1, ep, dense_out(128)); }
-            if (!wdone) lin_wgrad(d_f1, a.g0, 128, Nf, 512, 128, e.fc1.dW, 128, e.fc1.db);
-            { EpiP ep = epi(dact3, false); ep.mask = a.a3; lin_dgrad(d_g0, Nf, e.fc7, ep, dense_out(3136)); }
-            // dW7 in packed (NHWC) column order -> temp, then permute-accumulate into the torch-layout grad
-            if (!(wdone && tail_fc7_done)) {
-                lin_wgrad(d_g0, a.a3, 3136, Nf, 128, 3136, dw7_tmp, 3136, e.fc7.db);
-                hipLaunchKernelGGL((permute_cols_kernel<float, float>), dim3(cdiv(128 * 3136, 256)), dim3(256), 0, st, dw7_tmp, e.fc7.dW, 128, 64, 49, 1, 1);
+        if (phases & 1) {
+            // LN bwd on demb[:, col0:col0+64]
+            if (!tail_done) ln_bwd(demb + col0, EMB, a.f2, 64, a.lnst, e.lng, Nf, 64, nullptr, 0, 0, d_f2t, 64, e.dlng, e.dlnb);
+            // fc2
+            if (!tail_done) { EpiP ep = epi(d_f1, false); ep.mask = a.f1; lin_dgrad(d_f2t, Nf, e.fc2, ep, dense_out(512)); }
+            const bool wdone = tail_done;       // enc_tail_bwd_both ran the tails' weight gradients too
+            if (!wdone) lin_wgrad(d_f2t, a.f1, 512, Nf, 64, 512, e.fc2.dW, 512, e.fc2.db);
+            const int H3 = e.H3;
+            if (!e.gripper) {
+                if (!tail_done) { EpiP ep = epi(d_ss, true); lin_dgrad(d_f1, Nf, e.fc1, ep, dense_out(128)); }
+                if (!wdone) lin_wgrad(d_f1, a.ss, 128, Nf, 512, 128, e.fc1.dW, 128, e.fc1.db);
+                if constexpr (std::is_same<T, h16_t>::value) hipLaunchKernelGGL(spatial_softmax_bwd64_kernel, dim3(Nf), dim3(256), 0, st, a.a3, a.ssstats, d_ss, H3, H3, dact3);
+                else hipLaunchKernelGGL((spatial_softmax_bwd_kernel<T>), dim3(Nf), dim3(256), 0, st, a.a3, a.ssstats, d_ss, H3, H3, 64, dact3);
+            } else {
+                if (!tail_done) { EpiP ep = epi(d_g0, false); ep.mask = a.g0; lin_dgrad(d_f1, Nf, e.fc1, ep, dense_out(128)); }
+                if (!wdone) lin_wgrad(d_f1, a.g0, 128, Nf, 512, 128, e.fc1.dW, 128, e.fc1.db);
+                { EpiP ep = epi(dact3, false); ep.mask = a.a3; lin_dgrad(d_g0, Nf, e.fc7, ep, dense_out(3136)); }
+                // dW7 in packed (NHWC) column order -> temp, then permute-accumulate into the torch-layout grad
+                if (!(wdone && tail_fc7_done)) {
+                    lin_wgrad(d_g0, a.a3, 3136, Nf, 128, 3136, dw7_tmp, 3136, e.fc7.db);
+                    hipLaunchKernelGGL((permute_cols_kernel<float, float>), dim3(cdiv(128 * 3136, 256)), dim3(256), 0, st, dw7_tmp, e.fc7.dW, 128, 64, 49, 1, 1);
+                }
             }
         }
-        conv_wgrad(e.c3, dact3, a.a2, g3, false);
-        conv_dgrad(e.c3, dact3, g3, dact2, a.a2, a.m2bits);
-        conv_wgrad(e.c2, dact2, a.a1, g2, false);
-        conv_dgrad(e.c2, dact2, g2, dact1, a.a1, a.m1bits);
+        if (phases & 2) conv_wgrad(e.c3, dact3, a.a2, g3, false);
+        if (phases & 4) conv_dgrad(e.c3, dact3, g3, dact2, a.a2, a.m2bits);
+        if (phases & 8) conv_wgrad(e.c2, dact2, a.a1, g2, false);
+        if (phases & 16) conv_dgrad(e.c2, dact2, g2, dact1, a.a1, a.m1bits);
+        if (!(phases & 32)) return;
         if (!src2) { conv_wgrad(e.c1, dact1, x, g1, true); return; }
         for (int h = 0; h < 2; ++h) {          // paired pass: the weight gradient of conv1 once per frame source
             const Conv1Src& sh = h ? *src2 : src;
@@ -386,5 +533,35 @@
             if constexpr (std::is_same<T, float>::value) xh = sh.u8 ? x32[e.gripper ? 1 : 0] + foff * 3 * e.IH * e.IH : reinterpret_cast<const float*>(sh.X);
             conv_wgrad(e.c1, dact1 + foff * g1.OH * g1.OW * 32, xh, geom(Nf / 2, e.IH, 3, 8, 4), true);
         }
+    }
+    // Both encoders' backward: per camera down to the gradient of a3, then stage by stage — the weight gradient
+    // and the data gradient of a stage for both cameras as one launch each (conv_wgrad_both, conv_dgrad_both, conv1_wgrad_both)
+    void enc_bwd_both(const Conv1Src& srcS, const Conv1Src& srcG, int Nf, const Conv1Src* src2s, const Conv1Src* src2g, bool tail_done) {
+        if constexpr (std::is_same<T, h16_t>::value) {
+            if (dact1g && dact2g && dact3g) {
+                ConvGeom g2S = geom(Nf, encS.H1, 32, 4, 2), g3S = geom(Nf, encS.H2, 64, 3, 1), g2G = geom(Nf, encG.H1, 32, 4, 2), g3G = geom(Nf, encG.H2, 64, 3, 1);
+                enc_bwd(encS, aS, srcS, Nf, 0, src2s, tail_done, 1);
+                enc_bwd(encG, aG, srcG, Nf, 64, src2g, tail_done, 1);
+                if (!conv_wgrad_both(encS.c3, encG.c3, dact3, dact3g, aS.a2, aG.a2, g3S, g3G)) {
+                    enc_bwd(encS, aS, srcS, Nf, 0, src2s, tail_done, 2);
+                    enc_bwd(encG, aG, srcG, Nf, 64, src2g, tail_done, 2);
+                }
+                const bool m3 = conv_dgrad_both(encS.c3, encG.c3, dact3, dact3g, g3S, g3G, dact2, dact2g, aS.m2bits, aG.m2bits);
+                if (!m3) { enc_bwd(encS, aS, srcS, Nf, 0, src2s, tail_done, 4); enc_bwd(encG, aG, srcG, Nf, 64, src2g, tail_done, 4); }
+                if (!conv_wgrad_both(encS.c2, encG.c2, dact2, dact2g, aS.a1, aG.a1, g2S, g2G)) {
+                    enc_bwd(encS, aS, srcS, Nf, 0, src2s, tail_done, 8);
+                    enc_bwd(encG, aG, srcG, Nf, 64, src2g, tail_done, 8);
+                }
+                const bool m2 = conv_dgrad_both(encS.c2, encG.c2, dact2, dact2g, g2S, g2G, dact1, dact1g, aS.m1bits, aG.m1bits);
+                if (!m2) { enc_bwd(encS, aS, srcS, Nf, 0, src2s, tail_done, 16); enc_bwd(encG, aG, srcG, Nf, 64, src2g, tail_done, 16); }
+                if (!conv1_wgrad_both(srcS, srcG, Nf, src2s, src2g)) {
+                    enc_bwd(encS, aS, srcS, Nf, 0, src2s, tail_done, 32);
+                    enc_bwd(encG, aG, srcG, Nf, 64, src2g, tail_done, 32);
+                }
+                return;
+            }
+        }
+        enc_bwd(encS, aS, srcS, Nf, 0, src2s, tail_done);
+        enc_bwd(encG, aG, srcG, Nf, 64, src2g, tail_done);
     }
 

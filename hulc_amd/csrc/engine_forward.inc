@@ -76,8 +76,7 @@
         {
             const Conv1Src s2s = conv1_src(cur2, false), s2g = conv1_src(cur2, true);
             const bool tail_fused = enc_tail_fusable();
-            enc_fwd(encS, aS, conv1_src(*b, false), N, 0, pair ? &s2s : nullptr, tail_fused);
-            enc_fwd(encG, aG, conv1_src(*b, true), N, 64, pair ? &s2g : nullptr, tail_fused);
+            enc_fwd_both(conv1_src(*b, false), conv1_src(*b, true), N, pair ? &s2s : nullptr, pair ? &s2g : nullptr, tail_fused);
             x0_done = false;
             if (tail_fused) enc_tail_fwd_both(N, !mcil && tr_fused_mode && S <= 64 && EMB == 128, S, dp);
         }

@@ -259,8 +259,7 @@
         hulc_batch bb; memset(&bb, 0, sizeof(bb));
         bb.B = 1; bb.S = 1; bb.step = roll_counter++;
         cur = bb;
-        enc_fwd(encS, aS, Conv1Src{obs->rgb_static, nullptr, 0, 0}, 1, 0);
-        enc_fwd(encG, aG, Conv1Src{obs->rgb_gripper, nullptr, 0, 0}, 1, 64);
+        enc_fwd_both(Conv1Src{obs->rgb_static, nullptr, 0, 0}, Conv1Src{obs->rgb_gripper, nullptr, 0, 0}, 1, nullptr, nullptr, false);
         HIP_CHECK(hipMemcpyAsync(goal_t, roll_goal, sizeof(T) * GOAL, hipMemcpyDeviceToDevice, st));
         if (mcil) HIP_CHECK(hipMemcpyAsync(plan_t, roll_plan_c, sizeof(T) * (PLAN / 2), hipMemcpyDeviceToDevice, st));
         dec_fwd(roll_plan, 1, 1, roll_has_h ? roll_h0 : nullptr, roll_has_h ? roll_h1 : nullptr);

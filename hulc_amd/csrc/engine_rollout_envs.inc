@@ -172,8 +172,7 @@
         HIP_CHECK(hipMemcpyAsync(env_ro, obs->robot_obs_raw, sizeof(float) * 15 * n, hipMemcpyDefault, st));
         if (u_mix) { HIP_CHECK(hipMemcpyAsync(nz_mix, u_mix, sizeof(float) * n * NDIM * NMIX, hipMemcpyDefault, st)); u_mix = nz_mix; }
         if (u_act) { HIP_CHECK(hipMemcpyAsync(nz_act, u_act, sizeof(float) * n * NDIM, hipMemcpyDefault, st)); u_act = nz_act; }
-        enc_fwd(encS, aS, Conv1Src{obs->rgb_static, nullptr, 0, 0}, n, 0);
-        enc_fwd(encG, aG, Conv1Src{obs->rgb_gripper, nullptr, 0, 0}, n, 64);
+        enc_fwd_both(Conv1Src{obs->rgb_static, nullptr, 0, 0}, Conv1Src{obs->rgb_gripper, nullptr, 0, 0}, n, nullptr, nullptr, false);
         if constexpr (std::is_same<T, h16_t>::value) {
             // embedding -> actions: three launches, no copy (rollout_step.h)
             auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };

@@ -149,6 +149,8 @@ struct IEngine {
             t->flops += flops; t->bytes += bytes; t->launches += nlaunch;
             hipEventRecord(t->ev[t->used].first, e->st);
         }
+        // work of a launch that is known only once the launcher has taken the shape (scope opened with 0 flops / bytes / launches)
+        void add(double flops, double bytes, int nlaunch = 1) { if (t) { t->flops += flops; t->bytes += bytes; t->launches += nlaunch; } }
         ~TimerScope() { if (t) { hipEventRecord(t->ev[t->used].second, e->st); t->used++; e->timer_depth--; } }
     };
     int timers_read(char* out, int64_t cap, bool reset) {

@@ -440,6 +440,25 @@ int hulc_k_conv1_wgrad_u8(const void* X, const int32_t* shifts, int32_t pad, con
  * bitmask words (2 / 1 per output pixel).  relu: bit 0 = ReLU, bit 5 (32) = dynamic work claiming, bits 1..4 = bench ablations. */
 int hulc_k_conv_tile(int32_t mode, const void* img, const void* w, const float* bias, const void* mask, void* out, int32_t Nf, int32_t IMH,
                      int32_t OUTH, int32_t relu, void* hip_stream);
+/* host arithmetic only: how a launch of `grid` persistent workgroups is divided between the two cameras' jobs of one stage: the gripper job gets
+ * round(grid * work_gripper / (work_static + work_gripper)), both at least 1 and the two sum to grid; work_gripper <= 0 (one job): the whole grid is the
+ * static job's.  work = a job's multiply work in the launchers' cost-model units (items x rounds per item). */
+int hulc_k_camera_split(int32_t grid, double work_static, double work_gripper, int32_t* wg_static, int32_t* wg_gripper);
+/* One encoder stage for BOTH cameras as one launch (bf16 NHWC, square frames), in the forms the engine runs.  A job = one camera's operands:
+ * forward: in = the layer input (side in_side), w = [co][(kh,kw,ci)], bias fp32, out (side out_side), bits = NULL or (conv2) the ReLU bit words of the
+ * output, uint32 [frames][out_side][out_side][2];  data gradient: in = dY (side in_side), w = per-parity [class][ci][(a,b,co)], out = dX (side out_side),
+ * bits = the ReLU bit words of the layer input (2 / 1 words per pixel for conv3 / conv2), bias unused.
+ * weight gradient (conv3 / conv2; both jobs required; synchronises): in = the layer input X (side in_side), w = dY (side out_side), out = dW fp32 [64][KH*KW*CI] in
+ * packed (kh,kw,ci) order and bits = db fp32 [64], both overwritten; job a must have the static camera's maps, job b the gripper camera's.
+ * conv1's weight gradient: in = fp32 NCHW frames (3, in_side, in_side), w = dY (side out_side, 32 channels), out = dW fp32 [32][192] in (c,kh,kw) order, bits = db fp32 [32].
+ * The weight-gradient jobs claim their work dynamically, each through a counter of its own, as in the engine.
+ * wg_a / wg_b = the workgroups of each job (>= 1; a job never gets more than it has items).  b == NULL: job a alone.  Asynchronous on hip_stream unless noted. */
+typedef struct hulc_conv_job {
+    const void* in; const void* w; const float* bias; void* out; void* bits;
+    int32_t frames, in_side, out_side;
+} hulc_conv_job;
+enum { HULC_PAIR_CONV2_FWD = 2, HULC_PAIR_CONV3_FWD = 3, HULC_PAIR_CONV2_DGRAD = 12, HULC_PAIR_CONV3_DGRAD = 13, HULC_PAIR_CONV1_WGRAD = 21, HULC_PAIR_CONV2_WGRAD = 22, HULC_PAIR_CONV3_WGRAD = 23 };
+int hulc_k_conv_pair(int32_t stage, const hulc_conv_job* a, const hulc_conv_job* b, int32_t wg_a, int32_t wg_b, void* hip_stream);
 /* skinny GEMM kernel alone (bf16 in / bf16 out), variant = waves*10 + row-tiles-per-workgroup; 300 = the production router; 400 = TWO
  * independent problems in one launch (second one at A + M*K, W + N*K, out + M*N; 32 < M <= 64, K = 2048); 500 = W repacked into the
  * fragment order first (every 16-row x 32-column block = 1 KB in MFMA lane order) and read that way by the K-chunked kernel (K = n x 2048,

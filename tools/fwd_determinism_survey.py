@@ -23,7 +23,7 @@ if dtype == "fp16":
     eng.scaler_enable(init_scale=1024.0)
 eng.load_numpy(spec.init_all(dims, seed=0, ln_jitter=True))
 names = dict(birnn_h0=S * B * 2048, birnn_h0_rev=S * B * 2048, birnn_h1=S * B * 4096, plan=B * 256, emb=B * S * 128, s_a3=2048 * 441 * 64, seq_feat=B * 4096, pr_logits=B * 1024, dec_h0=S * B * 2048, dec_h1=S * B * 2048, heads=S * B * 192, a_tcp=S * B * 7,
-             dheads=S * B * 192, dec_dz1=S * B * 2048, dec_dz0=S * B * 2048, demb=B * S * 128, dplan=B * 1024, dact3=2048 * 49 * 64, dact2=2048 * 81 * 64, dact1=2048 * 400 * 32)
+             dheads=S * B * 192, dec_dz1=S * B * 2048, dec_dz0=S * B * 2048, demb=B * S * 128, dplan=B * 1024, g_dact3=2048 * 49 * 64, g_dact2=2048 * 81 * 64, g_dact1=2048 * 400 * 32)
 runs = []
 for _ in range(3):
     eng.zero_grads(); eng.forward_loss(mb, False, 1.0, 3.0, step=2, sync_losses=False); eng.backward(); torch.cuda.synchronize()
