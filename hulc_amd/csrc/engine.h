@@ -159,10 +159,13 @@ struct Engine : IEngine {
     }
 
     // ---- workspace (per modality pass)
-    struct EncA { T *a1, *a2, *a3, *ss, *g0, *f1; float *ssstats, *f2, *lnst; unsigned* m1bits = nullptr; unsigned* m2bits = nullptr; } aS, aG;
-    T *dact1, *dact2, *dact3, *d_g0, *d_f1, *d_f2t; float* d_ss;
-    T *dact1g = nullptr, *dact2g = nullptr, *dact3g = nullptr;      // 16-bit engines: the gripper encoder's own activation gradients (a stage's data gradient runs for both cameras in one launch)
-    T *d_f1g = nullptr, *d_f2tg = nullptr;      // 16-bit engines: the gripper encoder's own copies (both tails' data gradients run as one launch)
+    // per camera: the activations, and the gradients of a1..a3, f1, f2 and of the tail's input (ss of the static camera: d_ss, fp32; g0 of the gripper camera: d_g0), set once
+    // in alloc_all.  16-bit engines: each camera has its own gradient buffers (a stage runs for both cameras in one launch, both cameras' gradients are alive at once);
+    // fp32 engine: the cameras run one after the other and point to the same buffers
+    struct EncA {
+        T *a1, *a2, *a3, *ss, *g0, *f1; float *ssstats, *f2, *lnst; unsigned* m1bits = nullptr; unsigned* m2bits = nullptr;
+        T *dact1 = nullptr, *dact2 = nullptr, *dact3 = nullptr, *d_f1 = nullptr, *d_f2t = nullptr, *d_g0 = nullptr; float* d_ss = nullptr;
+    } aS, aG;
     T *emb, *lang_t, *gl1, *gl2, *goal_t, *ppx, *ppa[4], *xm, *seqf_t, *embg, *Cb, *Zx0, *Zx1, *H0, *H1, *dheads, *dH1, *dZ1, *dH0, *dZ0, *dC;
     float *gl3, *goal_st, *pp_logits, *seqf, *pr_logits, *probs, *klcat, *dpp_kl, *dpr_kl, *Cplan, *heads, *rowloss, *a_tcp;
     int* pidx; int* pidx_in;
@@ -224,11 +227,13 @@ struct Engine : IEngine {
         const int64_t N = maxN, B = maxB, S = maxS, SB = (int64_t)maxS * maxB;
         alloc_enc(aS, 200, false, "s_");
         alloc_enc(aG, 84, true, "g_");
-        dact1 = alloc<T>(N * 49 * 49 * 32, "dact1"); dact2 = alloc<T>(N * 23 * 23 * 64, "dact2"); dact3 = alloc<T>(N * 21 * 21 * 64, "dact3");
-        d_g0 = alloc<T>(N * 128); d_f1 = alloc<T>(N * 512); d_f2t = alloc<T>(N * 64); d_ss = alloc<float>(N * 128, "d_ss");
+        aS.dact1 = alloc<T>(N * 49 * 49 * 32, "dact1"); aS.dact2 = alloc<T>(N * 23 * 23 * 64, "dact2"); aS.dact3 = alloc<T>(N * 21 * 21 * 64, "dact3");
+        aG.d_g0 = alloc<T>(N * 128); aS.d_f1 = alloc<T>(N * 512); aS.d_f2t = alloc<T>(N * 64); aS.d_ss = alloc<float>(N * 128, "d_ss");
         if constexpr (std::is_same<T, h16_t>::value) {
-            d_f1g = alloc<T>(N * 512); d_f2tg = alloc<T>(N * 64);
-            dact1g = alloc<T>(N * 20 * 20 * 32, "g_dact1"); dact2g = alloc<T>(N * 9 * 9 * 64, "g_dact2"); dact3g = alloc<T>(N * 7 * 7 * 64, "g_dact3");      // 42 KB per frame (87 MB at 2048 frames)
+            aG.d_f1 = alloc<T>(N * 512); aG.d_f2t = alloc<T>(N * 64);
+            aG.dact1 = alloc<T>(N * 20 * 20 * 32, "g_dact1"); aG.dact2 = alloc<T>(N * 9 * 9 * 64, "g_dact2"); aG.dact3 = alloc<T>(N * 7 * 7 * 64, "g_dact3");      // 42 KB per frame (87 MB at 2048 frames)
+        } else {
+            aG.d_f1 = aS.d_f1; aG.d_f2t = aS.d_f2t; aG.dact1 = aS.dact1; aG.dact2 = aS.dact2; aG.dact3 = aS.dact3;
         }
         emb = alloc<T>(N * EMB, "emb"); lang_t = alloc<T>(B * LANG); gl1 = alloc<T>(B * HID); gl2 = alloc<T>(B * HID);
         gl3 = alloc<float>(B * GOAL, "goal_pre"); goal_t = alloc<T>(B * GOAL, "goal"); goal_st = alloc<float>(B * 2);

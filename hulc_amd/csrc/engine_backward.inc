@@ -461,10 +461,10 @@
     encoders:
         // ---- encoders backward
         {
-            const Conv1Src s2s = conv1_src(cur2, false), s2g = conv1_src(cur2, true);
+            const Conv1Src src[2] = {conv1_src(*b, false), conv1_src(*b, true)}, src2[2] = {conv1_src(cur2, false), conv1_src(cur2, true)};
             const bool tail_fused = enc_tail_fusable();
             if (tail_fused) enc_tail_bwd_both(N);
-            enc_bwd_both(conv1_src(*b, false), conv1_src(*b, true), N, pair ? &s2s : nullptr, pair ? &s2g : nullptr, tail_fused);
+            enc_bwd_both(src, pair ? src2 : nullptr, N, tail_fused);
             flush_unpacks();
         }
         if (bucket_ready(4)) return 1;       // perceptual_encoder.* final

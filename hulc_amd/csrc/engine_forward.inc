@@ -74,9 +74,9 @@
         bool ppx_packed = false;
         // ---- perceptual encoders (concat_encoders.py:59-109): static -> emb[..., 0:64], gripper -> emb[..., 64:128]
         {
-            const Conv1Src s2s = conv1_src(cur2, false), s2g = conv1_src(cur2, true);
+            const Conv1Src src[2] = {conv1_src(*b, false), conv1_src(*b, true)}, src2[2] = {conv1_src(cur2, false), conv1_src(cur2, true)};
             const bool tail_fused = enc_tail_fusable();
-            enc_fwd_both(conv1_src(*b, false), conv1_src(*b, true), N, pair ? &s2s : nullptr, pair ? &s2g : nullptr, tail_fused);
+            enc_fwd_both(src, pair ? src2 : nullptr, N, tail_fused);
             x0_done = false;
             if (tail_fused) enc_tail_fwd_both(N, !mcil && tr_fused_mode && S <= 64 && EMB == 128, S, dp);
         }

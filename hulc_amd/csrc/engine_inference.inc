@@ -259,7 +259,8 @@
         hulc_batch bb; memset(&bb, 0, sizeof(bb));
         bb.B = 1; bb.S = 1; bb.step = roll_counter++;
         cur = bb;
-        enc_fwd_both(Conv1Src{obs->rgb_static, nullptr, 0, 0}, Conv1Src{obs->rgb_gripper, nullptr, 0, 0}, 1, nullptr, nullptr, false);
+        const Conv1Src src[2] = {conv1_src_f32(obs->rgb_static), conv1_src_f32(obs->rgb_gripper)};
+        enc_fwd_both(src, nullptr, 1, false);
         HIP_CHECK(hipMemcpyAsync(goal_t, roll_goal, sizeof(T) * GOAL, hipMemcpyDeviceToDevice, st));
         if (mcil) HIP_CHECK(hipMemcpyAsync(plan_t, roll_plan_c, sizeof(T) * (PLAN / 2), hipMemcpyDeviceToDevice, st));
         dec_fwd(roll_plan, 1, 1, roll_has_h ? roll_h0 : nullptr, roll_has_h ? roll_h1 : nullptr);

@@ -172,7 +172,8 @@
         HIP_CHECK(hipMemcpyAsync(env_ro, obs->robot_obs_raw, sizeof(float) * 15 * n, hipMemcpyDefault, st));
         if (u_mix) { HIP_CHECK(hipMemcpyAsync(nz_mix, u_mix, sizeof(float) * n * NDIM * NMIX, hipMemcpyDefault, st)); u_mix = nz_mix; }
         if (u_act) { HIP_CHECK(hipMemcpyAsync(nz_act, u_act, sizeof(float) * n * NDIM, hipMemcpyDefault, st)); u_act = nz_act; }
-        enc_fwd_both(Conv1Src{obs->rgb_static, nullptr, 0, 0}, Conv1Src{obs->rgb_gripper, nullptr, 0, 0}, n, nullptr, nullptr, false);
+        const Conv1Src src[2] = {conv1_src_f32(obs->rgb_static), conv1_src_f32(obs->rgb_gripper)};
+        enc_fwd_both(src, nullptr, n, false);
         if constexpr (std::is_same<T, h16_t>::value) {
             // embedding -> actions: three launches, no copy (rollout_step.h)
             auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };

@@ -258,7 +258,8 @@ __global__ void unpack_conv_wgrad_kernel(const float* __restrict__ part, int nsp
 // the same for up to eight convolutions in ONE launch (the encoders' backward deferred its six unpack launches to its end): job = the
 // convolution whose block range holds blockIdx.x; every job owns its own slab region
 struct UnpackJob { const float* part; float* grad; long long slab; int nsplit, O, I, KH, KW, nhwc, blk0, ysplit; };   // ysplit > 0: this job's slabs over that many grid.y parts only
-struct UnpackBatch { UnpackJob j[12]; int n; };
+constexpr int UNPACK_MAX_JOBS = 12;
+struct UnpackBatch { UnpackJob j[UNPACK_MAX_JOBS]; int n; };
 __global__ void unpack_conv_wgrad_batched_kernel(UnpackBatch ub) {
     int k = 0;
     while (k + 1 < ub.n && (int)blockIdx.x >= ub.j[k + 1].blk0) ++k;

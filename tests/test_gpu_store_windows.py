@@ -151,18 +151,28 @@ def test_padded_store_windows_equal_the_materialised_batch(dtype):
 
 
 def test_full_length_and_absent_window_len_are_the_plain_store_batch():
-    """window_len = [S] * B and no window_len at all: bit-identical loss (bf16, see DET, and fp32) and fp32 gradients of the plain store batch."""
+    """window_len = [S] * B and no window_len at all: bit-identical loss (bf16, see DET, and fp32) and fp32 gradients of the plain store batch — in the
+    single pass and in the paired vis + lang pass (fixed windows of both modalities gathered from the store, each modality with its own starts), where the
+    plain store batches also agree with the materialised pair as in test_padded_store_windows_equal_the_materialised_batch."""
     dims, P, batch, S, F, store_s, store_g, rng, starts, _ = _small_case(22)
     full = np.full(B1, S, np.int32)
-    _, sto = _modality(batch["vis"], store_s, store_g, starts, full, S, rng)
+    mat, sto = _modality(batch["vis"], store_s, store_g, starts, full, S, rng)
     plain = {k: v for k, v in sto.items() if k != "window_len"}
+    lang = rng.standard_normal((B1, 384)).astype(np.float32)
+    mat_l, sto_l = _modality(batch["lang"], store_s, store_g, np.array([F - S, 1, -7, F + 3], np.int64), full, S, rng, lang=lang / np.linalg.norm(lang, axis=-1, keepdims=True))
+    plain_l = {k: v for k, v in sto_l.items() if k != "window_len"}
     for dtype in ("fp32", "bf16"):
-        eng = _engine(dims, P, B1, S, dtype, **(DET if dtype == "bf16" else {}))
-        la, ga = _step(eng, plain)
-        lb, gb = _step(eng, sto)
-        assert all(la[k] == lb[k] for k in la), (dtype, la, lb)
-        if dtype == "fp32":
-            assert torch.equal(ga, gb)
+        eng = _engine(dims, P, 2 * B1, S, dtype, **(DET if dtype == "bf16" else {}))
+        for a, b in (((plain,), (sto,)), ((plain, plain_l), (sto, sto_l))):
+            la, ga = _step(eng, *a)
+            lb, gb = _step(eng, *b)
+            assert all(la[k] == lb[k] for k in la), (dtype, len(a), la, lb)
+            if dtype == "fp32":
+                assert torch.equal(ga, gb)
+        # the paired pass on fixed store windows against the same windows materialised
+        (l0, g0), (l1, g1), (_, g2) = _step(eng, mat, mat_l), _step(eng, plain, plain_l), _step(eng, mat, mat_l)
+        assert _same_loss(l0, l1, dtype), (dtype, l0, l1)
+        _grads_agree(g0, g1, g2, dtype, "pair, fixed windows")
         eng.close()
 
 
