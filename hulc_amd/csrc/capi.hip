@@ -10,6 +10,7 @@
 #include "engine.h"
 #include "sbert.h"
 #include "store_gather.h"
+#include "store_stage.h"
 
 using namespace hulc_bf16;      // this translation unit: fp32 (parity) + bf16 engines and the per-kernel test entry points; fp16: engine_f16.hip
 
@@ -23,6 +24,7 @@ void hulc_set_error(const char* fmt, ...) {
 
 struct hulc_ctx {
     IEngine* e = nullptr;
+    StoreStager stager;      // host tier of a two-tier frame store (store_stage.h); its stream and events are created by the first hulc_store_stage
 };
 
 extern "C" {
@@ -92,6 +94,21 @@ int hulc_store_gather(hulc_ctx* ctx, const hulc_store_tables* t, const int64_t* 
     const int total = B * S * 22 + (lang_out ? B * 384 : 0);
     hipLaunchKernelGGL(store_gather_kernel, dim3((total + 255) / 256), dim3(256), 0, ctx->e->st, p);
     if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_store_gather: launch failed"); return 1; }
+    return 0;
+}
+int64_t hulc_store_stage(hulc_ctx* ctx, const hulc_stage_copy* copies, int32_t n) {
+    if (!ctx) { hulc_set_error("hulc_store_stage: null context"); return -1; }
+    return ctx->stager.stage(ctx->e->st, copies, n);
+}
+int hulc_store_stage_join(hulc_ctx* ctx, int64_t ticket) {
+    if (!ctx) { hulc_set_error("hulc_store_stage_join: null context"); return 1; }
+    return ctx->stager.join(ctx->e->st, ticket);
+}
+int hulc_store_stage_stats(hulc_ctx* ctx, int64_t* calls, int64_t* copies, int64_t* bytes) {
+    if (!ctx) { hulc_set_error("hulc_store_stage_stats: null context"); return 1; }
+    if (calls) *calls = ctx->stager.n_calls;
+    if (copies) *copies = ctx->stager.n_copies;
+    if (bytes) *bytes = ctx->stager.n_bytes;
     return 0;
 }
 int hulc_clip_gt_encode(hulc_ctx* ctx, const float* lang_emb, int32_t m, int32_t slot) {
@@ -277,6 +294,7 @@ int hulc_set_option(hulc_ctx* ctx, const char* name, int64_t value) {
 }
 int hulc_get_option(hulc_ctx* ctx, const char* name, int64_t* value) {
     if (!ctx || !value) { hulc_set_error("hulc_get_option: null argument"); return 1; }
+    if (name && !strcmp(name, "stage_tickets")) { *value = HULC_STAGE_TICKETS; return 0; }      // the event ring of hulc_store_stage, as compiled
     long long v = 0;
     const int rc = ctx->e->get_option(name, &v);
     *value = (int64_t)v;

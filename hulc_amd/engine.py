@@ -45,6 +45,7 @@ class StepEngine:
         self._nums = (C.c_int64 * len(names))(*[int(np.prod(self.layout[n][1])) if len(self.layout[n][1]) else 1 for n in names])
         self._bound = False
         self._keep = []
+        self._staged_pending = []      # StagedWindows handles of forwards whose backward has not been enqueued yet (_staged_read)
         self.adam_t = 0
 
     # ---- parameters -------------------------------------------------------------------------------------------
@@ -131,6 +132,7 @@ class StepEngine:
                         actions=ptr(mb["actions"]), robot_obs=ptr(mb["robot_obs"]), lang=ptr(mb["lang"]) if is_lang else None,
                         plan_idx=ptr(mb["plan_idx"]) if mb.get("plan_idx") is not None else None, aux_rows=None, n_aux=0, step=step,
                         **self._ingest_fields(mb, ptr))
+        self._staged_read(mb)
         if mb.get("plan_eps") is not None:          # mcil: injected N(0,1) draw of the reparametrised plan sample
             b.plan_eps = ptr(mb["plan_eps"].to(torch.float32))
         if is_lang and mb.get("aux_rows") is not None and len(mb["aux_rows"]) > 0:
@@ -208,6 +210,44 @@ class StepEngine:
                                            B, int(S), a_out.data_ptr(), r_out.data_ptr(), None if lang_out is None else lang_out.data_ptr()))
         return a_out, r_out, lang_out
 
+    # ---- host tier of a two-tier frame store (include/hulc_hip.h: hulc_store_stage; hulc_amd/utils/frame_store.py) ---------------------------
+    def store_stage(self, copies) -> int:
+        """hulc_store_stage: `copies` = [(src pointer, dst pointer, bytes)] — src pinned host or device memory, dst device memory — as ONE call on the
+        context's copy stream, which first waits for everything enqueued on the engine's stream so far.  Returns the ticket (> 0) for store_stage_join.
+        The caller keeps the buffers alive until the ticket has been joined and its readers have run."""
+        n = len(copies)
+        arr = (L.HulcStageCopy * max(n, 1))(*[L.HulcStageCopy(src=int(s), dst=int(d), bytes=int(b)) for s, d, b in copies])
+        ticket = int(self.lib.hulc_store_stage(self.ctx, arr, n))
+        if ticket <= 0:
+            L.check(1)
+        return ticket
+
+    def store_stage_join(self, ticket: int) -> None:
+        """hulc_store_stage_join: the engine's stream waits for that ticket's copies (no host synchronisation)."""
+        L.check(self.lib.hulc_store_stage_join(self.ctx, int(ticket)))
+
+    def store_stage_stats(self) -> Dict:
+        """{"calls", "copies", "bytes"} staged by this context so far."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(self.lib.hulc_store_stage_stats(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(calls=a.value, copies=b.value, bytes=c.value)
+
+    def _staged_read(self, mb: Dict) -> None:
+        """A batch that reads staging slots (FrameStore.batch: `staged`): its handle is marked once the LAST reader of the slots has been enqueued —
+        the backward that follows this forward (conv1's weight gradient re-reads the frames), or the validate itself."""
+        h = mb.get("staged")
+        if h is None or h.done:      # all-resident batches hold no slot: nothing to wait for
+            return
+        # forward-only use (no backward ever marks): handles given up with release() drop out here, the others are bounded by the ring, whose guard
+        # raises once their slots would be needed again
+        self._staged_pending = [p for p in self._staged_pending if not p.done and p is not h]
+        self._staged_pending.append(h)
+
+    def _staged_done(self) -> None:
+        for h in self._staged_pending:
+            h.mark_enqueued()
+        self._staged_pending = []
+
     # ------------------------------------------------------------------ validation / rollout (forward only)
     @staticmethod
     def _dev_or_host_ptr(x, keep, dtype):
@@ -254,6 +294,8 @@ class StepEngine:
         pred_pr = torch.zeros(B, S, 7, device=self.device) if want_pred else None
         L.check(self.lib.hulc_validate(self.ctx, C.byref(b), C.byref(nz), out, ppp.data_ptr(), ppr.data_ptr(),
                                        pred_pp.data_ptr() if want_pred else None, pred_pr.data_ptr() if want_pred else None))
+        if mb.get("staged") is not None:
+            mb["staged"].mark_enqueued()
         o = list(out)
         res = dict(action_loss_pp=o[0], action_loss_pr=o[1], kl_loss=o[2], gripper_sr_pp=o[3], gripper_sr_pr=o[4],
                    mae_pp=np.array(o[5:11], np.float32), mae_pr=np.array(o[11:17], np.float32), sampled_plan_idx_pp=ppp, sampled_plan_idx_pr=ppr, val_pred_clip_loss=o[17])
@@ -472,6 +514,8 @@ class StepEngine:
             L.check(self.lib.hulc_backward(self.ctx))
         else:
             L.check(self.lib.hulc_backward_part(self.ctx, part))
+        if part != 0:                  # the encoders' backward (conv1's weight gradient) is the last reader of a batch's frames
+            self._staged_done()
 
     @property
     def encoder_numel(self) -> int:
@@ -554,6 +598,7 @@ class StepEngine:
     def backward_allreduce(self, bucket_dtype: str = "fp32"):
         """backward() of the step's last forward with the bucketed SUM all-reduce overlapped (reverse-forward order)."""
         L.check(self.lib.hulc_backward_allreduce(self.ctx, L.DTYPE[bucket_dtype]))
+        self._staged_done()
 
     # ---- dynamic loss scaling (fp16 mode; torch.cuda.amp.GradScaler semantics, include/hulc_hip.h: hulc_scaler_*) ----------
     def scaler_enable(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000):

@@ -560,6 +560,8 @@ class Hulc(torch.nn.Module):
             mb["window_start"] = dataset_batch["window_start"].to(device=device, dtype=torch.int64)
         if dataset_batch.get("window_len") is not None:        # variable-length windows padded to S by repetition (hulc_batch::window_len)
             mb["window_len"] = dataset_batch["window_len"].to(device=device, dtype=torch.int32)
+        if dataset_batch.get("staged") is not None:            # two-tier frame store: the engine marks the handle once the slots' last reader is enqueued
+            mb["staged"] = dataset_batch["staged"]
         for k in ("shift_static", "shift_gripper", "pad_static", "pad_gripper"):       # optional RandomShiftsAug draws of the ingest path
             if dataset_batch.get(k) is not None:
                 mb[k] = dataset_batch[k].to(device=device) if torch.is_tensor(dataset_batch[k]) else dataset_batch[k]

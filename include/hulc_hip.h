@@ -85,7 +85,7 @@ typedef struct hulc_batch {
     /* ---- HBM-resident frame store (zero-initialise for a materialised batch) ----------------------------------
      * window_start != NULL (requires frames_u8): rgb_static / rgb_gripper do not hold this batch's (B,S,H,W,C) frames but a device-resident STORE
      * of `store_frames` uint8 (H,W,C) frames — whole episodes, uploaded once (CALVIN's ~2.4 M frames of both cameras are 340 GB as uint8: a split
-     * per GPU of the node fits its 288 GB) — and window b is the S consecutive store frames [window_start[b], window_start[b] + S).  conv1's forward
+     * per GPU of the node fits its 288 GB; a larger split keeps a host tier, hulc_store_stage below) — and window b is the S consecutive store frames [window_start[b], window_start[b] + S).  conv1's forward
      * and weight gradient gather their bands by index: no (B,S,H,W,C) tensor is materialised on either side of PCIe and nothing but B indices
      * (+ actions / robot_obs / shifts) crosses it per step.  This replaces the reference's host-side shared-memory frame cache
      * (README.md:85-86: ~20 minutes to fill; dataset/README.md:55-56) and its per-step uint8 -> fp32 -> H2D path.
@@ -288,6 +288,27 @@ typedef struct hulc_store_tables {
 int hulc_store_gather(hulc_ctx* ctx, const hulc_store_tables* tables, const int64_t* window_start /* (B) device */, const int32_t* window_len /* (B) device or NULL */,
                       const int32_t* lang_row /* (B) device, with lang_out */, int32_t B, int32_t S, float* actions_out /* (B,S,7) */,
                       float* robot_obs_out /* (B,S,15) */, float* lang_out /* (B,384) or NULL */);
+
+/* ---- The host tier of a two-tier frame store (hulc_amd/utils/frame_store.py: resident_frames).  A split larger than HBM keeps as many whole episodes as
+ * fit resident; the others stay in PINNED host memory.  The device allocation of each camera ends in a ring of staging slots; the windows of the next
+ * batch that lie on the host are copied into slots while the current step computes, and hulc_batch::window_start names the slot — the step kernels
+ * cannot tell the difference.  The copies go through the copy engines (hipMemcpyAsync on a private stream), not through a kernel: they occupy no CU
+ * next to the persistent recurrences.
+ * hulc_store_stage: n copies (the list lives in HOST memory and is consumed before the call returns) on the context's private copy stream.  The copy
+ * stream first waits for everything enqueued on the context's stream so far — the slots' previous readers, forward and backward — so a slot may be
+ * reused as soon as the step that read it has been ENQUEUED.  Every src must be pinned-host memory or memory of the context's device, every dst memory
+ * of the context's device, each range inside ONE allocation (the pinned buffer, the device allocation), bytes > 0: a pageable or null pointer is an
+ * error that leaves nothing enqueued.  Returns a ticket > 0, < 0 on error.  Only a runtime failure in the middle of the list (a copy the runtime
+ * refuses) can leave a PARTIAL stage behind: the copies before it stay enqueued, no ticket is issued, and the slots named by the list must not be read.
+ * hulc_store_stage_join: the context's stream waits for that ticket's copies (an event wait, no host synchronisation).  A bounded ring of events
+ * backs the tickets: only the last HULC_STAGE_TICKETS - 1 tickets can be joined, an older (recycled) or never issued one is an error
+ * (hulc_get_option "stage_tickets" reads the compiled value back).
+ * hulc_store_stage_stats: calls, copies and bytes staged so far (each pointer optional); failed calls count nothing. */
+#define HULC_STAGE_TICKETS 32
+typedef struct hulc_stage_copy { const void* src; void* dst; int64_t bytes; } hulc_stage_copy;
+int64_t hulc_store_stage(hulc_ctx* ctx, const hulc_stage_copy* copies, int32_t n);
+int hulc_store_stage_join(hulc_ctx* ctx, int64_t ticket);
+int hulc_store_stage_stats(hulc_ctx* ctx, int64_t* calls, int64_t* copies, int64_t* bytes);
 
 /* ---- CLIP ground-truth validation metric (Hulc.on_validation_epoch_start, hulc/models/hulc.py:967-974, and the device part of
  * Hulc._clip_groundtruth_loss, :1024-1029).  hulc_clip_gt_encode runs language_goal (goal_encoders.py:64-69) and proj_vis_lang.mlp_lang

@@ -138,6 +138,28 @@ w("datamodule/synthetic.yaml", dict(_target_="hulc_amd.trainer.SyntheticDataModu
                                    modalities=["vis", "lang"], steps_per_epoch=50),
   "synthetic CALVIN-shaped windows (SURVEY.md §8d); the reference's CalvinDataModule (calvin_agent, absent) is out of scope — only its\n"
   "batch contract (hulc/models/hulc.py:395-414) and the keys the model tree interpolates are kept")
+w("datamodule/calvin_store.yaml", """# a CALVIN dataset directory (<root_data_dir>/training, <root_data_dir>/validation; reference dataset/README.md:50-119) held in HBM-resident frame
+# stores; variable-length windows padded to max_window_size on the device (hulc_batch::window_len, hulc_store_gather).  Keys as in the reference's
+# conf/datamodule/default.yaml + datasets/vision_dataset/vision.yaml / lang_dataset/lang.yaml; pads = transforms/rand_shift.yaml.
+#   python -m hulc_amd.training datamodule=calvin_store datamodule.root_data_dir=/path/to/task_D_D
+_target_: hulc_amd.utils.calvin_store.CalvinStoreDataModule
+action_max: [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]
+action_min: [-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0]
+action_space: 7
+root_data_dir: ???
+batch_size: 32
+min_window_size: 20
+max_window_size: 32
+lang_folder: lang_annotations
+aux_lang_loss_window: 8
+modalities: [vis, lang]
+pad_static: 10
+pad_gripper: 4
+val_batches: 1
+# GiB of device memory for the frames of both splits, or null = every split wholly in HBM.  With a budget, validation is resident first and
+# training gets the rest; the episodes beyond the cut stay in pinned host memory and are staged one step ahead (INTEGRATION.md 4e)
+resident_gb: null
+""")
 w("callbacks/default.yaml", """defaults:
   - kl_schedule: constant
   - checkpoint: all

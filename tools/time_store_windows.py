@@ -5,12 +5,20 @@ timed steps, each step timed with its own pair of events.
     python tools/time_store_windows.py                                   # fixed windows, then lens uniform 20..32, of this tree's library
     HULC_LIB_PATH=<older libhulc_hip.so> python tools/time_store_windows.py --modes fixed      # the same fixed-window run on another build
 
-Prints one JSON line per mode.  profiles/store_windows.txt records the numbers of the commit that added window_len.
+    python tools/time_store_windows.py --modes padded --host-share 0,0.25,1.0      # two-tier store: that share of the frames in pinned host memory
+
+Prints one JSON line per mode.  profiles/store_windows.txt records the numbers of the commit that added window_len, profiles/store_tiers.txt those
+of the two-tier store.
+
+--host-share f (a list): the store is cut so that the last f of its frames (whole 64-frame episodes) live on the host; the padded windows of every
+step are staged through FrameStore.stage — once one step ahead (`lookahead`: stage n + 1, then run n) and once serialised (`serial`: stage n, run n).
+Each line adds the bytes staged per step, the achieved copy rate of the serialised form's staging alone and persistent_rnn_fallbacks.
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -32,6 +40,7 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--modes", default="fixed,padded")
     ap.add_argument("--repeat", type=int, default=1, help="timed passes per mode (run-to-run spread inside one process)")
+    ap.add_argument("--host-share", default="", help="comma-separated shares of the store kept in pinned host memory (two-tier store; padded windows)")
     args = ap.parse_args()
     B, S, F, dev = args.batch, args.seq, args.store, torch.device("cuda:0")
     dims = spec.ModelDims(kind="hulc", max_window=max(32, S), use_clip=False)
@@ -58,6 +67,10 @@ def main():
         eng.backward()
         eng.adam_step(lr=2e-4)
 
+    if args.host_share:
+        tiers(args, eng, mb, starts, lens)
+        eng.close()
+        return
     for mode in args.modes.split(","):
         padded = mode == "padded"
         for rep in range(args.repeat):
@@ -75,6 +88,74 @@ def main():
                                   median_ms=round(float(np.median(ms)), 4), mean_ms=round(float(ms.mean()), 4), p10_ms=round(float(np.percentile(ms, 10)), 4),
                                   p90_ms=round(float(np.percentile(ms, 90)), 4), mean_window_len=round(float(lens.float().mean()), 2) if padded else float(S))), flush=True)
     eng.close()
+
+
+def tiers(args, eng, mb, starts, lens):
+    """The padded-window step on a two-tier store built from the same frames: episodes of 64 frames, the last `share` of them on the host."""
+    from hulc_amd.utils.frame_store import FrameStore
+    B, S, F = args.batch, args.seq, args.store
+    ends = list(range(64, F, 64)) + [F]
+    # every window inside one 64-frame episode (the all-resident tool draws them anywhere; a tiered store cuts on episode boundaries)
+    st_h = starts.cpu().numpy()
+    ln_h = lens.cpu().numpy()
+    st_h = np.minimum(st_h, (st_h // 64) * 64 + 64 - ln_h)
+    st_h = np.minimum(st_h, F - ln_h)
+    host_s, host_g = mb["rgb_static"].cpu(), mb["rgb_gripper"].cpu()
+    for share in [float(x) for x in args.host_share.split(",")]:
+        store = FrameStore(host_s, host_g, episode_ends=ends, device="cuda:0", resident_frames=int(round(F * (1.0 - share))), stage_slots=2 * B,
+                           stage_slot_frames=S).attach(eng)
+
+        def run(i, h):
+            d = dict(mb, rgb_static=store.rgb_static, rgb_gripper=store.rgb_gripper, window_start=torch.from_numpy(h.frame_starts).cuda(),
+                     window_len=torch.from_numpy(h.lens).cuda(), staged=h)
+            if h.ticket:
+                eng.store_stage_join(h.ticket)
+            eng.zero_grads()
+            eng.forward_loss(d, False, 1.0, 3.0, step=i, sync_losses=False)
+            eng.backward()
+            eng.adam_step(lr=2e-4)
+
+        stage = lambda i: store.stage(st_h[i % 64], S, ln_h[i % 64])
+        for order in ("lookahead", "serial"):
+            for rep in range(args.repeat):
+                n = args.warmup + args.steps
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+                torch.cuda.synchronize()
+                b0 = eng.store_stage_stats()["bytes"]
+                ahead = stage(0) if order == "lookahead" else None
+                host_t = 0.0                   # time the launching thread spends inside FrameStore.stage (planning + one hulc_store_stage)
+                for i, (a, b) in enumerate(ev):
+                    a.record()
+                    t_host = time.perf_counter()
+                    if order == "lookahead":
+                        cur, ahead = ahead, (stage(i + 1) if i + 1 < n else None)
+                    else:
+                        cur = stage(i)
+                    host_t += time.perf_counter() - t_host
+                    run(i, cur)
+                    b.record()
+                torch.cuda.synchronize()
+                ms = np.array([a.elapsed_time(b) for a, b in ev])[args.warmup:]
+                per_step = (eng.store_stage_stats()["bytes"] - b0) / n
+                # the copy rate: the same staging calls alone, nothing else on the device
+                torch.cuda.synchronize()
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                c0 = eng.store_stage_stats()["bytes"]
+                t0.record()
+                for i in range(8):
+                    h = stage(i)
+                    if h.ticket:
+                        eng.store_stage_join(h.ticket)
+                    h.release()
+                t1.record()
+                torch.cuda.synchronize()
+                copied = eng.store_stage_stats()["bytes"] - c0
+                rate = copied / (t0.elapsed_time(t1) * 1e-3) / 1e9 if copied else 0.0
+                print(json.dumps(dict(mode="tiers", order=order, host_share=share, resident_frames=store.R, rep=rep, B=B, S=S, store_frames=F, dtype=args.dtype, steps=args.steps,
+                                      median_ms=round(float(np.median(ms)), 4), mean_ms=round(float(ms.mean()), 4), p10_ms=round(float(np.percentile(ms, 10)), 4),
+                                      p90_ms=round(float(np.percentile(ms, 90)), 4), staged_mb_per_step=round(per_step / 1e6, 2), copy_gb_per_s=round(rate, 2), stage_host_us=round(host_t / n * 1e6, 1),
+                                      persistent_rnn_fallbacks=eng.get_option("persistent_rnn_fallbacks"))), flush=True)
+        del store
 
 
 if __name__ == "__main__":
