@@ -119,6 +119,18 @@ int hulc_clip_gt_scores(hulc_ctx* ctx, int32_t slot, float* scores_host, int64_t
     if (!ctx) { hulc_set_error("hulc_clip_gt_scores: null context"); return 1; }
     return ctx->e->clip_gt_scores(slot, scores_host, cap_floats, n_out, m_out);
 }
+int hulc_aux_heads_enable(hulc_ctx* ctx, int32_t bc_z, int32_t mia) {
+    if (!ctx) { hulc_set_error("hulc_aux_heads_enable: null context"); return 1; }
+    return ctx->e->aux_heads_enable(bc_z, mia);
+}
+int hulc_aux_weights_set(hulc_ctx* ctx, float bc_z_weight, float mia_weight) {
+    if (!ctx) { hulc_set_error("hulc_aux_weights_set: null context"); return 1; }
+    return ctx->e->aux_weights_set(bc_z_weight, mia_weight);
+}
+int hulc_aux_losses_get(hulc_ctx* ctx, float* out_host) {
+    if (!ctx) { hulc_set_error("hulc_aux_losses_get: null context"); return 1; }
+    return ctx->e->aux_losses_get(out_host);
+}
 int hulc_rollout_reset(hulc_ctx* ctx) { return ctx->e->rollout_reset(); }
 int hulc_rollout_plan(hulc_ctx* ctx, const hulc_rollout_obs* obs, const float* goal_rgb_static, const float* goal_rgb_gripper, const float* goal_lang,
                       const int32_t* plan_idx_inject, int32_t* plan_idx_out) {

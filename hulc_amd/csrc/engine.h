@@ -18,6 +18,7 @@
 #include "rnn_persist.h"
 #include "enc_tail.h"
 #include "rollout_step.h"
+#include "aux_heads.h"
 
 namespace HULC_NS {
 
@@ -183,6 +184,16 @@ struct Engine : IEngine {
     // clip
     int* auxrows; T *sf_m, *im1, *g_m, *la1, *img_t, *txt_t; float *img, *txt, *dimg, *dtxt, *dsf_m, *dg_m; T *dimg_t, *dtxt_t, *dim1, *dla1;
     float* losses;   // [8]: 0 action, 1 kl(sum klcat), 2 clip
+    // BC-Z / MIA language auxiliary heads (aux_heads.h; hulc_aux_heads_enable): off unless enabled before the bind — then nothing below is allocated, bound or launched
+    bool aux_bcz = false, aux_mia = false;
+    float aux_w_bcz = 1.f, aux_w_mia = 1.f;
+    LinW bz0, bz2;                                            // bc_z_lang_decoder.mlp.0 (4096 -> 512, ReLU), .mlp.2 (512 -> 384)
+    const float *mia_w0 = nullptr, *mia_b0 = nullptr, *mia_w1 = nullptr, *mia_b1 = nullptr;      // mia_lang_discriminator.mlp.0 (64 -> 512), .mlp.3 (512 -> 1): read as fp32 by mia_head_kernel
+    float *d_mia_w0 = nullptr, *d_mia_b0 = nullptr, *d_mia_w1 = nullptr, *d_mia_b1 = nullptr;
+    T *bz1 = nullptr, *dbz1 = nullptr, *bz_dpred_t = nullptr; float *bz_pred = nullptr, *bz_tgt = nullptr, *bz_dpred = nullptr;
+    float* aux_loss = nullptr;                               // device [4]: 0 bc_z, 1 mia (unweighted)
+    int bcz_n = 0, mia_n = 0;                                // rows the heads of the last forward ran on (0: not launched, loss 0)
+    int aux_rows_last = 0;                                   // rows of the last forward / validate, for hulc_aux_losses_get
     // ---- state of the last forward
     hulc_batch cur; float cur_lw = 0, cur_cw = 0; bool have_fwd = false;
 
@@ -296,6 +307,63 @@ struct Engine : IEngine {
 #ifdef HULC_HALF_F16
         if (!std::is_same<T, float>::value) return scaler_enable(65536.f, 2.f, 0.5f, 2000);      // torch.cuda.amp.GradScaler() defaults
 #endif
+        return 0;
+    }
+
+    // ---------------------------------------------------------------- BC-Z / MIA language auxiliary heads (include/hulc_hip.h: hulc_aux_heads_enable)
+    int aux_heads_enable(int bc_z, int mia) override {
+        if (bound) { hulc_set_error("hulc_aux_heads_enable after hulc_bind_params (the heads' tensors are bound by name: enable them first)"); return 1; }
+        if (mcil) { hulc_set_error("hulc_aux_heads_enable: HULC_KIND_MCIL has no proj_vis_lang and trains without the language auxiliary losses (conf/model/mcil.yaml)"); return 1; }
+        if (aux_bcz || aux_mia) { hulc_set_error("hulc_aux_heads_enable: the heads of this context are already enabled"); return 1; }
+        if (!bc_z && !mia) return 0;
+        const int64_t B = maxB;
+        if (bc_z) {
+            bz1 = alloc<T>(B * 512); dbz1 = alloc<T>(B * 512); bz_dpred_t = alloc<T>(B * LANG);
+            bz_pred = alloc<float>(B * LANG, "bcz_pred"); bz_tgt = alloc<float>(B * LANG); bz_dpred = alloc<float>(B * LANG);
+        }
+        aux_loss = alloc<float>(4);
+        if (alloc_failed) { hulc_set_error("hulc_aux_heads_enable: workspace allocation failed"); return 1; }
+        aux_bcz = bc_z != 0; aux_mia = mia != 0;
+        return 0;
+    }
+    int aux_weights_set(float bc_z_weight, float mia_weight) override { aux_w_bcz = bc_z_weight; aux_w_mia = mia_weight; return 0; }
+    // [bc_z, mia, rows, 0] of the last forward / validate, unweighted; a head that did not run (not enabled, no flagged row, no forward yet) reads 0
+    int aux_losses_get(float* out_host) override {
+        if (!out_host) { hulc_set_error("hulc_aux_losses_get: null output"); return 1; }
+        float h[4] = {0.f, 0.f, 0.f, 0.f};
+        if (bcz_n > 0 || mia_n > 0) HIP_CHECK(hipMemcpyAsync(h, aux_loss, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        out_host[0] = bcz_n > 0 ? h[0] : 0.f; out_host[1] = mia_n > 0 ? h[1] : 0.f; out_host[2] = (float)aux_rows_last; out_host[3] = 0.f;
+        return 0;
+    }
+    // the heads' forward on the n gathered rows (auxrows uploaded); `shared` = the CLIP block of this pass already gathered sf_m / g_m and projected img / txt.
+    // train: gradients of the losses w.r.t. img / txt / pred are left for the backward, the discriminator's own gradients are added by its kernel
+    int aux_heads_fwd(const hulc_batch* b, int n, bool shared, bool train, int lang_row0) {
+        if (!shared) hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * FCH, 256)), dim3(256), 0, st, seqf_t, (long long)FCH, auxrows, n, FCH, sf_m);
+        if (aux_mia) {
+            if (!shared) {
+                hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * GOAL, 256)), dim3(256), 0, st, goal_t, (long long)GOAL, auxrows, n, GOAL, g_m);
+                { EpiP ep = epi(im1, false); ep.relu = 1; lin_fwd(sf_m, FCH, n, cl_im0, ep, 128); }
+                { EpiP ep = epi(img, true); lin_fwd(im1, 128, n, cl_im2, ep, GOAL); }
+                { EpiP ep = epi(la1, false); ep.relu = 1; lin_fwd(g_m, GOAL, n, cl_la0, ep, 128); }
+                { EpiP ep = epi(txt, true); lin_fwd(la1, 128, n, cl_la2, ep, GOAL); }
+            }
+            static_assert(GOAL == MIA_D, "mia_head_kernel is built for 32-wide projections");
+            if (train) hipLaunchKernelGGL(mia_head_kernel, dim3(1), dim3(1024), 0, st, img, txt, n, mia_w0, mia_b0, mia_w1, mia_b1, aux_w_mia, aux_loss + 1, dimg, dtxt, shared ? 1 : 0,
+                                          d_mia_w0, d_mia_b0, d_mia_w1, d_mia_b1, lscale());
+            else hipLaunchKernelGGL(mia_head_kernel, dim3(1), dim3(1024), 0, st, img, txt, n, mia_w0, mia_b0, mia_w1, mia_b1, 0.f, aux_loss + 1, (float*)nullptr, (float*)nullptr, 0,
+                                    (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr);
+            mia_n = n;
+        }
+        if (aux_bcz) {
+            // lang[rows]: the batch's fp32 embeddings; the paired pass numbers the lang rows from Bv
+            hipLaunchKernelGGL((gather_rows_kernel<float, float>), dim3(cdiv(n * LANG, 256)), dim3(256), 0, st, b->lang - (long long)lang_row0 * LANG, (long long)LANG, auxrows, n, LANG, bz_tgt);
+            { EpiP ep = epi(bz1, false); ep.relu = 1; lin_fwd(sf_m, FCH, n, bz0, ep, 512); }
+            { EpiP ep = epi(bz_pred, true); lin_fwd(bz1, 512, n, bz2, ep, LANG); }
+            hipLaunchKernelGGL(cosine_dist_loss_kernel, dim3(1), dim3(1024), 0, st, bz_pred, bz_tgt, n, LANG, train ? aux_w_bcz : 0.f, aux_loss + 0, train ? bz_dpred : (float*)nullptr,
+                               train ? lscale() : (const float*)nullptr);
+            bcz_n = n;
+        }
         return 0;
     }
 
@@ -453,10 +521,18 @@ struct Engine : IEngine {
                 head_w32[i] = pw(ad + hn[i] + ".weight"); head_b32[i] = pw(ad + hn[i] + ".bias");
                 head_dw[i] = gw(ad + hn[i] + ".weight"); head_db[i] = gw(ad + hn[i] + ".bias");
             }
-            if (cfg.use_clip) {
+            if (cfg.use_clip || aux_mia) {      // the MIA head scores the same projections (hulc.py:621): proj_vis_lang.* without logit_scale when the CLIP loss is off
                 bind_lin(cl_im0, "proj_vis_lang.mlp_im.0", 128, FCH); bind_lin(cl_im2, "proj_vis_lang.mlp_im.2", GOAL, 128);
                 bind_lin(cl_la0, "proj_vis_lang.mlp_lang.0", 128, GOAL); bind_lin(cl_la2, "proj_vis_lang.mlp_lang.2", GOAL, 128);
-                logit_scale = pw("logit_scale"); dlogit_scale = gw("logit_scale");
+            }
+            if (cfg.use_clip) { logit_scale = pw("logit_scale"); dlogit_scale = gw("logit_scale"); }
+            if (aux_bcz) { bind_lin(bz0, "bc_z_lang_decoder.mlp.0", 512, FCH); bind_lin(bz2, "bc_z_lang_decoder.mlp.2", LANG, 512); }
+            if (aux_mia) {
+                const std::string md = "mia_lang_discriminator.mlp.";
+                mia_w0 = pw(md + "0.weight"); mia_b0 = pw(md + "0.bias"); mia_w1 = pw(md + "3.weight"); mia_b1 = pw(md + "3.bias");
+                d_mia_w0 = gw(md + "0.weight"); d_mia_b0 = gw(md + "0.bias"); d_mia_w1 = gw(md + "3.weight"); d_mia_b1 = gw(md + "3.bias");
+                if (tab.at(md + "0.weight").n != (int64_t)MIA_H * MIA_IN || tab.at(md + "0.bias").n != MIA_H || tab.at(md + "3.weight").n != MIA_H || tab.at(md + "3.bias").n != 1) {
+                    hulc_set_error("hulc_bind_params: mia_lang_discriminator.* must be Linear(64, 512) and Linear(512, 1)"); return 1; }
             }
         } catch (const std::out_of_range&) {
             hulc_set_error("hulc_bind_params: a required parameter name is missing from the table");

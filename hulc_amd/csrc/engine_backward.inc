@@ -171,23 +171,36 @@
         if (poison_partials) HIP_CHECK(hipMemsetAsync(this->part, 0xFF, sizeof(float) * (size_t)this->partcap, st));
         {
         bool have_dseq = false, dseq_cast_done = false;
-        // ---- CLIP backward
-        if (clip_n > 0) {
-            const int n = clip_n;
-            hipLaunchKernelGGL((cast_kernel<float, T>), dim3(1), dim3(256), 0, st, dimg, dimg_t, (long long)n * GOAL);
-            hipLaunchKernelGGL((cast_kernel<float, T>), dim3(1), dim3(256), 0, st, dtxt, dtxt_t, (long long)n * GOAL);
-            // image branch: img = im2(relu(im0(sf)))
-            lin_wgrad(dimg_t, im1, 128, n, GOAL, 128, cl_im2.dW, 128, cl_im2.db);
-            { EpiP ep = epi(dim1, false); ep.mask = im1; lin_dgrad(dimg_t, n, cl_im2, ep, dense_out(128)); }
-            lin_wgrad(dim1, sf_m, FCH, n, 128, FCH, cl_im0.dW, FCH, cl_im0.db);
-            { EpiP ep = epi(dsf_m, true); lin_dgrad(dim1, n, cl_im0, ep, dense_out(FCH)); }
+        // ---- CLIP / MIA / BC-Z backward: the heads' own gradients, then the shared proj_vis_lang ONCE on the summed dimg / dtxt (the MIA kernel added its share to
+        // what the CLIP kernel stored), then one scatter per destination
+        const int proj_n = clip_n > 0 ? clip_n : mia_n;
+        if (proj_n > 0 || bcz_n > 0) {
+            const int n = proj_n > 0 ? proj_n : bcz_n;
+            if (proj_n > 0) {
+                hipLaunchKernelGGL((cast_kernel<float, T>), dim3(1), dim3(256), 0, st, dimg, dimg_t, (long long)n * GOAL);
+                hipLaunchKernelGGL((cast_kernel<float, T>), dim3(1), dim3(256), 0, st, dtxt, dtxt_t, (long long)n * GOAL);
+                // image branch: img = im2(relu(im0(sf)))
+                lin_wgrad(dimg_t, im1, 128, n, GOAL, 128, cl_im2.dW, 128, cl_im2.db);
+                { EpiP ep = epi(dim1, false); ep.mask = im1; lin_dgrad(dimg_t, n, cl_im2, ep, dense_out(128)); }
+                lin_wgrad(dim1, sf_m, FCH, n, 128, FCH, cl_im0.dW, FCH, cl_im0.db);
+                { EpiP ep = epi(dsf_m, true); lin_dgrad(dim1, n, cl_im0, ep, dense_out(FCH)); }
+            }
+            if (bcz_n > 0) {      // pred = mlp.2(relu(mlp.0(sf))): its share of d seq_feat joins the image branch's in dsf_m
+                hipLaunchKernelGGL((cast_kernel<float, T>), dim3(cdiv(n * LANG, 256)), dim3(256), 0, st, bz_dpred, bz_dpred_t, (long long)n * LANG);
+                lin_wgrad(bz_dpred_t, bz1, 512, n, LANG, 512, bz2.dW, 512, bz2.db);
+                { EpiP ep = epi(dbz1, false); ep.mask = bz1; lin_dgrad(bz_dpred_t, n, bz2, ep, dense_out(512)); }
+                lin_wgrad(dbz1, sf_m, FCH, n, 512, FCH, bz0.dW, FCH, bz0.db);
+                { EpiP ep = epi(dsf_m, true); if (proj_n > 0) ep.accumulate = 1; lin_dgrad(dbz1, n, bz0, ep, dense_out(FCH)); }
+            }
             hipLaunchKernelGGL(scatter_rows_add_kernel, dim3(cdiv(n * FCH, 256)), dim3(256), 0, st, dsf_m, auxrows, n, FCH, dseqf, (long long)FCH);
-            // text branch
-            lin_wgrad(dtxt_t, la1, 128, n, GOAL, 128, cl_la2.dW, 128, cl_la2.db);
-            { EpiP ep = epi(dla1, false); ep.mask = la1; lin_dgrad(dtxt_t, n, cl_la2, ep, dense_out(128)); }
-            lin_wgrad(dla1, g_m, GOAL, n, 128, GOAL, cl_la0.dW, GOAL, cl_la0.db);
-            { EpiP ep = epi(dg_m, true); lin_dgrad(dla1, n, cl_la0, ep, dense_out(GOAL)); }
-            hipLaunchKernelGGL(scatter_rows_add_kernel, dim3(cdiv(n * GOAL, 256)), dim3(256), 0, st, dg_m, auxrows, n, GOAL, dgoal, (long long)GOAL);
+            if (proj_n > 0) {
+                // text branch
+                lin_wgrad(dtxt_t, la1, 128, n, GOAL, 128, cl_la2.dW, 128, cl_la2.db);
+                { EpiP ep = epi(dla1, false); ep.mask = la1; lin_dgrad(dtxt_t, n, cl_la2, ep, dense_out(128)); }
+                lin_wgrad(dla1, g_m, GOAL, n, 128, GOAL, cl_la0.dW, GOAL, cl_la0.db);
+                { EpiP ep = epi(dg_m, true); lin_dgrad(dla1, n, cl_la0, ep, dense_out(GOAL)); }
+                hipLaunchKernelGGL(scatter_rows_add_kernel, dim3(cdiv(n * GOAL, 256)), dim3(256), 0, st, dg_m, auxrows, n, GOAL, dgoal, (long long)GOAL);
+            }
             have_dseq = true;
         }
         // ---- decoder backward

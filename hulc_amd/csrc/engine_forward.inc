@@ -341,6 +341,15 @@
             else
             hipLaunchKernelGGL(clip_loss_kernel, dim3(1), dim3(64), 0, st, img, txt, n, GOAL, logit_scale, cw, (pair ? losses2 : losses) + 2, dimg, dtxt, dlogit_scale, lscale());
         }
+        // ---- BC-Z / MIA auxiliary losses (hulc.py:567-648) on the same rows; the MIA head shares the CLIP projections
+        bcz_n = mia_n = 0; aux_rows_last = 0;
+        if ((aux_bcz || aux_mia) && (b->is_lang || pair) && b->n_aux > 0) {
+            const int n = b->n_aux;
+            if (n > 64 || n > B) { hulc_set_error("auxiliary-loss rows n=%d unsupported (max 64, <= B)", n); return 1; }
+            if (!clip_n) HIP_CHECK(hipMemcpyAsync(auxrows, b->aux_rows, sizeof(int) * n, hipMemcpyHostToDevice, st));
+            if (aux_heads_fwd(b, n, clip_n > 0, true, pair ? pairBv : 0)) return 1;
+            aux_rows_last = n;
+        }
         if (hipGetLastError() != hipSuccess) { hulc_set_error("kernel launch failed in forward"); return 1; }
         have_fwd = true;
         // [total_mod, kl, action, clip]; a device `out` is written by the kernels themselves

@@ -97,6 +97,15 @@
             hipLaunchKernelGGL(clip_loss_kernel, dim3(1), dim3(64), 0, st, img, txt, n, GOAL, logit_scale, 0.f, valm + 3, dimg, dtxt, valm + 31);
             val_clip_n = n;
         }
+        // val/lang_pred_loss, val/lang_contrastive_loss (hulc.py:798-813): the BC-Z / MIA losses of the masked lang rows, forward only (hulc_aux_losses_get)
+        bcz_n = mia_n = 0; aux_rows_last = 0;
+        if ((aux_bcz || aux_mia) && b->is_lang && b->n_aux > 0) {
+            const int n = b->n_aux;
+            if (n > 64 || n > B) { hulc_set_error("auxiliary-loss rows n=%d unsupported (max 64, <= B)", n); return 1; }
+            if (!val_clip_n) HIP_CHECK(hipMemcpyAsync(auxrows, b->aux_rows, sizeof(int) * n, hipMemcpyHostToDevice, st));
+            if (aux_heads_fwd(b, n, val_clip_n > 0, false, 0)) return 1;
+            aux_rows_last = n;
+        }
         if (hipGetLastError() != hipSuccess) { hulc_set_error("kernel launch failed in validate"); return 1; }
         if (plan_pp_out && hulc) HIP_CHECK(hipMemcpyAsync(plan_pp_out, pidx_pp, sizeof(int) * B * NCAT, hipMemcpyDefault, st));
         if (plan_pr_out && hulc) HIP_CHECK(hipMemcpyAsync(plan_pr_out, pidx, sizeof(int) * B * NCAT, hipMemcpyDefault, st));

@@ -26,6 +26,10 @@ struct IEngine {
                          float* pred_pr_out) = 0;
     virtual int clip_gt_encode(const float* lang_emb, int m, int slot) = 0;
     virtual int clip_gt_scores(int slot, float* out_host, int64_t cap, int32_t* n_out, int32_t* m_out) = 0;
+    // ---- BC-Z / MIA language auxiliary heads (engine.h, aux_heads.h)
+    virtual int aux_heads_enable(int bc_z, int mia) = 0;
+    virtual int aux_weights_set(float bc_z_weight, float mia_weight) = 0;
+    virtual int aux_losses_get(float* out_host4) = 0;
     virtual int rollout_reset() = 0;
     virtual int rollout_plan(const hulc_rollout_obs* obs, const float* goal_static, const float* goal_gripper, const float* goal_lang,
                              const int32_t* plan_inject, int32_t* plan_out) = 0;

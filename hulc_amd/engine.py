@@ -39,6 +39,9 @@ class StepEngine:
         self.ctx = C.c_void_p()
         L.check(self.lib.hulc_ctx_create(C.byref(cfg), C.byref(self.ctx)))
         L.check(self.lib.hulc_set_stream(self.ctx, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self.aux_heads = bool(dims.use_bc_z or dims.use_mia)
+        if self.aux_heads:      # before the bind: the heads' tensors are then required by name (include/hulc_hip.h: hulc_aux_heads_enable)
+            L.check(self.lib.hulc_aux_heads_enable(self.ctx, int(dims.use_bc_z), int(dims.use_mia)))
         names = list(self.layout.keys())
         self._names = (C.c_char_p * len(names))(*[n.encode() for n in names])
         self._offs = (C.c_int64 * len(names))(*[self.layout[n][0] for n in names])
@@ -152,7 +155,7 @@ class StepEngine:
         if sync_losses:
             out = (C.c_float * 8)()
             L.check(self.lib.hulc_forward_loss_pair(self.ctx, C.byref(bv), C.byref(bl), loss_weight, clip_weight, out, 1))
-            return (dict(total_mod=out[0], kl=out[1], action=out[2], clip=out[3]), dict(total_mod=out[4], kl=out[5], action=out[6], clip=out[7]))
+            return (dict(total_mod=out[0], kl=out[1], action=out[2], clip=out[3]), self._with_aux(dict(total_mod=out[4], kl=out[5], action=out[6], clip=out[7]), True))
         if not hasattr(self, "_loss_dev8"):
             self._loss_dev8 = torch.zeros(8, dtype=torch.float32, device=self.device)
         L.check(self.lib.hulc_forward_loss_pair(self.ctx, C.byref(bv), C.byref(bl), loss_weight, clip_weight, self._loss_dev8.data_ptr(), 0))
@@ -169,11 +172,28 @@ class StepEngine:
         if sync_losses:
             out = (C.c_float * 4)()
             L.check(self.lib.hulc_forward_loss(self.ctx, C.byref(b), loss_weight, clip_weight, out, 1))
-            return dict(total_mod=out[0], kl=out[1], action=out[2], clip=out[3])
+            return self._with_aux(dict(total_mod=out[0], kl=out[1], action=out[2], clip=out[3]), is_lang)
         if not hasattr(self, "_loss_dev"):
             self._loss_dev = torch.zeros(4, dtype=torch.float32, device=self.device)
         L.check(self.lib.hulc_forward_loss(self.ctx, C.byref(b), loss_weight, clip_weight, self._loss_dev.data_ptr(), 0))
         return self._loss_dev
+
+    # ---- BC-Z / MIA language auxiliary heads (include/hulc_hip.h: hulc_aux_*; dims.use_bc_z / dims.use_mia) -------------------------------
+    def set_aux_weights(self, bc_z_weight: float = 1.0, mia_weight: float = 1.0) -> None:
+        """hulc_aux_weights_set: the factors multiplied into the two losses' gradients by every following forward (default 1 each)."""
+        L.check(self.lib.hulc_aux_weights_set(self.ctx, float(bc_z_weight), float(mia_weight)))
+
+    def aux_losses(self) -> Dict:
+        """hulc_aux_losses_get: {"bc_z", "mia", "aux_rows"} of the last forward_loss / forward_loss_pair / validate, unweighted; a head that did
+        not run (not enabled, no flagged row, no forward yet) reads 0.  Synchronises the stream."""
+        out = (C.c_float * 4)()
+        L.check(self.lib.hulc_aux_losses_get(self.ctx, out))
+        return dict(bc_z=out[0], mia=out[1], aux_rows=int(out[2]))
+
+    def _with_aux(self, losses: Dict, is_lang: bool) -> Dict:
+        if self.aux_heads and is_lang:
+            losses.update(self.aux_losses())
+        return losses
 
     def store_gather(self, actions: torch.Tensor, robot_obs: torch.Tensor, window_start: torch.Tensor, S: int, window_len: Optional[torch.Tensor] = None,
                      lang: Optional[torch.Tensor] = None, lang_row: Optional[torch.Tensor] = None, absolute: bool = False):
@@ -299,6 +319,9 @@ class StepEngine:
         o = list(out)
         res = dict(action_loss_pp=o[0], action_loss_pr=o[1], kl_loss=o[2], gripper_sr_pp=o[3], gripper_sr_pr=o[4],
                    mae_pp=np.array(o[5:11], np.float32), mae_pr=np.array(o[11:17], np.float32), sampled_plan_idx_pp=ppp, sampled_plan_idx_pr=ppr, val_pred_clip_loss=o[17])
+        if self.aux_heads and is_lang:      # val/lang_pred_loss, val/lang_contrastive_loss (hulc.py:798-813)
+            a = self.aux_losses()
+            res.update(lang_pred_loss=a["bc_z"], lang_contrastive_loss=a["mia"], aux_rows=a["aux_rows"])
         if mcil:
             res.update(sampled_plan_pp=ppp, sampled_plan_pr=ppr)
         if want_pred:

@@ -213,8 +213,31 @@ class Hulc(torch.nn.Module):
     ):
         super().__init__()
         # ---- options outside the hot path are rejected loudly instead of silently ignored (SURVEY §2.1 OUT OF SCOPE rows)
-        if state_recons or use_bc_z_auxiliary_loss or use_mia_auxiliary_loss or bc_z_lang_decoder or mia_lang_discriminator:
-            raise NotImplementedError("state_recons / bc_z / mia auxiliary losses are disabled in every BASELINE config and not built")
+        if state_recons:
+            raise NotImplementedError("state_recons needs the proprio encoder, which changes the width of the perceptual latent (disabled in every BASELINE config): not built")
+        # the language auxiliary losses (hulc.py:567-648): flag and network config go together, like the reference's `model.use_*=true model/*=default` overrides
+        for flag, net, fname, nname in ((use_bc_z_auxiliary_loss, bc_z_lang_decoder, "use_bc_z_auxiliary_loss", "bc_z_lang_decoder"),
+                                        (use_mia_auxiliary_loss, mia_lang_discriminator, "use_mia_auxiliary_loss", "mia_lang_discriminator")):
+            if flag and not net:
+                raise ValueError(f"{fname}=True needs the network config {nname} (model/{nname}=default)")
+            if net and not flag:
+                raise ValueError(f"{nname} is configured but {fname} is False (set model.{fname}=true or model/{nname}=none)")
+        if use_mia_auxiliary_loss:
+            if float(_get(mia_lang_discriminator, "dropout_p", 0.0) or 0.0) != 0.0:
+                raise NotImplementedError("mia_lang_discriminator.dropout_p != 0: the built discriminator has no dropout (the reference default is 0.0)")
+            for key in ("in_features", "lang_dim"):
+                v = _get(mia_lang_discriminator, key, 32)
+                if not isinstance(v, str) and int(v) != 32:
+                    raise NotImplementedError(f"mia_lang_discriminator.{key} {v!r}: the built discriminator scores two 32-wide projections")
+            for key, want in (("im_dim", 4096), ("lang_dim", 32), ("output_dim", 32)):
+                v = _get(proj_vis_lang, key, want)
+                if not isinstance(v, str) and int(v) != want:
+                    raise NotImplementedError(f"proj_vis_lang.{key} {v!r}: the built projection is {want} wide")
+        if use_bc_z_auxiliary_loss:
+            for key, want in (("in_features", 4096), ("lang_dim", 384)):
+                v = _get(bc_z_lang_decoder, key, want)
+                if not isinstance(v, str) and int(v) != want:
+                    raise NotImplementedError(f"bc_z_lang_decoder.{key} {v!r}: the built decoder maps {4096} features to a {384}-wide embedding")
         pr = plan_recognition
         ad = action_decoder
         self.kind = self.KIND
@@ -229,6 +252,8 @@ class Hulc(torch.nn.Module):
                                           "discrete_gripper false, no perceptual_emb_slice) are only built together (conf/model/mcil.yaml)")
             if use_clip_auxiliary_loss:
                 raise NotImplementedError("conf/model/mcil.yaml trains without the CLIP auxiliary loss (proj_vis_lang: none)")
+            if use_bc_z_auxiliary_loss or use_mia_auxiliary_loss:
+                raise NotImplementedError("the BC-Z / MIA auxiliary losses are not built for the mcil option group (conf/model/mcil.yaml has no proj_vis_lang)")
             rnn_type = str(_get(pr, "rnn_type", "nn.RNN"))
             if rnn_type not in ("nn.RNN", "nn.GRU"):
                 raise NotImplementedError(f"plan_recognition.rnn_type {rnn_type!r}: nn.RNN (birnn.yaml default) and nn.GRU are built")
@@ -266,6 +291,10 @@ class Hulc(torch.nn.Module):
                 raise NotImplementedError(f"configuration value {got!r} differs from the built architecture ({want!r})")
         self.use_clip_auxiliary_loss = bool(use_clip_auxiliary_loss)
         self.clip_auxiliary_loss_beta = float(clip_auxiliary_loss_beta)
+        self.use_bc_z_auxiliary_loss = bool(use_bc_z_auxiliary_loss)
+        self.bc_z_auxiliary_loss_beta = float(bc_z_auxiliary_loss_beta)
+        self.use_mia_auxiliary_loss = bool(use_mia_auxiliary_loss)
+        self.mia_auxiliary_loss_beta = float(mia_auxiliary_loss_beta)
         self.kl_beta = float(kl_beta)
         self.kl_balancing_mix = float(kl_balancing_mix)
         self.replan_freq = replan_freq
@@ -276,7 +305,7 @@ class Hulc(torch.nn.Module):
         self.lr_scheduler = lr_scheduler
         mw = _get(pr, "max_position_embeddings", 32) or 32
         max_window = 32 if isinstance(mw, str) else int(mw)      # a dangling ${...} (vision_only datasets) falls back to 32
-        self.dims = spec.ModelDims(kind=self.kind, max_window=max_window, use_clip=self.use_clip_auxiliary_loss,
+        self.dims = spec.ModelDims(kind=self.kind, max_window=max_window, use_clip=self.use_clip_auxiliary_loss, use_bc_z=self.use_bc_z_auxiliary_loss, use_mia=self.use_mia_auxiliary_loss,
                                    rnn_type="gru" if (self.kind == "mcil" and rnn_type == "nn.GRU") else "rnn")
         # Lightning precision flags: 16 / "16-mixed" = native AMP fp16 + GradScaler (the reference's conf/trainer/play_trainer.yaml:3) ->
         # the fp16 engine with its on-device loss scaler; bf16 needs none; 32 = the fp32 parity engine
@@ -291,6 +320,8 @@ class Hulc(torch.nn.Module):
                                num_classes=int(_get(ad, "num_classes", 256 if self.kind == "mcil" else 10)), gripper_alpha=float(_get(ad, "gripper_alpha", 1.0)),
                                log_scale_min=float(_get(ad, "log_scale_min", -7.0)), seed=int(seed))
         self.engine = StepEngine(self.dims, dropout_p=self.dropout_p, **self._engine_kw)
+        if self.engine.aux_heads:
+            self.engine.set_aux_weights(self.bc_z_auxiliary_loss_beta, self.mia_auxiliary_loss_beta)
         self._train_mode = True
         self._params = {n: torch.nn.Parameter(v, requires_grad=True) for n, v in self.engine.views(self.engine.flat_params).items()}
         for n, g in self.engine.views(self.engine.flat_grads).items():
@@ -584,9 +615,11 @@ class Hulc(torch.nn.Module):
             parallel.setup_comm(eng, os.environ.get("HULC_BUCKET_DTYPE", "fp32"))
         eng.zero_grads()
         nmod = len(batch)
-        if self.use_clip_auxiliary_loss and not any("lang" in s for s in batch):
-            raise KeyError("aux_lang")                       # SURVEY trap T4: reference raises at hulc.py:531
-        kl = act = tot = clip = 0.0
+        aux_heads = self.use_bc_z_auxiliary_loss or self.use_mia_auxiliary_loss
+        if (self.use_clip_auxiliary_loss or aux_heads) and not any("lang" in s for s in batch):
+            raise KeyError("aux_lang")                       # SURVEY trap T4: reference raises at hulc.py:511 / 521 / 531
+        kl = act = tot = clip = bcz = mia = 0.0
+        aux_bs = 1
         total_bs = 0
         bs: Dict[str, int] = {}
         scopes = list(batch)
@@ -626,7 +659,16 @@ class Hulc(torch.nn.Module):
             kl += l["kl"]; act += l["action"]; tot += l["total_mod"]
             if is_lang and self.use_clip_auxiliary_loss:
                 clip += l["clip"]
+            if is_lang and aux_heads:                          # unweighted, of the flagged rows (hulc.py:447-462); 0 when no row is flagged
+                bcz += l["bc_z"]; mia += l["mia"]
+                aux_bs = max(1, int(l["aux_rows"]))
         total = tot / nmod
+        if self.use_bc_z_auxiliary_loss:                       # added after the division by the number of modalities (hulc.py:504-523)
+            total = total + self.bc_z_auxiliary_loss_beta * bcz
+            self.log("train/pred_lang", parallel.mean_scalar(self.bc_z_auxiliary_loss_beta * bcz, device=eng.device), on_step=False, on_epoch=True, batch_size=aux_bs, sync_dist=True)
+        if self.use_mia_auxiliary_loss:
+            total = total + self.mia_auxiliary_loss_beta * mia
+            self.log("train/lang_contrastive", parallel.mean_scalar(self.mia_auxiliary_loss_beta * mia, device=eng.device), on_step=False, on_epoch=True, batch_size=aux_bs, sync_dist=True)
         if self.use_clip_auxiliary_loss:
             total = total + self.clip_auxiliary_loss_beta * clip
             self.log("train/lang_clip_loss", parallel.mean_scalar(self.clip_auxiliary_loss_beta * clip, device=eng.device), on_step=False, on_epoch=True, sync_dist=True)
@@ -663,6 +705,7 @@ class Hulc(torch.nn.Module):
             if is_lang and self.use_clip_auxiliary_loss:
                 self.log("val/val_pred_clip_loss", r["val_pred_clip_loss"], sync_dist=True)       # hulc.py:804-808
                 self.clip_groundtruth(dataset_batch.get("idx"), dataset_batch.get("use_for_aux_lang_loss"))
+            self._log_val_aux(is_lang, r)
             self.log(f"val_kl/{sc}_kl_loss", r["kl_loss"], sync_dist=True)
             self.log(f"val_act/{sc}_act_loss_pp", r["action_loss_pp"], sync_dist=True)
             self.log(f"val_act/{sc}_act_loss_pr", r["action_loss_pr"], sync_dist=True)
@@ -677,6 +720,13 @@ class Hulc(torch.nn.Module):
                 output[f"sampled_plan_pr_{sc}"] = one_hot(r["sampled_plan_idx_pr"])
             output[f"idx_{sc}"] = dataset_batch.get("idx")
         return output
+
+    def _log_val_aux(self, is_lang: bool, r: Dict) -> None:
+        """hulc.py:798-813 / gcbc.py:247-262: the unweighted BC-Z / MIA losses of a lang batch's flagged rows."""
+        if is_lang and self.use_bc_z_auxiliary_loss:
+            self.log("val/lang_pred_loss", r["lang_pred_loss"], sync_dist=True)
+        if is_lang and self.use_mia_auxiliary_loss:
+            self.log("val/lang_contrastive_loss", r["lang_contrastive_loss"], sync_dist=True)
 
     def _validation_step_gcbc(self, batch, batch_idx, noise=None):
         """gcbc.py:183-270: one decoder pass without a plan (loss_and_act), mae / gripper success rate, the reference's metric names."""
@@ -696,6 +746,7 @@ class Hulc(torch.nn.Module):
             self.log(f"val_pos_mae/{sc}_pos_mae", float(mae[:3].mean()), sync_dist=True)
             self.log(f"val_orn_mae/{sc}_orn_mae", float(mae[3:6].mean()), sync_dist=True)
             self.log(f"val_act/{sc}_act_loss", r["action_loss_pp"], sync_dist=True)
+            self._log_val_aux(is_lang, r)
             self.log(f"val_grip/{sc}_grip_sr", r["gripper_sr_pp"], sync_dist=True)
             self.log("val_act/action_loss", val_total / nmod, sync_dist=True)
             output[f"idx_{sc}"] = dataset_batch.get("idx")

@@ -21,6 +21,8 @@ class ModelDims:
     kind: str = "hulc"            # "hulc" | "gcbc" | "mcil" (conf/model/mcil.yaml: BiRNN plan encoder, continuous latent; use_clip must be False)
     max_window: int = 32          # rows of plan_recognition.position_embeddings
     use_clip: bool = True         # use_clip_auxiliary_loss (creates proj_vis_lang + logit_scale)
+    use_bc_z: bool = False        # use_bc_z_auxiliary_loss (creates bc_z_lang_decoder)
+    use_mia: bool = False         # use_mia_auxiliary_loss (creates mia_lang_discriminator; proj_vis_lang even without the CLIP loss)
     emb: int = 128                # perceptual latent size (64 static + 64 gripper)
     vf: int = 64
     goal: int = 32
@@ -157,12 +159,20 @@ def param_table(d: ModelDims) -> List[Tuple[str, Tuple[int, ...], tuple]]:
     if d.kind != "mcil":
         lin(ad + "gripper_fc", 2, H)
 
-    if d.use_clip:
+    if d.use_clip or d.use_mia:
         lin("proj_vis_lang.mlp_im.0", 128, d.fc_hidden)
         lin("proj_vis_lang.mlp_im.2", d.goal, 128)
         lin("proj_vis_lang.mlp_lang.0", 128, d.goal)
         lin("proj_vis_lang.mlp_lang.2", d.goal, 128)
+    if d.use_clip:
         t.append(("logit_scale", (), ("const", math.log(1.0 / 0.07))))
+    # the language auxiliary heads follow logit_scale: the tail of the flat buffer, final before the decoder backward (the first all-reduce bucket)
+    if d.use_bc_z:                # BCZLangDecoder: Linear(fc_hidden, 512), ReLU, Linear(512, lang)
+        lin("bc_z_lang_decoder.mlp.0", 512, d.fc_hidden)
+        lin("bc_z_lang_decoder.mlp.2", d.lang, 512)
+    if d.use_mia:                 # MIALangDiscriminator: Linear(2 * goal, 512), ReLU, Dropout, Linear(512, 1)
+        lin("mia_lang_discriminator.mlp.0", 512, 2 * d.goal)
+        lin("mia_lang_discriminator.mlp.3", 1, 512)
     return t
 
 

@@ -324,6 +324,23 @@ int hulc_store_stage_stats(hulc_ctx* ctx, int64_t* calls, int64_t* copies, int64
 int hulc_clip_gt_encode(hulc_ctx* ctx, const float* lang_emb, int32_t m, int32_t slot);
 int hulc_clip_gt_scores(hulc_ctx* ctx, int32_t slot, float* scores_host, int64_t cap_floats, int32_t* n_out, int32_t* m_out);
 
+/* ---- BC-Z and MIA language auxiliary losses (hulc/models/hulc.py:567-648; use_bc_z_auxiliary_loss / use_mia_auxiliary_loss), trained on the rows of a lang
+ * batch named by hulc_batch::aux_rows, next to the CLIP loss.  BC-Z: pred = bc_z_lang_decoder (Linear(4096,512), ReLU, Linear(512,384)) on seq_feat[rows],
+ * loss = mean(1 - cos(pred, lang[rows])).  MIA: the proj_vis_lang projections of seq_feat[rows] / latent_goal[rows] scored by mia_lang_discriminator
+ * (Linear(64,512), ReLU, Linear(512,1)) as matching pairs and as pairs with the text rolled by one row; binary cross entropy with logits over the 2n scores.
+ * hulc_aux_heads_enable: after hulc_ctx_create and BEFORE hulc_bind_params (later: an error; HULC_KIND_MCIL*: an error).  The bound table must then name
+ * bc_z_lang_decoder.mlp.{0,2}.{weight,bias} / mia_lang_discriminator.mlp.{0,3}.{weight,bias}; MIA also needs proj_vis_lang.* even with use_clip == 0
+ * (logit_scale only with use_clip).  A context that never calls it launches, allocates and copies exactly what it did before.
+ * hulc_aux_weights_set: the factors multiplied into the two losses' gradients (like clip_weight; default 1 each).
+ * hulc_aux_losses_get: out_host[4] = [bc_z, mia, rows, 0], unweighted, of the last hulc_forward_loss / _pair / hulc_validate; synchronises the stream.  A head that
+ * did not run — not enabled, a batch without flagged rows (nothing is launched, its gradients stay zero), or no forward yet — reads 0.  The four values of
+ * hulc_forward_loss keep their meaning: the caller adds weight x loss to its total as it does for the CLIP loss.
+ * BC-Z selects the rows once: where the reference indexes seq_feat by the mask a second time (and so raises unless every row is flagged) this computes the
+ * loss on the flagged rows. */
+int hulc_aux_heads_enable(hulc_ctx* ctx, int32_t bc_z, int32_t mia);
+int hulc_aux_weights_set(hulc_ctx* ctx, float bc_z_weight, float mia_weight);
+int hulc_aux_losses_get(hulc_ctx* ctx, float* out_host /* (4) */);
+
 /* ---- Rollout (Hulc.reset / step, hulc/models/hulc.py:843-957; stateful LogisticDecoderRNN.act, logistic_decoder_rnn.py:102-116).
  * hulc_rollout_plan  = get_pp_plan_vision (:905-927: obs and goal frame encoded as one 2-frame window) or get_pp_plan_lang
  *                      (:929-948): latent goal + a plan sampled from the plan proposal; clears the decoder's hidden state.

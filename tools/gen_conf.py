@@ -45,6 +45,8 @@ for name, tgt in (("hulc", "hulc.models.hulc.Hulc"), ("gcbc", "hulc.models.gcbc.
   - action_decoder: hulc_default
   - optimizer: adam
   - lr_scheduler: constant
+  - bc_z_lang_decoder: none
+  - mia_lang_discriminator: none
   - proj_vis_lang: default
 _target_: {tgt}
 _recursive_: false
@@ -60,8 +62,6 @@ state_recons: false
 use_bc_z_auxiliary_loss: false
 use_mia_auxiliary_loss: false
 replan_freq: 30
-bc_z_lang_decoder: null
-mia_lang_discriminator: null
 val_instructions: {{}}
 # ---- engine additions (hulc_amd.Hulc keyword arguments)
 precision: ${{trainer.precision}}
@@ -123,6 +123,15 @@ w("model/proj_vis_lang/default.yaml", dict(_target_="hulc.models.auxiliary_loss_
                                           im_dim="${model.plan_recognition.fc_hidden_size}", lang_dim="${model.language_goal.latent_goal_features}",
                                           output_dim="${model.language_goal.latent_goal_features}", proj_lang=True), H.format("proj_vis_lang/default.yaml"))
 w("model/proj_vis_lang/none.yaml", "{}\n", H.format("proj_vis_lang/none.yaml"))
+# the language auxiliary heads: model.use_bc_z_auxiliary_loss=true model/bc_z_lang_decoder=default, model.use_mia_auxiliary_loss=true model/mia_lang_discriminator=default
+w("model/bc_z_lang_decoder/default.yaml", dict(_target_="hulc.models.auxiliary_loss_networks.bc_z_lang_decoder.BCZLangDecoder",
+                                              in_features="${model.plan_recognition.fc_hidden_size}", lang_dim="${model.language_goal.in_features}"),
+  H.format("bc_z_lang_decoder/default.yaml"))
+w("model/bc_z_lang_decoder/none.yaml", "{}\n", H.format("bc_z_lang_decoder/none.yaml"))
+w("model/mia_lang_discriminator/default.yaml", dict(_target_="hulc.models.auxiliary_loss_networks.mia_lang_discriminator.MIALangDiscriminator",
+                                                   in_features="${model.proj_vis_lang.output_dim}", lang_dim="${model.proj_vis_lang.output_dim}", dropout_p=0.0),
+  H.format("mia_lang_discriminator/default.yaml"))
+w("model/mia_lang_discriminator/none.yaml", "{}\n", H.format("mia_lang_discriminator/none.yaml"))
 w("loss/default.yaml", dict(kl_beta=0.01, kl_balancing_mix=0.8, state_recon_beta=0.5, bc_z_auxiliary_loss_beta=1.0, mia_auxiliary_loss_beta=1.0,
                            clip_auxiliary_loss_beta=3.0), H.format("loss/default.yaml"))
 w("training/default_training.yaml", dict(lr=2.0e-4), H.format("training/default_training.yaml"))

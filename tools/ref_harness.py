@@ -120,7 +120,7 @@ def install_stubs():
         sys.path.insert(0, REF)
 
 
-def model_cfg(kind="hulc", max_window=32, use_clip=True, dropout_p=0.1):
+def model_cfg(kind="hulc", max_window=32, use_clip=True, dropout_p=0.1, use_bc_z=False, use_mia=False):
     """The resolved conf/model/{hulc,gcbc}.yaml tree (values copied from conf/**)."""
     vf = 64
     cfg = dict(
@@ -170,6 +170,13 @@ def model_cfg(kind="hulc", max_window=32, use_clip=True, dropout_p=0.1):
         proj_vis_lang=dict(_target_="hulc.models.auxiliary_loss_networks.proj_vis_lang.ProjVisLang",
                            im_dim=4096, lang_dim=32, output_dim=32, proj_lang=True),
     )
+    if use_bc_z:      # model.use_bc_z_auxiliary_loss=true model/bc_z_lang_decoder=default (conf/model/bc_z_lang_decoder/default.yaml, resolved)
+        cfg["use_bc_z_auxiliary_loss"] = True
+        cfg["bc_z_lang_decoder"] = dict(_target_="hulc.models.auxiliary_loss_networks.bc_z_lang_decoder.BCZLangDecoder", in_features=4096, lang_dim=384)
+    if use_mia:       # model.use_mia_auxiliary_loss=true model/mia_lang_discriminator=default
+        cfg["use_mia_auxiliary_loss"] = True
+        cfg["mia_lang_discriminator"] = dict(_target_="hulc.models.auxiliary_loss_networks.mia_lang_discriminator.MIALangDiscriminator", in_features=32, lang_dim=32,
+                                             dropout_p=0.0)
     return to_cfg(cfg)
 
 
