@@ -1,5 +1,6 @@
-// hulc_amd/csrc/aux_heads.h — the two language auxiliary heads next to the CLIP loss (kernels.h clip_loss_kernel), on the n <= 64 gathered rows
-// flagged by use_for_aux_lang_loss:
+// hulc_amd/csrc/aux_heads.h — the two language auxiliary heads next to the CLIP loss (kernels.h clip_loss_kernel), on the gathered rows flagged by
+// use_for_aux_lang_loss.  mia_head_kernel serves n <= 64 rows (MIA_MAXN); more rows go to the multi-workgroup kernels of aux_rows.h, which routes
+// (launch_mia_head).  cosine_dist_loss_kernel strides its rows and serves any n:
 //   mia_head_kernel          MIA cross-modality matching loss (hulc/models/hulc.py:606-648): the whole discriminator, forward and backward, one launch
 //   cosine_dist_loss_kernel  BC-Z language regression loss (hulc.py:567-604): mean(1 - cos(pred, lang)) and its gradient
 // fp32 arithmetic in every engine; single workgroup each (deterministic: fixed-order reductions, no atomics).

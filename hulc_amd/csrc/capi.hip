@@ -330,6 +330,45 @@ int hulc_k_cast(int32_t dtype, const float* src, void* dst, int64_t n, void* str
     return 0;
 }
 
+// the language auxiliary losses alone, routed on n as the engines route them (aux_rows.h): n <= 64 runs the single-workgroup kernels.  Synchronise.
+static int k_clip_loss(bool wide, const float* img, const float* txt, int32_t n, const float* logit_scale, float w, float* loss_out, float* dimg, float* dtxt,
+                       float* dlogit_scale, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || !img || !txt || !logit_scale || !loss_out || !dimg || !dtxt || !dlogit_scale) { hulc_set_error("hulc_k_clip_loss: n=%d or a null argument", (int)n); return 1; }
+    float* ws = nullptr;
+    if (n > AUX_ROWS_SINGLE && hipMalloc((void**)&ws, sizeof(float) * (size_t)clip_rows_ws_floats(n)) != hipSuccess) { hulc_set_error("hulc_k_clip_loss: hipMalloc failed"); return 1; }
+    const bool ok = launch_clip_loss(st, wide, img, txt, n, logit_scale, w, loss_out, dimg, dtxt, dlogit_scale, nullptr, ws);
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);
+    if (ws) hipFree(ws);
+    if (!ok || e1 != hipSuccess || e2 != hipSuccess) { hulc_set_error("hulc_k_clip_loss: %s", !ok ? "not launched" : hipGetErrorString(e1 != hipSuccess ? e1 : e2)); return 1; }
+    return 0;
+}
+int hulc_k_clip_loss(const float* img, const float* txt, int32_t n, const float* logit_scale, float w, float* loss_out, float* dimg, float* dtxt, float* dlogit_scale,
+                     void* stream) { return k_clip_loss(true, img, txt, n, logit_scale, w, loss_out, dimg, dtxt, dlogit_scale, stream); }
+int hulc_k_clip_loss_fp32(const float* img, const float* txt, int32_t n, const float* logit_scale, float w, float* loss_out, float* dimg, float* dtxt,
+                          float* dlogit_scale, void* stream) { return k_clip_loss(false, img, txt, n, logit_scale, w, loss_out, dimg, dtxt, dlogit_scale, stream); }
+int hulc_k_mia_head(const float* img, const float* txt, int32_t n, const float* W0, const float* b0, const float* W1, const float* b1, float w, float* loss_out,
+                    float* dimg, float* dtxt, int32_t accum, float* dW0, float* db0, float* dW1, float* db1, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || !img || !txt || !W0 || !b0 || !W1 || !b1 || !loss_out) { hulc_set_error("hulc_k_mia_head: n=%d or a null argument", (int)n); return 1; }
+    if (dW0 && (!dimg || !dtxt || !db0 || !dW1 || !db1)) { hulc_set_error("hulc_k_mia_head: the backward needs every gradient pointer"); return 1; }
+    float* ws = nullptr;
+    if (n > AUX_ROWS_SINGLE && hipMalloc((void**)&ws, sizeof(float) * (size_t)mia_rows_ws_floats(n)) != hipSuccess) { hulc_set_error("hulc_k_mia_head: hipMalloc failed"); return 1; }
+    const bool ok = launch_mia_head(st, img, txt, n, W0, b0, W1, b1, w, loss_out, dimg, dtxt, accum, dW0, db0, dW1, db1, nullptr, ws);
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);
+    if (ws) hipFree(ws);
+    if (!ok || e1 != hipSuccess || e2 != hipSuccess) { hulc_set_error("hulc_k_mia_head: %s", !ok ? "not launched" : hipGetErrorString(e1 != hipSuccess ? e1 : e2)); return 1; }
+    return 0;
+}
+int hulc_k_cosine_dist(const float* pred, const float* tgt, int32_t n, int32_t D, float w, float* loss_out, float* dpred, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || D < 1 || !pred || !tgt || !loss_out) { hulc_set_error("hulc_k_cosine_dist: n=%d D=%d or a null argument", (int)n, (int)D); return 1; }
+    hipLaunchKernelGGL(cosine_dist_loss_kernel, dim3(1), dim3(1024), 0, st, pred, tgt, n, D, w, loss_out, dpred, (const float*)nullptr);
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);
+    if (e1 != hipSuccess || e2 != hipSuccess) { hulc_set_error("hulc_k_cosine_dist: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); return 1; }
+    return 0;
+}
+
 int hulc_k_attention(int32_t variant, const float* qkv, float* P, float* ao, const float* dao, float* dqkv, int32_t B, int32_t S, float drop_p,
                      uint64_t seed, void* stream) {
     hipStream_t st = (hipStream_t)stream;

@@ -19,6 +19,7 @@
 #include "enc_tail.h"
 #include "rollout_step.h"
 #include "aux_heads.h"
+#include "aux_rows.h"
 
 namespace HULC_NS {
 
@@ -193,6 +194,7 @@ struct Engine : IEngine {
     T *bz1 = nullptr, *dbz1 = nullptr, *bz_dpred_t = nullptr; float *bz_pred = nullptr, *bz_tgt = nullptr, *bz_dpred = nullptr;
     float* aux_loss = nullptr;                               // device [4]: 0 bc_z, 1 mia (unweighted)
     int bcz_n = 0, mia_n = 0;                                // rows the heads of the last forward ran on (0: not launched, loss 0)
+    float *clip_rows_ws = nullptr, *mia_rows_ws = nullptr;   // aux_rows.h workspaces of the n > 64 kernels: only a context with max_batch > 64 has them
     int aux_rows_last = 0;                                   // rows of the last forward / validate, for hulc_aux_losses_get
     // ---- state of the last forward
     hulc_batch cur; float cur_lw = 0, cur_cw = 0; bool have_fwd = false;
@@ -287,6 +289,7 @@ struct Engine : IEngine {
         dimg = alloc<float>(B * GOAL); dtxt = alloc<float>(B * GOAL); dimg_t = alloc<T>(B * GOAL); dtxt_t = alloc<T>(B * GOAL);
         dim1 = alloc<T>(B * 128); dla1 = alloc<T>(B * 128); dsf_m = alloc<float>(B * FCH); dg_m = alloc<float>(B * GOAL);
         losses = alloc<float>(8);
+        if (B > AUX_ROWS_SINGLE && cfg.use_clip) clip_rows_ws = alloc<float>(clip_rows_ws_floats(B));
         if (gru) {
             for (int c = 0; c < 4; ++c) {
                 const int64_t rows = c < 3 ? SB : B;
@@ -322,6 +325,7 @@ struct Engine : IEngine {
             bz_pred = alloc<float>(B * LANG, "bcz_pred"); bz_tgt = alloc<float>(B * LANG); bz_dpred = alloc<float>(B * LANG);
         }
         aux_loss = alloc<float>(4);
+        if (mia && B > AUX_ROWS_SINGLE) mia_rows_ws = alloc<float>(mia_rows_ws_floats(B));
         if (alloc_failed) { hulc_set_error("hulc_aux_heads_enable: workspace allocation failed"); return 1; }
         aux_bcz = bc_z != 0; aux_mia = mia != 0;
         return 0;
@@ -349,10 +353,11 @@ struct Engine : IEngine {
                 { EpiP ep = epi(txt, true); lin_fwd(la1, 128, n, cl_la2, ep, GOAL); }
             }
             static_assert(GOAL == MIA_D, "mia_head_kernel is built for 32-wide projections");
-            if (train) hipLaunchKernelGGL(mia_head_kernel, dim3(1), dim3(1024), 0, st, img, txt, n, mia_w0, mia_b0, mia_w1, mia_b1, aux_w_mia, aux_loss + 1, dimg, dtxt, shared ? 1 : 0,
-                                          d_mia_w0, d_mia_b0, d_mia_w1, d_mia_b1, lscale());
-            else hipLaunchKernelGGL(mia_head_kernel, dim3(1), dim3(1024), 0, st, img, txt, n, mia_w0, mia_b0, mia_w1, mia_b1, 0.f, aux_loss + 1, (float*)nullptr, (float*)nullptr, 0,
-                                    (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr);
+            const bool ok = train ? launch_mia_head(st, img, txt, n, mia_w0, mia_b0, mia_w1, mia_b1, aux_w_mia, aux_loss + 1, dimg, dtxt, shared ? 1 : 0, d_mia_w0, d_mia_b0, d_mia_w1,
+                                                    d_mia_b1, lscale(), mia_rows_ws)
+                                  : launch_mia_head(st, img, txt, n, mia_w0, mia_b0, mia_w1, mia_b1, 0.f, aux_loss + 1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                    mia_rows_ws);
+            if (!ok) { hulc_set_error("MIA head: n=%d rows not covered by this context's workspace (max_batch=%d)", n, maxB); return 1; }
             mia_n = n;
         }
         if (aux_bcz) {

@@ -327,7 +327,7 @@
         clip_n = 0;
         if ((b->is_lang || pair) && cfg.use_clip && b->n_aux > 0) {
             const int n = b->n_aux;
-            if (n > 64 || n > B) { hulc_set_error("clip aux rows n=%d unsupported (max 64, <= B)", n); return 1; }
+            if (n > B) { hulc_set_error("clip aux rows n=%d unsupported (<= B=%d)", n, B); return 1; }
             clip_n = n;
             HIP_CHECK(hipMemcpyAsync(auxrows, b->aux_rows, sizeof(int) * n, hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * FCH, 256)), dim3(256), 0, st, seqf_t, (long long)FCH, auxrows, n, FCH, sf_m);
@@ -336,16 +336,16 @@
             { EpiP ep = epi(img, true); lin_fwd(im1, 128, n, cl_im2, ep, GOAL); }
             { EpiP ep = epi(la1, false); ep.relu = 1; lin_fwd(g_m, GOAL, n, cl_la0, ep, 128); }
             { EpiP ep = epi(txt, true); lin_fwd(la1, 128, n, cl_la2, ep, GOAL); }
-            if (GOAL <= 32 && !std::is_same<T, float>::value)
-                hipLaunchKernelGGL(clip_loss_wide_kernel, dim3(1), dim3(1024), 0, st, img, txt, n, GOAL, logit_scale, cw, (pair ? losses2 : losses) + 2, dimg, dtxt, dlogit_scale, lscale());
-            else
-            hipLaunchKernelGGL(clip_loss_kernel, dim3(1), dim3(64), 0, st, img, txt, n, GOAL, logit_scale, cw, (pair ? losses2 : losses) + 2, dimg, dtxt, dlogit_scale, lscale());
+            static_assert(GOAL == CLIP_D, "the CLIP loss kernels are built for 32-wide projections");
+            // n <= 64: one workgroup (the 1024-thread form on the 16-bit engines, the serial one on the fp32 parity engine); above: the tiled launches of aux_rows.h
+            if (!launch_clip_loss(st, !std::is_same<T, float>::value, img, txt, n, logit_scale, cw, (pair ? losses2 : losses) + 2, dimg, dtxt, dlogit_scale, lscale(), clip_rows_ws)) {
+                hulc_set_error("clip loss: n=%d rows not covered by this context's workspace (max_batch=%d)", n, maxB); return 1; }
         }
         // ---- BC-Z / MIA auxiliary losses (hulc.py:567-648) on the same rows; the MIA head shares the CLIP projections
         bcz_n = mia_n = 0; aux_rows_last = 0;
         if ((aux_bcz || aux_mia) && (b->is_lang || pair) && b->n_aux > 0) {
             const int n = b->n_aux;
-            if (n > 64 || n > B) { hulc_set_error("auxiliary-loss rows n=%d unsupported (max 64, <= B)", n); return 1; }
+            if (n > B) { hulc_set_error("auxiliary-loss rows n=%d unsupported (<= B=%d)", n, B); return 1; }
             if (!clip_n) HIP_CHECK(hipMemcpyAsync(auxrows, b->aux_rows, sizeof(int) * n, hipMemcpyHostToDevice, st));
             if (aux_heads_fwd(b, n, clip_n > 0, true, pair ? pairBv : 0)) return 1;
             aux_rows_last = n;

@@ -86,7 +86,7 @@
         // val/val_pred_clip_loss (hulc.py:804-808): the CLIP auxiliary loss of the lang modality on the masked rows, forward only
         if (b->is_lang && cfg.use_clip && b->n_aux > 0) {
             const int n = b->n_aux;
-            if (n > 64 || n > B) { hulc_set_error("clip aux rows n=%d unsupported (max 64, <= B)", n); return 1; }
+            if (n > B) { hulc_set_error("clip aux rows n=%d unsupported (<= B=%d)", n, B); return 1; }
             HIP_CHECK(hipMemcpyAsync(auxrows, b->aux_rows, sizeof(int) * n, hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * FCH, 256)), dim3(256), 0, st, seqf_t, (long long)FCH, auxrows, n, FCH, sf_m);
             hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * GOAL, 256)), dim3(256), 0, st, goal_t, (long long)GOAL, auxrows, n, GOAL, g_m);
@@ -94,14 +94,16 @@
             { EpiP ep = epi(img, true); lin_fwd(im1, 128, n, cl_im2, ep, GOAL); }
             { EpiP ep = epi(la1, false); ep.relu = 1; lin_fwd(g_m, GOAL, n, cl_la0, ep, 128); }
             { EpiP ep = epi(txt, true); lin_fwd(la1, 128, n, cl_la2, ep, GOAL); }
-            hipLaunchKernelGGL(clip_loss_kernel, dim3(1), dim3(64), 0, st, img, txt, n, GOAL, logit_scale, 0.f, valm + 3, dimg, dtxt, valm + 31);
+            const bool one_wg = n <= AUX_ROWS_SINGLE;          // the single-workgroup kernel also writes gradients (times 0, into scratch); above 64 rows: loss only
+            if (!launch_clip_loss(st, false, img, txt, n, logit_scale, 0.f, valm + 3, one_wg ? dimg : nullptr, one_wg ? dtxt : nullptr, one_wg ? valm + 31 : nullptr, nullptr, clip_rows_ws)) {
+                hulc_set_error("clip loss: n=%d rows not covered by this context's workspace (max_batch=%d)", n, maxB); return 1; }
             val_clip_n = n;
         }
         // val/lang_pred_loss, val/lang_contrastive_loss (hulc.py:798-813): the BC-Z / MIA losses of the masked lang rows, forward only (hulc_aux_losses_get)
         bcz_n = mia_n = 0; aux_rows_last = 0;
         if ((aux_bcz || aux_mia) && b->is_lang && b->n_aux > 0) {
             const int n = b->n_aux;
-            if (n > 64 || n > B) { hulc_set_error("auxiliary-loss rows n=%d unsupported (max 64, <= B)", n); return 1; }
+            if (n > B) { hulc_set_error("auxiliary-loss rows n=%d unsupported (<= B=%d)", n, B); return 1; }
             if (!val_clip_n) HIP_CHECK(hipMemcpyAsync(auxrows, b->aux_rows, sizeof(int) * n, hipMemcpyHostToDevice, st));
             if (aux_heads_fwd(b, n, val_clip_n > 0, false, 0)) return 1;
             aux_rows_last = n;

@@ -60,8 +60,8 @@ typedef struct hulc_batch {
     const float* robot_obs;      /* (B,S,15) state_info.robot_obs (raw; euler angles in [3:6]) */
     const float* lang;           /* (B,384) language embedding, lang modality only */
     const int32_t* plan_idx;     /* optional (B,32) injected categorical sample (parity tests); NULL = sample on device */
-    const int32_t* aux_rows;     /* HOST: indices b with use_for_aux_lang_loss[b] != 0 (lang modality, clip loss) */
-    int32_t n_aux;
+    const int32_t* aux_rows;     /* HOST: indices b with use_for_aux_lang_loss[b] != 0 (lang modality; rows of the CLIP, MIA and BC-Z losses) */
+    int32_t n_aux;               /* any 0 <= n_aux <= B; above 64 rows the losses run as multi-workgroup kernels (csrc/aux_rows.h) */
     uint64_t step;               /* optimizer step index, mixed into the dropout / sampling seeds */
     /* ---- uint8 ingest (zero-initialise for the reference's fp32 boundary) ------------------------------
      * frames_u8 != 0: rgb_static / rgb_gripper point to uint8 (B,S,H,W,C) frames as stored in the dataset; the dataloader transforms of
@@ -517,6 +517,22 @@ int hulc_k_cast(int32_t dtype, const float* src, void* dst, int64_t n, void* hip
  * engine runs (two lanes per query row), 2 = its kernels for 32 < S <= 64 (four waves per head, any S <= 64).  drop_p / seed: the attention-probability dropout (mask = hash(seed, element index)). */
 int hulc_k_attention(int32_t variant, const float* qkv, float* P, float* ao, const float* dao, float* dqkv, int32_t B, int32_t S,
                      float drop_p, uint64_t seed, void* hip_stream);
+
+/* the language auxiliary losses alone (fp32, device pointers; synchronise), routed on n exactly as the engines route them: n <= 64 runs the single-workgroup
+ * kernels, n > 64 the multi-workgroup ones (csrc/aux_rows.h); any n >= 1.
+ * CLIP: img, txt (n, 32); logit_scale one device float (the log of the scale); loss_out[0] written; dimg, dtxt (n, 32) written, already times w;
+ * dlogit_scale[0] += its gradient.  hulc_k_clip_loss takes the route of the 16-bit engines (n <= 64: the 1024-thread kernel), hulc_k_clip_loss_fp32 that of the
+ * fp32 engine and of validation (n <= 64: the 64-thread kernel); above 64 rows both run the same launches.
+ * MIA: W0 (512, 64), b0 (512), W1 (1, 512), b1 (1); loss_out[0] written (unweighted); dimg, dtxt (n, 32) stored, or added to when accum != 0; dW0, db0, dW1, db1
+ * added to; dW0 == NULL: the loss only.
+ * BC-Z: pred, tgt (n, D); loss_out[0] = mean(1 - cos); dpred (n, D) written unless NULL. */
+int hulc_k_clip_loss(const float* img, const float* txt, int32_t n, const float* logit_scale, float w, float* loss_out, float* dimg, float* dtxt,
+                     float* dlogit_scale, void* hip_stream);
+int hulc_k_clip_loss_fp32(const float* img, const float* txt, int32_t n, const float* logit_scale, float w, float* loss_out, float* dimg, float* dtxt,
+                          float* dlogit_scale, void* hip_stream);
+int hulc_k_mia_head(const float* img, const float* txt, int32_t n, const float* W0, const float* b0, const float* W1, const float* b1, float w, float* loss_out,
+                    float* dimg, float* dtxt, int32_t accum, float* dW0, float* db0, float* dW1, float* db1, void* hip_stream);
+int hulc_k_cosine_dist(const float* pred, const float* tgt, int32_t n, int32_t D, float w, float* loss_out, float* dpred, void* hip_stream);
 
 #ifdef __cplusplus
 }
