@@ -322,6 +322,33 @@ int hulc_k_gemm_nt(int32_t dtype, const void* A, const void* B, float* C, int32_
     if (dtype == HULC_DTYPE_F16) return hulc_f16::k_gemm_nt(0, A, B, C, M, N, K, lda, ldb, ldc, bias, relu, stream);
     return hulc_bf16::k_gemm_nt(dtype == HULC_DTYPE_F32, A, B, C, M, N, K, lda, ldb, ldc, bias, relu, stream);
 }
+// the 16-bit encoder head and the action loss (k_entries.h): dispatched on dtype like hulc_k_gemm_nt
+#define HULC_K_16BIT(name, call)                                                                                          \
+    if (dtype == HULC_DTYPE_F16) return hulc_f16::call;                                                                    \
+    if (dtype == HULC_DTYPE_BF16) return hulc_bf16::call;                                                                  \
+    hulc_set_error(name ": dtype %d is not a 16-bit type", (int)dtype);                                                    \
+    return 1
+int hulc_k_spatial_softmax64(int32_t dtype, const void* f, int32_t H, int32_t W, int32_t Nf, void* out, float* stats, const float* dout, void* df, void* stream) {
+    HULC_K_16BIT("hulc_k_spatial_softmax64", k_spatial_softmax64(f, H, W, Nf, out, stats, dout, df, stream));
+}
+int hulc_k_enc_tail_fwd(int32_t dtype, int32_t Nf, int32_t ldemb, const hulc_enc_tail_job* a, const hulc_enc_tail_job* b, void* emb, const float* pos, int32_t S,
+                        float drop_p, uint64_t seed, float* xf, void* xt, float* z0, float* z1, void* stream) {
+    HULC_K_16BIT("hulc_k_enc_tail_fwd", k_enc_tail_fwd(Nf, ldemb, a, b, emb, pos, S, drop_p, (unsigned long long)seed, xf, xt, z0, z1, stream));
+}
+int hulc_k_enc_tail_bwd(int32_t dtype, int32_t Nf, int32_t ldemb, const hulc_enc_tail_bwd_job* a, const hulc_enc_tail_bwd_job* b, const float* demb, void* stream) {
+    HULC_K_16BIT("hulc_k_enc_tail_bwd", k_enc_tail_bwd(Nf, ldemb, a, b, demb, stream));
+}
+#undef HULC_K_16BIT
+int hulc_k_logistic_loss(int32_t dtype, int32_t wide, const float* heads, int32_t ldh, const float* actions, const float* robot_obs, int32_t B, int32_t S,
+                         int32_t n_mix, int32_t n_dim, int32_t num_classes, float log_scale_min, float gripper_alpha, int32_t gripper_control,
+                         int32_t discrete_gripper, float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* stream) {
+    if (dtype == HULC_DTYPE_F16)
+        return hulc_f16::k_logistic_loss(1, wide, heads, ldh, actions, robot_obs, B, S, n_mix, n_dim, num_classes, log_scale_min, gripper_alpha, gripper_control,
+                                         discrete_gripper, grad_scale, lscale, row_loss, a_tcp_out, dheads, stream);
+    if (dtype != HULC_DTYPE_F32 && dtype != HULC_DTYPE_BF16) { hulc_set_error("hulc_k_logistic_loss: unknown dtype %d", (int)dtype); return 1; }
+    return hulc_bf16::k_logistic_loss(dtype == HULC_DTYPE_BF16, wide, heads, ldh, actions, robot_obs, B, S, n_mix, n_dim, num_classes, log_scale_min, gripper_alpha,
+                                      gripper_control, discrete_gripper, grad_scale, lscale, row_loss, a_tcp_out, dheads, stream);
+}
 int hulc_k_cast(int32_t dtype, const float* src, void* dst, int64_t n, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (dtype == HULC_DTYPE_F32) hipLaunchKernelGGL((cast_kernel<float, float>), dim3(1024), dim3(256), 0, st, src, (float*)dst, (long long)n);

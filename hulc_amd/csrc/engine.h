@@ -1135,3 +1135,5 @@ IEngine* make_engine(const hulc_config& cfg, int* rc) {
 }
 
 }  // namespace HULC_NS
+
+#include "k_entries.h"      // test entries of the 16-bit encoder head and the action loss (hulc_k_spatial_softmax64, hulc_k_enc_tail_*, hulc_k_logistic_loss)

@@ -182,6 +182,13 @@ struct IEngine {
 #define HULC_TU_DECLS                                                                                                                         \
     IEngine* make_engine(const hulc_config& cfg, int* rc);                                                                                   \
     int k_gemm_nt(int is_f32, const void* A, const void* B, float* C, int M, int N, int K, long long lda, long long ldb, long long ldc, \
-                  const float* bias, int relu, void* stream);
+                  const float* bias, int relu, void* stream);                                                                                \
+    int k_spatial_softmax64(const void* f, int H, int W, int Nf, void* out, float* stats, const float* dout, void* df, void* stream);          \
+    int k_enc_tail_fwd(int Nf, int ldemb, const hulc_enc_tail_job* a, const hulc_enc_tail_job* b, void* emb, const float* pos, int S,           \
+                       float drop_p, unsigned long long seed, float* xf, void* xt, float* z0, float* z1, void* stream);                         \
+    int k_enc_tail_bwd(int Nf, int ldemb, const hulc_enc_tail_bwd_job* a, const hulc_enc_tail_bwd_job* b, const float* demb, void* stream);     \
+    int k_logistic_loss(int t16, int wide, const float* heads, int ldh, const float* actions, const float* robot_obs, int B, int S, int nmix,   \
+                        int ndim, int num_classes, float log_scale_min, float gripper_alpha, int gripper_control, int discrete_gripper,         \
+                        float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* stream);
 namespace hulc_bf16 { HULC_TU_DECLS }   // capi.hip: HULC_DTYPE_F32 / HULC_DTYPE_BF16
 namespace hulc_f16 { HULC_TU_DECLS }    // engine_f16.hip: HULC_DTYPE_F16

@@ -458,8 +458,10 @@ int hulc_timers_read(hulc_ctx* ctx, char* json_out, int64_t cap, int32_t reset);
 int hulc_get_tensor(hulc_ctx* ctx, const char* name, float* host_out, int64_t cap, int64_t* n);
 int hulc_get_plan_idx(hulc_ctx* ctx, int32_t* host_out, int64_t cap);
 
-/* Per-kernel test entry points (device pointers; dtype selects fp32 / bf16 / fp16 storage of A, B — HULC_DTYPE_F16 for hulc_k_gemm_nt only,
- * the other half-precision entries run the bf16 build of the kernels; the fp16 build of every kernel is covered by the fp16 step tests). */
+/* Per-kernel test entry points (device pointers).  Entries with a `dtype` argument run the build of the kernels for that 16-bit type: HULC_DTYPE_BF16 or
+ * HULC_DTYPE_F16 (hulc_k_gemm_nt, hulc_k_spatial_softmax64, hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss; HULC_DTYPE_F32 where noted).
+ * The half-precision entries without one run the bf16 build; the fp16 build of their kernels is covered by the fp16 step tests.
+ * hulc_k_gemm_nt: dtype selects fp32 / bf16 / fp16 storage of A, B. */
 int hulc_k_gemm_nt(int32_t dtype, const void* A, const void* B, float* C, int32_t M, int32_t N, int32_t K, int64_t lda,
                    int64_t ldb, int64_t ldc, const float* bias, int32_t relu, void* hip_stream);
 /* conv weight-gradient kernel alone (bf16 NHWC activations): which = 2 (4x4 s2, 32->64) or 3 (3x3 s1, 64->64); square frames of
@@ -533,6 +535,46 @@ int hulc_k_clip_loss_fp32(const float* img, const float* txt, int32_t n, const f
 int hulc_k_mia_head(const float* img, const float* txt, int32_t n, const float* W0, const float* b0, const float* W1, const float* b1, float w, float* loss_out,
                     float* dimg, float* dtxt, int32_t accum, float* dW0, float* db0, float* dW1, float* db1, void* hip_stream);
 int hulc_k_cosine_dist(const float* pred, const float* tgt, int32_t n, int32_t D, float w, float* loss_out, float* dpred, void* hip_stream);
+
+/* ---- the 16-bit encoder head and the action loss, kernel by kernel (dtype = HULC_DTYPE_BF16 / HULC_DTYPE_F16 unless noted; asynchronous on hip_stream).
+ * Every entry checks its arguments first: a bad shape or a null required pointer returns 1 (hulc_last_error) and launches nothing.
+ *
+ * hulc_k_spatial_softmax64: the static camera's spatial softmax over 64 channels (csrc/kernels.h).  f = feature maps [Nf][H*W][64], 16 bit; H, W >= 2.
+ *   dout == NULL: forward.  out [Nf][128] 16 bit (channel 2c = expectation of linspace(-1,1,H)[h], 2c+1 = of linspace(-1,1,W)[w]) and
+ *   stats [Nf][64][4] fp32 = (max, 1 / sum exp, ex, ey) are written.  dout [Nf][128] fp32 given: backward from f, stats and dout into df [Nf][H*W][64] 16 bit,
+ *   masked by f > 0 (the ReLU of conv3); out is unused.  f, stats, dout, df 16-byte aligned. */
+int hulc_k_spatial_softmax64(int32_t dtype, const void* f, int32_t H, int32_t W, int32_t Nf, void* out, float* stats, const float* dout, void* df, void* hip_stream);
+/* hulc_k_enc_tail_fwd: fc1 + ReLU (128 -> 512), fc2 (512 -> 64) and LayerNorm of BOTH cameras in one launch (csrc/enc_tail.h).  A job = one camera:
+ *   x [Nf][128], W1 [512][128], W2 [64][512] 16 bit; b1 [512], b2 [64], lng [64], lnb [64] fp32; saved for the backward: f1 [Nf][512] 16 bit, f2 [Nf][64] fp32,
+ *   lnst [Nf][2] fp32 (mean, rstd); the job's 64 features go to columns col0 .. col0 + 63 of emb [Nf][ldemb] 16 bit.
+ *   pos [S][ldemb] fp32 given: also x0 = dropout(emb + pos[row % S]) as xf [Nf][ldemb] fp32 and xt (16 bit), keep mask = hash(seed, element index) >= drop_p,
+ *   and z0 = z1 = 0 ([Nf][ldemb] fp32), on the jobs' columns.  pos == NULL: S, drop_p, seed, xf, xt, z0, z1 are unused. */
+typedef struct hulc_enc_tail_job {
+    const void* x; const void* W1; const void* W2; const float* b1; const float* b2; const float* lng; const float* lnb;
+    void* f1; float* f2; float* lnst;
+    int32_t col0;
+} hulc_enc_tail_job;
+int hulc_k_enc_tail_fwd(int32_t dtype, int32_t Nf, int32_t ldemb, const hulc_enc_tail_job* a, const hulc_enc_tail_job* b, void* emb, const float* pos, int32_t S,
+                        float drop_p, uint64_t seed, float* xf, void* xt, float* z0, float* z1, void* hip_stream);
+/* hulc_k_enc_tail_bwd: the data-gradient chain of the same tail, both cameras in one launch: from demb [Nf][ldemb] fp32 (a job reads columns col0 .. col0 + 63)
+ *   and the saved f2, lnst, f1: d_f2 [Nf][64] and d_f1 [Nf][512] (16 bit; d_f1 masked by f1 > 0) are written, dlng [64] / dlnb [64] are ADDED to, and the input
+ *   gradient [Nf][128] goes to exactly one of dx_f32 (fp32, no mask: the static camera) and dx_t (16 bit, masked by xmask > 0 when xmask [Nf][128] is given: the
+ *   gripper camera).  W2t [512][64] and W1t [128][512] are the transposed weights, 16 bit. */
+typedef struct hulc_enc_tail_bwd_job {
+    const float* f2; const float* lnst; const float* lng; const void* f1; const void* W2t; const void* W1t; const void* xmask;
+    float* dlng; float* dlnb; void* d_f2; void* d_f1; float* dx_f32; void* dx_t;
+    int32_t col0;
+} hulc_enc_tail_bwd_job;
+int hulc_k_enc_tail_bwd(int32_t dtype, int32_t Nf, int32_t ldemb, const hulc_enc_tail_bwd_job* a, const hulc_enc_tail_bwd_job* b, const float* demb, void* hip_stream);
+/* hulc_k_logistic_loss: the action loss (discretised logistic mixture + gripper cross entropy) and its gradient.  dtype = type T of dheads: HULC_DTYPE_F32,
+ *   HULC_DTYPE_BF16 or HULC_DTYPE_F16.  wide = 0: logistic_loss_kernel<T, 10> with the engine's block size (one thread per row and dimension); wide = 1:
+ *   logistic_loss_wide_kernel<T> (one lane per mixture component).  heads [S*B][ldh] fp32, time-major rows r = t*B + b, columns = logit_probs | means |
+ *   log_scales (n_mix * n_dim each, index d * n_mix + k) | 2 gripper logits when discrete_gripper | pad.  actions [B][S][7], robot_obs [B][S][15] fp32 (needed
+ *   when gripper_control).  n_mix must be 10; n_dim 1..6 (7 without the gripper head).  Written: row_loss [S*B][8] (per dimension, then the gripper term; never
+ *   scaled), a_tcp_out [B][S][7] (optional), dheads [S*B][ldh] = gradient * grad_scale (* lscale[0] when the device float lscale is given), pad columns zero. */
+int hulc_k_logistic_loss(int32_t dtype, int32_t wide, const float* heads, int32_t ldh, const float* actions, const float* robot_obs, int32_t B, int32_t S,
+                         int32_t n_mix, int32_t n_dim, int32_t num_classes, float log_scale_min, float gripper_alpha, int32_t gripper_control,
+                         int32_t discrete_gripper, float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* hip_stream);
 
 #ifdef __cplusplus
 }
