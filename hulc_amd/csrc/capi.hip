@@ -457,9 +457,10 @@ int hulc_k_conv1_interior_groups(int32_t IW, int32_t pad, int32_t cap, int32_t* 
 }
 
 // conv1's weight gradient from uint8 (Nf,IH,IH,3) frames alone (tests): dW (32,192) [torch (o, c, kh, kw) order] and db (32) of the frames after ScaleImageTensor / Normalize /
-// RandomShiftsAug — form 0: raw rows through LDS (conv1_wgrad_tr2u_kernel), 1: conversion from the prefetch registers (conv1_wgrad_tr2r_kernel), 2: the same with interior / row-end slots; fold = Conv1Src::fold
+// RandomShiftsAug — form 1: conversion from the prefetch registers (conv1_wgrad_tr2r_kernel), 2: the same with interior / row-end slots (the engine's); fold = Conv1Src::fold
 int hulc_k_conv1_wgrad_u8(const void* X, const int32_t* shifts, int32_t pad, const void* dY, float* dw_out, float* db_out, int32_t Nf, int32_t IH, int32_t form, int32_t fold, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    if (form != 1 && form != 2) { hulc_set_error("hulc_k_conv1_wgrad_u8: form must be 1 or 2 (got %d)", (int)form); return 1; }      // before any device call
     float *part = nullptr, *bias = nullptr;
     if (hipMalloc(&part, sizeof(float) * 512ll * 32 * 192) != hipSuccess || hipMalloc(&bias, sizeof(float) * 64) != hipSuccess) { hulc_set_error("hulc_k_conv1_wgrad_u8: hipMalloc failed"); return 1; }
     hipMemsetAsync(bias, 0, sizeof(float) * 64, st);
@@ -482,8 +483,12 @@ int hulc_k_conv1_wgrad_u8(const void* X, const int32_t* shifts, int32_t pad, con
 int hulc_k_conv_tile(int32_t mode, const void* img, const void* w, const float* bias, const void* mask, void* out, int32_t Nf, int32_t IMH,
                      int32_t OUTH, int32_t relu, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    // every argument is checked before anything is allocated or launched.  relu: bit 0 = ReLU, bit 5 (32) = dynamic work claiming, bit 8 (256, modes 5 / 6) = the
+    // register-staged uint8 conv1 forward (conv1_fwd_kernel<4, true>, the cross-check of the LDS-DMA kernel)
+    if (mode < 0 || mode > 29 || (mode >= 14 && mode <= 16) || (mode >= 24 && mode <= 26)) { hulc_set_error("hulc_k_conv_tile: unsupported mode %d", (int)mode); return 1; }
+    if ((relu & ~(1 | 32 | 256)) || ((relu & 256) && mode != 5 && mode != 6)) { hulc_set_error("hulc_k_conv_tile: unknown bits in relu (%d) for mode %d", (int)relu, (int)mode); return 1; }
     ConvTileP p{}; p.img = (const h16_t*)img; p.IMH = p.IMW = IMH; p.w = (const h16_t*)w; p.out = (h16_t*)out; p.OUTH = p.OUTW = OUTH;
-    p.bias = bias; p.mask = (const h16_t*)mask; p.relu = relu & 1; p.dbg = relu & (30 | 64 | 128 | 256); p.Nf = Nf;
+    p.bias = bias; p.mask = (const h16_t*)mask; p.relu = relu & 1; p.Nf = Nf;
     // modes 7..9 = the production forms: 7 = mode 1 that also EMITS the ReLU bitmask of its output into `mask` (unsigned[Nf][OUTH][OUTW][2]);
     // 8 / 9 = modes 2 / 3 with `mask` = ReLU bitmask words (2 / 1 per output pixel) staged through LDS.  relu bit 5 (32): dynamic work claiming.
     if (mode == 7) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 1; }
@@ -504,37 +509,19 @@ int hulc_k_conv_tile(int32_t mode, const void* img, const void* w, const float* 
     if (mode == 17) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 11; }
     if (mode == 18) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 12; }
     if (mode == 19) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 13; }      // 13 / 19: modes 3 / 9 (conv2 data gradient, four parity classes)
-    if (mode == 12 || mode == 13) {
-        static void* zp = nullptr;
-        if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_tile: hipMalloc failed"); return 1; } hipMemset(zp, 0, 256); }
-        p.zeros = (const h16_t*)zp;
-    }
     // modes 20 / 21 / 27 / 22 / 28 / 23 / 29: modes 10 .. 19 in the form with two 256-thread workgroups per CU (conv_reg.h, NWV = 4)
     if (mode == 27) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 21; }
     if (mode == 28) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 22; }
     if (mode == 29) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 23; }
-    if (mode == 22 || mode == 23) {
-        static void* zp2 = nullptr;
-        if (!zp2) { if (hipMalloc(&zp2, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_tile: hipMalloc failed"); return 1; } hipMemset(zp2, 0, 256); }
-        p.zeros = (const h16_t*)zp2;
+    if (mode == 12 || mode == 13 || mode == 22 || mode == 23) {      // the data-gradient forms stage their zero border from a zero page
+        static void* zp = nullptr;
+        if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_tile: hipMalloc failed"); return 1; } hipMemset(zp, 0, 256); }
+        p.zeros = (const h16_t*)zp;
     }
-    // modes 30 .. 39: the two-workgroup form with TWO (smaller) band buffers per workgroup
-    if (mode == 37) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 31; }
-    if (mode == 38) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 32; }
-    if (mode == 39) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 33; }
-    if (mode == 32 || mode == 33) {
-        static void* zp3 = nullptr;
-        if (!zp3) { if (hipMalloc(&zp3, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_tile: hipMalloc failed"); return 1; } hipMemset(zp3, 0, 256); }
-        p.zeros = (const h16_t*)zp3;
-    }
-    if (mode == 30) ok = launch_conv_reg<64, 3, 3, 1, false, 1, 4, 2>(st, p);
-    else if (mode == 31) ok = launch_conv_reg<32, 4, 4, 2, false, 1, 4, 2>(st, p);
-    else if (mode == 32) ok = launch_conv_reg<64, 3, 3, 1, true, 1, 4, 2>(st, p);
-    else if (mode == 33) ok = launch_conv_reg<64, 2, 2, 1, true, 2, 4, 2>(st, p);
-    else if (mode == 20) ok = launch_conv_reg<64, 3, 3, 1, false, 1, 4>(st, p);
-    else if (mode == 21) ok = launch_conv_reg<32, 4, 4, 2, false, 1, 4, 0, true>(st, p);      // the production form for small maps: slot decode in registers (conv_reg.h PKR)
-    else if (mode == 22) ok = launch_conv_reg<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, p);    // the production forms: PKR + pipelined epilogue (EPI; 16-bit mask values
-    else if (mode == 23) ok = launch_conv_reg<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, p);    // = modes 22 / 23 fall back to the pair form inside launch_conv_reg)
+    if (mode == 20) ok = launch_conv_reg<64, 3, 3, 1, false, 1, 4>(st, p);
+    else if (mode == 21) ok = launch_conv_reg<32, 4, 4, 2, false, 1, 4, true>(st, p);         // the production form for small maps: slot decode in registers (conv_reg.h PKR)
+    else if (mode == 22) ok = launch_conv_reg<64, 3, 3, 1, true, 1, 4, true, 1>(st, p);       // the production forms: PKR + pipelined epilogue (EPI; 16-bit mask values
+    else if (mode == 23) ok = launch_conv_reg<64, 2, 2, 1, true, 2, 4, true, 1>(st, p);       // = modes 22 / 23 fall back to the pair form inside launch_conv_reg)
     else if (mode == 10) ok = launch_conv_reg_fwd<64, 3, 3, 1>(st, p);
     else if (mode == 11) ok = launch_conv_reg_fwd<32, 4, 4, 2>(st, p);
     else if (mode == 12) ok = launch_conv_reg<64, 3, 3, 1, true>(st, p);
@@ -543,10 +530,10 @@ int hulc_k_conv_tile(int32_t mode, const void* img, const void* w, const float* 
     else if (mode == 1) ok = launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p);
     else if (mode == 2) ok = launch_conv_tile<64, 64, 3, 3, 1, 1, true>(st, p);
     else if (mode == 3) ok = launch_conv_tile<64, 32, 2, 2, 1, 2, true>(st, p);
-    else if (mode == 4) { launch_conv1_fwd(st, Conv1Src{img, nullptr, 0, 0}, (const h16_t*)w, bias, (h16_t*)out, Nf, IMH, IMH, OUTH, OUTH, relu & ~1); ok = true; }
+    else if (mode == 4) { launch_conv1_fwd(st, Conv1Src{img, nullptr, 0, 0}, (const h16_t*)w, bias, (h16_t*)out, Nf, IMH, IMH, OUTH, OUTH); ok = true; }
     else if (mode == 5 || mode == 6) {      // conv1 forward from uint8 NHWC frames; mode 6: `mask` = (Nf,2) int32 RandomShiftsAug shifts, pad 10 (IMH >= 100) or 4
         launch_conv1_fwd(st, Conv1Src{img, mode == 6 ? (const int*)mask : nullptr, 1, IMH >= 100 ? 10 : 4}, (const h16_t*)w, bias, (h16_t*)out, Nf, IMH, IMH, OUTH,
-                         OUTH, relu & ~1);
+                         OUTH, (relu & 256) != 0);
         ok = true;
     }
     if (!ok) { hulc_set_error("hulc_k_conv_tile: unsupported mode/shape"); return 1; }
@@ -651,8 +638,8 @@ int hulc_k_conv_pair(int32_t stage, const hulc_conv_job* a, const hulc_conv_job*
     bool ok = false;
     if (stage == HULC_PAIR_CONV2_FWD) ok = launch_conv_reg_fwd_jobs<32, 4, 4, 2>(st, j, n, wg);
     else if (stage == HULC_PAIR_CONV3_FWD) ok = launch_conv_reg_fwd_jobs<64, 3, 3, 1>(st, j, n, wg);
-    else if (stage == HULC_PAIR_CONV3_DGRAD) ok = launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, j, n, wg);
-    else ok = launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, j, n, wg);
+    else if (stage == HULC_PAIR_CONV3_DGRAD) ok = launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, true, 1>(st, j, n, wg);
+    else ok = launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, true, 1>(st, j, n, wg);
     if (!ok) { hulc_set_error("hulc_k_conv_pair: unsupported shape"); return 1; }
     if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_conv_pair: launch failed"); return 1; }
     return 0;

@@ -80,7 +80,10 @@ struct ConvRegCfg {
 //   ~50 VALU instructions of that decode per round (three reciprocal divisions, clamps, the 64-bit address), with the matrix pipe idle for that wave.
 //   Where the weights leave registers (conv2: 128 / 64 weight registers) or the allocator finds them (conv3 forward at 8 waves), the decode is done
 //   ONCE per launch (pk[]: 10 registers) and a round costs a row clamp and one multiply-add: conv2 forward 143 -> 135 us, conv3 forward 81 -> 77 us,
-//   conv2 data gradient (2 x 4 waves) 147 -> 140 us on 2048 static frames (profiles/r05_conv_reg_forms.txt).  conv3's data gradient spills with it.
+//   conv2 data gradient (2 x 4 waves) 147 -> 140 us on 2048 static frames (profiles/r05_conv_reg_forms.txt).  Only the packed words pk[] are kept: the
+//   dma lambda reads each through an opaque copy, so that the two bit fields of a word (staged row, column offset: a shift + mask and a mask) are extracted again
+//   per band instead of being hoisted into twenty more live registers — hoisted, the 4-wave forms spilled (conv3's data gradient 13 VGPRs, 0 now:
+//   profiles/ablation_hooks_removed_resources.txt).
 //
 // EPI (round 5): the epilogue of a tile rides in the multiply loop of the NEXT tile.  Until now a wave alternated [multiply loop of a tile pair]
 //   [epilogue of the pair: ~110 VALU + 4 - 6 stores] and, with the band barrier putting the waves in lockstep, the epilogues of all eight waves fell
@@ -92,19 +95,8 @@ struct ConvRegCfg {
 //   rows beyond the band, "no previous tile") goes to a 4 KB dump page (p.dump).  Production forms only (forward + ReLU, data gradient with ReLU bit
 //   words); p.dump == nullptr or the test-only epilogues select the round-4 pair form below.
 //
-// LDR = 2 (round 5): two of the eight waves are LOADERS.  tools/cr_stamps.hip: a wave that issues its ten LDS-DMA rounds of the next band sits in the
-//   issue of those instructions for 2 700 - 4 200 cycles even with the slot decode in registers — the CU's vector-memory queue is shallow, and a band
-//   (72 - 77 KB) takes ~7 000 cycles to arrive at the ~10 B/clk a CU gets of the HBM stream, so whoever issues the pieces is blocked for about as long as
-//   they take to arrive.  With every wave issuing its share at the start of a band, that blocked time preceded the multiply phase on all of them (the band's
-//   phases ADD).  Now waves 6 and 7 do nothing but request the next band (all its pieces, blocked in issue most of the time, no weights, no tiles) and the
-//   six compute waves (3 pixel parts x 2 channel halves) never touch the load path: no DMA issue, no vmcnt wait — their output stores are never waited
-//   for — one barrier per band.  A band then costs max(arrival of the next band, 4/3 of the old multiply + epilogue time) instead of their sum.
-//   Forms with one output class only (OS == 1); the loaders keep their 40 rounds' slot decode in registers (PKR) — recomputing it per round made THEM
-//   the bottleneck (conv2 forward 185 us).  MEASURED (2048 static frames, profiles/r05_conv_reg_forms.txt): conv2 forward 132 us against 134 - 137 for
-//   the eight-wave form, conv3 forward 93 against 77 (compute-bound: six waves multiply), conv3 data gradient with EPI 107 against 98 for the
-//   two-workgroup EPI form — all forms of conv2's forward converge at ~1.4 x the mixed read / write streaming time of its 500 MB, so the blocked
-//   issue was not the whole story.  Kept selectable, not the production form.
-template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, int NBUF_ = 0, bool PKR = false, int EPI = 0, int LDR = 0>
+// (Two dedicated loader waves next to six compute waves were measured and rejected: profiles/r05_conv_reg_forms.txt.)
+template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, bool PKR = false, int EPI = 0>
 __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(ConvRegBatch bt) {
     using C = ConvRegCfg<CK, TA, TB, SI>;
     // the job of this workgroup (wave-uniform: kernel arguments and blockIdx only, its fields are scalar loads; copied by value — through a reference the
@@ -118,12 +110,8 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
     static_assert(!REV || SI == 1, "the data-gradient forms are stride-1 correlations (per parity class for OS = 2)");
     static_assert(OS == 1 || REV, "output parity classes only exist in the data-gradient form");
     static_assert(NWV == 8 || NWV == 4, "8 waves (one workgroup per CU, two band buffers) or 4 (two workgroups per CU, one buffer each)");
-    constexpr int NBUF = NBUF_ ? NBUF_ : (NWV == 8 ? 2 : 1), PF = C::PIECES / NWV;      // band buffers of a workgroup (NWV = 4: 1, or 2 with smaller bands)
-    static_assert(LDR == 0 || (LDR == 2 && NWV == 8 && OS == 1), "loader waves: 6 compute + 2 loader waves of a 512-thread workgroup, one output class");
-    constexpr int NCW = NWV - LDR;                              // compute waves
-    constexpr int NLD = LDR ? LDR : NWV;                        // waves that issue a band's DMA pieces, and the rounds each of them needs
-    constexpr int PFL = (C::PIECES + NLD - 1) / NLD;
-    constexpr int NCLS = OS * OS, CN = NCLS == 1 ? 64 : 32, PPARTS = NCLS == 1 ? NCW / 2 : NCW / 4, WPP = CN / 32;
+    constexpr int NBUF = NWV == 8 ? 2 : 1, PF = C::PIECES / NWV;      // band buffers of a workgroup; DMA rounds of a wave per band at most
+    constexpr int NCLS = OS * OS, CN = NCLS == 1 ? 64 : 32, PPARTS = NCLS == 1 ? NWV / 2 : NWV / 4, WPP = CN / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, lj = lane & 31;
@@ -138,20 +126,17 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
     // ---- weights -> registers (once).  MFMA row i of this wave's A operand carries channel chw*32 + 16*((i>>2)&1) + 4*(i>>3) + (i&3):
     // with the 32x32 C/D map (row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)) lane half h then owns channels chw*32 + 16h + reg, reg = 0..15
     h16x8_t wf[C::NS];
-    if (!LDR || wave < NCW) {
-        const int chn = chw * 32 + 16 * ((lj >> 2) & 1) + 4 * (lj >> 3) + (lj & 3);
-        const h16_t* wr = p.w + ((long long)cls * CN + chn) * C::K + h * 8;
+    const int chn = chw * 32 + 16 * ((lj >> 2) & 1) + 4 * (lj >> 3) + (lj & 3);
+    const h16_t* const wr = p.w + ((long long)cls * CN + chn) * C::K + h * 8;
 #pragma unroll
-        for (int s = 0; s < C::NS; ++s) wf[s] = *reinterpret_cast<const h16x8_t*>(wr + s * 16);
-    }
+    for (int s = 0; s < C::NS; ++s) wf[s] = *reinterpret_cast<const h16x8_t*>(wr + s * 16);
     // ---- DMA plan: thread (wave, lane) fills LDS slot q = (k*8 + wave)*64 + lane in round k (one wave instruction = 1 KB of consecutive
     // slots).  Slot -> (plane, plane row, plane col, chunk) -> staged (row, col, chunk); the pad slot of a pixel and the cells beyond the
     // band re-load a valid chunk (never read).  pk: bit 31 = column inside the image, bits 20..30 staged row of the band, bits 0..19
     // (image col * CH + chunk)
     const int multi = p.FPB > 1;
     const int nitems = multi ? (p.Nf + p.FPB - 1) / p.FPB : p.Nf * p.nbands;
-    const int lw = LDR ? wave - NCW : wave;                     // index among the issuing waves
-    const int npieces = (int)(bbytes / 1024), nrounds = (npieces + NLD - 1) / NLD;      // 1 KB pieces of a band; piece k*NLD + lw is this wave's in round k
+    const int npieces = (int)(bbytes / 1024), nrounds = (npieces + NWV - 1) / NWV;      // 1 KB pieces of a band; piece k*NWV + wave is this wave's in round k
     const float invX = 1.f / (float)C::XSS, invPP = 1.f / (float)plane_px, invPLCd = 1.f / (float)PLC;
     // slot q of a band -> bit 31 = column inside the image, bits 20..30 staged row of the band, bits 0..19 (image col * CH + chunk).  Recomputed per
     // band (a dozen VALU operations per 16-byte piece) rather than kept in registers: the weights need them
@@ -172,25 +157,24 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
     };
     const int rowel = p.IMW * CK;
     const float invVPI = 1.f / (float)(p.IMH + TA - 1);
-    unsigned pk[PKR ? PFL : 1];
-    if (PKR && (!LDR || wave >= NCW)) {                         // LDR: the loader waves hold their 40 rounds' decode in the registers the compute waves give to weights
+    unsigned pk[PKR ? PF : 1];
+    if (PKR) {
 #pragma unroll
-        for (int k = 0; k < PFL; ++k) pk[k] = slot_src(min(k * NLD + lw, npieces - 1) * 64 + lane);
+        for (int k = 0; k < PF; ++k) pk[k] = slot_src(min(k * NWV + wave, npieces - 1) * 64 + lane);
     }
     auto dma = [&](int item, int bi) {
-        if (p.dbg & 4) return;                                  // timing ablation (tools/time_conv_reg.py): no loads
         const int f = multi ? item * p.FPB : item / p.nbands, b = multi ? 0 : item % p.nbands;
         const int nfr = multi ? min(p.FPB, p.Nf - f) : 1;
         const int r0 = b * p.RB * SI, rmax = nfr * p.IMH - 1;
         const h16_t* src0 = p.img + (long long)f * p.IMH * rowel;
-        lds_char* dst = lbase + bi * bbytes + lw * 1024;
+        lds_char* dst = lbase + bi * bbytes + wave * 1024;
 #pragma unroll
-        for (int k = 0; k < PFL; ++k) {
-            if (k >= nrounds || k * NLD + lw >= npieces) break;     // wave-uniform
+        for (int k = 0; k < PF; ++k) {
+            if (k >= nrounds || k * NWV + wave >= npieces) break;     // wave-uniform
             unsigned pkk;
-            if (PKR) pkk = pk[k];
+            if (PKR) { pkk = pk[k]; asm volatile("" : "+v"(pkk)); }      // opaque: the fields of pk[k] are extracted per band, not hoisted (see PKR above)
             else {
-                int q = (k * NLD + lw) * 64 + lane;
+                int q = (k * NWV + wave) * 64 + lane;
                 asm volatile("" : "+v"(q));                         // opaque: keeps the (band-invariant) decode from being hoisted back into ten live registers
                 pkk = slot_src(q);
             }
@@ -201,7 +185,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
                 const bool ok = (pkk >> 31) && r >= 0 && r < p.IMH && ff < nfr;
                 s = ok ? src0 + (long long)(ff * p.IMH + r) * rowel + (int)(pkk & 0xfffffu) * 8 : p.zeros;
             } else s = src0 + (long long)min(sr, rmax) * rowel + (int)(pkk & 0xfffffu) * 8;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)s, (__attribute__((address_space(3))) void*)(dst + k * NLD * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)s, (__attribute__((address_space(3))) void*)(dst + k * NWV * 1024), 16, 0, 0);
         }
         if (REV && p.maskbits) {
             // the ReLU bit words of the item's output pixels (whole rows of one frame, or whole stacked frames: contiguous in memory) ride along as
@@ -211,10 +195,10 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
             const int orow0 = multi ? 0 : b * p.RB * OS, nrow = multi ? nfr * p.OUTH : min(p.RB * OS, p.OUTH - orow0);
             const int nwords = nrow * p.OUTW * WPP;
             const unsigned* src = p.maskbits + ((long long)f * p.OUTH + orow0) * p.OUTW * WPP;
-            lds_char* mdst = ml + bi * p.MB + lw * 256;
-            for (int k = 0; (k * NLD + lw) * 64 < nwords; ++k) {      // wave-uniform
-                const int w = min((k * NLD + lw) * 64 + lane, nwords - 1);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + w), (__attribute__((address_space(3))) void*)(mdst + k * NLD * 256), 4, 0, 0);
+            lds_char* mdst = ml + bi * p.MB + wave * 256;
+            for (int k = 0; (k * NWV + wave) * 64 < nwords; ++k) {      // wave-uniform
+                const int w = min((k * NWV + wave) * 64 + lane, nwords - 1);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + w), (__attribute__((address_space(3))) void*)(mdst + k * NWV * 256), 4, 0, 0);
             }
         }
     };
@@ -227,19 +211,9 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
     }
     const float invPLC = 1.f / (float)PLC, invVPO = 1.f / (float)max(p.VPO, 1);
     int item = bid, nb = 0;
-    if (NBUF == 2 && (!LDR || wave >= NCW)) {
+    if (NBUF == 2) {
         if (item < nitems) dma(item, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (LDR && wave >= NCW) {                                   // ---- a loader wave: request band i+1 while the compute waves multiply band i
-        static_assert(!(LDR && EPI && !REV), "(the forward EPI form has an extra barrier in front of the band loop)");
-        int it = item, b = 0;
-        while (it < nitems) {
-            __syncthreads();                                    // band `it` has landed (this wave waited for its pieces); the compute waves are done with the other buffer
-            it += nwg; b ^= 1;
-            if (it < nitems) { dma(it, b); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        }
-        return;
     }
     const int NI0 = (p.OUTH + OS - 1) / OS, NJ0 = (p.OUTW + OS - 1) / OS;      // output rows / columns of the largest class
     const bool fastmask = REV && p.maskbits && !p.relu;        // the production data-gradient form: 1-bit ReLU mask words, no activation
@@ -274,7 +248,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
         const int i0 = b * p.RB;
         const int rows_total = multi ? p.RB : NI0;              // output-row slots of the whole item
         const int RBe = min(p.RB, rows_total - i0);
-        const int npi = RBe * PLC, ntiles = (p.dbg & 2) ? 0 : (npi + 31) >> 5, last = npi - PLC + NJ0 - 1;      // dbg bit 1: no compute
+        const int npi = RBe * PLC, ntiles = (npi + 31) >> 5, last = npi - PLC + NJ0 - 1;
         // this wave's tiles: a contiguous, balanced share of the band's tiles (10 tiles over 4 parts = 2 + 3 + 2 + 3, walked as pairs + a single)
         const int tbeg = pq * ntiles / PPARTS, tend = (pq + 1) * ntiles / PPARTS;
         // output pixels of a tile pair (-1: nothing to store)
@@ -308,7 +282,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
         // NBUF 2: the next band streams in under this band's MFMAs.  Waves 0-3 issue their DMA pieces now; waves 4-7 (the second wave of each
         // SIMD) after their first tile pair when they have two, so that one wave of a SIMD starts multiplying at once while the other
         // spends its ~0.3 us of DMA issue
-        bool pend = NBUF == 2 && !LDR && item < nitems;
+        bool pend = NBUF == 2 && item < nitems;
         if (pend && (wave < NWV / 2 || tend - tbeg <= 2)) { dma(item, nb); pend = false; }
         bool waited = false;
         // output pixel of ONE tile (EPI form)
@@ -390,7 +364,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
             for (int t = tbeg; t < tend; ++t) do_tile(t);
             CRSTAMP(3);
             if (pend) { dma(item, nb); pend = false; }
-            if (NBUF == 2 && !LDR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next band's pieces (issued at the band's start) and the stores of the drains
+            if (NBUF == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next band's pieces (issued at the band's start) and the stores of the drains
             waited = true;
             CRSTAMP(4);
         }
@@ -433,17 +407,15 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
                     __builtin_amdgcn_sched_barrier(0);          // the scheduler may not sink the reads of step s+2 below this step's MFMAs
                 }
             };
-            if (p.dbg & 16) {                                   // ablation: no multiply loop
-            } else if (two) mloop(std::true_type{});
+            if (two) mloop(std::true_type{});
             else mloop(std::false_type{});
             if (t0 + 2 >= tend) CRSTAMP(3);
             if (pend) { dma(item, nb); pend = false; }
-            if (NBUF == 2 && !LDR && t0 + 2 >= tend) {          // last pair of this wave in the band: its DMA pieces of the NEXT band (issued a
+            if (NBUF == 2 && t0 + 2 >= tend) {          // last pair of this wave in the band: its DMA pieces of the NEXT band (issued a
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // multiply loop ago) and the earlier stores are waited for HERE, so that the
                 waited = true;                                  // stores below stay in flight across the barrier
             }
             if (t0 + 2 >= tend) CRSTAMP(4);
-            if ((p.dbg & 8) && acc0[0] != 12345.678f) continue;   // ablation: no epilogue
             // ---- epilogue: lane = (pixel lj, half h) holds channels chw*32 + 16h + [0, 16)
             if (REV && fastmask) {
                 // data gradient, production form: out = bit ? acc : 0 -> a sign-extended 1-bit field ANDed onto the fp32 pattern (2 VALU per value)
@@ -510,7 +482,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
         }
         CRSTAMP(5);
         if (pend) dma(item, nb);
-        if (NBUF == 2 && !LDR && !waited) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (NBUF == 2 && !waited) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     if (EPI && popx >= 0) {                                     // the last tile of this wave
         const f32x16& a = accP;
@@ -548,10 +520,10 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) conv_reg_kernel(Co
 // host side: band height for two resident bands (fewest bands), stacked frames for the gripper camera's small maps
 inline int g_conv_reg_wgpc = 0;      // tools/cr_bench.hip only: workgroups per CU the band geometry is sized for (0 = the form's own: 1 for 8 waves, 2 for 4)
 // band / stack geometry of ONE job that will run on `wgs` workgroups: fills p, its dynamic LDS bytes, its items and its multiply work (items x (0.35 + wave passes per item))
-template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, int NBUF_ = 0, bool PKR = false, int EPI = 0, int LDR = 0>
+template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, bool PKR = false, int EPI = 0>
 static inline bool plan_conv_reg(ConvTileP& p, int wgs_job, size_t& lds, int& items_out, double& work) {
     using C = ConvRegCfg<CK, TA, TB, SI>;
-    constexpr int NBUF = NBUF_ ? NBUF_ : (NWV == 8 ? 2 : 1);                                  // band buffers per workgroup
+    constexpr int NBUF = NWV == 8 ? 2 : 1;                                                    // band buffers per workgroup
     const int WGPC = g_conv_reg_wgpc ? g_conv_reg_wgpc : (NWV == 8 ? 1 : 2);                  // workgroups per CU
     if (p.IMW != p.IMH || p.OUTW != p.OUTH) return false;
     if (!REV && (p.mask || p.maskbits || !p.relu)) return false;
@@ -574,7 +546,7 @@ static inline bool plan_conv_reg(ConvTileP& p, int wgs_job, size_t& lds, int& it
     p.nbands = (NI + p.RB - 1) / p.RB;
     p.LR = REV ? p.RB + TA - 1 : (p.RB - 1) * SI + TA;
     p.VPI = (p.LR + SI - 1) / SI;
-    constexpr int per = 2 * (OS == 1 ? (NWV - LDR) / 2 : NWV / 4);                                                        // a wave pass = 2 tiles x the pixel parts
+    constexpr int per = 2 * (OS == 1 ? NWV / 2 : NWV / 4);                                                        // a wave pass = 2 tiles x the pixel parts
     if (p.nbands == 1 && p.Nf > 1 && (REV ? p.OUTH == OS * (p.IMH + TA - 1) : p.IMH % SI == 0)) {   // stack FPB frames to a band: a band should feed the 8 waves' 16 tile slots
         const int vpo = REV ? p.IMH + TA - 1 : p.IMH / SI;
         int bestf = 1; double bc = 1e30;
@@ -600,19 +572,19 @@ static inline bool plan_conv_reg(ConvTileP& p, int wgs_job, size_t& lds, int& it
 }
 // n <= 4 jobs of one stage in ONE launch.  wg == nullptr: one job takes the grid it always took (min(items, 256 x workgroups per CU)); two jobs share
 // that grid by camera_split over their work, every job's stack geometry sized for its own share.  wg != nullptr: the workgroups of each job, as given (tests).
-template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, int NBUF_ = 0, bool PKR = false, int EPI = 0, int LDR = 0>
+template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, bool PKR = false, int EPI = 0>
 static inline bool launch_conv_reg_jobs(hipStream_t st, const ConvTileP* jobs, int n, const int* wg = nullptr) {
     if (n < 1 || n > 4 || (!wg && n > 2)) return false;
     for (int k = 0; k < n; ++k) {
         const ConvTileP& p = jobs[k];
         if (EPI && (!p.dump || (REV && (!p.maskbits || p.relu || p.mask))))       // the pipelined epilogue covers the production forms only
-            return launch_conv_reg_jobs<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, 0, LDR>(st, jobs, n, wg);
+            return launch_conv_reg_jobs<CK, TA, TB, SI, REV, OS, NWV, PKR, 0>(st, jobs, n, wg);
     }
     const int WGPC = g_conv_reg_wgpc ? g_conv_reg_wgpc : (NWV == 8 ? 1 : 2);
     const int grid_max = 256 * WGPC;
     ConvRegBatch bt{}; bt.n = n;
     size_t lds[4] = {0, 0, 0, 0}; int items[4] = {0, 0, 0, 0}, nw[4] = {0, 0, 0, 0}; double work[4] = {0, 0, 0, 0};
-    auto plan = [&](int k, int wgs) { bt.j[k] = jobs[k]; return bt.j[k].Nf >= 1 && plan_conv_reg<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>(bt.j[k], wgs, lds[k], items[k], work[k]); };
+    auto plan = [&](int k, int wgs) { bt.j[k] = jobs[k]; return bt.j[k].Nf >= 1 && plan_conv_reg<CK, TA, TB, SI, REV, OS, NWV, PKR, EPI>(bt.j[k], wgs, lds[k], items[k], work[k]); };
     for (int k = 0; k < n; ++k) if (!plan(k, wg ? std::max(wg[k], 1) : grid_max)) return false;
     if (wg) { for (int k = 0; k < n; ++k) nw[k] = std::min(std::max(wg[k], 1), items[k]); }
     else if (n == 1) nw[0] = std::min(items[0], grid_max);
@@ -627,17 +599,17 @@ static inline bool launch_conv_reg_jobs(hipStream_t st, const ConvTileP* jobs, i
     for (int k = 0; k < n; ++k) { bt.blk0[k + 1] = bt.blk0[k] + nw[k]; ldsmax = std::max(ldsmax, lds[k]); }
     static bool attr_set = false;
     if (!attr_set) {
-        hipFuncSetAttribute((const void*)conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / (NWV == 8 ? 1 : 2) - 64);
+        hipFuncSetAttribute((const void*)conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, PKR, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / (NWV == 8 ? 1 : 2) - 64);
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>), dim3(bt.blk0[n]), dim3(NWV * 64), ldsmax, st, bt);
+    hipLaunchKernelGGL((conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, PKR, EPI>), dim3(bt.blk0[n]), dim3(NWV * 64), ldsmax, st, bt);
     return true;
 }
-template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, int NBUF_ = 0, bool PKR = false, int EPI = 0, int LDR = 0>
-static inline bool launch_conv_reg(hipStream_t st, ConvTileP p) { return launch_conv_reg_jobs<CK, TA, TB, SI, REV, OS, NWV, NBUF_, PKR, EPI, LDR>(st, &p, 1); }
+template <int CK, int TA, int TB, int SI, bool REV, int OS = 1, int NWV = 8, bool PKR = false, int EPI = 0>
+static inline bool launch_conv_reg(hipStream_t st, ConvTileP p) { return launch_conv_reg_jobs<CK, TA, TB, SI, REV, OS, NWV, PKR, EPI>(st, &p, 1); }
 template <int CK, int TA, int TB, int SI>
-static inline bool launch_conv_reg_fwd(hipStream_t st, const ConvTileP& p) { return launch_conv_reg<CK, TA, TB, SI, false, 1, 8, 0, true>(st, p); }
+static inline bool launch_conv_reg_fwd(hipStream_t st, const ConvTileP& p) { return launch_conv_reg<CK, TA, TB, SI, false, 1, 8, true>(st, p); }
 template <int CK, int TA, int TB, int SI>
-static inline bool launch_conv_reg_fwd_jobs(hipStream_t st, const ConvTileP* jobs, int n, const int* wg = nullptr) { return launch_conv_reg_jobs<CK, TA, TB, SI, false, 1, 8, 0, true>(st, jobs, n, wg); }
+static inline bool launch_conv_reg_fwd_jobs(hipStream_t st, const ConvTileP* jobs, int n, const int* wg = nullptr) { return launch_conv_reg_jobs<CK, TA, TB, SI, false, 1, 8, true>(st, jobs, n, wg); }
 
 }  // namespace HULC_NS

@@ -26,7 +26,6 @@ struct ConvTileP {
     const unsigned* maskbits; // CN/32 words per output pixel, bit c%32 of word c/32 = (layer input channel c > 0) — 16x fewer mask bytes than `mask`;
                              // staged through LDS with the band, so the multiply loop issues no global loads (the next band's prefetch stays in flight)
     int relu;
-    int dbg;                 // bench ablation: bit 1 = skip the MFMA/epilogue phase, bit 2 = skip the global prefetch loads
     int Nf, RB, nbands, LW, LR;
     int LP;                  // LDS row pitch of the staged band in pixels (>= LW; a multiple of the input stride)
     int* work_ctr;           // optional zero-initialised device counter: items beyond the first round are CLAIMED (atomicAdd) instead of strided,
@@ -155,7 +154,6 @@ __global__ void __launch_bounds__(NWV * 64) conv_tile_kernel(ConvTileP p) {
     }
     const int rowel = p.IMW * CK;                               // elements per image row
     auto prefetch = [&](int item) {
-        if (p.dbg & 4) return;
         const int f = multi ? item * p.FPB : item / p.nbands, b = multi ? 0 : item % p.nbands;
         const int nfr = multi ? min(p.FPB, p.Nf - f) : 1;       // frames of this band (the last stacked band may be short: its missing frames stage as zeros)
         const int i0 = b * p.RB;
@@ -218,7 +216,7 @@ __global__ void __launch_bounds__(NWV * 64) conv_tile_kernel(ConvTileP p) {
         // by the same barrier, the two would otherwise run every phase in lockstep — both computing addresses while the matrix pipe idles,
         // then both contending for it; skewed, one half's prefetch and epilogues run beside the other half's MFMAs.
         bool pref_pending = item < nitems;
-        if (pref_pending && (wave < NWV / 2 || (p.dbg & 64))) { prefetch(item); pref_pending = false; }       // dbg bit 6: no skew (A/B)
+        if (pref_pending && wave < NWV / 2) { prefetch(item); pref_pending = false; }
         CTSTAMP(4);
         ++iter;
         const int f = multi ? cur * p.FPB : cur / p.nbands, b = multi ? 0 : cur % p.nbands;
@@ -236,7 +234,6 @@ __global__ void __launch_bounds__(NWV * 64) conv_tile_kernel(ConvTileP p) {
         int total_groups = 0;
 #pragma unroll
         for (int c = 0; c < C::NCLS; ++c) total_groups += groups_of(c);
-        if (p.dbg & 2) total_groups = 0;
 #pragma unroll 1
         for (int wi = wave; wi < total_groups; wi += NWV) {
             int cls = 0, mybase = 0, base = 0;
@@ -303,11 +300,11 @@ __global__ void __launch_bounds__(NWV * 64) conv_tile_kernel(ConvTileP p) {
 #endif
             if constexpr (NWV > 8) {             // four waves per SIMD hide each other's LDS latency: one fragment set (24 VGPRs less)
 #pragma unroll 1
-                for (int s1 = (p.dbg & 16) ? NS : 0; s1 < NS; ++s1) { frag_load(xf0, wf0, s1); frag_mma(xf0, wf0); }
+                for (int s1 = 0; s1 < NS; ++s1) { frag_load(xf0, wf0, s1); frag_mma(xf0, wf0); }
             } else {
             frag_load(xf0, wf0, 0);
 #pragma unroll 1
-            for (int s2 = (p.dbg & 16) ? NS : 0; s2 < NS; s2 += 2) {
+            for (int s2 = 0; s2 < NS; s2 += 2) {
                 frag_load(xf1, wf1, s2 + 1);
                 frag_mma(xf0, wf0);
                 if (s2 + 2 < NS) frag_load(xf0, wf0, s2 + 2);
@@ -319,7 +316,7 @@ __global__ void __launch_bounds__(NWV * 64) conv_tile_kernel(ConvTileP p) {
             asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[C::MT - 1][C::NT - 1][3]));      // the stamp below must follow the last MFMA's result
             --iter; CTSTAMP(6); ++iter;
 #endif
-            if ((p.dbg & 8) && acc[0][0][0] != 12345.678f) continue;
+            __builtin_amdgcn_sched_barrier(0);      // the epilogue's address arithmetic and LDS reads stay behind the multiply phase (scheduled into it, the 16-wave forms spill)
             // ---- epilogue: lane holds channels g*4*NT .. +4*NT-1 of pixel li of each m-tile
             float bb[NWV > 8 ? 1 : 4 * C::NT];      // 16 waves: the bias quads are read from LDS where they are added (16 VGPRs less)
             if constexpr (NWV <= 8) {
@@ -470,11 +467,11 @@ static inline bool launch_conv_tile(hipStream_t st, ConvTileP p) {
 
 // the multiply + epilogue of one staged band (shared by the fp32 / register-staged kernel and the uint8 LDS-DMA kernel below)
 DEVI void conv1_fwd_band_tiles(lds_char* ximg, const h16x8_t (&wf)[6][2], const int (&rowsel)[6], const float4 (&bb)[2], h16_t* __restrict__ out,
-                               unsigned* __restrict__ maskbits, int f, int oh0, int R, int OH, int OW, int XRS, int dbg, int wave, int g, int li, float osc = 1.f) {
+                               unsigned* __restrict__ maskbits, int f, int oh0, int R, int OH, int OW, int XRS, int wave, int g, int li, float osc = 1.f) {
         // osc: Conv1Src::fold — the staged operand is the raw byte value, out = relu(osc * acc + bias_fold)
         const int RBe = min(R, OH - oh0);
         const int npix = RBe * OW;
-        const int ntm = (dbg & 2) ? 0 : (npix + 15) >> 4;
+        const int ntm = (npix + 15) >> 4;
         for (int mt = wave * 2; mt < ntm; mt += 8) {                      // two m-tiles per pass: independent MFMA chains interleave
             bool ok[2]; int rr[2], oww[2];
             lds_char* xb[2];
@@ -542,7 +539,7 @@ DEVI void conv1_fwd_band_tiles(lds_char* ximg, const h16x8_t (&wf)[6][2], const 
 // ---------------------------------------------------------------------------------------------------------------------
 template <int MINW, bool REGCONV = false>
 __global__ void __launch_bounds__(256, MINW) conv1_fwd_kernel(Conv1Src X, const h16_t* __restrict__ W, const float* __restrict__ bias,
-                                                           h16_t* __restrict__ out, int Nf, int IH, int IW, int OH, int OW, int R, int nbands, int dbg,
+                                                           h16_t* __restrict__ out, int Nf, int IH, int IW, int OH, int OW, int R, int nbands,
                                                            unsigned* __restrict__ maskbits, float* __restrict__ zero8a = nullptr, float* __restrict__ zero8b = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     lds_char* ximg = (lds_char*)smem;
@@ -567,21 +564,20 @@ __global__ void __launch_bounds__(256, MINW) conv1_fwd_kernel(Conv1Src X, const 
     for (int ks = 0; ks < 6; ++ks) { const int ck = ks * 4 + g; rowsel[ks] = ((ck >> 3) * XR + (ck & 7)) * XRS; }
     const float4 bb[2] = {*reinterpret_cast<const float4*>(bias + g * 8), *reinterpret_cast<const float4*>(bias + g * 8 + 4)};
     const int nitems = Nf * nbands;
-    // frame-wise (fw: dbg bit 32 clear): a workgroup walks the bands of one frame back to back so that the rows two bands share come
-    // from L2 — what cut conv1's weight gradient by 25 % measured 0.4 % SLOWER here (4 resident workgroups per CU already re-read those rows
-    // from the XCD's L2 within microseconds; the frame-wise order only removes the interleaving of their phases): default item-wise
-    const bool fw = Nf >= (int)gridDim.x && !(dbg & 32);
-    for (int it = blockIdx.x; fw ? (it < Nf) : (it < nitems); it += gridDim.x)
-    for (int bnd = 0; bnd < (fw ? nbands : 1); ++bnd) {
-        const int item = fw ? it * nbands + bnd : it;
+    // item-wise bands.  (A frame-wise order — a workgroup walks the bands of one frame back to back so that the rows two bands share come from
+    // L2 — cut conv1's weight gradient by 25 % but measured 0.4 % SLOWER here: 4 resident workgroups per CU already re-read those rows from the
+    // XCD's L2 within microseconds.)
+    for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
         const int f = item / nbands, b = item % nbands;
         const int oh0 = b * R;
         const int ih0 = oh0 * 4;
         const int rows = min(XR, IH - ih0);
         __syncthreads();
-        if (!(dbg & 4)) conv1_stage_band<REGCONV>(X, f, ih0, rows, IH, IW, ximg, XR, XRS, tid, ximg + 3 * XR * XRS + 64);      // REGCONV: uint8 converted from registers (no raw rows)
+        int tq = tid;
+        asm volatile("" : "+v"(tq));      // opaque: the staging's thread-derived (band-invariant) indices are recomputed per band — hoisted out of the item loop they spilled
+        conv1_stage_band<REGCONV>(X, f, ih0, rows, IH, IW, ximg, XR, XRS, tq, ximg + 3 * XR * XRS + 64);      // REGCONV: uint8 converted from registers (no raw rows)
         __syncthreads();
-        conv1_fwd_band_tiles(ximg, wf, rowsel, bb, out, maskbits, f, oh0, R, OH, OW, XRS, dbg, wave, g, li, (X.u8 && X.fold) ? CONV1_FOLD_SCALE : 1.f);
+        conv1_fwd_band_tiles(ximg, wf, rowsel, bb, out, maskbits, f, oh0, R, OH, OW, XRS, wave, g, li, (X.u8 && X.fold) ? CONV1_FOLD_SCALE : 1.f);
     }
 }
 // ---------------------------------------------------------------------------------------------------------------------
@@ -604,7 +600,7 @@ DEVI void c1_lds_dma16(const void* src, lds_char* dst) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(a) : "memory", "m0");
 }
 __global__ void __launch_bounds__(256, 4) conv1_fwd_u8dma_kernel(Conv1Src X, const h16_t* __restrict__ W, const float* __restrict__ bias, h16_t* __restrict__ out,
-                                                                 int Nf, int IH, int IW, int OH, int OW, int R, int nbands, int dbg, unsigned* __restrict__ maskbits,
+                                                                 int Nf, int IH, int IW, int OH, int OW, int R, int nbands, unsigned* __restrict__ maskbits,
                                                                  float* __restrict__ zero8a, float* __restrict__ zero8b) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
@@ -686,45 +682,41 @@ __global__ void __launch_bounds__(256, 4) conv1_fwd_u8dma_kernel(Conv1Src X, con
             }
         }
         __syncthreads();                                          // raw complete for every wave; the previous band's multiply is over (ximg free)
-        if (!(dbg & 4)) {
-            const float sc = X.fold ? 1.f : 2.f / 255.f, of = X.fold ? 0.f : -1.f;      // fold: the exact value of the byte (Conv1Src::fold)
-            for (RowCol p = q0; p.r < rows; sq.adv(p)) {
-                const int o = p.r * RP + LM + (p.c * 4 + dx) * 3;
-                const int sh = o & 3;
-                const __attribute__((address_space(3))) unsigned* wp = (const __attribute__((address_space(3))) unsigned*)(raw + (o & ~3));
-                const unsigned w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
-                const unsigned d[3] = {__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh), __builtin_amdgcn_alignbyte(w3, w2, sh)};
-                float v[12];
+        const float sc = X.fold ? 1.f : 2.f / 255.f, of = X.fold ? 0.f : -1.f;      // fold: the exact value of the byte (Conv1Src::fold)
+        for (RowCol p = q0; p.r < rows; sq.adv(p)) {
+            const int o = p.r * RP + LM + (p.c * 4 + dx) * 3;
+            const int sh = o & 3;
+            const __attribute__((address_space(3))) unsigned* wp = (const __attribute__((address_space(3))) unsigned*)(raw + (o & ~3));
+            const unsigned w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
+            const unsigned d[3] = {__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh), __builtin_amdgcn_alignbyte(w3, w2, sh)};
+            float v[12];
 #pragma unroll
-                for (int k = 0; k < 12; ++k) v[k] = fmaf((float)((d[k >> 2] >> (8 * (k & 3))) & 0xffu), sc, of);
+            for (int k = 0; k < 12; ++k) v[k] = fmaf((float)((d[k >> 2] >> (8 * (k & 3))) & 0xffu), sc, of);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    u32x2_t ov;
-                    ov[0] = pack2h(v[c], v[3 + c]);
-                    ov[1] = pack2h(v[6 + c], v[9 + c]);
-                    *(__attribute__((address_space(3))) u32x2_t*)(ximg + (c * XR + p.r) * XRS + p.c * 8) = ov;
-                }
+            for (int c = 0; c < 3; ++c) {
+                u32x2_t ov;
+                ov[0] = pack2h(v[c], v[3 + c]);
+                ov[1] = pack2h(v[6 + c], v[9 + c]);
+                *(__attribute__((address_space(3))) u32x2_t*)(ximg + (c * XR + p.r) * XRS + p.c * 8) = ov;
             }
         }
         __syncthreads();                                          // ximg complete, raw consumed
         if (item + (int)gridDim.x < nitems) prefetch(item + (int)gridDim.x);         // lands during the multiply below
-        conv1_fwd_band_tiles(ximg, wf, rowsel, bb, out, maskbits, f, oh0, R, OH, OW, XRS, dbg, wave, g, li, X.fold ? CONV1_FOLD_SCALE : 1.f);
+        conv1_fwd_band_tiles(ximg, wf, rowsel, bb, out, maskbits, f, oh0, R, OH, OW, XRS, wave, g, li, X.fold ? CONV1_FOLD_SCALE : 1.f);
     }
 }
-static inline void launch_conv1_fwd(hipStream_t st, const Conv1Src& X, const h16_t* W, const float* bias, h16_t* out, int Nf, int IH, int IW, int OH, int OW, int dbg = 0,
+static inline void launch_conv1_fwd(hipStream_t st, const Conv1Src& X, const h16_t* W, const float* bias, h16_t* out, int Nf, int IH, int IW, int OH, int OW, bool regconv = false,
                                     unsigned* maskbits = nullptr, float* zero8a = nullptr, float* zero8b = nullptr) {
     // (tried: an 8-wave, 2-workgroups-per-CU version with the next band prefetched in registers like conv1_wgrad_tr2_kernel — 4.355 vs 4.341
     //  ms/step on one box: with 4 resident workgroups per CU the staging of one already overlaps the MFMAs of the others; not kept)
-    // uint8, dbg bit 8: the register-staged kernel with the conversion from 16-byte windows (conv1_stage_band regconv: no raw rows in LDS)
-    const bool regconv = X.u8 && (dbg & 256) && (IW % 4) == 0 && IW >= 8 && ((uintptr_t)X.X & 3) == 0;
-    if (regconv) dbg |= 256; else dbg &= ~256;
+    // regconv (uint8 only): the register-staged kernel with the conversion from 16-byte windows (conv1_stage_band regconv: no raw rows in LDS)
+    regconv = regconv && X.u8 && (IW % 4) == 0 && IW >= 8 && ((uintptr_t)X.X & 3) == 0;
     auto lds_of = [&](int R) { const int XR = (R - 1) * 4 + 8; return (size_t)3 * XR * (IW * 2 + 16) + 64 + ((X.u8 && !regconv) ? (size_t)XR * conv1_raw_pitch16(IW) + 16 : 0); };   // + raw uint8 rows
     constexpr int lds_kb = 39, max_wg = 1024;   // 4 workgroups per CU: one stages while others multiply (255 vs 299 us at 2 per CU)
     int R = OH;
     while (R > 1 && lds_of(R) > (size_t)lds_kb * 1024) --R;
     const int nbands = (OH + R - 1) / R;
     R = (OH + nbands - 1) / nbands;
-    dbg |= 32;      // item-wise bands (frame-wise measured slower in the step)
     // OCC = 4: min waves per SIMD the register allocation targets: 128 VGPRs (5 spilled) lets all 4 workgroups of a CU be resident
     static bool attr_set = false;
     if (!attr_set) { hipFuncSetAttribute((const void*)conv1_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
@@ -732,16 +724,16 @@ static inline void launch_conv1_fwd(hipStream_t st, const Conv1Src& X, const h16
     if (X.u8 && !regconv && (IW * 3) % 4 == 0 && ((uintptr_t)X.X & 3) == 0) {
         static bool a2 = false;
         if (!a2) { hipFuncSetAttribute((const void*)conv1_fwd_u8dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a2 = true; }
-        hipLaunchKernelGGL(conv1_fwd_u8dma_kernel, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, dbg, maskbits, zero8a, zero8b);
+        hipLaunchKernelGGL(conv1_fwd_u8dma_kernel, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, maskbits, zero8a, zero8b);
         return;
     }
     if (regconv) {       // uint8 cross-check path (tests, tools/time_conv1_u8reg.py): its own instance, so that the window code does not weigh on the fp32 kernel's registers
         static bool a3 = false;
         if (!a3) { hipFuncSetAttribute((const void*)conv1_fwd_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a3 = true; }
-        hipLaunchKernelGGL((conv1_fwd_kernel<4, true>), dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, dbg, maskbits, zero8a, zero8b);
+        hipLaunchKernelGGL((conv1_fwd_kernel<4, true>), dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, maskbits, zero8a, zero8b);
         return;
     }
-    hipLaunchKernelGGL(conv1_fwd_kernel<4>, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, dbg, maskbits, zero8a, zero8b);
+    hipLaunchKernelGGL(conv1_fwd_kernel<4>, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, maskbits, zero8a, zero8b);
 }
 
 }  // namespace HULC_NS

@@ -196,13 +196,13 @@ static inline void camera_split(int grid, double wA, double wB, int& nA, int& nB
 // part = the job's OWN slab area (slab index = the workgroup's index within the job), work_ctr its own claim counter.
 struct WgradJob {
     const h16_t* X; const h16_t* dY; float* part; float* bias_part; const h16_t* zeros;
-    int Nf, IH, IW, OH, OW, R, nbands, dbg; int* work_ctr; int FPB;
+    int Nf, IH, IW, OH, OW, R, nbands; int* work_ctr; int FPB;
 };
 // bid / nwg: index of this workgroup within its job and the job's workgroup count (blockIdx.x / gridDim.x of a one-job launch)
 template <int CI, int CO, int KH, int KW, int S, int NWV, int D = 3, int IWC = 0>      // IWC: compile-time image width (0: run time), see conv_wgrad_dma_kernel
 DEVI void conv_wgrad_tr8_body(const WgradJob& J, const int bid, const int nwg) {
     const h16_t* __restrict__ const X = J.X; const h16_t* __restrict__ const dY = J.dY; float* __restrict__ const part = J.part; float* __restrict__ const bias_part = J.bias_part;
-    const int Nf = J.Nf, IH = J.IH, IW = J.IW, OH = J.OH, OW = J.OW, R = J.R, nbands = J.nbands, dbg = J.dbg, FPB = J.FPB;
+    const int Nf = J.Nf, IH = J.IH, IW = J.IW, OH = J.OH, OW = J.OW, R = J.R, nbands = J.nbands, FPB = J.FPB;
     int* __restrict__ const work_ctr = J.work_ctr;
     // FPB > 1 (small frames, nbands == 1): FPB frames are stacked to one band.  X rows of consecutive frames are contiguous in memory; dY is staged
     // with a pitch of VP = IH / S rows per frame, its OH real rows followed by rows that stay zero from the initial LDS fill, so that dY row v still
@@ -265,7 +265,6 @@ DEVI void conv_wgrad_tr8_body(const WgradJob& J, const int bid, const int nwg) {
     unsigned zmask = 0, zmask_cur = 0;
     auto prefetch = [&](int item) {
         zmask = 0;
-        if (dbg & 2) return;
         const int f = stacked ? item * FPB : item / nbands, oh0 = stacked ? 0 : (item % nbands) * R;
         const int nfr = stacked ? min(FPB, Nf - f) : 1;         // the last stacked band may be short: its missing frames stage as zero dY
         const h16_t* ybase = dY + ((long long)f * OH + oh0) * OW * CO;
@@ -303,7 +302,7 @@ DEVI void conv_wgrad_tr8_body(const WgradJob& J, const int bid, const int nwg) {
         item = work_ctr ? s_next[iter & 1] : item + nwg;
         ++iter;
         if (item < nitems) prefetch(item);             // in flight during the MFMAs below
-        const int units = (dbg & 1) ? 0 : R * U;
+        const int units = R * U;
         // k <-> pixel assignment of a 32-pixel step (4 runs of 8): k = g*8 + e; e < 4 (first tr-read): run g>>1, pixel (g&1)*4 + e;
         // e >= 4 (second tr-read): run 2 + (g>>1), pixel (g&1)*4 + e - 4.  A 32-lane half of one read then covers 8 consecutive
         // pixels of ONE run -> conflict-free with the pitches of WgradCfg.
@@ -355,7 +354,6 @@ DEVI void conv_wgrad_tr8_body(const WgradJob& J, const int bid, const int nwg) {
     }
     constexpr int KC = KH * KW * CI;
     float* out = part + (long long)bid * CO * KC;
-    if (!(dbg & 4) || acc[0][0][0] == 12345.678f)
 #pragma unroll
     for (int j = 0; j < C::NTW; ++j)
 #pragma unroll
@@ -376,9 +374,9 @@ DEVI void conv_wgrad_tr8_body(const WgradJob& J, const int bid, const int nwg) {
 }
 template <int CI, int CO, int KH, int KW, int S, int NWV, int D = 3, int IWC = 0>
 __global__ void __launch_bounds__(NWV * 64) conv_wgrad_tr8_kernel(const h16_t* __restrict__ X, const h16_t* __restrict__ dY, float* __restrict__ part,
-                                                            float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands, int dbg,
+                                                            float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands,
                                                             int* __restrict__ work_ctr, int FPB) {
-    const WgradJob J{X, dY, part, bias_part, nullptr, Nf, IH, IW, OH, OW, R, nbands, dbg, work_ctr, FPB};
+    const WgradJob J{X, dY, part, bias_part, nullptr, Nf, IH, IW, OH, OW, R, nbands, work_ctr, FPB};
     conv_wgrad_tr8_body<CI, CO, KH, KW, S, NWV, D, IWC>(J, (int)blockIdx.x, (int)gridDim.x);
 }
 
@@ -410,7 +408,7 @@ template <int CI, int CO, int KH, int KW, int S, int IWC = 0>      // IWC: the i
 DEVI void conv_wgrad_dma_body(const WgradJob& J, const int bid, const int nwg) {
     const h16_t* __restrict__ const X = J.X; const h16_t* __restrict__ const dY = J.dY; float* __restrict__ const part = J.part; float* __restrict__ const bias_part = J.bias_part;
     const h16_t* __restrict__ const zeros = J.zeros;
-    const int Nf = J.Nf, IH = J.IH, IW = J.IW, OH = J.OH, OW = J.OW, R = J.R, nbands = J.nbands, dbg = J.dbg;
+    const int Nf = J.Nf, IH = J.IH, IW = J.IW, OH = J.OH, OW = J.OW, R = J.R, nbands = J.nbands;
     int* __restrict__ const work_ctr = J.work_ctr;
     using C = WgradCfg<CI, CO, KH, KW, S>;
     constexpr int NWV = 8, NTH = NWV * 64, CTH = C::CT / (NWV / 4), CHY = CO / 8, CHX = CI / 8, XSS = C::XS / 16, YSS = C::DYS / 16;
@@ -448,7 +446,6 @@ DEVI void conv_wgrad_dma_body(const WgradJob& J, const int bid, const int nwg) {
         pk[k] = v;
     }
     auto dma = [&](int item, int buf) {
-        if (dbg & 2) return;
         const int f = item / nbands, oh0 = (item - f * nbands) * R, ih0 = oh0 * S;
         const int yrows = min(R, OH - oh0), xrows = min(XR, IH - ih0);
         const h16_t* xsrc = X + ((long long)f * IH + ih0) * IW * CI;
@@ -518,7 +515,7 @@ DEVI void conv_wgrad_dma_body(const WgradJob& J, const int bid, const int nwg) {
                 for (int e = 0; e < 4; ++e) { bsum[2 * e] += h2f_lo(v[e]); bsum[2 * e + 1] += h2f_hi(v[e]); }
             }
         }
-        const int units = (dbg & 1) ? 0 : R * U;
+        const int units = R * U;
         int uo[2], pbv[2];
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
@@ -568,7 +565,6 @@ DEVI void conv_wgrad_dma_body(const WgradJob& J, const int bid, const int nwg) {
     }
     constexpr int KC = KH * KW * CI;
     float* out = part + (long long)bid * CO * KC;
-    if (!(dbg & 4) || acc[0][0][0] == 12345.678f)
 #pragma unroll
     for (int j = 0; j < C::NTW; ++j)
 #pragma unroll
@@ -590,8 +586,8 @@ DEVI void conv_wgrad_dma_body(const WgradJob& J, const int bid, const int nwg) {
 template <int CI, int CO, int KH, int KW, int S, int IWC = 0>
 __global__ void __launch_bounds__(512) conv_wgrad_dma_kernel(const h16_t* __restrict__ X, const h16_t* __restrict__ dY, float* __restrict__ part,
                                                              float* __restrict__ bias_part, const h16_t* __restrict__ zeros, int Nf, int IH, int IW, int OH, int OW,
-                                                             int R, int nbands, int dbg, int* __restrict__ work_ctr) {
-    const WgradJob J{X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nbands, dbg, work_ctr, 1};
+                                                             int R, int nbands, int* __restrict__ work_ctr) {
+    const WgradJob J{X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nbands, work_ctr, 1};
     conv_wgrad_dma_body<CI, CO, KH, KW, S, IWC>(J, (int)blockIdx.x, (int)gridDim.x);
 }
 // The weight gradient of one stage for BOTH cameras in one launch: the static camera's job on the LDS-DMA body (IWS = its map width), the gripper camera's on the
@@ -674,8 +670,8 @@ static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16
                 attr3 = true;
             }
             const int grid = std::min(std::min(Nf * nb, 256), max_blocks);
-            if (IWS && IW == IWS) hipLaunchKernelGGL((conv_wgrad_dma_kernel<CI, CO, KH, KW, S, IWS>), dim3(grid), dim3(512), lds, st, X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nb, 0, work_ctr);
-            else hipLaunchKernelGGL((conv_wgrad_dma_kernel<CI, CO, KH, KW, S, 0>), dim3(grid), dim3(512), lds, st, X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nb, 0, work_ctr);
+            if (IWS && IW == IWS) hipLaunchKernelGGL((conv_wgrad_dma_kernel<CI, CO, KH, KW, S, IWS>), dim3(grid), dim3(512), lds, st, X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nb, work_ctr);
+            else hipLaunchKernelGGL((conv_wgrad_dma_kernel<CI, CO, KH, KW, S, 0>), dim3(grid), dim3(512), lds, st, X, dY, part, bias_part, zeros, Nf, IH, IW, OH, OW, R, nb, work_ctr);
             return grid;
         }
     }
@@ -690,17 +686,16 @@ static inline int launch_conv_wgrad_tr(hipStream_t st, const h16_t* X, const h16
         }
         const int items = fpb > 1 ? (Nf + fpb - 1) / fpb : Nf * nb;
         const int grid = std::min(std::min(items, 256), max_blocks);
-        constexpr int dbg = 0;
         {      // the gripper camera's maps (84 x 84 frames): conv3 reads 9 x 9, conv2 20 x 20 — the compile-time-width instance (tap offsets as ds_read immediates)
             constexpr int IWG = WgradCamW<CI, KH>::gripper;
             if (IWG && IW == IWG) {
                 static bool ag = false;
                 if (!ag) { hipFuncSetAttribute((const void*)conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 3, IWG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); ag = true; }
-                hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 3, IWG>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
+                hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV, 3, IWG>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, work_ctr, fpb);
                 return grid;
             }
         }
-        hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, dbg, work_ctr, fpb);
+        hipLaunchKernelGGL((conv_wgrad_tr8_kernel<CI, CO, KH, KW, S, NWV>), dim3(grid), dim3(NWV * 64), lds, st, X, dY, part, bias_part, Nf, IH, IW, OH, OW, R, nb, work_ctr, fpb);
         return grid;
         }
     }
@@ -1403,227 +1398,8 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2_kernel(Wgrad1Batch bt)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The same v2 structure for the uint8 (.., H, W, C) boundary (the uint8 path had kept v1).  The next
-// band is prefetched as RAW bytes — 4-byte chunks of the interleaved RGB rows (rows are multiples of 4 bytes for both cameras; 8 for the
-// static one only), the row clamp of RandomShiftsAug's replicate pad applied to the source row, plus the two edge pixels of every row —
-// 12 + 1 registers per thread for a quarter of the fp32 path's bytes.  Commit = raw rows + replicated margins into LDS, barrier, then the
-// ScaleImageTensor / Normalize / column-shift conversion of conv1_stage_band's second stage into the bf16 [c][row][iw] image.
-// ---------------------------------------------------------------------------------------------------------------------
-template <int PFX, int PFY>
-__global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2u_kernel(Conv1Src S, int* __restrict__ work_ctr, const h16_t* __restrict__ dY, float* __restrict__ part,
-                                                                  float* __restrict__ bias_part, int Nf, int IH, int IW, int OH, int OW, int R, int nbands) {
-    using C = Wgrad1Cfg;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int OWp = (OW + 7) & ~7, U = OWp >> 3;
-    const int XR = (R - 1) * C::S + C::KH;
-    const int XRS = IW * 2 + 16;
-    const int xbytes = C::C * XR * XRS + 512;
-    const int dypix = R * OWp + 8;
-    lds_char* ximg = (lds_char*)smem;
-    lds_char* dyimg = ximg + xbytes;
-    lds_char* raw = dyimg + dypix * C::DYS;
-    for (int i = tid * 16; i < xbytes + dypix * C::DYS; i += 512 * 16) *(lds_u32x4*)((lds_char*)smem + i) = u32x4_t{0u, 0u, 0u, 0u};
-    const int W4 = IW >> 2;
-    const int RB = IW * 3, n4 = RB >> 2;                          // bytes / 4-byte chunks per source row
-    const int RP = conv1_raw_pitch(IW);
-    constexpr int LM = CONV1_RAW_MARGIN * 3;
-    const int nx = XR * n4, ny = R * OW * 4;
-    const unsigned char* Xb = reinterpret_cast<const unsigned char*>(S.X);
-    // raw slot k of this thread = chunk tid + 512 k of the [XR][n4] grid: (row, chunk) advanced incrementally from slot 0's — twelve
-    // descriptor registers next to twelve slots of in-flight data spilled 17 registers at the 128-VGPR budget and serialised the prefetch
-    // ... and the compiler hoists whatever is band-invariant out of the band loop and spills it just the same (a scratch reload in front of
-    // every prefetch load waits for the loads issued before it): slot 0's (row, chunk) is recomputed per band behind an opaque copy of tid
-    const int xdq = 512 / n4, xdr = 512 - xdq * n4;
-    int yd[PFY];
-#pragma unroll
-    for (int k = 0; k < PFY; ++k) {
-        const int e = min(tid + k * 512, ny - 1);
-        const int r = e / (OW * 4), i = e - r * (OW * 4);
-        yd[k] = (r << 16) | i;
-    }
-    f32x4 acc[3][2];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) acc[j][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int g = lane >> 4, a = lane & 15;
-    const int prow = a >> 2, q = a & 3;
-    const int ccolA = q * 8;
-    const int nt0 = (wave & 3) * 3, uh = wave >> 2;
-    float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    unsigned px[PFX], pe = 0;
-    u32x4_t py[PFY];
-    int xrows = 0, yrows = 0, pdx = 0;
-    auto prefetch = [&](int item) {
-        const int f = item / nbands, oh0 = (item % nbands) * R;
-        const int ih0 = oh0 * C::S;
-        xrows = min(XR, IH - ih0); yrows = min(R, OH - oh0);
-        int dy = 0;
-        pdx = 0;
-        S.offsets(f, pdx, dy);
-        const unsigned char* fb = Xb + S.frame(f) * IH * RB;
-        const h16_t* yb = dY + ((long long)f * OH + oh0) * OW * C::CO;
-        {
-            int t = tid;
-            asm volatile("" : "+v"(t));
-            int r = t / n4, c4 = t - r * n4;
-#pragma unroll
-            for (int k = 0; k < PFX; ++k) {
-                const int rr = min(r, min(XR, xrows) - 1);            // slots past the band / rows below the frame: a valid row (dropped / zeroed at the commit)
-                px[k] = *reinterpret_cast<const unsigned*>(fb + min(max(ih0 + rr + dy, 0), IH - 1) * RB + c4 * 4);
-                c4 += xdr; r += xdq; if (c4 >= n4) { c4 -= n4; ++r; }
-            }
-        }
-        if (tid < 2 * XR) {                                       // the edge pixels of every row (replicated into the margins at the commit)
-            const int rr = tid >> 1, side = tid & 1;
-            pe = *reinterpret_cast<const unsigned*>(fb + (long long)min(max(ih0 + min(rr, xrows - 1) + dy, 0), IH - 1) * RB + (side ? RB - 4 : 0));
-        }
-#pragma unroll
-        for (int k = 0; k < PFY; ++k) {
-            const int r = yd[k] >> 16, i = yd[k] & 0xffff;
-            py[k] = *reinterpret_cast<const u32x4_t*>(yb + (min(r, yrows - 1) * OW) * C::CO + i * 8);
-        }
-    };
-    __shared__ int s_next[2];
-    int frame = blockIdx.x, fiter = 0, band = 0;
-    int item = frame * nbands;
-    if (frame < Nf) prefetch(item);
-    while (frame < Nf) {
-        if (band == 0 && work_ctr && tid == 0) s_next[fiter & 1] = (int)gridDim.x + atomicAdd(work_ctr, 1);
-        __syncthreads();                                          // previous band consumed (first pass: zero fill visible)
-        const int cxr = xrows, cyr = yrows, dx = pdx;
-        {
-            int t = tid;
-            asm volatile("" : "+v"(t));
-            int r = t / n4, c4 = t - r * n4;
-#pragma unroll
-            for (int k = 0; k < PFX; ++k) {
-                if (t + k * 512 < nx) *(__attribute__((address_space(3))) unsigned*)(raw + r * RP + LM + c4 * 4) = px[k];
-                c4 += xdr; r += xdq; if (c4 >= n4) { c4 -= n4; ++r; }
-            }
-        }
-        if (tid < 2 * XR && !W1_PROBE_SKIP(4)) {
-            const int rr = tid >> 1, side = tid & 1;
-            const unsigned pxl = side ? (pe >> 8) : (pe & 0xffffffu);
-            lds_char* dst = raw + rr * RP + (side ? LM + RB : 0);
-            for (int k = 0; k < CONV1_RAW_MARGIN; ++k) {
-                dst[k * 3 + 0] = (char)(pxl & 0xff); dst[k * 3 + 1] = (char)((pxl >> 8) & 0xff); dst[k * 3 + 2] = (char)((pxl >> 16) & 0xff);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < PFY; ++k)
-            if (tid + k * 512 < ny) {
-                const int r = yd[k] >> 16, i = yd[k] & 0xffff;
-                const u32x4_t v = r < cyr ? py[k] : u32x4_t{0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { bsum[2 * e] += h2f_lo(v[e]); bsum[2 * e + 1] += h2f_hi(v[e]); }
-                *(lds_u32x4*)(dyimg + (r * OWp + (i >> 2)) * C::DYS + (i & 3) * 16) = v;
-            }
-        __syncthreads();                                          // raw rows complete
-        {
-            const float sc = S.fold ? 1.f : 2.f / 255.f, of = S.fold ? 0.f : -1.f;
-            for (int e = W1_PROBE_SKIP(8) ? XR * W4 : tid; e < XR * W4; e += 512) {
-                const int r = e / W4, c = e - r * W4;
-                u32x2_t ov[3] = {u32x2_t{0u, 0u}, u32x2_t{0u, 0u}, u32x2_t{0u, 0u}};
-                if (r < cxr) {                                    // rows below the frame stay zero
-                    const int o = r * RP + LM + (c * 4 + dx) * 3;
-                    const int sh = o & 3;
-                    const __attribute__((address_space(3))) unsigned* wp = (const __attribute__((address_space(3))) unsigned*)(raw + (o & ~3));
-                    const unsigned w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
-                    const unsigned d[3] = {__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh), __builtin_amdgcn_alignbyte(w3, w2, sh)};
-                    float v[12];
-#pragma unroll
-                    for (int k = 0; k < 12; ++k) v[k] = fmaf((float)((d[k >> 2] >> (8 * (k & 3))) & 0xffu), sc, of);
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) { ov[ch][0] = pack2h(v[ch], v[3 + ch]); ov[ch][1] = pack2h(v[6 + ch], v[9 + ch]); }
-                }
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) *(__attribute__((address_space(3))) u32x2_t*)(ximg + (ch * XR + r) * XRS + c * 8) = ov[ch];
-            }
-        }
-        __syncthreads();
-        if (++band == nbands) {
-            band = 0;
-            frame = work_ctr ? s_next[fiter & 1] : frame + (int)gridDim.x;
-            ++fiter;
-        }
-        item = frame * nbands + band;
-        if (frame < Nf && !W1_PROBE_SKIP(2)) prefetch(item);      // in flight during the MFMAs below
-        const int units = R * U;
-        // run u = u0 + g -> (row ur, run uo of the row) advanced by adds (8 runs per step): a runtime division per step stood next to 6 MFMAs
-        int joff[3];                                   // per n-tile: (channel, kernel row) of this lane's B rows + its column half
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { const int nt = nt0 + j; joff[j] = ((nt >> 2) * XR + (nt & 3) * 2 + (q >> 1)) * XRS + (q & 1) * 8; }
-        const int q8 = 8 / U, r8 = 8 - q8 * U;
-        int ur, uo;
-        { const int u = uh * 4 + g; ur = u / U; uo = u - ur * U; }
-#pragma unroll 1
-        for (int u0 = W1_PROBE_SKIP(1) ? units : uh * 4; u0 < units; u0 += 8) {
-            const int u = u0 + g;
-            const bool valid = u < units;
-            const int r = valid ? ur : 0, ow0 = valid ? uo * 8 : 0;
-            ur += q8; uo += r8;
-            if (uo >= U) { uo -= U; ++ur; }
-            const int pixA = valid ? r * OWp + ow0 : R * OWp;
-            lds_char* abase = dyimg + (pixA + prow) * C::DYS + ccolA;
-            h16x8_t af[2];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) af[c] = tr_read8(abase + c * 32, abase + 4 * C::DYS + c * 32);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                lds_char* bbase = ximg + joff[j] + (r * C::S) * XRS + (ow0 + prow) * C::S * 2;
-                const h16x8_t bf = tr_read8(bbase, bbase + 4 * C::S * 2);
-#pragma unroll
-                for (int c = 0; c < 2; ++c) acc[j][c] = MFMA_16x16x32_H(af[c], bf, acc[j][c], 0, 0, 0);
-            }
-        }
-    }
-    // ---- the bias partial of this workgroup first (Conv1Src::fold needs it for the slab), then the two unit halves (waves w and w + 4) are summed
-    // through LDS and one slab per workgroup is written
-    __syncthreads();
-    float* redf = reinterpret_cast<float*>(smem);
-    float* dbw = redf + 6144;                                    // [CO]: this workgroup's bias-gradient partial (24 KB in: behind redf's 16 KB and red's 24 KB)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) redf[tid * 8 + e] = bsum[e];
-    __syncthreads();
-    if (tid < C::CO) {
-        const int cgrp = tid >> 3, e = tid & 7;
-        float sacc = 0.f;
-        for (int t = cgrp; t < 512; t += 4) sacc += redf[t * 8 + e];
-        unsafeAtomicAdd(bias_part + tid, sacc);
-        dbw[tid] = sacc;
-    }
-    __syncthreads();
-    f32x4* red = reinterpret_cast<f32x4*>(smem);
-    if (uh == 1) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) red[((wave & 3) * 6 + j * 2 + c) * 64 + lane] = acc[j][c];
-    }
-    __syncthreads();
-    if (uh == 0) {
-        float* out = part + (long long)blockIdx.x * C::CO * 192;
-        const float fsc = S.fold ? CONV1_FOLD_SCALE : 1.f;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const f32x4 v = acc[j][c] + red[((wave & 3) * 6 + j * 2 + c) * 64 + lane];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = c * 16 + g * 4 + r;
-                    out[(long long)co * 192 + (nt0 + j) * 16 + a] = S.fold ? fmaf(v[r], fsc, -dbw[co]) : v[r];      // dW = (2/255) (dY * u) - db (x) 1
-                }
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Round 6: the uint8 kernel above with the conversion done FROM THE PREFETCH REGISTERS (tools/conv1_wgrad_probe.hip: commit + conversion were 119 of its 251 us — raw
-// rows into LDS, margins, a barrier, a second pass that reads them back — and the 4 x smaller frames bought nothing over the fp32 boundary's 261 us).  A prefetch slot is
+// Round 6: the v2 structure for the uint8 (.., H, W, C) boundary with the conversion done FROM THE PREFETCH REGISTERS (round 5 prefetched the next band as raw bytes and
+// converted them in LDS; tools/conv1_wgrad_probe.hip: commit + conversion were 119 of that kernel's 251 us — raw rows into LDS, margins, a barrier, a second pass that reads them back — and the 4 x smaller frames bought nothing over the fp32 boundary's 261 us).  A prefetch slot is
 // the aligned 16-byte window around a 4-pixel group's 12 bytes (one dwordx4 load; 33 % more bytes requested, the overlaps hit in L2); the column shift and the replicate
 // pad are resolved per pixel from the window at the commit.  One barrier per band less, no raw rows in LDS.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1878,9 +1654,9 @@ __global__ void __launch_bounds__(512, 4) conv1_wgrad_tr2r_kernel(Wgrad1Batch bt
     conv1_wgrad_tr2r_body<PFX, PFY, SPLIT>(J.S, J.work_ctr, J.dY, J.part, J.bias_part, J.Nf, J.IH, J.IW, J.OH, J.OW, J.R, J.nbands, bid, nwg);
 }
 
-inline int g_conv1_wgrad_u8reg = -1;      // hulc_k_conv1_wgrad_u8's `form` (tests): 0 / 1 / 2 force the uint8 kernel form (-1: the engine's, 2)
+inline int g_conv1_wgrad_u8reg = -1;      // hulc_k_conv1_wgrad_u8's `form` (tests): 1 / 2 force the uint8 kernel form (-1: the engine's, 2)
 // Kernel form and band height of one conv1 weight-gradient job: 1 = conv1_wgrad_tr2_kernel<6, 2> (fp32 frames), 2 = conv1_wgrad_tr2r_kernel<3, 2, true>,
-// 3 = conv1_wgrad_tr2r_kernel<4, 2>, 4 = conv1_wgrad_tr2u_kernel<12, 2> (uint8 frames), 5 = conv1_wgrad_tr_kernel (any shape)
+// 3 = conv1_wgrad_tr2r_kernel<4, 2> (uint8 frames), 5 = conv1_wgrad_tr_kernel (any shape)
 static inline int conv1_wgrad_plan(const Conv1Src& X, int IH, int IW, int OH, int OW, int& R_out, int& nb_out, size_t& lds_out) {
     auto balanced = [&](int R) { const int nb = (OH + R - 1) / R; nb_out = nb; R_out = (OH + nb - 1) / nb; };
     if (!X.u8 && (IW % 4) == 0) {
@@ -1898,7 +1674,7 @@ static inline int conv1_wgrad_plan(const Conv1Src& X, int IH, int IW, int OH, in
             return 1;
         }
     }
-    // uint8 forms: 2 = conversion from the prefetch registers with interior / row-end slots (conv1_wgrad_tr2r_kernel<3, 2, true>), 1 = one general slot kind, 0 = raw rows through LDS
+    // uint8 forms: 2 = conversion from the prefetch registers with interior / row-end slots (conv1_wgrad_tr2r_kernel<3, 2, true>), 1 = one general slot kind
     const int u8form = g_conv1_wgrad_u8reg < 0 ? 2 : g_conv1_wgrad_u8reg;
     if (X.u8 && (IW % 4) == 0 && IW >= 8 && u8form >= 2) {
         // round 6, second pass: 2 slots of interior groups (fast conversion) + 1 slot of row-end groups + 2 dY slots per thread (conv1_wgrad_tr2r_kernel<3, 2, true>)
@@ -1917,7 +1693,7 @@ static inline int conv1_wgrad_plan(const Conv1Src& X, int IH, int IW, int OH, in
             return 2;
         }
     }
-    if (X.u8 && (IW % 4) == 0 && IW >= 8 && u8form) {
+    if (X.u8 && (IW % 4) == 0 && IW >= 8) {
         // uint8 boundary, round 6: 4 window slots of 16 bytes + 2 dY slots per thread, converted from the registers (conv1_wgrad_tr2r_kernel); no raw rows in LDS
         int R = OH;
         auto fits = [&](int r) {
@@ -1929,20 +1705,6 @@ static inline int conv1_wgrad_plan(const Conv1Src& X, int IH, int IW, int OH, in
             balanced(R);
             lds_out = std::max<size_t>(Wgrad1Cfg::lds_bytes(R_out, IW, OW, false), 32 * 1024);      // (>= the epilogue's reduction areas: 24.6 KB)
             return 3;
-        }
-    }
-    if (X.u8 && (IW % 4) == 0) {
-        // uint8 boundary: 12 raw 4-byte slots + 2 dY slots per thread; the raw rows add their LDS area to the two images
-        int R = OH;
-        auto fits = [&](int r) {
-            const int XR = (r - 1) * Wgrad1Cfg::S + Wgrad1Cfg::KH;
-            return Wgrad1Cfg::lds_bytes(r, IW, OW, true) <= (size_t)79 * 1024 && (long long)XR * (IW * 3 / 4) <= 12 * 512 && (long long)r * OW * 4 <= 2 * 512 && 2 * XR <= 512 && r < 128;
-        };
-        while (R > 1 && !fits(R)) --R;
-        if (fits(R)) {
-            balanced(R);
-            lds_out = std::max<size_t>(Wgrad1Cfg::lds_bytes(R_out, IW, OW, true), 512 * 8 * sizeof(float));
-            return 4;
         }
     }
     constexpr int lds_kb = 39;   // 4 workgroups per CU (0.44 vs 0.50 ms/step at 2 per CU with 78 KB bands)
@@ -1964,7 +1726,7 @@ static inline bool launch_conv1_wgrad_jobs(hipStream_t st, Wgrad1Job* j, int n, 
         size_t l = 0;
         const int f = conv1_wgrad_plan(j[k].S, j[k].IH, j[k].IW, j[k].OH, j[k].OW, j[k].R, j[k].nbands, l);
         if (k && f != form) return false;
-        if (j[k].Nf < 1 || (f == 4 && n > 1)) return false;      // (the raw-row uint8 form takes one job)
+        if (j[k].Nf < 1) return false;
         form = f; lds = std::max(lds, l);
         const int U = (j[k].OW + 7) / 8;
         w[k] = (double)j[k].Nf * j[k].nbands * ((j[k].R * U + 7) / 8 + 1);
@@ -2007,11 +1769,6 @@ static inline bool launch_conv1_wgrad_jobs(hipStream_t st, Wgrad1Job* j, int n, 
         static bool attr2r = false;
         if (!attr2r) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2r_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2r = true; }
         hipLaunchKernelGGL((conv1_wgrad_tr2r_kernel<4, 2>), dim3(blk), dim3(512), lds, st, bt);
-    } else if (form == 4) {
-        static bool attr2u = false;
-        if (!attr2u) { hipFuncSetAttribute((const void*)conv1_wgrad_tr2u_kernel<12, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr2u = true; }
-        const Wgrad1Job& q = j[0];
-        hipLaunchKernelGGL((conv1_wgrad_tr2u_kernel<12, 2>), dim3(blk), dim3(512), lds, st, q.S, q.work_ctr, q.dY, q.part, q.bias_part, q.Nf, q.IH, q.IW, q.OH, q.OW, q.R, q.nbands);
     } else {
         static bool attr_set = false;
         if (!attr_set) { hipFuncSetAttribute((const void*)conv1_wgrad_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr_set = true; }

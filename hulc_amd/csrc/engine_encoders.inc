@@ -119,7 +119,7 @@
             if constexpr (std::is_same<T, h16_t>::value) {
                 const double px = (double)nf * g.OH * g.OW;
                 TimerScope ts(this, "conv1_fwd", "hbm", 2.0 * px * 32 * 192, (double)nf * 3 * e.IH * e.IH * (sh.u8 ? 1 : 4) + px * 32 * 2);
-                launch_conv1_fwd(st, sh, e.c1.Wf, conv1_bias(e, sh), a.a1 + poff * 32, nf, e.IH, e.IH, g.OH, g.OW, 0, a.m1bits ? a.m1bits + poff : nullptr, pend_zero[0], pend_zero[1]);
+                launch_conv1_fwd(st, sh, e.c1.Wf, conv1_bias(e, sh), a.a1 + poff * 32, nf, e.IH, e.IH, g.OH, g.OW, false, a.m1bits ? a.m1bits + poff : nullptr, pend_zero[0], pend_zero[1]);
                 pend_zero[0] = pend_zero[1] = nullptr;
             } else {
                 const float* x = conv1_f32(sh, e.gripper, nf, e.IH, foff);
@@ -142,7 +142,7 @@
             const ConvTileP p = conv_fwd_job(s);
             const bool big = encw(k).H2 >= 16;
             TimerScope ts(this, "conv_tile_fwd", "mfma", conv_fwd_flops(s.c, s.g), conv_fwd_bytes(s.c, s.g));
-            if (sn == 2 ? (big ? launch_conv_reg_fwd<32, 4, 4, 2>(st, p) : launch_conv_reg<32, 4, 4, 2, false, 1, 4, 0, true>(st, p)) || launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p)
+            if (sn == 2 ? (big ? launch_conv_reg_fwd<32, 4, 4, 2>(st, p) : launch_conv_reg<32, 4, 4, 2, false, 1, 4, true>(st, p)) || launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p)
                         : (big ? launch_conv_reg_fwd<64, 3, 3, 1>(st, p) : launch_conv_reg<64, 3, 3, 1, false, 1, 4>(st, p)) || launch_conv_tile<64, 64, 3, 3, 1, 1, false>(st, p)) return;
         }
         const int Kc = s.c.I * s.c.KH * s.c.KW;
@@ -444,7 +444,7 @@
             if (!k3 && !k2) return false;
             const ConvTileP j[2] = {conv_dgrad_job(S, true), conv_dgrad_job(G, true)};
             TimerScope ts(this, "conv_tile_dgrad", "mfma", 0, 0, 0);
-            const bool ok = k3 ? launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, j, 2) : launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, j, 2);
+            const bool ok = k3 ? launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, true, 1>(st, j, 2) : launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, true, 1>(st, j, 2);
             if (ok) ts.add(conv_dgrad_flops(S.c, S.g) + conv_dgrad_flops(G.c, G.g), conv_dgrad_bytes(S.c, S.g, true, false) + conv_dgrad_bytes(G.c, G.g, true, false));
             return ok;
         }
@@ -460,8 +460,8 @@
             bool ok = false;
             TimerScope ts(this, "conv_tile_dgrad", "mfma", conv_dgrad_flops(c, g), conv_dgrad_bytes(c, g, bits, true));
             // both data gradients run on conv_reg.h's pipelined-epilogue form (EPI: a tile's epilogue rides in the next tile's multiply loop), two 256-thread workgroups per CU
-            if (dgrad_is3(c)) ok = (bits && launch_conv_reg<64, 3, 3, 1, true, 1, 4, 0, true, 1>(st, p)) || launch_conv_tile<64, 64, 3, 3, 1, 1, true>(st, p);
-            else if (dgrad_is2(c)) ok = (bits && launch_conv_reg<64, 2, 2, 1, true, 2, 4, 0, true, 1>(st, p)) || launch_conv_tile<64, 32, 2, 2, 1, 2, true>(st, p);
+            if (dgrad_is3(c)) ok = (bits && launch_conv_reg<64, 3, 3, 1, true, 1, 4, true, 1>(st, p)) || launch_conv_tile<64, 64, 3, 3, 1, 1, true>(st, p);
+            else if (dgrad_is2(c)) ok = (bits && launch_conv_reg<64, 2, 2, 1, true, 2, 4, true, 1>(st, p)) || launch_conv_tile<64, 32, 2, 2, 1, 2, true>(st, p);
             if (ok) return;
         }
         ConvDgradLoader<T> l{s.dy, g, c.O};

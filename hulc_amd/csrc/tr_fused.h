@@ -624,7 +624,6 @@ struct TrAttnBwdP {
     float *dy_f, *dx;                            // [N][128] fp32
     int B, S;
     float dp; unsigned long long seed_o, seed_att;
-    int dbg;                                     // phases switched off (1: P0, 2: P2, 4: P1, 8: P3); 0 from the engine
 };
 constexpr int TRA_HP = 48;                                          // bytes per row of a head's [32][16] 16-bit operand: two 16-byte reads per row
 constexpr int TRA_HEADB = 4 * 32 * TRA_HP + 2 * 32 * 33 * 4;        // q, k, v, dO + dS, dropped P
@@ -662,7 +661,7 @@ __global__ void __launch_bounds__(512) tr_attn_bwd_kernel(TrAttnBwdP p) {
         for (int rr = 0; rr < 4; ++rr) {
             const int r = wave * 4 + rr;
             float t0 = 0.f, t1 = 0.f;
-            if (r < S && !(p.dbg & 1)) {
+            if (r < S) {
                 const long long row = row0 + r;
                 const float mean = p.st1[2 * row], rstd = p.st1[2 * row + 1];
                 const float* xr = p.y1 + row * TRF_D;
@@ -716,7 +715,7 @@ __global__ void __launch_bounds__(512) tr_attn_bwd_kernel(TrAttnBwdP p) {
     }
 
     // ---- P1: dao[:, head] = b_d W_o[:, head]  -> dO of this head (16 bit)
-    if (!(p.dbg & 4)) {
+    {
         f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -743,7 +742,7 @@ __global__ void __launch_bounds__(512) tr_attn_bwd_kernel(TrAttnBwdP p) {
         for (int e = 0; e < 4; ++e) { x[2 * e] = h2f_lo(a[e]); x[2 * e + 1] = h2f_hi(a[e]); x[8 + 2 * e] = h2f_lo(b[e]); x[8 + 2 * e + 1] = h2f_hi(b[e]); }
     };
     constexpr int HJ = 16;
-    if (ai < S && !(p.dbg & 2)) {
+    if (ai < S) {
         const float* Pr = p.Pat + (((long long)w * TRF_NH + wave) * S + ai) * S;
         float dot = 0.f;
         float dpv[HJ], pv[HJ];
@@ -772,7 +771,7 @@ __global__ void __launch_bounds__(512) tr_attn_bwd_kernel(TrAttnBwdP p) {
         for (int jj = 0; jj < HJ; ++jj) if (hf * HJ + jj < S) *(lds_f32*)(dSb + (ai * 33 + hf * HJ + jj) * 4) = pv[jj] * (dpv[jj] - dot);
     }
     __syncthreads();
-    if (ai < S && !(p.dbg & 2)) {
+    if (ai < S) {
         float dq[16], dk[16], dv[16];
 #pragma unroll
         for (int d = 0; d < 16; ++d) { dq[d] = 0.f; dk[d] = 0.f; dv[d] = 0.f; }
@@ -806,7 +805,7 @@ __global__ void __launch_bounds__(512) tr_attn_bwd_kernel(TrAttnBwdP p) {
     __syncthreads();
 
     // ---- P3: dx = d qkv W_in + dy1 (features wave * 16 .. + 15)
-    if (!(p.dbg & 8)) {
+    {
         f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int ks = 0; ks < 12; ++ks) {

@@ -188,3 +188,17 @@ def test_conv1_interior_groups_never_touch_a_row_end():
         first, count = C.c_int32(), C.c_int32()
         lib.hulc_k_conv1_interior_groups(IW, pad, 1000, C.byref(first), C.byref(count))
         assert count.value == want, (IW, pad, count.value)
+
+
+def test_kernel_test_entries_reject_retired_flags_modes_and_forms_before_touching_the_device():
+    """hulc_k_conv_tile takes the relu bits 1 (ReLU), 32 (dynamic claiming) and 256 (register-staged uint8 cross-check, modes 5 / 6) only, and no mode 30 .. 39 (the
+    two-buffer 4-wave forms are gone); hulc_k_conv1_wgrad_u8 takes form 1 or 2 (the raw-rows form 0 is gone).  Every data pointer is null: a check that came after an
+    allocation or a launch would not return an error here, it would crash or (without a GPU) report a HIP failure instead of naming the argument."""
+    from hulc_amd import lib as L
+    lib = L.load()
+    for mode, relu, word in ((10, 1 | 4, b"relu"), (0, 1 | 2, b"relu"), (4, 64, b"relu"), (4, 256, b"relu"), (6, 1 | 128, b"relu"), (30, 1, b"unsupported mode 30"), (39, 0, b"unsupported mode 39")):
+        assert lib.hulc_k_conv_tile(mode, None, None, None, None, None, 1, 23, 21, relu, None) != 0, (mode, relu)
+        err = lib.hulc_last_error()
+        assert b"hulc_k_conv_tile" in err and word in err, (mode, relu, err)
+    assert lib.hulc_k_conv1_wgrad_u8(None, None, 4, None, None, None, 1, 84, 0, 1, None) != 0
+    assert b"hulc_k_conv1_wgrad_u8: form" in lib.hulc_last_error()

@@ -189,7 +189,7 @@ def test_frame_store_windows_equal_the_materialised_batch(dtype):
 @pytest.mark.parametrize("IH,pad", [(200, 10), (84, 4)])
 def test_u8_conv1_forward_at_launch_scale_matches_a_direct_convolution_and_itself(IH, pad):
     """Round 6: conv1's uint8 forward on 2048 frames with random RandomShiftsAug shifts — the LDS-DMA kernel the step uses, twice, and the register-staged kernel
-    (16-byte windows, dbg bit 8) — against torch's convolution of the shifted / clamped / normalised frames.  The small ingest fixtures (8 frames) never showed
+    (16-byte windows, relu bit 256) — against torch's convolution of the shifted / clamped / normalised frames.  The small ingest fixtures (8 frames) never showed
     what this size does: a row's last DMA piece spills 8 bytes of the next row onto the row's right margin, and the margin fill raced with slower waves' pieces
     (positive column shifts: the three rightmost output columns of some rows wrong by O(0.1), differently per run).  Gates: both kernels within bf16 rounding of
     torch on sampled frames incl. the buffer's last, the two DMA runs and the register kernel bit-identical."""
@@ -203,8 +203,8 @@ def test_u8_conv1_forward_at_launch_scale_matches_a_direct_convolution_and_itsel
     sh = torch.randint(0, 2 * pad + 1, (Nf, 2), device="cuda", generator=g, dtype=torch.int32)
     sh[0] = torch.tensor([0, 2 * pad]); sh[1] = torch.tensor([2 * pad, 0]); sh[Nf - 1] = torch.tensor([2 * pad, 2 * pad])
     outs = [torch.zeros(Nf, OH, OH, 32, device="cuda", dtype=torch.bfloat16) for _ in range(3)]
-    for o, dbg in zip(outs, (0, 256, 0)):
-        L.check(lib.hulc_k_conv_tile(6, x.data_ptr(), w.data_ptr(), b.data_ptr(), sh.data_ptr(), o.data_ptr(), Nf, IH, OH, dbg, None))
+    for o, flags in zip(outs, (0, 256, 0)):
+        L.check(lib.hulc_k_conv_tile(6, x.data_ptr(), w.data_ptr(), b.data_ptr(), sh.data_ptr(), o.data_ptr(), Nf, IH, OH, flags, None))
     torch.cuda.synchronize()
     assert torch.equal(outs[0], outs[2]), int((outs[0] != outs[2]).sum())           # the same launch twice
     assert torch.equal(outs[0], outs[1]), int((outs[0] != outs[1]).sum())           # same arithmetic on the same 16-bit operands
@@ -222,7 +222,7 @@ def test_u8_conv1_forward_at_launch_scale_matches_a_direct_convolution_and_itsel
 @pytest.mark.parametrize("IH,pad", [(200, 10), (84, 4)])
 def test_u8_conv1_weight_gradient_at_launch_scale_matches_torch(IH, pad):
     """Round 6: conv1's weight / bias gradient from uint8 frames on 2048 frames with random RandomShiftsAug shifts — the kernel the step uses (conversion from the
-    prefetch registers, conv1_wgrad_tr2r_kernel, with interior / row-end slots), the same kernel with one general slot kind, round 5's form (raw rows through LDS, tr2u) and both without the affine fold — against an fp64 torch reference
+    prefetch registers, conv1_wgrad_tr2r_kernel, with interior / row-end slots), the same kernel with one general slot kind, and both without the affine fold — against an fp64 torch reference
     dW[o][c][kh][kw] = sum dY[n][oh][ow][o] x[n][c][4 oh + kh][4 ow + kw] over the shifted / clamped / normalised frames.  With the fold the MFMA operand is the exact
     byte, so the only error is the fp32 accumulation (and atomics' order); without it x is rounded to bf16 first and the reference rounds the same way."""
     from hulc_amd import lib as L
@@ -248,7 +248,7 @@ def test_u8_conv1_weight_gradient_at_launch_scale_matches_torch(IH, pad):
                     refs[fold][:, :, kh, kw] += torch.einsum("nhwd,nchw->dc", d, xx[:, :, kh:kh + 4 * OH:4, kw:kw + 4 * OH:4])
     refb = dY.double().sum(dim=(0, 1, 2))
     got = {}
-    for form in (2, 1, 0):
+    for form in (2, 1):
         for fold in (1, 0):
             gw = torch.zeros(32, 192, device="cuda"); gb = torch.zeros(32, device="cuda")
             L.check(lib.hulc_k_conv1_wgrad_u8(x.data_ptr(), sh.data_ptr(), pad, dY.data_ptr(), gw.data_ptr(), gb.data_ptr(), Nf, IH, form, fold, None))
@@ -260,7 +260,6 @@ def test_u8_conv1_weight_gradient_at_launch_scale_matches_torch(IH, pad):
             assert err < (2e-5 if fold else 1e-4), (form, fold, err)
             assert errb < 1e-5, (form, fold, errb)
     # the two forms feed the MFMAs the same operands in the same order; only the slab atomics' order differs
-    assert float((got[(1, 1)] - got[(0, 1)]).abs().max() / got[(1, 1)].abs().max()) < 2e-6
     assert float((got[(2, 1)] - got[(1, 1)]).abs().max() / got[(1, 1)].abs().max()) < 2e-6
     assert float((got[(2, 0)] - got[(1, 0)]).abs().max() / got[(1, 0)].abs().max()) < 2e-6
 

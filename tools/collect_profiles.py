@@ -9,7 +9,7 @@ P = lambda f: os.path.join(ROOT, "profiles", f)
 copies = {"bench_n1.json": "bench_n1.json", "kernel_stats.csv": "kernel_stats.csv", "kernel_stats_summary.txt": "kernel_stats_summary.txt",
           "pmc_hbm_per_kernel.csv": "pmc_hbm_per_kernel.csv", "pmc_traffic.json": "pmc_traffic.json", "sq/mfma_util.csv": "mfma_util.csv",
           "sq/summary.txt": "mfma_util_summary.txt", "gridbar2.txt": "gridbar_xcd_barrier.txt", "gridbar.txt": "gridbar_naive_barrier.txt", "step_sequence.txt": "step_sequence.txt",
-          "conv_tile_gripper.txt": "conv_tile_gripper_fpb.txt", "conv_reg_vs_tile.txt": "conv_reg_vs_tile.txt", "conv_reg_ablation.txt": "conv_reg_ablation.txt",
+          "conv_tile_gripper.txt": "conv_tile_gripper_fpb.txt", "conv_reg_vs_tile.txt": "conv_reg_vs_tile.txt",
           "step_timeline.txt": "step_timeline.txt", "rnn_persist_stamps.txt": "rnn_persist_stamps.txt",
           "storebench.txt": "storebench_write_patterns.txt", "mixbench.txt": "mixbench_conv1_traffic_shape.txt",
           "cr_bench.txt": "conv_reg_forms.txt", "cr_stamps.txt": "conv_reg_phase_stamps.txt", "vmcnt_probe.txt": "vmcnt_order_probe.txt"}
@@ -71,7 +71,7 @@ files = f"""| file | what | command |
 | `{T}_step_sequence.txt` | every launch of ONE step in order (consecutive identical launches collapsed) from the same kernel trace: launches per step, which memsets / transposes / small kernels remain and how long each takes.  The per-step call counts of `{T}_kernel_stats_summary.txt` divide a 9-step profile that also holds the engine's one-time workspace zero-fills (≈160 `fillBufferAligned`) and bench.py's input generation; a step itself issues 3 memsets (gradient buffer, loss slots, the backward's zero arena) | `tools/step_seq.py` |
 | `{T}_bench_n1_fp32.json` | the fp32 PARITY engine (exact-fp32 MFMA, `v_mfma_f32_16x16x4_f32`: 1/16 of the bf16 matrix rate): {var['fp32']['value']:.0f} windows/s, {var['fp32']['ms_per_step']} ms/step | `python bench.py --full --dtype fp32 --steps 20 --no-cpu-baseline` |
 | `{T}_bench_n1_u8_h2d.json` | uint8 ingest with every step's frames copied from PINNED HOST memory (async H2D on a copy stream, double-buffered; 289 MB per step): {var['u8_h2d']['value']:.0f} windows/s, median step {(var['u8_h2d'].get('step_ms') or {{}}).get('median')} ms — PCIe-bound, SURVEY §8(d)'s H2D-inclusive row (never the headline) | `python bench.py --full --ingest u8 --h2d 1 --no-cpu-baseline` |
-| `{T}_conv_reg_vs_tile.txt`, `{T}_conv_reg_ablation.txt` | conv2 / conv3 forward and data gradient on 2048 frames: LDS-resident-weights kernels (conv_tile.h) against the weights-in-registers kernels (conv_reg.h); and conv_reg with phases switched off (no DMA / no multiply loop / no epilogue) | `tools/time_conv_reg.py`, `ABLATE=1 tools/time_conv_reg.py` |
+| `{T}_conv_reg_vs_tile.txt` | conv2 / conv3 forward and data gradient on 2048 frames: LDS-resident-weights kernels (conv_tile.h) against the weights-in-registers kernels (conv_reg.h) | `tools/time_conv_reg.py` |
 | `{T}_rnn_persist_stamps.txt` | the persistent recurrence alone (`csrc/rnn_persist.h`): every step checked against a CPU recurrence, us per step at B = 64 / 128 (S = 32) and B = 32 (S = 64), shader-clock stamps of the phases of a step (poll, payload, MFMA + LDS, barrier, epilogue, drain) | `tools/bin/rnn_persist_bench_st` (tools/rnn_persist_bench.hip, -DRP_STAMPS) |
 | `{T}_step_timeline.txt` | every launch of one step with start offset, duration, gap and queue | `tools/step_timeline.py` |
 | `{T}_conv_tile_gripper_fpb.txt` | the four conv tile kernels on the gripper camera's shapes with the stacked bands the launch picks (rounds up to 6: also with 1 frame per band) | `tools/time_conv_tile_gripper.py` |

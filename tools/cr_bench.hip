@@ -1,7 +1,7 @@
 // tools only: the weights-in-registers conv2 / conv3 kernels (csrc/conv_reg.h) in their workgroup / slot-decode forms, standalone:
 // every form's output compared with the production form's (bit-identical: a pixel's dot product has one summation order in all of them) and
-// with a direct fp32 evaluation on a sample of pixels, time per launch on 2048 static-camera and gripper-camera frames, phase ablations.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/cr_bench.hip -o tools/bin/cr_bench && tools/bin/cr_bench [ablate]
+// with a direct fp32 evaluation on a sample of pixels, time per launch on 2048 static-camera and gripper-camera frames.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/cr_bench.hip -o tools/bin/cr_bench && tools/bin/cr_bench
 #include <cstdio>
 #include <cstdlib>
 #include <cstdarg>
@@ -28,15 +28,15 @@ template <typename T> static T* dev(const std::vector<T>& h) { T* d; hipMalloc(&
 
 struct Case { const char* name; int kind; int IMH, OUTH; };      // kind 0: conv3 fwd, 1: conv2 fwd, 2: conv3 dgrad, 3: conv2 dgrad
 
-template <int CK, int TA, int TB, int SI, bool REV, int OS, int NWV, int NBUF, bool ORD, int EPI = 0, int LDR = 0>
+template <int CK, int TA, int TB, int SI, bool REV, int OS, int NWV, bool ORD, int EPI = 0>
 static float run_form(ConvTileP p, int reps, bool* ok) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    *ok = launch_conv_reg<CK, TA, TB, SI, REV, OS, NWV, NBUF, ORD, EPI, LDR>(0, p);
+    *ok = launch_conv_reg<CK, TA, TB, SI, REV, OS, NWV, ORD, EPI>(0, p);
     if (!*ok) return 0.f;
-    for (int i = 0; i < 2; ++i) launch_conv_reg<CK, TA, TB, SI, REV, OS, NWV, NBUF, ORD, EPI, LDR>(0, p);
+    for (int i = 0; i < 2; ++i) launch_conv_reg<CK, TA, TB, SI, REV, OS, NWV, ORD, EPI>(0, p);
     hipDeviceSynchronize();
     hipEventRecord(e0);
-    for (int i = 0; i < reps; ++i) launch_conv_reg<CK, TA, TB, SI, REV, OS, NWV, NBUF, ORD, EPI, LDR>(0, p);
+    for (int i = 0; i < reps; ++i) launch_conv_reg<CK, TA, TB, SI, REV, OS, NWV, ORD, EPI>(0, p);
     hipEventRecord(e1); hipDeviceSynchronize();
     float ms; hipEventElapsedTime(&ms, e0, e1);
     if (hipGetLastError() != hipSuccess) { *ok = false; }
@@ -44,7 +44,7 @@ static float run_form(ConvTileP p, int reps, bool* ok) {
 }
 
 template <int CK, int TA, int TB, int SI, bool REV, int OS>
-static void bench(const char* name, int Nf, int IMH, int OUTH, bool ablate) {
+static void bench(const char* name, int Nf, int IMH, int OUTH) {
     constexpr int CN = OS == 1 ? 64 : 32, K = TA * TB * CK, NCLS = OS * OS;
     const size_t nimg = (size_t)Nf * IMH * IMH * CK, nout = (size_t)Nf * OUTH * OUTH * CN, nw = (size_t)NCLS * CN * K;
     std::vector<h16_t> himg = rnd16(nimg, 1.f, 12345u), hw = rnd16(nw, 0.05f, 777u);
@@ -65,7 +65,7 @@ static void bench(const char* name, int Nf, int IMH, int OUTH, bool ablate) {
     // reference = the production form of round 4 (8 waves, two buffers, old order; conv3 dgrad ran it too)
     hipMemset(ref, 0xEE, nout * 2);
     p.out = ref;
-    const float t_ref = run_form<CK, TA, TB, SI, REV, OS, 8, 0, false>(p, 10, &ok);
+    const float t_ref = run_form<CK, TA, TB, SI, REV, OS, 8, false>(p, 10, &ok);
     std::vector<h16_t> href(nout); hipMemcpy(href.data(), ref, nout * 2, hipMemcpyDeviceToHost);
     // direct evaluation of a sample of output pixels in double
     double worst = 0;
@@ -112,53 +112,35 @@ static void bench(const char* name, int Nf, int IMH, int OUTH, bool ablate) {
         printf("\n");
     };
     p.out = out; if (!REV && SI == 2) p.bits_out = bits_out;
-#define FORM(nwv, nbuf, ord, label) FORME(nwv, nbuf, ord, 0, label)
-#define FORML(epi, label) do { if constexpr (OS == 1) { hipMemset(out, 0xEE, nout * 2); if (!REV && SI == 2) hipMemset(bits_out, 0xEE, hbits.size() * 4); const float t = run_form<CK, TA, TB, SI, REV, OS, 8, 0, true, epi, 2>(p, 10, &ok); if (ok) cmp(label, t); else printf("    %-44s not launchable\n", label); } } while (0)
-#define FORME(nwv, nbuf, ord, epi, label) do { hipMemset(out, 0xEE, nout * 2); if (!REV && SI == 2) hipMemset(bits_out, 0xEE, hbits.size() * 4); const float t = run_form<CK, TA, TB, SI, REV, OS, nwv, nbuf, ord, epi>(p, 10, &ok); if (ok) cmp(label, t); else printf("    %-44s not launchable\n", label); } while (0)
-    FORM(8, 0, true, "8 waves, 2 buffers, slot decode in registers");
-    FORM(4, 0, false, "2 x 4 waves, 1 buffer each");
-    FORM(4, 0, true, "2 x 4 waves, 1 buffer, slot decode in registers");
-    FORME(8, 0, false, 1, "8 waves, pipelined epilogue (1 accumulator)");
-    FORME(8, 0, true, 1, "8 waves, pipelined epilogue (1) + slot registers");
-    FORME(4, 0, false, 1, "2 x 4 waves, pipelined epilogue (1)");
-    FORME(4, 0, true, 1, "2 x 4 waves, pipelined epilogue (1) + slot registers");
-    FORML(0, "6 compute + 2 LOADER waves");
-    if constexpr (REV) FORML(1, "6 compute + 2 LOADER waves, pipelined epilogue");
+#define FORM(nwv, ord, label) FORME(nwv, ord, 0, label)
+#define FORME(nwv, ord, epi, label) do { hipMemset(out, 0xEE, nout * 2); if (!REV && SI == 2) hipMemset(bits_out, 0xEE, hbits.size() * 4); const float t = run_form<CK, TA, TB, SI, REV, OS, nwv, ord, epi>(p, 10, &ok); if (ok) cmp(label, t); else printf("    %-44s not launchable\n", label); } while (0)
+    FORM(8, true, "8 waves, 2 buffers, slot decode in registers");
+    FORM(4, false, "2 x 4 waves, 1 buffer each");
+    FORM(4, true, "2 x 4 waves, 1 buffer, slot decode in registers");
+    FORME(8, false, 1, "8 waves, pipelined epilogue (1 accumulator)");
+    FORME(8, true, 1, "8 waves, pipelined epilogue (1) + slot registers");
+    FORME(4, false, 1, "2 x 4 waves, pipelined epilogue (1)");
+    FORME(4, true, 1, "2 x 4 waves, pipelined epilogue (1) + slot registers");
     // workgroups per CU: the band geometry sized for 3 / 4 co-resident 4-wave workgroups (53 / 40 KB of LDS each) and for 2 co-resident 8-wave ones
     for (int wg : {3, 4}) {
         g_conv_reg_wgpc = wg;
         char lb[96]; snprintf(lb, sizeof(lb), "%d x 4 waves per CU, slot registers%s", wg, REV ? ", pipelined epilogue" : "");
-        if constexpr (REV) FORME(4, 0, true, 1, lb); else FORM(4, 0, true, lb);
+        if constexpr (REV) FORME(4, true, 1, lb); else FORM(4, true, lb);
     }
     g_conv_reg_wgpc = 2;
-    FORM(8, 0, true, "2 x 8 waves per CU (2 buffers each), slot registers");
+    FORM(8, true, "2 x 8 waves per CU (2 buffers each), slot registers");
     g_conv_reg_wgpc = 0;
-    if (ablate) {
-        const int flags[] = {0, 4, 8, 16, 12, 20, 24, 2};
-        const char* fn[] = {"full", "no-dma", "no-epilogue", "no-mfma", "mfma-only", "epilogue-only", "dma-only", "no-compute"};
-        for (int v = 0; v < 3; ++v) {
-            printf("    ablation %s:", v == 0 ? "8w + registers" : (v == 1 ? "2x4w" : "8w (r4)"));
-            for (int k = 0; k < 8; ++k) {
-                p.dbg = flags[k];
-                float t = v == 0 ? run_form<CK, TA, TB, SI, REV, OS, 8, 0, true>(p, 10, &ok) : (v == 1 ? run_form<CK, TA, TB, SI, REV, OS, 4, 0, false>(p, 10, &ok) : run_form<CK, TA, TB, SI, REV, OS, 8, 0, false>(p, 10, &ok));
-                printf("  %s %.1f", fn[k], t);
-            }
-            printf("\n");
-            p.dbg = 0;
-        }
-    }
     hipFree(img); hipFree(w); hipFree(out); hipFree(ref); hipFree(bias); hipFree(bits); hipFree(bits_out); hipFree(bits_ref); hipFree(zp);
 }
 
-int main(int argc, char** argv) {
-    const bool ablate = argc > 1 && !strcmp(argv[1], "ablate");
+int main() {
     for (int cam = 0; cam < 2; ++cam) {
         const int H1 = cam ? 20 : 49, H2 = cam ? 9 : 23, H3 = cam ? 7 : 21, Nf = cam ? 2051 : 2048;
         printf("==== %s camera ====\n", cam ? "gripper" : "static");
-        bench<64, 3, 3, 1, false, 1>("conv3 fwd", Nf, H2, H3, ablate && !cam);
-        bench<32, 4, 4, 2, false, 1>("conv2 fwd (+bits)", Nf, H1, H2, ablate && !cam);
-        bench<64, 3, 3, 1, true, 1>("conv3 dgrad (bits)", Nf, H3, H2, ablate && !cam);
-        bench<64, 2, 2, 1, true, 2>("conv2 dgrad (bits)", Nf, H2, H1, ablate && !cam);
+        bench<64, 3, 3, 1, false, 1>("conv3 fwd", Nf, H2, H3);
+        bench<32, 4, 4, 2, false, 1>("conv2 fwd (+bits)", Nf, H1, H2);
+        bench<64, 3, 3, 1, true, 1>("conv3 dgrad (bits)", Nf, H3, H2);
+        bench<64, 2, 2, 1, true, 2>("conv2 dgrad (bits)", Nf, H2, H1);
     }
     return 0;
 }

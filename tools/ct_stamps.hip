@@ -26,7 +26,7 @@ static void fill_random(h16_t* d, size_t n, float scale) {
 }
 
 template <int CK, int CN, int TA, int TB, int SI, int OS, bool REV>
-static void run(const char* name, int Nf, int IMH, int OUTH, int wrows, int wcols, bool mask, int dbg = 0) {
+static void run(const char* name, int Nf, int IMH, int OUTH, int wrows, int wcols, bool mask) {
     h16_t *img, *w, *out; float* bias; unsigned* bits;
     const size_t nimg = (size_t)Nf * IMH * IMH * CK, nout = (size_t)Nf * OUTH * OUTH * CN;
     hipMalloc(&img, nimg * 2 + 256); hipMalloc(&w, (size_t)wrows * wcols * 2 + 256); hipMalloc(&out, nout * 2 + 256); hipMalloc(&bias, 256 * 4);
@@ -34,7 +34,6 @@ static void run(const char* name, int Nf, int IMH, int OUTH, int wrows, int wcol
     fill_random(img, nimg, 1.f); fill_random(w, (size_t)wrows * wcols, 0.1f);
     hipMemset(bias, 0, 256 * 4); hipMemset(bits, 0x5a, (size_t)Nf * OUTH * OUTH * 2 * 4);
     ConvTileP p{}; p.img = img; p.IMH = p.IMW = IMH; p.w = w; p.out = out; p.OUTH = p.OUTW = OUTH; p.bias = REV ? nullptr : bias; p.relu = REV ? 0 : 1; p.Nf = Nf;
-    p.dbg = dbg;
     if (mask) p.maskbits = bits;
     if (!REV && CN == 64 && SI == 2) p.bits_out = bits;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
@@ -82,10 +81,5 @@ int main() {
     run<64, 64, 3, 3, 1, 1, true>("dgrad3 (21x21x64 -> 23x23x64)", Nf, 21, 23, 64, 576, true);
     run<64, 32, 2, 2, 1, 2, true>("dgrad2 (23x23x64 -> 49x49x32)", Nf, 23, 49, 128, 256, true);
     run<64, 64, 3, 3, 1, 1, false>("fwd3 gripper (9x9 -> 7x7)", Nf, 9, 7, 64, 576, false);
-    printf("---- the same without the phase skew between wave halves (dbg bit 6)\n");
-    run<64, 64, 3, 3, 1, 1, false>("fwd3  no-skew", Nf, 23, 21, 64, 576, false, 64);
-    run<32, 64, 4, 4, 2, 1, false>("fwd2  no-skew", Nf, 49, 23, 64, 512, false, 64);
-    run<64, 64, 3, 3, 1, 1, true>("dgrad3 no-skew", Nf, 21, 23, 64, 576, true, 64);
-    run<64, 32, 2, 2, 1, 2, true>("dgrad2 no-skew", Nf, 23, 49, 128, 256, true, 64);
     return 0;
 }

@@ -43,8 +43,7 @@ b u8_store --ingest u8 --store 16384          # windows gathered by index from a
 MASTER_PORT=29878 b rehearsal_mcil --force-comm 1 --model mcil --lang 1                               # config 4 on the N > 1 code path: buckets held behind the persistent BiRNN backward
 MASTER_PORT=29879 b rehearsal_mcil_early --force-comm 1 --model mcil --lang 1 --opt dp_hold_buckets=0    # ... round 5's schedule: early buckets, BiRNN backward one launch per step
 python tools/time_conv_reg.py > $O/conv_reg_vs_tile.txt 2>/dev/null
-ABLATE=1 python tools/time_conv_reg.py 2>/dev/null | tail -12 > $O/conv_reg_ablation.txt
-test -x tools/bin/cr_bench && timeout 400 tools/bin/cr_bench ablate > $O/cr_bench.txt 2>&1          # conv_reg.h forms: slot decode in registers, pipelined epilogue, loader waves (round 5)
+test -x tools/bin/cr_bench && timeout 400 tools/bin/cr_bench > $O/cr_bench.txt 2>&1                 # conv_reg.h forms: slot decode in registers, pipelined epilogue (round 5)
 test -x tools/bin/cr_stamps && timeout 200 tools/bin/cr_stamps > $O/cr_stamps.txt 2>&1              # ... phase stamps of a band
 test -x tools/bin/vmcnt_probe && timeout 200 tools/bin/vmcnt_probe > $O/vmcnt_probe.txt 2>&1        # LDS-DMA then store, counted vmcnt: in-order retirement probe
 test -x tools/bin/storebench && timeout 120 tools/bin/storebench > $O/storebench.txt 2>&1

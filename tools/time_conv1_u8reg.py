@@ -1,13 +1,13 @@
 """conv1 forward from uint8 frames: the LDS-DMA kernel (raw rows -> LDS -> conversion pass; conv1_fwd_u8dma_kernel) against the register-staged kernel with the conversion
-from 16-byte windows (conv1_stage_band regconv, dbg bit 8), alternating in one process; outputs compared bit for bit.   python tools/time_conv1_u8reg.py"""
+from 16-byte windows (conv1_stage_band regconv, relu bit 256), alternating in one process; outputs compared bit for bit.   python tools/time_conv1_u8reg.py"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hulc_amd import lib as L
 lib = L.load()
 Nf = 2048
-def run(img, w, bias, out, IMH, OUTH, dbg, mode, shifts, n=10):
-    args = (mode, img.data_ptr(), w.data_ptr(), bias.data_ptr(), shifts.data_ptr() if shifts is not None else None, out.data_ptr(), Nf, IMH, OUTH, dbg, None)
+def run(img, w, bias, out, IMH, OUTH, relu, mode, shifts, n=10):
+    args = (mode, img.data_ptr(), w.data_ptr(), bias.data_ptr(), shifts.data_ptr() if shifts is not None else None, out.data_ptr(), Nf, IMH, OUTH, relu, None)
     for _ in range(3): L.check(lib.hulc_k_conv_tile(*args))
     torch.cuda.synchronize(); e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True); e0.record()
     for _ in range(n): lib.hulc_k_conv_tile(*args)

@@ -6,8 +6,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hulc_amd import lib as L
 lib = L.load()
 Nf = 2048
-def run(mode, img, w, bias, mask, out, IMH, OUTH, dbg):
-    args = (mode, img.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, mask.data_ptr() if mask is not None else None, out.data_ptr(), Nf, IMH, OUTH, dbg, None)
+def run(mode, img, w, bias, mask, out, IMH, OUTH, relu):
+    args = (mode, img.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, mask.data_ptr() if mask is not None else None, out.data_ptr(), Nf, IMH, OUTH, relu, None)
     for _ in range(3): L.check(lib.hulc_k_conv_tile(*args))
     torch.cuda.synchronize(); e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True); e0.record()
     for _ in range(10): lib.hulc_k_conv_tile(*args)
@@ -21,8 +21,8 @@ cases = [(f"fwd3 {H2}->{H3}", 0, (Nf, H2, H2, 64), (64, 576), b64, None, (Nf, H3
          (f"dgrad3 {H3}->{H2} (bits)", 8, (Nf, H3, H3, 64), (64, 576), None, i32(Nf, H2, H2, 2), (Nf, H2, H2, 64), H3, H2, 32),
          (f"dgrad2 {H2}->{H1} (bits)", 9, (Nf, H2, H2, 64), (128, 256), None, i32(Nf, H1, H1, 1), (Nf, H1, H1, 32), H2, H1, 32)]
 res = []
-for name, mode, ishape, wshape, bias, mask, oshape, IMH, OUTH, dbg in cases:
+for name, mode, ishape, wshape, bias, mask, oshape, IMH, OUTH, relu in cases:
     img = torch.randn(*ishape, device="cuda").to(torch.bfloat16); w = (torch.randn(*wshape, device="cuda") * 0.05).to(torch.bfloat16)
     out = torch.zeros(*oshape, device="cuda", dtype=torch.bfloat16)
-    res.append(f"{name}: {run(mode, img, w, bias, mask, out, IMH, OUTH, dbg):.1f} us")
+    res.append(f"{name}: {run(mode, img, w, bias, mask, out, IMH, OUTH, relu):.1f} us")
 print("   ".join(res))
