@@ -349,6 +349,49 @@ int hulc_k_logistic_loss(int32_t dtype, int32_t wide, const float* heads, int32_
     return hulc_bf16::k_logistic_loss(dtype == HULC_DTYPE_BF16, wide, heads, ldh, actions, robot_obs, B, S, n_mix, n_dim, num_classes, log_scale_min, gripper_alpha,
                                       gripper_control, discrete_gripper, grad_scale, lscale, row_loss, a_tcp_out, dheads, stream);
 }
+// the latent-plan kernels and the LayerNorm family (k_entries.h): fp32 and bf16 instances in this unit, fp16 in the other; the first argument of the entry is
+// "16-bit type of the unit" (1) or float (0)
+#define HULC_K_ANY(name, fn, ...)                                                                                                     \
+    if (dtype == HULC_DTYPE_F16) return hulc_f16::fn(1, __VA_ARGS__);                                                                  \
+    if (dtype != HULC_DTYPE_F32 && dtype != HULC_DTYPE_BF16) { hulc_set_error(name ": unknown dtype %d", (int)dtype); return 1; }      \
+    return hulc_bf16::fn(dtype == HULC_DTYPE_BF16 ? 1 : 0, __VA_ARGS__)
+int hulc_k_plan_kl_sample(const float* pr_logits, const float* pp_logits, int32_t B, int32_t NCAT, int32_t NCLS, const int32_t* idx_in, int32_t* idx_out, float* probs,
+                          float* kl_cat, float* dpp, float* dpr, float w_pp, float w_pr, uint64_t seed, const float* lscale, void* stream) {
+    return hulc_bf16::k_plan_kl_sample(pr_logits, pp_logits, B, NCAT, NCLS, idx_in, idx_out, probs, kl_cat, dpp, dpr, w_pp, w_pr, (unsigned long long)seed, lscale, stream);
+}
+int hulc_k_st_softmax_bwd(int32_t dtype, const float* probs, const float* dplan, const float* dpr_kl, const float* dpp_kl, int32_t rows, int32_t NCLS, float* out, void* out_t,
+                          void* dpp_t, void* stream) {
+    HULC_K_ANY("hulc_k_st_softmax_bwd", k_st_softmax_bwd, probs, dplan, dpr_kl, dpp_kl, rows, NCLS, out, out_t, dpp_t, stream);
+}
+int hulc_k_plan_gather(int32_t dtype, const void* w_t, const int32_t* idx, int32_t B, int32_t NCAT, int32_t NCLS, int32_t H, const float* b1, const float* b2, float* out,
+                       const void* emb, void* embg, int32_t S, int32_t W, const void* goal, int32_t G, int32_t grow0, void* cb, void* stream) {
+    HULC_K_ANY("hulc_k_plan_gather", k_plan_gather, w_t, idx, B, NCAT, NCLS, H, b1, b2, out, emb, embg, S, W, goal, G, grow0, cb, stream);
+}
+int hulc_k_plan_scatter_grad(int32_t dtype, int32_t form, const void* dC, const int32_t* idx, int32_t B, int32_t NCAT, int32_t NCLS, int32_t H, int32_t KIN, float* dw,
+                             int32_t store, void* stream) {
+    HULC_K_ANY("hulc_k_plan_scatter_grad", k_plan_scatter_grad, form, dC, idx, B, NCAT, NCLS, H, KIN, dw, store, stream);
+}
+int hulc_k_normal_kl_sample(int32_t dtype, const float* pr_state, const float* pp_state, int32_t B, int32_t n, const float* eps_in, float* eps_out, float* plan_f, void* plan_t,
+                            float* kl_elem, float* dpp, float* dpr, float w_pp, float w_pr, uint64_t seed, const float* lscale, void* stream) {
+    HULC_K_ANY("hulc_k_normal_kl_sample", k_normal_kl_sample, pr_state, pp_state, B, n, eps_in, eps_out, plan_f, plan_t, kl_elem, dpp, dpr, w_pp, w_pr, (unsigned long long)seed, lscale, stream);
+}
+int hulc_k_normal_rsample_bwd(int32_t dtype, const float* dplan, const float* eps, const float* pr_state, const float* dpr_kl, int32_t B, int32_t n, void* out, void* stream) {
+    HULC_K_ANY("hulc_k_normal_rsample_bwd", k_normal_rsample_bwd, dplan, eps, pr_state, dpr_kl, B, n, out, stream);
+}
+int hulc_k_layernorm_fwd(int32_t dtype, const float* x, int64_t ldx, int32_t rows, int32_t n, const float* g, const float* b, void* out, int64_t ldo, float* out_f32, int64_t ldf,
+                         float* stats, void* stream) {
+    HULC_K_ANY("hulc_k_layernorm_fwd", k_layernorm_fwd, x, (long long)ldx, rows, n, g, b, out, (long long)ldo, out_f32, (long long)ldf, stats, stream);
+}
+int hulc_k_layernorm_bwd(int32_t dtype, const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* stats, const float* g, int32_t rows, int32_t n, float* dx_f32,
+                         int64_t ldd, int32_t accumulate, void* dx_t, int64_t ldt, float* dg, float* db, float drop_p, uint64_t seed, int32_t bcast_rows, float bcast_div,
+                         int32_t dy_parts, int64_t dy_part_stride, float* scratch, void* stream) {
+    HULC_K_ANY("hulc_k_layernorm_bwd", k_layernorm_bwd, dy, (long long)lddy, x, (long long)ldx, stats, g, rows, n, dx_f32, (long long)ldd, accumulate, dx_t, (long long)ldt, dg, db,
+               drop_p, (unsigned long long)seed, bcast_rows, bcast_div, dy_parts, (long long)dy_part_stride, scratch, stream);
+}
+int hulc_k_layernorm_mean(int32_t dtype, const float* x, int32_t B, int32_t S, int32_t n, const float* g, const float* b, float* stats, void* out, float* yout, void* stream) {
+    HULC_K_ANY("hulc_k_layernorm_mean", k_layernorm_mean, x, B, S, n, g, b, stats, out, yout, stream);
+}
+#undef HULC_K_ANY
 int hulc_k_cast(int32_t dtype, const float* src, void* dst, int64_t n, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (dtype == HULC_DTYPE_F32) hipLaunchKernelGGL((cast_kernel<float, float>), dim3(1024), dim3(256), 0, st, src, (float*)dst, (long long)n);

@@ -11,6 +11,7 @@
 #include "iengine.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "plan_ln_launch.h"
 #include "conv_wgrad.h"
 #include "conv_tile.h"
 #include "conv_reg.h"
@@ -23,7 +24,6 @@
 
 namespace HULC_NS {
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 #define HIP_CHECK_VOID(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { hulc_set_error("%s:%d %s", __FILE__, __LINE__, hipGetErrorString(e_)); } } while (0)
 
 template <typename T>
@@ -736,30 +736,17 @@ struct Engine : IEngine {
     void lin_dgrad(const T* dY, int M, const LinW& L, EpiP ep, const DenseOut& om) {
         gemm(dense<T>(dY, M, L.N), dense<T>(L.Wt, L.K, L.N), om, ep, M, L.K, L.N);
     }
+    // the LayerNorm launches and their decisions live in plan_ln_launch.h (shared with the test entries of k_entries.h)
     void ln_fwd(const float* x, long long ldx, int rows, int n, const float* g, const float* b, T* out, long long ldo, float* outf, long long ldf,
                 float* stats) {
-        hipLaunchKernelGGL((layernorm_fwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), 0, st, x, ldx, rows, n, g, b, out, ldo, outf, ldf, stats);
+        launch_ln_fwd<T>(st, x, ldx, rows, n, g, b, out, ldo, outf, ldf, stats);
     }
     // bcast_rows > 0 (fused kernel only, see ln_bwd_can_bcast): dy holds one row per WINDOW, broadcast over its bcast_rows rows and divided by bcast_div
-    static constexpr bool ln_bwd_can_bcast = std::is_same<T, h16_t>::value;
+    static constexpr bool ln_bwd_can_bcast = ln_bwd_fused<T>();
     void ln_bwd(const float* dy, long long lddy, const float* x, long long ldx, const float* stats, const float* g, int rows, int n, float* dxf,
                 long long ldd, int acc, T* dxt, long long ldt, float* dg, float* db, float drop_p = 0.f, unsigned long long drop_seed = 0,
                 int bcast_rows = 0, float bcast_div = 1.f, int dy_parts = 1, long long dy_part_stride = 0) {
-        if constexpr (std::is_same<T, h16_t>::value) {
-            const int rpb = rows >= 1024 ? 16 : 4;
-            hipLaunchKernelGGL((layernorm_bwd_fused_kernel<T>), dim3(cdiv(rows, rpb)), dim3(rpb == 16 ? 1024 : 256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt,
-                               drop_p, drop_seed, rpb, dg, db, bcast_rows, bcast_div, dy_parts, dy_part_stride);
-        } else {        // fp32 (parity) mode: unfused and deterministic
-            if ((drop_p > 0.f || drop_seed != 0) && dxt && dxf) {       // dx first, its copy through the dropout mask in a second launch
-                hipLaunchKernelGGL((layernorm_bwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, (T*)nullptr, 0);
-                hipLaunchKernelGGL((dropout_apply_kernel<T>), dim3(cdiv((long long)rows * n, 256)), dim3(256), 0, st, dxf, (float*)nullptr, dxt, (long long)rows * n, drop_p, drop_seed);
-            } else
-                hipLaunchKernelGGL((layernorm_bwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt);
-            const int nsplit = std::max(1, std::min(64, cdiv(rows, 64)));
-            hipLaunchKernelGGL(layernorm_param_grad_kernel, dim3(cdiv(n, 64), nsplit), dim3(256), 0, st, dy, lddy, x, ldx, stats, rows, n, cdiv(rows, nsplit), cspart, (float*)nullptr, (float*)nullptr);
-            hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, cspart, nsplit, n, dg, (float*)nullptr, 1.f);
-            hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, cspart + (long long)nsplit * n, nsplit, n, db, (float*)nullptr, 1.f);
-        }
+        launch_ln_bwd<T>(st, cspart, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt, dg, db, drop_p, drop_seed, bcast_rows, bcast_div, dy_parts, dy_part_stride);
     }
 
     // ---------------------------------------------------------------- weight preparation

@@ -257,6 +257,16 @@
         if (!rc && out && on_host && persist_check("hulc_forward_loss_pair", true)) rc = forward_impl(&jb, lw, cw, out, on_host);
         return rc;
     }
+    // An injected categorical sample (host or device memory) is a row of the plan gather's weight and of the plan scatter's LDS tile, unchecked in both kernels:
+    // it is read back and refused on the host when any class lies outside [0, NCLS) — nothing is launched with it (the rollout paths clamp theirs on the device)
+    int plan_idx_bad(const int* src, int count, const char* who) {
+        std::vector<int> h((size_t)count);
+        HIP_CHECK(hipMemcpyAsync(h.data(), src, sizeof(int) * (size_t)count, hipMemcpyDefault, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int i = 0; i < count; ++i)
+            if (h[i] < 0 || h[i] >= NCLS) { hulc_set_error("%s: injected plan index %d (window %d, category %d) is outside [0, %d)", who, h[i], i / NCAT, i % NCAT, NCLS); return 1; }
+        return 0;
+    }
     int forward_impl(const hulc_batch* b, float lw, float cw, float* out, int on_host) {
         if (!bound) { hulc_set_error("hulc_forward_loss before hulc_bind_params"); return 1; }
         persist_check("hulc_forward_loss", false);
@@ -268,6 +278,7 @@
         if (b->actions_absolute && !(b->max_rel_pos > 0.f && b->max_rel_orn > 0.f)) { hulc_set_error("actions_absolute needs max_rel_pos > 0 and max_rel_orn > 0 (RelativeActions, transforms.py:35-37)"); return 1; }
         if (store_args_bad(b)) return 1;
         if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
+        if (cfg.kind == HULC_KIND_HULC && b->plan_idx && plan_idx_bad(b->plan_idx, b->B * NCAT, "hulc_forward_loss")) return 1;
         cur = *b; cur_lw = lw; cur_cw = cw; have_fwd = false; val_clip_n = 0;
         if (window_len_expand(*b, pair ? pairBv : b->B, 0) || (pair && window_len_expand(cur2, cur2.B, 1))) return 1;
         const int B = b->B, S = b->S, N = B * S, SB = S * B;

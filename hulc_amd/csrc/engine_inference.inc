@@ -45,6 +45,8 @@
         if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
         static const hulc_val_noise none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         if (!nz) nz = &none;
+        if (hulc && ((nz->plan_idx_pr && plan_idx_bad(nz->plan_idx_pr, b->B * NCAT, "hulc_validate (plan_idx_pr)")) ||
+                     (nz->plan_idx_pp && plan_idx_bad(nz->plan_idx_pp, b->B * NCAT, "hulc_validate (plan_idx_pp)")))) return 1;
         cur = *b; have_fwd = false; pair = false; val_clip_n = 0;
         if (window_len_expand(*b, b->B, 0)) return 1;
         const int B = b->B, S = b->S, SB = S * B;

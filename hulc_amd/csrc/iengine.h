@@ -189,6 +189,27 @@ struct IEngine {
     int k_enc_tail_bwd(int Nf, int ldemb, const hulc_enc_tail_bwd_job* a, const hulc_enc_tail_bwd_job* b, const float* demb, void* stream);     \
     int k_logistic_loss(int t16, int wide, const float* heads, int ldh, const float* actions, const float* robot_obs, int B, int S, int nmix,   \
                         int ndim, int num_classes, float log_scale_min, float gripper_alpha, int gripper_control, int discrete_gripper,         \
-                        float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* stream);
+                        float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* stream);                  \
+    int k_plan_kl_sample(const float* pr_logits, const float* pp_logits, int B, int NCAT, int NCLS, const int* idx_in, int* idx_out, float* probs,  \
+                         float* kl_cat, float* dpp, float* dpr, float w_pp, float w_pr, unsigned long long seed, const float* lscale, void* stream); \
+    int k_st_softmax_bwd(int t16, const float* probs, const float* dplan, const float* dpr_kl, const float* dpp_kl, int rows, int NCLS, float* out,  \
+                         void* out_t, void* dpp_t, void* stream);                                                                               \
+    int k_plan_gather(int t16, const void* w_t, const int* idx, int B, int NCAT, int NCLS, int H, const float* b1, const float* b2, float* out,   \
+                      const void* emb, void* embg, int S, int W, const void* goal, int G, int grow0, void* cb, void* stream);                     \
+    int k_plan_scatter_grad(int t16, int form, const void* dC, const int* idx, int B, int NCAT, int NCLS, int H, int KIN, float* dw, int store,   \
+                            void* stream);                                                                                                      \
+    int k_normal_kl_sample(int t16, const float* pr_state, const float* pp_state, int B, int n, const float* eps_in, float* eps_out, float* plan_f, \
+                           void* plan_t, float* kl_elem, float* dpp, float* dpr, float w_pp, float w_pr, unsigned long long seed,                 \
+                           const float* lscale, void* stream);                                                                                  \
+    int k_normal_rsample_bwd(int t16, const float* dplan, const float* eps, const float* pr_state, const float* dpr_kl, int B, int n, void* out,  \
+                             void* stream);                                                                                                     \
+    int k_layernorm_fwd(int t16, const float* x, long long ldx, int rows, int n, const float* g, const float* b, void* out, long long ldo,        \
+                        float* out_f32, long long ldf, float* stats, void* stream);                                                             \
+    int k_layernorm_bwd(int t16, const float* dy, long long lddy, const float* x, long long ldx, const float* stats, const float* g, int rows,    \
+                        int n, float* dx_f32, long long ldd, int accumulate, void* dx_t, long long ldt, float* dg, float* db, float drop_p,       \
+                        unsigned long long seed, int bcast_rows, float bcast_div, int dy_parts, long long dy_part_stride, float* scratch,        \
+                        void* stream);                                                                                                          \
+    int k_layernorm_mean(int t16, const float* x, int B, int S, int n, const float* g, const float* b, float* stats, void* out, float* yout,      \
+                         void* stream);
 namespace hulc_bf16 { HULC_TU_DECLS }   // capi.hip: HULC_DTYPE_F32 / HULC_DTYPE_BF16
 namespace hulc_f16 { HULC_TU_DECLS }    // engine_f16.hip: HULC_DTYPE_F16

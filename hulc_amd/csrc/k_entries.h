@@ -1,11 +1,14 @@
 // hulc_amd/csrc/k_entries.h — per-kernel test entries of the 16-bit encoder head and of the action loss (include/hulc_hip.h: hulc_k_spatial_softmax64,
-// hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss).  Included by engine.h inside each translation unit, so every entry exists once per
+// hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss), of the latent-plan kernels (hulc_k_plan_*, hulc_k_st_softmax_bwd, hulc_k_normal_*) and of
+// the LayerNorm family (hulc_k_layernorm_*; launched through plan_ln_launch.h, which the engine calls too).  Included by engine.h inside each translation unit, so every entry exists once per
 // 16-bit type (hulc_bf16 / hulc_f16; iengine.h declares them).  Nothing here restates a kernel: each entry checks its arguments, then launches through the
 // helper the engine calls (enc_tail.h) or with the grid and block of the engine's launch site (engine_encoders.inc, engine_forward.inc).
 #pragma once
 #include "iengine.h"
 #include "kernels.h"
 #include "enc_tail.h"
+#include "plan_ln_launch.h"
+#include <vector>
 
 namespace HULC_NS {
 
@@ -106,5 +109,180 @@ int k_logistic_loss(int t16, int wide, const float* heads, int ldh, const float*
 #undef HULC_K_LL
     return k_launched("hulc_k_logistic_loss");
 }
+
+// ---------------------------------------------------------------------------------------------------- latent plan + LayerNorm
+// t16 of the entries below: 0 = float, 1 = this translation unit's 16-bit type (the fp32 instances live in the bf16 unit, as for hulc_k_logistic_loss)
+#ifdef HULC_HALF_F16
+#define HULC_K_T(who, LAUNCH)                                                                                            \
+    do { if (t16) { LAUNCH(h16_t); } else { hulc_set_error(who ": the fp32 instances live in the bf16 translation unit"); return 1; } } while (0)
+#else
+#define HULC_K_T(who, LAUNCH) do { if (t16) { LAUNCH(h16_t); } else { LAUNCH(float); } } while (0)
+#endif
+static inline bool k_misaligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) != 0; }
+// plan indices address LDS rows and weight rows unchecked inside the kernels: the entry reads them back (a synchronous copy) and refuses any outside [0, NCLS)
+static int k_idx_out_of_range(const char* who, const int* idx, long long count, int NCLS, hipStream_t st) {
+    std::vector<int> h((size_t)count);
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(h.data(), idx, sizeof(int) * (size_t)count, hipMemcpyDefault) != hipSuccess) {
+        hulc_set_error("%s: the plan indices could not be read", who); return 1;
+    }
+    for (long long i = 0; i < count; ++i)
+        if (h[i] < 0 || h[i] >= NCLS) { hulc_set_error("%s: plan index %d at position %lld is outside [0, %d)", who, h[i], i, NCLS); return 1; }
+    return 0;
+}
+
+int k_plan_kl_sample(const float* pr_logits, const float* pp_logits, int B, int NCAT, int NCLS, const int* idx_in, int* idx_out, float* probs, float* kl_cat, float* dpp,
+                     float* dpr, float w_pp, float w_pr, unsigned long long seed, const float* lscale, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 1 || NCAT < 1 || NCLS < 1 || NCLS > 64 || (long long)B * NCAT * NCLS > (1ll << 30)) { hulc_set_error("hulc_k_plan_kl_sample: B=%d NCAT=%d NCLS=%d (need B, NCAT >= 1 and 1 <= NCLS <= 64)", B, NCAT, NCLS); return 1; }
+    if (!pr_logits || !idx_out || !probs || (pp_logits && (!kl_cat || !dpp || !dpr))) { hulc_set_error("hulc_k_plan_kl_sample: null argument"); return 1; }
+    if (k_misaligned(pr_logits, 4) || k_misaligned(pp_logits, 4) || k_misaligned(idx_in, 4) || k_misaligned(idx_out, 4) || k_misaligned(probs, 4) || k_misaligned(kl_cat, 4) ||
+        k_misaligned(dpp, 4) || k_misaligned(dpr, 4) || k_misaligned(lscale, 4)) { hulc_set_error("hulc_k_plan_kl_sample: every pointer must be 4-byte aligned"); return 1; }
+    if (idx_in && k_idx_out_of_range("hulc_k_plan_kl_sample", idx_in, (long long)B * NCAT, NCLS, st)) return 1;
+    hipLaunchKernelGGL(plan_kl_sample_kernel, dim3(B * NCAT), dim3(64), 0, st, pr_logits, pp_logits, B, NCAT, NCLS, idx_in, idx_out, probs, kl_cat, dpp, dpr, w_pp, w_pr, seed, lscale);
+    return k_launched("hulc_k_plan_kl_sample");
+}
+
+int k_st_softmax_bwd(int t16, const float* probs, const float* dplan, const float* dpr_kl, const float* dpp_kl, int rows, int NCLS, float* out, void* out_t, void* dpp_t,
+                     void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (rows < 1 || NCLS < 1 || NCLS > 64 || (long long)rows * NCLS > (1ll << 30)) { hulc_set_error("hulc_k_st_softmax_bwd: rows=%d NCLS=%d (need rows >= 1 and 1 <= NCLS <= 64)", rows, NCLS); return 1; }
+    if (!probs || !dplan || !dpr_kl || !dpp_kl || !out || !out_t || !dpp_t) { hulc_set_error("hulc_k_st_softmax_bwd: null argument"); return 1; }
+    const int ta = t16 ? 2 : 4;
+    if (k_misaligned(probs, 4) || k_misaligned(dplan, 4) || k_misaligned(dpr_kl, 4) || k_misaligned(dpp_kl, 4) || k_misaligned(out, 4) || k_misaligned(out_t, ta) || k_misaligned(dpp_t, ta)) {
+        hulc_set_error("hulc_k_st_softmax_bwd: a pointer is not aligned to its element type"); return 1;
+    }
+#define HULC_K_L(TT) hipLaunchKernelGGL((st_softmax_bwd_kernel<TT>), dim3(rows), dim3(64), 0, st, probs, dplan, dpr_kl, NCLS, out, (TT*)out_t, dpp_kl, (TT*)dpp_t)
+    HULC_K_T("hulc_k_st_softmax_bwd", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_st_softmax_bwd");
+}
+
+// embg == null: no trailing blocks (the engine's grid always carries them; without the copy they have nothing to do).  The rows grow0 .. grow0 + G - 1 of w_t
+// and its plan rows 0 .. NCAT * NCLS - 1 are the caller's to provide.
+int k_plan_gather(int t16, const void* w_t, const int* idx, int B, int NCAT, int NCLS, int H, const float* b1, const float* b2, float* out, const void* emb, void* embg, int S,
+                  int W, const void* goal, int G, int grow0, void* cb, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 1 || H < 256 || (H % 256) != 0 || NCAT < 0 || NCAT > 64 || NCLS < 1 || (long long)B * H > (1ll << 30)) {
+        hulc_set_error("hulc_k_plan_gather: B=%d H=%d NCAT=%d NCLS=%d (need B >= 1, H a multiple of 256, 0 <= NCAT <= 64, NCLS >= 1)", B, H, NCAT, NCLS); return 1;
+    }
+    if (!w_t || !b1 || !b2 || !out || (NCAT > 0 && !idx) || (!emb != !embg) || (cb && !goal)) { hulc_set_error("hulc_k_plan_gather: null argument (emb and embg go together, cb needs goal)"); return 1; }
+    if (embg && (S < 1 || W < 1 || W > 128 || (long long)S * B * W > (1ll << 30))) { hulc_set_error("hulc_k_plan_gather: embg given: S=%d W=%d (need S >= 1, 1 <= W <= 128)", S, W); return 1; }
+    if (cb && (G < 1 || grow0 < NCAT * NCLS)) { hulc_set_error("hulc_k_plan_gather: cb given: G=%d grow0=%d (need G >= 1 and grow0 past the %d plan rows)", G, grow0, NCAT * NCLS); return 1; }
+    const int ta = t16 ? 2 : 4;
+    if (k_misaligned(w_t, ta) || k_misaligned(idx, 4) || k_misaligned(b1, 4) || k_misaligned(b2, 4) || k_misaligned(out, 4) || k_misaligned(emb, ta) || k_misaligned(embg, ta) ||
+        k_misaligned(goal, ta) || k_misaligned(cb, ta)) { hulc_set_error("hulc_k_plan_gather: a pointer is not aligned to its element type"); return 1; }
+    if (NCAT > 0 && k_idx_out_of_range("hulc_k_plan_gather", idx, (long long)B * NCAT, NCLS, st)) return 1;
+    const int SBW = embg ? S * B * W : 0;
+    if (!embg) { S = 0; W = 0; }
+#define HULC_K_L(TT)                                                                                                                                             \
+    hipLaunchKernelGGL((plan_gather_t_kernel<TT>), dim3(cdiv((long long)B * H, 256) + cdiv(SBW, 256)), dim3(256), 0, st, (const TT*)w_t, idx, B, NCAT, NCLS, H, b1, b2, out, \
+                       (const TT*)emb, (TT*)embg, S, W, (const TT*)goal, G, grow0, (TT*)cb)
+    HULC_K_T("hulc_k_plan_gather", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_plan_gather");
+}
+
+// form 0 = plan_scatter_grad_lds_kernel, 1 = plan_scatter_grad_w4_kernel (16-bit types only: plan_scatter_w4, the engine's own choice)
+int k_plan_scatter_grad(int t16, int form, const void* dC, const int* idx, int B, int NCAT, int NCLS, int H, int KIN, float* dw, int store, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 1 || NCAT < 1 || NCAT > 64 || NCLS < 1 || NCLS > 32 || H < 1 || KIN < NCAT * NCLS || (long long)B * H > (1ll << 30) || (long long)H * KIN > (1ll << 30)) {
+        hulc_set_error("hulc_k_plan_scatter_grad: B=%d NCAT=%d NCLS=%d H=%d KIN=%d (need 1 <= NCAT <= 64, 1 <= NCLS <= 32: the LDS tile has 32 rows, KIN >= NCAT * NCLS)", B, NCAT, NCLS, H, KIN); return 1;
+    }
+    if (form != 0 && form != 1) { hulc_set_error("hulc_k_plan_scatter_grad: form must be 0 (lds) or 1 (w4), got %d", form); return 1; }
+    if (store && form != 1) { hulc_set_error("hulc_k_plan_scatter_grad: store goes with form 1 (w4) only"); return 1; }
+    if (store != 0 && store != 1) { hulc_set_error("hulc_k_plan_scatter_grad: store must be 0 or 1"); return 1; }
+    if (!dC || !idx || !dw) { hulc_set_error("hulc_k_plan_scatter_grad: null argument"); return 1; }
+    if (k_misaligned(dC, t16 ? 2 : 4) || k_misaligned(idx, 4) || k_misaligned(dw, 4)) { hulc_set_error("hulc_k_plan_scatter_grad: a pointer is not aligned to its element type"); return 1; }
+    if (form == 1 && !(t16 ? plan_scatter_w4<h16_t>(NCLS) : plan_scatter_w4<float>(NCLS))) { hulc_set_error("hulc_k_plan_scatter_grad: form 1 (w4) serves the 16-bit types only"); return 1; }
+    if (k_idx_out_of_range("hulc_k_plan_scatter_grad", idx, (long long)B * NCAT, NCLS, st)) return 1;
+#define HULC_K_L(TT) launch_plan_scatter_grad<TT>(st, form == 1, (const TT*)dC, idx, B, NCAT, NCLS, H, KIN, dw, store)
+    HULC_K_T("hulc_k_plan_scatter_grad", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_plan_scatter_grad");
+}
+
+int k_normal_kl_sample(int t16, const float* pr_state, const float* pp_state, int B, int n, const float* eps_in, float* eps_out, float* plan_f, void* plan_t, float* kl_elem,
+                       float* dpp, float* dpr, float w_pp, float w_pr, unsigned long long seed, const float* lscale, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 1 || n < 1 || (long long)B * n > (1ll << 29)) { hulc_set_error("hulc_k_normal_kl_sample: B=%d n=%d", B, n); return 1; }
+    if (!pr_state || !eps_out || !plan_f || !plan_t || (pp_state && (!kl_elem || !dpp || !dpr))) { hulc_set_error("hulc_k_normal_kl_sample: null argument"); return 1; }
+    if (k_misaligned(pr_state, 4) || k_misaligned(pp_state, 4) || k_misaligned(eps_in, 4) || k_misaligned(eps_out, 4) || k_misaligned(plan_f, 4) || k_misaligned(plan_t, t16 ? 2 : 4) ||
+        k_misaligned(kl_elem, 4) || k_misaligned(dpp, 4) || k_misaligned(dpr, 4) || k_misaligned(lscale, 4)) { hulc_set_error("hulc_k_normal_kl_sample: a pointer is not aligned to its element type"); return 1; }
+#define HULC_K_L(TT)                                                                                                                                               \
+    hipLaunchKernelGGL((normal_kl_sample_kernel<TT>), dim3(cdiv((long long)B * n, 256)), dim3(256), 0, st, pr_state, pp_state, B, n, eps_in, eps_out, plan_f, (TT*)plan_t, kl_elem, \
+                       dpp, dpr, w_pp, w_pr, seed, lscale)
+    HULC_K_T("hulc_k_normal_kl_sample", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_normal_kl_sample");
+}
+
+int k_normal_rsample_bwd(int t16, const float* dplan, const float* eps, const float* pr_state, const float* dpr_kl, int B, int n, void* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 1 || n < 1 || (long long)B * n > (1ll << 29)) { hulc_set_error("hulc_k_normal_rsample_bwd: B=%d n=%d", B, n); return 1; }
+    if (!dplan || !eps || !pr_state || !dpr_kl || !out) { hulc_set_error("hulc_k_normal_rsample_bwd: null argument"); return 1; }
+    if (k_misaligned(dplan, 4) || k_misaligned(eps, 4) || k_misaligned(pr_state, 4) || k_misaligned(dpr_kl, 4) || k_misaligned(out, t16 ? 2 : 4)) {
+        hulc_set_error("hulc_k_normal_rsample_bwd: a pointer is not aligned to its element type"); return 1;
+    }
+#define HULC_K_L(TT) hipLaunchKernelGGL((normal_rsample_bwd_kernel<TT>), dim3(cdiv((long long)B * n, 256)), dim3(256), 0, st, dplan, eps, pr_state, dpr_kl, B, n, (TT*)out)
+    HULC_K_T("hulc_k_normal_rsample_bwd", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_normal_rsample_bwd");
+}
+
+int k_layernorm_fwd(int t16, const float* x, long long ldx, int rows, int n, const float* g, const float* b, void* out, long long ldo, float* out_f32, long long ldf, float* stats,
+                    void* stream) {
+    if (rows < 1 || n < 1 || n > 128 || ldx < n || (out && ldo < n) || (out_f32 && ldf < n) || rows > (1 << 24)) {
+        hulc_set_error("hulc_k_layernorm_fwd: rows=%d n=%d ldx=%lld ldo=%lld ldf=%lld (need 1 <= n <= 128 and leading dimensions >= n)", rows, n, ldx, ldo, ldf); return 1;
+    }
+    if (!x || !g || !b) { hulc_set_error("hulc_k_layernorm_fwd: null argument"); return 1; }
+    if (k_misaligned(x, 4) || k_misaligned(g, 4) || k_misaligned(b, 4) || k_misaligned(out, t16 ? 2 : 4) || k_misaligned(out_f32, 4) || k_misaligned(stats, 4)) {
+        hulc_set_error("hulc_k_layernorm_fwd: a pointer is not aligned to its element type"); return 1;
+    }
+#define HULC_K_L(TT) launch_ln_fwd<TT>((hipStream_t)stream, x, ldx, rows, n, g, b, (TT*)out, ldo, out_f32, ldf, stats)
+    HULC_K_T("hulc_k_layernorm_fwd", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_layernorm_fwd");
+}
+
+// scratch: ln_bwd_scratch_floats(rows, n) floats for the fp32 pair (at most 2 * 64 * n), unused by the fused kernel
+int k_layernorm_bwd(int t16, const float* dy, long long lddy, const float* x, long long ldx, const float* stats, const float* g, int rows, int n, float* dx_f32, long long ldd,
+                    int accumulate, void* dx_t, long long ldt, float* dg, float* db, float drop_p, unsigned long long seed, int bcast_rows, float bcast_div, int dy_parts,
+                    long long dy_part_stride, float* scratch, void* stream) {
+    if (rows < 1 || n < 1 || n > 128 || lddy < n || ldx < n || (dx_f32 && ldd < n) || (dx_t && ldt < n) || rows > (1 << 24)) {
+        hulc_set_error("hulc_k_layernorm_bwd: rows=%d n=%d lddy=%lld ldx=%lld ldd=%lld ldt=%lld (need 1 <= n <= 128 and leading dimensions >= n)", rows, n, lddy, ldx, ldd, ldt); return 1;
+    }
+    if (!dy || !x || !stats || !g || !dg || !db || (!dx_f32 && !dx_t)) { hulc_set_error("hulc_k_layernorm_bwd: null argument (dg, db and one of dx_f32, dx_t are required)"); return 1; }
+    if (!(drop_p >= 0.f && drop_p < 1.f) || bcast_rows < 0 || dy_parts < 1 || dy_parts > 4 || (dy_parts > 1 && dy_part_stride < (long long)(rows - 1) * lddy + n) ||
+        (bcast_rows > 0 && (!(bcast_div > 0.f) || rows % bcast_rows != 0))) {
+        hulc_set_error("hulc_k_layernorm_bwd: drop_p=%g bcast_rows=%d bcast_div=%g dy_parts=%d dy_part_stride=%lld", (double)drop_p, bcast_rows, (double)bcast_div, dy_parts, dy_part_stride); return 1;
+    }
+    if (accumulate && !dx_f32) { hulc_set_error("hulc_k_layernorm_bwd: accumulate needs dx_f32"); return 1; }
+    if (!t16 && (bcast_rows > 0 || dy_parts > 1)) { hulc_set_error("hulc_k_layernorm_bwd: fp32 runs the unfused pair, which has no bcast_rows / dy_parts (ln_bwd_can_bcast)"); return 1; }
+    if (!t16 && !scratch) { hulc_set_error("hulc_k_layernorm_bwd: fp32 needs the scratch buffer of the parameter gradients"); return 1; }
+    if (!t16 && drop_p > 0.f && !(dx_t && dx_f32)) { hulc_set_error("hulc_k_layernorm_bwd: fp32 masks dx_t as a copy of dx_f32: drop_p needs both"); return 1; }
+    if (!t16 && (drop_p > 0.f || seed != 0) && dx_t && dx_f32 && (ldd != n || ldt != n)) { hulc_set_error("hulc_k_layernorm_bwd: fp32 with a dropout mask and both outputs needs ldd == ldt == n"); return 1; }
+    if (k_misaligned(dy, 4) || k_misaligned(x, 4) || k_misaligned(stats, 4) || k_misaligned(g, 4) || k_misaligned(dx_f32, 4) || k_misaligned(dx_t, t16 ? 2 : 4) || k_misaligned(dg, 4) ||
+        k_misaligned(db, 4) || k_misaligned(scratch, 4)) { hulc_set_error("hulc_k_layernorm_bwd: a pointer is not aligned to its element type"); return 1; }
+#define HULC_K_L(TT)                                                                                                                                                  \
+    launch_ln_bwd<TT>((hipStream_t)stream, scratch, dy, lddy, x, ldx, stats, g, rows, n, dx_f32, ldd, accumulate, (TT*)dx_t, ldt, dg, db, drop_p, seed, bcast_rows, bcast_div, \
+                      dy_parts, dy_part_stride)
+    HULC_K_T("hulc_k_layernorm_bwd", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_layernorm_bwd");
+}
+
+int k_layernorm_mean(int t16, const float* x, int B, int S, int n, const float* g, const float* b, float* stats, void* out, float* yout, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 1 || S < 1 || n < 1 || n > 128 || (long long)B * S * n > (1ll << 30)) { hulc_set_error("hulc_k_layernorm_mean: B=%d S=%d n=%d (need B, S >= 1 and 1 <= n <= 128)", B, S, n); return 1; }
+    if (!x || !g || !b || !stats || !out || !yout) { hulc_set_error("hulc_k_layernorm_mean: null argument"); return 1; }
+    if (k_misaligned(x, 4) || k_misaligned(g, 4) || k_misaligned(b, 4) || k_misaligned(stats, 4) || k_misaligned(out, t16 ? 2 : 4) || k_misaligned(yout, 4)) {
+        hulc_set_error("hulc_k_layernorm_mean: a pointer is not aligned to its element type"); return 1;
+    }
+#define HULC_K_L(TT) hipLaunchKernelGGL((layernorm_mean_kernel<TT>), dim3(B), dim3(1024), 0, st, x, S, n, g, b, stats, (TT*)out, yout)      /* engine_forward.inc */
+    HULC_K_T("hulc_k_layernorm_mean", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_layernorm_mean");
+}
+#undef HULC_K_T
 
 }  // namespace HULC_NS

@@ -1434,6 +1434,10 @@ __global__ void __launch_bounds__(64) plan_kl_sample_kernel(const float* __restr
     }
     if (lane == 0) idx_out[bc] = sel;
 }
+// v, as the fp32 value a store of it writes.  Without this the compiler folds a following fp32 -> fp16 conversion into the multiply-add that produced v
+// (v_fma_mixlo_f16 rounds the exact product-sum once), and the 16-bit copy of a value is then not the rounding of its fp32 copy: one fp16 ulp apart wherever
+// the fp32 value lies half way between two fp16 values
+DEVI float as_stored_f32(float v) { asm volatile("" : "+v"(v)); return v; }
 // mcil: continuous latent plan.  state = [mean | var] (B, 2n), std = softplus(var) + 1e-4 (distributions.py:55-59);
 // KL(N(m1,s1) || N(m2,s2)) per element with the balancing weights (hulc.py:539-561), reparametrised sample plan = m1 + s1 * eps
 // (hulc.py:289) with an injected or Box-Muller draw.  One thread per (b, j).
@@ -1456,7 +1460,7 @@ __global__ void normal_kl_sample_kernel(const float* __restrict__ pr_state, cons
         e = sqrtf(-2.f * __logf(u1)) * __cosf(6.28318530717958647692f * u2);
     }
     eps_out[idx] = e;
-    const float pl = m1 + s1 * e;
+    const float pl = as_stored_f32(m1 + s1 * e);      // plan_t below is the rounding of plan_f
     plan_f[idx] = pl;
     plan_t[idx] = from_f<T>(pl);
     if (pp_state) {
@@ -1535,7 +1539,7 @@ __global__ void __launch_bounds__(64) st_softmax_bwd_kernel(const float* __restr
     const float p = ok ? probs[base + lane] : 0.f, d = ok ? dplan[base + lane] : 0.f;
     const float dot = wave_sum(p * d);
     if (ok) {
-        const float v = p * (d - dot) + dpr_kl[base + lane];
+        const float v = as_stored_f32(p * (d - dot) + dpr_kl[base + lane]);      // out_t below is the rounding of out
         out[base + lane] = v;
         out_t[base + lane] = from_f<T>(v);
         dpp_t[base + lane] = from_f<T>(dpp_kl[base + lane]);

@@ -59,7 +59,8 @@ typedef struct hulc_batch {
     const float* actions;        /* (B,S,7) relative actions, last = +-1 gripper */
     const float* robot_obs;      /* (B,S,15) state_info.robot_obs (raw; euler angles in [3:6]) */
     const float* lang;           /* (B,384) language embedding, lang modality only */
-    const int32_t* plan_idx;     /* optional (B,32) injected categorical sample (parity tests); NULL = sample on device */
+    const int32_t* plan_idx;     /* optional (B,32) injected categorical sample (parity tests), host or device; NULL = sample on device.  Read back and
+                                  * refused when a class lies outside [0, 32) */
     const int32_t* aux_rows;     /* HOST: indices b with use_for_aux_lang_loss[b] != 0 (lang modality; rows of the CLIP, MIA and BC-Z losses) */
     int32_t n_aux;               /* any 0 <= n_aux <= B; above 64 rows the losses run as multi-workgroup kernels (csrc/aux_rows.h) */
     uint64_t step;               /* optimizer step index, mixed into the dropout / sampling seeds */
@@ -250,7 +251,9 @@ int hulc_grad_norm_get(hulc_ctx* ctx, float* total, float* coef, float* per_tens
  * (LogisticDecoderRNN.loss_and_act, logistic_decoder_rnn.py:85-100): NLL loss, a sampled action (_sample :234-258) mapped back to
  * the world frame (tcp_to_world_frame, gripper_control.py:39-63), its mean absolute error and the gripper success rate.
  * Eval-mode: dropout off.  Forward only — it invalidates the state hulc_backward needs.
- * Every pointer of hulc_val_noise is optional (device or host memory); NULL = draw on the device with the counter RNG. */
+ * Every pointer of hulc_val_noise is optional (device or host memory); NULL = draw on the device with the counter RNG.
+ * HULC_KIND_HULC: plan_idx_pp / plan_idx_pr are read back (a stream synchronisation and a copy to the host, so not inside a stream capture; the same holds for
+ * hulc_batch.plan_idx) and the call returns an error when a class lies outside [0, 32). */
 /* HULC_KIND_MCIL: the plans are continuous — plan_idx_pp / plan_idx_pr (here, in hulc_validate's plan_idx_*_out and in
  * hulc_rollout_plan's plan_inject / plan_out) then point to (B,256) fp32 sampled plans instead of (B,32) int32 category indices,
  * u_mix_* is (B,S,7,10) and u_act_* (B,S,7) (7 mixture dimensions, no gripper head). */
@@ -577,6 +580,53 @@ int hulc_k_enc_tail_bwd(int32_t dtype, int32_t Nf, int32_t ldemb, const hulc_enc
 int hulc_k_logistic_loss(int32_t dtype, int32_t wide, const float* heads, int32_t ldh, const float* actions, const float* robot_obs, int32_t B, int32_t S,
                          int32_t n_mix, int32_t n_dim, int32_t num_classes, float log_scale_min, float gripper_alpha, int32_t gripper_control,
                          int32_t discrete_gripper, float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* hip_stream);
+
+/* ---- the latent-plan kernels and the LayerNorm family, one kernel per entry (csrc/kernels.h; launched as the engine launches them, csrc/plan_ln_launch.h).
+ * dtype = the engine type T of the kernel instance: HULC_DTYPE_F32, HULC_DTYPE_BF16 or HULC_DTYPE_F16; "T" below is float or the 16-bit type.  Every entry
+ * refuses null or misaligned pointers and out-of-range sizes without launching.  Plan indices address LDS and weight rows unchecked inside the kernels: the
+ * entries read them back (a synchronous copy) and refuse any index outside [0, NCLS). */
+/* plan_kl_sample_kernel: one wave per (b, category).  pr_logits / pp_logits [B][NCAT][NCLS] fp32, 1 <= NCLS <= 64.  probs = softmax(pr_logits); with pp_logits:
+ *   kl_cat [B][NCAT] = KL(pr || pp) per category, dpp = w_pp (softmax(pp) - probs), dpr = w_pr probs (log pr - log pp - kl_cat), both times lscale[0] when the
+ *   device float lscale is given (kl_cat and probs are never scaled).  idx_out [B][NCAT] = idx_in when given, else the Gumbel-max draw of pr_logits from
+ *   the counter-based uniform of element (b * NCAT + cat) * NCLS + class under `seed` (lowest class on ties). */
+int hulc_k_plan_kl_sample(const float* pr_logits, const float* pp_logits, int32_t B, int32_t NCAT, int32_t NCLS, const int32_t* idx_in, int32_t* idx_out, float* probs,
+                          float* kl_cat, float* dpp, float* dpr, float w_pp, float w_pr, uint64_t seed, const float* lscale, void* hip_stream);
+/* st_softmax_bwd_kernel: out [rows][NCLS] fp32 = probs * (dplan - sum(probs * dplan)) + dpr_kl; out_t = T(out), dpp_t = T(dpp_kl). */
+int hulc_k_st_softmax_bwd(int32_t dtype, const float* probs, const float* dplan, const float* dpr_kl, const float* dpp_kl, int32_t rows, int32_t NCLS, float* out,
+                          void* out_t, void* dpp_t, void* hip_stream);
+/* plan_gather_t_kernel: out [B][H] fp32 = b1 + b2 + sum_cat w_t[cat * NCLS + idx[b][cat]][:], w_t [KIN][H] T, H a multiple of 256, 0 <= NCAT <= 64 (0: no plan,
+ *   idx unused).  With emb [B*S][128] T and embg: embg [S][B][W] = the last W columns of emb, time-major (1 <= W <= 128).  With goal [B][G] T and cb: cb [B][H] T =
+ *   out + goal w_t[grow0 .. grow0 + G - 1]; grow0 >= NCAT * NCLS, and w_t must hold those rows (KIN is not an argument). */
+int hulc_k_plan_gather(int32_t dtype, const void* w_t, const int32_t* idx, int32_t B, int32_t NCAT, int32_t NCLS, int32_t H, const float* b1, const float* b2, float* out,
+                       const void* emb, void* embg, int32_t S, int32_t W, const void* goal, int32_t G, int32_t grow0, void* cb, void* hip_stream);
+/* plan_scatter_grad_{lds, w4}_kernel (form 0 / 1; w4 is the 16-bit engines' form and exists for the 16-bit types only): dw [H][KIN] fp32,
+ *   dw[i][cat * NCLS + cls] += sum over the windows b with idx[b][cat] == cls of dC[b][i], dC [B][H] T.  NCLS <= 32, NCAT <= 64, KIN >= NCAT * NCLS.  store = 1
+ *   (form 1 only): the plan columns are written, not added to. */
+int hulc_k_plan_scatter_grad(int32_t dtype, int32_t form, const void* dC, const int32_t* idx, int32_t B, int32_t NCAT, int32_t NCLS, int32_t H, int32_t KIN, float* dw,
+                             int32_t store, void* hip_stream);
+/* normal_kl_sample_kernel (mcil): pr_state / pp_state [B][2n] fp32 = mean | var, std = softplus(var) + 1e-4.  eps_out = eps_in when given, else a Box-Muller draw;
+ *   plan_f = mean + std * eps, plan_t = T(plan_f); with pp_state: kl_elem [B][n] = KL(N(pr) || N(pp)) and dpp, dpr [B][2n] its gradients times w_pp, w_pr (and
+ *   lscale[0]). */
+int hulc_k_normal_kl_sample(int32_t dtype, const float* pr_state, const float* pp_state, int32_t B, int32_t n, const float* eps_in, float* eps_out, float* plan_f, void* plan_t,
+                            float* kl_elem, float* dpp, float* dpr, float w_pp, float w_pr, uint64_t seed, const float* lscale, void* hip_stream);
+/* normal_rsample_bwd_kernel: out [B][2n] T = [dplan | dplan * eps * sigmoid(var)] + dpr_kl. */
+int hulc_k_normal_rsample_bwd(int32_t dtype, const float* dplan, const float* eps, const float* pr_state, const float* dpr_kl, int32_t B, int32_t n, void* out,
+                              void* hip_stream);
+/* layernorm_fwd_kernel: rows of n <= 128 fp32 values (leading dimension ldx), biased variance, eps 1e-5; out (T, ldo), out_f32 (ldf) and stats [rows][2] =
+ *   (mean, rstd) are each optional. */
+int hulc_k_layernorm_fwd(int32_t dtype, const float* x, int64_t ldx, int32_t rows, int32_t n, const float* g, const float* b, void* out, int64_t ldo, float* out_f32,
+                         int64_t ldf, float* stats, void* hip_stream);
+/* The LayerNorm backward as the engine of `dtype` runs it.  16-bit: layernorm_bwd_fused_kernel (4 rows and 4 waves per block, 16 and 16 from 1024 rows on); dg, db are
+ *   ADDED to by atomics; dx_t goes through the dropout mask of (seed, row * n + col) when drop_p > 0; bcast_rows > 0: dy holds one row per bcast_rows rows, divided by
+ *   bcast_div; dy_parts <= 4: dy is the sum of dy + i * dy_part_stride.  fp32: layernorm_bwd_kernel (+ dropout_apply_kernel) + layernorm_param_grad_kernel +
+ *   colsum_final_kernel, which ADDS to dg, db as well; needs scratch (2 * min(64, ceil(rows / 64)) * n floats) and has no bcast_rows / dy_parts.
+ *   dx_f32 (ldd; accumulate = 1 adds) and dx_t (T, ldt): at least one. */
+int hulc_k_layernorm_bwd(int32_t dtype, const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* stats, const float* g, int32_t rows, int32_t n, float* dx_f32,
+                         int64_t ldd, int32_t accumulate, void* dx_t, int64_t ldt, float* dg, float* db, float drop_p, uint64_t seed, int32_t bcast_rows, float bcast_div,
+                         int32_t dy_parts, int64_t dy_part_stride, float* scratch, void* hip_stream);
+/* layernorm_mean_kernel: x [B][S][n] fp32 -> yout [B][S][n] = LayerNorm(x), stats [B*S][2], out [B][n] T = mean over S of yout. */
+int hulc_k_layernorm_mean(int32_t dtype, const float* x, int32_t B, int32_t S, int32_t n, const float* g, const float* b, float* stats, void* out, float* yout,
+                          void* hip_stream);
 
 #ifdef __cplusplus
 }
