@@ -37,6 +37,8 @@ int hulc_ctx_create(const hulc_config* cfg, hulc_ctx** out) {
         hulc_set_error("hulc_ctx_create: need 1 <= max_seq <= 64, max_batch >= 1, max_window >= max_seq");
         return 1;
     }
+    // every dropout site divides by 1 - p (the fused transformer kernels among them): p = 1, p > 1 or NaN would reach the kernels as inf / NaN multipliers
+    if (!(cfg->dropout_p >= 0.f && cfg->dropout_p < 1.f)) { hulc_set_error("hulc_ctx_create: dropout_p=%g must be in [0, 1)", (double)cfg->dropout_p); return 1; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { hulc_set_error("hulc_ctx_create: no HIP device visible"); return 1; }
     hulc_ctx* c = new hulc_ctx();
@@ -296,7 +298,7 @@ int hulc_grad_norm_get(hulc_ctx* ctx, float* total, float* coef, float* per_tens
 }
 int hulc_set_kl_beta(hulc_ctx* ctx, float b) { ctx->e->set_kl_beta(b); return 0; }
 int hulc_set_dropout(hulc_ctx* ctx, float p) {
-    if (p < 0.f || p >= 1.f) { hulc_set_error("hulc_set_dropout: p must be in [0,1)"); return 1; }
+    if (!(p >= 0.f && p < 1.f)) { hulc_set_error("hulc_set_dropout: p must be in [0,1)"); return 1; }      // NaN is refused too
     ctx->e->set_dropout(p);
     return 0;
 }
@@ -337,6 +339,16 @@ int hulc_k_enc_tail_fwd(int32_t dtype, int32_t Nf, int32_t ldemb, const hulc_enc
 }
 int hulc_k_enc_tail_bwd(int32_t dtype, int32_t Nf, int32_t ldemb, const hulc_enc_tail_bwd_job* a, const hulc_enc_tail_bwd_job* b, const float* demb, void* stream) {
     HULC_K_16BIT("hulc_k_enc_tail_bwd", k_enc_tail_bwd(Nf, ldemb, a, b, demb, stream));
+}
+// the fused transformer layer kernels (tr_fused.h): 16-bit units only
+int hulc_k_tr_layer_fwd(int32_t dtype, const hulc_tr_layer_job* job, int32_t B, int32_t S, int32_t ln_in, float dp, void* stream) {
+    HULC_K_16BIT("hulc_k_tr_layer_fwd", k_tr_layer_fwd(job, B, S, ln_in, dp, stream));
+}
+int hulc_k_tr_ffn_bwd(int32_t dtype, const hulc_tr_ffn_bwd_job* job, int32_t B, int32_t S, int32_t bcast, float bdiv, float dp, void* stream) {
+    HULC_K_16BIT("hulc_k_tr_ffn_bwd", k_tr_ffn_bwd(job, B, S, bcast, bdiv, dp, stream));
+}
+int hulc_k_tr_attn_bwd(int32_t dtype, const hulc_tr_attn_bwd_job* job, int32_t B, int32_t S, int32_t nparts, int64_t part_stride, float dp, void* stream) {
+    HULC_K_16BIT("hulc_k_tr_attn_bwd", k_tr_attn_bwd(job, B, S, nparts, (long long)part_stride, dp, stream));
 }
 #undef HULC_K_16BIT
 int hulc_k_logistic_loss(int32_t dtype, int32_t wide, const float* heads, int32_t ldh, const float* actions, const float* robot_obs, int32_t B, int32_t S,

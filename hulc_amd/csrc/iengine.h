@@ -210,6 +210,9 @@ struct IEngine {
                         unsigned long long seed, int bcast_rows, float bcast_div, int dy_parts, long long dy_part_stride, float* scratch,        \
                         void* stream);                                                                                                          \
     int k_layernorm_mean(int t16, const float* x, int B, int S, int n, const float* g, const float* b, float* stats, void* out, float* yout,      \
-                         void* stream);
+                         void* stream);                                                                                                         \
+    int k_tr_layer_fwd(const hulc_tr_layer_job* j, int B, int S, int ln_in, float dp, void* stream);                                            \
+    int k_tr_ffn_bwd(const hulc_tr_ffn_bwd_job* j, int B, int S, int bcast, float bdiv, float dp, void* stream);                                \
+    int k_tr_attn_bwd(const hulc_tr_attn_bwd_job* j, int B, int S, int nparts, long long part_stride, float dp, void* stream);
 namespace hulc_bf16 { HULC_TU_DECLS }   // capi.hip: HULC_DTYPE_F32 / HULC_DTYPE_BF16
 namespace hulc_f16 { HULC_TU_DECLS }    // engine_f16.hip: HULC_DTYPE_F16

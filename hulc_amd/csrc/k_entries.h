@@ -1,6 +1,7 @@
 // hulc_amd/csrc/k_entries.h — per-kernel test entries of the 16-bit encoder head and of the action loss (include/hulc_hip.h: hulc_k_spatial_softmax64,
-// hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss), of the latent-plan kernels (hulc_k_plan_*, hulc_k_st_softmax_bwd, hulc_k_normal_*) and of
-// the LayerNorm family (hulc_k_layernorm_*; launched through plan_ln_launch.h, which the engine calls too).  Included by engine.h inside each translation unit, so every entry exists once per
+// hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss), of the latent-plan kernels (hulc_k_plan_*, hulc_k_st_softmax_bwd, hulc_k_normal_*), of
+// the LayerNorm family (hulc_k_layernorm_*; launched through plan_ln_launch.h, which the engine calls too) and of the fused transformer layer kernels
+// (hulc_k_tr_layer_fwd, hulc_k_tr_ffn_bwd, hulc_k_tr_attn_bwd; launched through tr_fused.h's helpers).  Included by engine.h inside each translation unit, so every entry exists once per
 // 16-bit type (hulc_bf16 / hulc_f16; iengine.h declares them).  Nothing here restates a kernel: each entry checks its arguments, then launches through the
 // helper the engine calls (enc_tail.h) or with the grid and block of the engine's launch site (engine_encoders.inc, engine_forward.inc).
 #pragma once
@@ -8,6 +9,8 @@
 #include "kernels.h"
 #include "enc_tail.h"
 #include "plan_ln_launch.h"
+#include "gemm.h"
+#include "tr_fused.h"
 #include <vector>
 
 namespace HULC_NS {
@@ -284,5 +287,119 @@ int k_layernorm_mean(int t16, const float* x, int B, int S, int n, const float* 
     return k_launched("hulc_k_layernorm_mean");
 }
 #undef HULC_K_T
+
+// ---------------------------------------------------------------------------------------------------- fused transformer layer (tr_fused.h)
+// The kernels read FRAGMENT-ORDERED weight copies (gemm.h: frag_pack_kernel).  The entries take plain row-major matrices, repack them into scratch exactly as
+// Engine::prepare_weights does (one frag_pack_kernel launch over a FragPackBatch), launch through the engine's launch helper, and free the scratch after a stream synchronise.
+struct KFragScratch {
+    h16_t* base = nullptr;
+    FragPackBatch fb{};
+    int blocks = 0;
+    size_t elems = 0, off[FRAG_PACK_MAX] = {};
+    ~KFragScratch() { if (base) hipFree(base); }
+    void add(const void* src, int N, int K) {      // N % 16 == 0, K % 128 == 0
+        fb.src[fb.n] = (const h16_t*)src; off[fb.n] = elems; fb.N[fb.n] = N; fb.K[fb.n] = K; fb.blk0[fb.n] = blocks;
+        blocks += frag_pack_blocks(N, K); elems += (size_t)N * K; ++fb.n; fb.blk0[fb.n] = blocks;
+    }
+    const h16_t* at(int i) const { return fb.dst[i]; }
+    int alloc_and_pack(const char* who, hipStream_t st) {
+        if (hipMalloc((void**)&base, elems * sizeof(h16_t)) != hipSuccess) { base = nullptr; hulc_set_error("%s: hipMalloc of the fragment-ordered weight copies failed", who); return 1; }
+        for (int i = 0; i < fb.n; ++i) fb.dst[i] = base + off[i];
+        hipLaunchKernelGGL(frag_pack_kernel, dim3(blocks), dim3(256), 0, st, fb);
+        return k_launched(who);
+    }
+    int finish(const char* who, hipStream_t st) {
+        if (k_launched(who)) return 1;
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { hulc_set_error("%s: %s", who, hipGetErrorString(e)); return 1; }
+        return 0;
+    }
+};
+static inline bool k_tr_shape_bad(const char* who, int B, int S, int smax, float dp) {
+    if (B < 1 || S < 1 || S > smax || (long long)B * S > (1ll << 22)) { hulc_set_error("%s: B=%d S=%d (need B >= 1, 1 <= S <= %d, B * S <= 2^22)", who, B, S, smax); return true; }
+    if (!(dp >= 0.f && dp < 1.f)) { hulc_set_error("%s: dp=%g outside [0, 1)", who, (double)dp); return true; }
+    return false;
+}
+
+int k_tr_layer_fwd(const hulc_tr_layer_job* j, int B, int S, int ln_in, float dp, void* stream) {
+    static const char* who = "hulc_k_tr_layer_fwd";
+    hipStream_t st = (hipStream_t)stream;
+    if (!j) { hulc_set_error("%s: null job", who); return 1; }
+    if (k_tr_shape_bad(who, B, S, 64, dp)) return 1;
+    if (ln_in != 0 && ln_in != 1) { hulc_set_error("%s: ln_in must be 0 or 1, got %d", who, ln_in); return 1; }
+    if (!j->xin || !j->Wqkv || !j->Wo || !j->W1 || !j->W2 || !j->bqkv || !j->bo || !j->b1 || !j->b2 || !j->n1g || !j->n1b || !j->qkv || !j->Pat || !j->ao || !j->y1 || !j->st1 ||
+        !j->x1t || !j->x1f || !j->hff || !j->y2) { hulc_set_error("%s: null pointer in the job", who); return 1; }
+    if (ln_in && (!j->ln_g || !j->ln_b || !j->xf_out || !j->xt_out || !j->st_out)) { hulc_set_error("%s: ln_in = 1 needs ln_g, ln_b, xf_out, xt_out, st_out", who); return 1; }
+    // 16-byte vectors: the weights (frag_pack_kernel), the four biases (f32x4), ao (u32x4), y1 (f32x4); 8-byte: qkv, hff (two packed pairs)
+    if (k_misaligned16(j->Wqkv) || k_misaligned16(j->Wo) || k_misaligned16(j->W1) || k_misaligned16(j->W2) || k_misaligned16(j->bqkv) || k_misaligned16(j->bo) || k_misaligned16(j->b1) ||
+        k_misaligned16(j->b2) || k_misaligned16(j->ao) || k_misaligned16(j->y1)) { hulc_set_error("%s: the weights, bqkv, bo, b1, b2, ao, y1 must be 16-byte aligned", who); return 1; }
+    if (k_misaligned(j->qkv, 8) || k_misaligned(j->hff, 8)) { hulc_set_error("%s: qkv, hff must be 8-byte aligned", who); return 1; }
+    if (k_misaligned(j->xin, 4) || k_misaligned(j->ln_g, 4) || k_misaligned(j->ln_b, 4) || k_misaligned(j->xf_out, 4) || k_misaligned(j->xt_out, 2) || k_misaligned(j->st_out, 4) ||
+        k_misaligned(j->n1g, 4) || k_misaligned(j->n1b, 4) || k_misaligned(j->Pat, 4) || k_misaligned(j->st1, 4) || k_misaligned(j->x1t, 2) || k_misaligned(j->x1f, 4) ||
+        k_misaligned(j->y2, 4)) { hulc_set_error("%s: a pointer is not aligned to its element type", who); return 1; }
+    KFragScratch fs;
+    fs.add(j->Wqkv, 3 * TRF_D, TRF_D); fs.add(j->Wo, TRF_D, TRF_D); fs.add(j->W1, TRF_FF, TRF_D); fs.add(j->W2, TRF_D, TRF_FF);
+    if (fs.alloc_and_pack(who, st)) return 1;
+    TrLayerP q{};
+    q.xin = j->xin; q.ln_in = ln_in; q.ln_g = j->ln_g; q.ln_b = j->ln_b; q.xf_out = j->xf_out; q.xt_out = (h16_t*)j->xt_out; q.st_out = j->st_out;
+    q.Wqkv = fs.at(0); q.Wo = fs.at(1); q.W1 = fs.at(2); q.W2 = fs.at(3);
+    q.bqkv = j->bqkv; q.bo = j->bo; q.b1 = j->b1; q.b2 = j->b2; q.n1g = j->n1g; q.n1b = j->n1b;
+    q.qkv = (h16_t*)j->qkv; q.Pat = j->Pat; q.ao = (h16_t*)j->ao; q.y1 = j->y1; q.st1 = j->st1; q.x1t = (h16_t*)j->x1t; q.x1f = j->x1f; q.hff = (h16_t*)j->hff; q.y2 = j->y2;
+    q.B = B; q.S = S; q.dp = dp;
+    q.seed_att = j->seed_att; q.seed_o = j->seed_o; q.seed_h = j->seed_h; q.seed_y = j->seed_y;
+    launch_tr_layer_fwd(st, q);
+    return fs.finish(who, st);
+}
+
+int k_tr_ffn_bwd(const hulc_tr_ffn_bwd_job* j, int B, int S, int bcast, float bdiv, float dp, void* stream) {
+    static const char* who = "hulc_k_tr_ffn_bwd";
+    hipStream_t st = (hipStream_t)stream;
+    if (!j) { hulc_set_error("%s: null job", who); return 1; }
+    if (k_tr_shape_bad(who, B, S, 64, dp)) return 1;
+    if ((bcast != 0 && bcast != 1) || (bcast && !(bdiv > 0.f))) { hulc_set_error("%s: bcast=%d bdiv=%g (bcast is 0 or 1; with bcast, bdiv > 0)", who, bcast, (double)bdiv); return 1; }
+    if (!j->dx || !j->y2 || !j->st2 || !j->n2g || !j->dg2 || !j->db2 || !j->W2t || !j->W1t || !j->hff || !j->dt_c || !j->dt_a || !j->part) { hulc_set_error("%s: null pointer in the job", who); return 1; }
+    // 16-byte vectors: the weights (frag_pack_kernel), part (f32x4); 8-byte: hff, dt_a (two packed pairs)
+    if (k_misaligned16(j->W2t) || k_misaligned16(j->W1t) || k_misaligned16(j->part)) { hulc_set_error("%s: W2t, W1t, part must be 16-byte aligned", who); return 1; }
+    if (k_misaligned(j->hff, 8) || k_misaligned(j->dt_a, 8)) { hulc_set_error("%s: hff, dt_a must be 8-byte aligned", who); return 1; }
+    if (k_misaligned(j->dx, 4) || k_misaligned(j->y2, 4) || k_misaligned(j->st2, 4) || k_misaligned(j->n2g, 4) || k_misaligned(j->dg2, 4) || k_misaligned(j->db2, 4) ||
+        k_misaligned(j->dt_c, 2)) { hulc_set_error("%s: a pointer is not aligned to its element type", who); return 1; }
+    KFragScratch fs;
+    fs.add(j->W2t, TRF_FF, TRF_D); fs.add(j->W1t, TRF_D, TRF_FF);
+    if (fs.alloc_and_pack(who, st)) return 1;
+    TrFfnBwdP q{};
+    q.dx = j->dx; q.bcast = bcast; q.bdiv = bdiv; q.y2 = j->y2; q.st2 = j->st2; q.n2g = j->n2g; q.dg2 = j->dg2; q.db2 = j->db2;
+    q.W2t = fs.at(0); q.W1t = fs.at(1); q.hff = (const h16_t*)j->hff; q.dt_c = (h16_t*)j->dt_c; q.dt_a = (h16_t*)j->dt_a; q.part = j->part;
+    q.B = B; q.S = S; q.N = (long long)B * S; q.dp = dp; q.seed_y = j->seed_y;
+    launch_tr_ffn_bwd(st, q);
+    return fs.finish(who, st);
+}
+
+int k_tr_attn_bwd(const hulc_tr_attn_bwd_job* j, int B, int S, int nparts, long long part_stride, float dp, void* stream) {
+    static const char* who = "hulc_k_tr_attn_bwd";
+    hipStream_t st = (hipStream_t)stream;
+    if (!j) { hulc_set_error("%s: null job", who); return 1; }
+    if (k_tr_shape_bad(who, B, S, 32, dp)) return 1;
+    if (nparts < 1 || nparts > 4 || (nparts > 1 && part_stride < (long long)B * S * TRF_D)) {
+        hulc_set_error("%s: nparts=%d part_stride=%lld (need 1 <= nparts <= 4 and, with more than one, part_stride >= B * S * 128)", who, nparts, part_stride); return 1;
+    }
+    if (!j->parts || !j->y1 || !j->st1 || !j->n1g || !j->dg1 || !j->db1 || !j->Wot || !j->Wint || !j->qkv || !j->Pat || !j->b_d || !j->b_b || !j->dy_f || !j->dx) {
+        hulc_set_error("%s: null pointer in the job", who); return 1;
+    }
+    // 16-byte vectors: the weights (frag_pack_kernel), qkv (load8), b_b (Vec8 stores), dy_f (re-read as f32x4), dx (f32x4)
+    if (k_misaligned16(j->Wot) || k_misaligned16(j->Wint) || k_misaligned16(j->qkv) || k_misaligned16(j->b_b) || k_misaligned16(j->dy_f) || k_misaligned16(j->dx)) {
+        hulc_set_error("%s: Wot, Wint, qkv, b_b, dy_f, dx must be 16-byte aligned", who); return 1;
+    }
+    if (k_misaligned(j->parts, 4) || k_misaligned(j->y1, 4) || k_misaligned(j->st1, 4) || k_misaligned(j->n1g, 4) || k_misaligned(j->dg1, 4) || k_misaligned(j->db1, 4) ||
+        k_misaligned(j->Pat, 4) || k_misaligned(j->b_d, 2)) { hulc_set_error("%s: a pointer is not aligned to its element type", who); return 1; }
+    KFragScratch fs;
+    fs.add(j->Wot, TRF_D, TRF_D); fs.add(j->Wint, TRF_D, 3 * TRF_D);
+    if (fs.alloc_and_pack(who, st)) return 1;
+    TrAttnBwdP q{};
+    q.parts = j->parts; q.part_stride = part_stride; q.nparts = nparts; q.y1 = j->y1; q.st1 = j->st1; q.n1g = j->n1g; q.dg1 = j->dg1; q.db1 = j->db1;
+    q.Wot = fs.at(0); q.Wint = fs.at(1); q.qkv = (const h16_t*)j->qkv; q.Pat = j->Pat; q.b_d = (h16_t*)j->b_d; q.b_b = (h16_t*)j->b_b; q.dy_f = j->dy_f; q.dx = j->dx;
+    q.B = B; q.S = S; q.dp = dp; q.seed_o = j->seed_o; q.seed_att = j->seed_att;
+    launch_tr_attn_bwd(st, q);
+    return fs.finish(who, st);
+}
 
 }  // namespace HULC_NS

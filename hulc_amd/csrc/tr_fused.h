@@ -646,7 +646,10 @@ __global__ void __launch_bounds__(512) tr_attn_bwd_kernel(TrAttnBwdP p) {
     const int w = blockIdx.x, S = p.S;
     const long long row0 = (long long)w * S;
     const bool mt1 = true;        // both 16-row tiles always (rows past S are zero).  With the second tile's MFMAs under `S > 16`, as in the kernels above,
-    // S <= 16 produced wrong d k / d v (transposed dS / P reads) while S >= 17 was exact — not understood
+    // S <= 16 produced wrong d k / d v (transposed dS / P reads) while S >= 17 was exact — not understood.  mt1 gates only the MFMAs of P1 and P3 on token rows
+    // 16 .. 31: for S <= 16 their B operand rows are the zero rows of b_d (P1: acc[1] stays 0, which is what d O rows 16 .. 31 hold either way) and their outputs
+    // are rows >= S that P3 never stores, so nothing d k / d v depend on can be read from this code.  With the kernel as it stands the experiment does not reproduce:
+    // tests/test_gpu_tr_fused.py passes at every S in {1, 2, 15, 16, 17, 31, 32} with `mt1 = S > 16` (bf16, dp 0 / 0.1 / 0.5).  Both tiles are kept: 16 MFMAs per wave
 
     // out_proj^T fragments (rows = the 16 features of head `wave`, 4 k-steps over the 128 columns of b_d): requested first
     h16x8_t wo[4];

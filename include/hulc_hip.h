@@ -628,6 +628,50 @@ int hulc_k_layernorm_bwd(int32_t dtype, const float* dy, int64_t lddy, const flo
 int hulc_k_layernorm_mean(int32_t dtype, const float* x, int32_t B, int32_t S, int32_t n, const float* g, const float* b, float* stats, void* out, float* yout,
                           void* hip_stream);
 
+/* ---- the fused plan-recognition transformer layer kernels (csrc/tr_fused.h), launched as the engine launches them.  dtype = HULC_DTYPE_BF16 or HULC_DTYPE_F16
+ * (the kernels exist in the 16-bit units only; HULC_DTYPE_F32 is refused).  d_model 128, 8 heads of 16, 2048 hidden units; N = B * S rows, window b = rows
+ * b * S .. b * S + S - 1.  Weights are plain row-major 16-bit matrices; each entry makes the fragment-ordered copies the kernels read in scratch memory
+ * (frag_pack_kernel, as the engine does), launches, synchronises the stream and frees the scratch.  Every entry refuses null or misaligned pointers and
+ * out-of-range sizes before it allocates or launches.  Dropout masks: keep = hash(seed, element index) >= dp over the row-major index spaces (N, 128) (seed_o,
+ * seed_y), (B, 8, S, S) (seed_att) and (N, 2048) (seed_h); kept values are divided by 1 - dp.
+ *
+ * hulc_k_tr_layer_fwd: tr_layer_fwd_kernel (S <= 32) / its two-half form (32 < S <= 64).  xin [N][128] fp32 = the layer input x (ln_in = 0) or the previous
+ *   layer's pre-norm sum (ln_in = 1: x = LayerNorm(xin; ln_g, ln_b), saved as xf_out [N][128] fp32, xt_out (16 bit) and st_out [N][2] = mean, rstd).
+ *   Wqkv [384][128], Wo [128][128], W1 [2048][128], W2 [128][2048] 16 bit; bqkv [384], bo [128], b1 [2048], b2 [128], n1g, n1b [128] fp32.  Written: qkv [N][384]
+ *   16 bit, Pat [B][8][S][S] fp32 (before its dropout), ao [N][128] 16 bit, y1 [N][128] fp32 = x + drop(ao Wo^T + bo), st1 [N][2], x1f / x1t = LayerNorm(y1; n1g,
+ *   n1b) (fp32 / 16 bit), hff [N][2048] 16 bit = drop(relu(x1t W1^T + b1)).  y2 [N][128] fp32 is ADDED to (atomics): y2 += x1f + drop(hff W2^T + b2).
+ *   16-byte aligned: the weights, bqkv, bo, b1, b2, ao, y1; 8-byte aligned: qkv, hff. */
+typedef struct hulc_tr_layer_job {
+    const float* xin; const float* ln_g; const float* ln_b; float* xf_out; void* xt_out; float* st_out;
+    const void* Wqkv; const void* Wo; const void* W1; const void* W2;
+    const float* bqkv; const float* bo; const float* b1; const float* b2; const float* n1g; const float* n1b;
+    void* qkv; float* Pat; void* ao; float* y1; float* st1; void* x1t; float* x1f; void* hff; float* y2;
+    uint64_t seed_att, seed_o, seed_h, seed_y;
+} hulc_tr_layer_job;
+int hulc_k_tr_layer_fwd(int32_t dtype, const hulc_tr_layer_job* job, int32_t B, int32_t S, int32_t ln_in, float dp, void* hip_stream);
+/* hulc_k_tr_ffn_bwd: tr_ffn_bwd_kernel, S <= 64.  dx [N][128] fp32 = the gradient of LayerNorm2's output, or (bcast = 1) [B][128]: one row per window, divided by
+ *   bdiv.  y2 [N][128], st2 [N][2], n2g [128] fp32; W2t [2048][128] = linear2.weight^T, W1t [128][2048] = linear1.weight^T, hff [N][2048] 16 bit.  dg2, db2 [128]
+ *   are ADDED to (atomics).  Written: dt_c [N][128] 16 bit = drop_y(dy2) with dy2 = LayerNorm2's input gradient, dt_a [N][2048] 16 bit = (dt_c W2) / (1 - dp) where
+ *   hff > 0, part [4][N][128] fp32: part[q] = dt_a[:, 512 q .. 512 q + 511] W1[512 q .. 512 q + 511, :], + dy2 in part[0].
+ *   16-byte aligned: W2t, W1t, part; 8-byte aligned: hff, dt_a. */
+typedef struct hulc_tr_ffn_bwd_job {
+    const float* dx; const float* y2; const float* st2; const float* n2g; float* dg2; float* db2;
+    const void* W2t; const void* W1t; const void* hff; void* dt_c; void* dt_a; float* part;
+    uint64_t seed_y;
+} hulc_tr_ffn_bwd_job;
+int hulc_k_tr_ffn_bwd(int32_t dtype, const hulc_tr_ffn_bwd_job* job, int32_t B, int32_t S, int32_t bcast, float bdiv, float dp, void* hip_stream);
+/* hulc_k_tr_attn_bwd: tr_attn_bwd_kernel, S <= 32 (the engine runs the per-operation kernels above that).  parts: the gradient of LayerNorm1's output as the sum
+ *   of nparts (1..4) arrays [N][128] fp32, part_stride floats apart (>= N * 128).  y1 [N][128], st1 [N][2], n1g [128] fp32; Wot [128][128] = out_proj.weight^T,
+ *   Wint [128][384] = in_proj_weight^T, qkv [N][384] 16 bit; Pat [B][8][S][S] fp32.  dg1, db1 [128] are ADDED to (atomics).  Written: dy_f [N][128] fp32 =
+ *   LayerNorm1's input gradient, b_d [N][128] 16 bit = drop_o(dy_f), b_b [N][384] 16 bit = the gradient of qkv (b_d through out_proj and the attention), dx [N][128]
+ *   fp32 = b_b W_in + dy_f.  16-byte aligned: Wot, Wint, qkv, b_b, dy_f, dx. */
+typedef struct hulc_tr_attn_bwd_job {
+    const float* parts; const float* y1; const float* st1; const float* n1g; float* dg1; float* db1;
+    const void* Wot; const void* Wint; const void* qkv; const float* Pat; void* b_d; void* b_b; float* dy_f; float* dx;
+    uint64_t seed_o, seed_att;
+} hulc_tr_attn_bwd_job;
+int hulc_k_tr_attn_bwd(int32_t dtype, const hulc_tr_attn_bwd_job* job, int32_t B, int32_t S, int32_t nparts, int64_t part_stride, float dp, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

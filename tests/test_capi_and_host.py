@@ -202,3 +202,93 @@ def test_kernel_test_entries_reject_retired_flags_modes_and_forms_before_touchin
         assert b"hulc_k_conv_tile" in err and word in err, (mode, relu, err)
     assert lib.hulc_k_conv1_wgrad_u8(None, None, 4, None, None, None, 1, 84, 0, 1, None) != 0
     assert b"hulc_k_conv1_wgrad_u8: form" in lib.hulc_last_error()
+
+
+def test_fused_transformer_entries_refuse_bad_arguments_before_touching_the_device():
+    """hulc_k_tr_layer_fwd / hulc_k_tr_ffn_bwd / hulc_k_tr_attn_bwd check their arguments before they allocate the fragment-ordered weight copies or launch: the
+    pointers here are made-up addresses that are never dereferenced, so a check that came late would fault, or (without a GPU) report a HIP failure instead
+    of naming the argument."""
+    import ctypes as C
+    from hulc_amd import lib as L
+    lib = L.load()
+    BF, F16, F32 = L.DTYPE["bf16"], L.DTYPE["fp16"], L.DTYPE["fp32"]
+    A = 0x10000          # a 16-byte aligned made-up address
+
+    def refused(rc, entry, word):
+        err = lib.hulc_last_error().decode()
+        assert rc != 0 and entry in err and word in err, (entry, word, rc, err)
+
+    def job(cls, **over):
+        j = cls()
+        for k, (name, ty) in enumerate(cls._fields_):
+            setattr(j, name, A + 256 * k if ty is C.c_void_p else 7)
+        for name, v in over.items():
+            setattr(j, name, v)
+        return C.byref(j)
+
+    e, J = "hulc_k_tr_layer_fwd", L.HulcTrLayerJob
+    fw = lambda dt=BF, B=2, S=8, ln_in=1, dp=0.1, **over: lib.hulc_k_tr_layer_fwd(dt, job(J, **over), B, S, ln_in, dp, None)
+    refused(lib.hulc_k_tr_layer_fwd(BF, None, 2, 8, 0, 0.0, None), e, "null job")
+    refused(fw(dt=F32), e, "not a 16-bit type")
+    for kw in (dict(B=0), dict(S=0), dict(S=65)):
+        refused(fw(**kw), e, "need B >= 1")
+    for dp in (1.0, -0.1, float("nan")):
+        refused(fw(dp=dp), e, "outside [0, 1)")
+    refused(fw(ln_in=2), e, "ln_in must be 0 or 1")
+    for name in ("xin", "Wqkv", "Wo", "W1", "W2", "bqkv", "bo", "b1", "b2", "n1g", "n1b", "qkv", "Pat", "ao", "y1", "st1", "x1t", "x1f", "hff", "y2"):
+        refused(fw(dt=F16, ln_in=0, **{name: None}), e, "null pointer")
+    for name in ("ln_g", "ln_b", "xf_out", "xt_out", "st_out"):
+        refused(fw(**{name: None}), e, "ln_in = 1 needs")
+        assert "null pointer" not in lib.hulc_last_error().decode()
+    for name in ("Wqkv", "Wo", "W1", "W2", "bqkv", "bo", "b1", "b2", "ao", "y1"):
+        refused(fw(**{name: A + 8}), e, "16-byte aligned")
+    for name in ("qkv", "hff"):
+        refused(fw(**{name: A + 4}), e, "8-byte aligned")
+    for name, off in (("xin", 2), ("ln_g", 2), ("xt_out", 1), ("st_out", 2), ("n1g", 1), ("Pat", 2), ("st1", 2), ("x1t", 1), ("x1f", 2), ("y2", 2)):
+        refused(fw(**{name: A + off}), e, "element type")
+
+    e, J = "hulc_k_tr_ffn_bwd", L.HulcTrFfnBwdJob
+    fb = lambda dt=F16, B=2, S=40, bcast=0, bdiv=1.0, dp=0.5, **over: lib.hulc_k_tr_ffn_bwd(dt, job(J, **over), B, S, bcast, bdiv, dp, None)
+    refused(lib.hulc_k_tr_ffn_bwd(BF, None, 2, 8, 0, 1.0, 0.0, None), e, "null job")
+    refused(fb(dt=F32), e, "not a 16-bit type")
+    for kw in (dict(B=0), dict(S=0), dict(S=65), dict(B=-3)):
+        refused(fb(**kw), e, "need B >= 1")
+    refused(fb(dp=1.0), e, "outside [0, 1)")
+    for kw in (dict(bcast=2), dict(bcast=1, bdiv=0.0), dict(bcast=-1)):
+        refused(fb(**kw), e, "bcast")
+    for name, _ in J._fields_[:-1]:
+        refused(fb(**{name: None}), e, "null pointer")
+    for name in ("W2t", "W1t", "part"):
+        refused(fb(**{name: A + 8}), e, "16-byte aligned")
+    for name in ("hff", "dt_a"):
+        refused(fb(**{name: A + 4}), e, "8-byte aligned")
+    for name, off in (("dx", 2), ("y2", 1), ("st2", 2), ("n2g", 2), ("dg2", 2), ("db2", 2), ("dt_c", 1)):
+        refused(fb(**{name: A + off}), e, "element type")
+
+    e, J = "hulc_k_tr_attn_bwd", L.HulcTrAttnBwdJob
+    ab = lambda dt=BF, B=3, S=17, nparts=4, stride=3 * 17 * 128 + 4, dp=0.0, **over: lib.hulc_k_tr_attn_bwd(dt, job(J, **over), B, S, nparts, stride, dp, None)
+    refused(lib.hulc_k_tr_attn_bwd(BF, None, 2, 8, 1, 0, 0.0, None), e, "null job")
+    refused(ab(dt=F32), e, "not a 16-bit type")
+    for kw in (dict(B=0), dict(S=0), dict(S=33), dict(S=64)):
+        refused(ab(**kw), e, "need B >= 1")
+    refused(ab(dp=1.5), e, "outside [0, 1)")
+    for kw in (dict(nparts=0), dict(nparts=5), dict(nparts=2, stride=3 * 17 * 128 - 1)):
+        refused(ab(**kw), e, "nparts")
+    for name, _ in J._fields_[:-2]:
+        refused(ab(**{name: None}), e, "null pointer")
+    for name in ("Wot", "Wint", "qkv", "b_b", "dy_f", "dx"):
+        refused(ab(**{name: A + 8}), e, "16-byte aligned")
+    for name, off in (("parts", 2), ("y1", 2), ("st1", 1), ("n1g", 2), ("dg1", 2), ("db1", 2), ("Pat", 2), ("b_d", 1)):
+        refused(ab(**{name: A + off}), e, "element type")
+
+
+def test_dropout_probability_outside_the_half_open_unit_interval_is_refused():
+    """every dropout site divides by 1 - p: hulc_ctx_create and hulc_set_dropout refuse p = 1, p > 1, p < 0 and NaN before anything else happens (no device needed)"""
+    from hulc_amd import lib
+    l = lib.load()
+    for p in (1.0, 1.5, -0.1, float("nan")):
+        cfg = lib.HulcConfig(kind=0, dtype=1, max_batch=2, max_seq=4, max_window=32, use_clip=1, kl_beta=0.01, kl_balancing_mix=0.8,
+                             dropout_p=p, num_classes=10, gripper_alpha=1.0, log_scale_min=-7.0, seed=0)
+        ctx = ctypes.c_void_p()
+        assert l.hulc_ctx_create(ctypes.byref(cfg), ctypes.byref(ctx)) != 0 and b"dropout_p" in l.hulc_last_error(), p
+        assert l.hulc_set_dropout(None, p) != 0 and b"hulc_set_dropout" in l.hulc_last_error(), p

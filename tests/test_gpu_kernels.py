@@ -228,7 +228,8 @@ def test_gemm_glds_matches_fp64(M, N, K):
 @pytest.mark.parametrize("drop_p", [0.0, 0.1])
 def test_attention_kernels(variant, S, drop_p):
     """Forward and backward attention kernels (plan_recognition_net.py:94-117: nn.TransformerEncoderLayer, 8 heads of 16) against float64;
-    with dropout the two kernel variants must draw the same mask (the backward re-derives it from the element index)."""
+    with dropout the two kernel variants must draw the same mask (the backward re-derives it from the element index), and every variant is also compared with
+    float64 under the engine's mask (oracle: engine_keep_mask over (B, 8, S, S)) at the tolerances of the branch without dropout."""
     L, lib = _lib()
     B, D, NH, HD = 3, 128, 8, 16
     g = torch.Generator(device="cuda"); g.manual_seed(S * 10 + variant)
@@ -250,8 +251,14 @@ def test_attention_kernels(variant, S, drop_p):
         torch.cuda.synchronize()
         assert (ao - ao0).abs().max().item() < 1e-5 * ao0.abs().max().item() + 1e-6
         assert (dqkv - dq0).abs().max().item() < 1e-5 * dq0.abs().max().item() + 1e-6
-        return
-    out = (Pref @ v).permute(0, 2, 1, 3).reshape(B * S, D)
+        # and every variant (variant 0, the mask oracle above, included) against float64 under the engine's mask of element ((b * NH + h) * S + i) * S + j
+        import hulc_oracle as O
+        keep = torch.from_numpy(O.engine_keep_mask(seed, (B, NH, S, S), drop_p)).cuda()
+        assert 0 < int((~keep).sum()) or S == 1
+        Pm = Pref * keep.double() / (1.0 - float(np.float32(drop_p)))
+    else:
+        Pm = Pref
+    out = (Pm @ v).permute(0, 2, 1, 3).reshape(B * S, D)
     assert (ao.double() - out).abs().max().item() < 1e-5
     out.backward(dao.double())
     ref = torch.stack([q.grad, k.grad, v.grad]).permute(1, 3, 0, 2, 4).reshape(B * S, 3 * D)
