@@ -411,6 +411,31 @@ int hulc_k_cast(int32_t dtype, const float* src, void* dst, int64_t n, void* str
     if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_cast: launch failed"); return 1; }
     return 0;
 }
+// the row kernels of the ragged encoder pass (conv_wgrad.h), through the engine's launchers.  lens / off are device arrays the caller built (ragged_plan)
+int hulc_k_window_compact(const int64_t* window_start, const int32_t* lens, const int32_t* off, int32_t off_base, int32_t B, int32_t S, int64_t store_frames,
+                          const int32_t* shift_static, const int32_t* shift_gripper, int64_t* frame_out, int32_t* shift_static_out, int32_t* shift_gripper_out, void* stream) {
+    if (!window_start || !lens || !off || !frame_out || B < 1 || S < 1 || store_frames < 1 || (shift_static && !shift_static_out) || (shift_gripper && !shift_gripper_out)) {
+        hulc_set_error("hulc_k_window_compact: null argument or B=%d, S=%d, store_frames=%lld out of range", (int)B, (int)S, (long long)store_frames); return 1; }
+    launch_window_compact((hipStream_t)stream, reinterpret_cast<const long long*>(window_start), lens, off, off_base, B, S, (long long)store_frames, shift_static, shift_gripper,
+                          reinterpret_cast<long long*>(frame_out), shift_static_out, shift_gripper_out);
+    if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_window_compact: launch failed"); return 1; }
+    return 0;
+}
+int hulc_k_rows_expand(int32_t elem_bytes, const void* src, const int32_t* lens, const int32_t* off, int32_t B, int32_t S, int32_t n, void* dst, void* stream) {
+    if (!src || !lens || !off || !dst || B < 1 || S < 1 || n < 1 || (elem_bytes != 2 && elem_bytes != 4) || (n * elem_bytes) % 16 || ((uintptr_t)src | (uintptr_t)dst) % 16) {
+        hulc_set_error("hulc_k_rows_expand: null or misaligned argument, or B=%d, S=%d, n=%d, elem_bytes=%d unsupported", (int)B, (int)S, (int)n, (int)elem_bytes); return 1; }
+    if (elem_bytes == 4) launch_rows_expand<float>((hipStream_t)stream, (const float*)src, lens, off, B, S, n, (float*)dst);
+    else launch_rows_expand<h16_t>((hipStream_t)stream, (const h16_t*)src, lens, off, B, S, n, (h16_t*)dst);
+    if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_rows_expand: launch failed"); return 1; }
+    return 0;
+}
+int hulc_k_rows_reduce(const float* src, const int32_t* lens, const int32_t* off, int32_t B, int32_t S, int32_t n, float* dst, void* stream) {
+    if (!src || !lens || !off || !dst || B < 1 || S < 1 || n < 4 || n % 4 || ((uintptr_t)src | (uintptr_t)dst) % 16) {
+        hulc_set_error("hulc_k_rows_reduce: null or misaligned argument, or B=%d, S=%d, n=%d unsupported", (int)B, (int)S, (int)n); return 1; }
+    launch_rows_reduce((hipStream_t)stream, src, lens, off, B, S, n, dst);
+    if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_rows_reduce: launch failed"); return 1; }
+    return 0;
+}
 
 // the language auxiliary losses alone, routed on n as the engines route them (aux_rows.h): n <= 64 runs the single-workgroup kernels.  Synchronise.
 static int k_clip_loss(bool wide, const float* img, const float* txt, int32_t n, const float* logit_scale, float w, float* loss_out, float* dimg, float* dtxt,

@@ -197,7 +197,7 @@ struct Engine : IEngine {
     float *clip_rows_ws = nullptr, *mia_rows_ws = nullptr;   // aux_rows.h workspaces of the n > 64 kernels: only a context with max_batch > 64 has them
     int aux_rows_last = 0;                                   // rows of the last forward / validate, for hulc_aux_losses_get
     // ---- state of the last forward
-    hulc_batch cur; float cur_lw = 0, cur_cw = 0; bool have_fwd = false;
+    hulc_batch cur{}; float cur_lw = 0, cur_cw = 0; bool have_fwd = false;
 
     // =====================================================================================================
     Engine(const hulc_config& c) : cfg(c) {

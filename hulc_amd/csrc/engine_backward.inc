@@ -474,8 +474,11 @@
         {
             const Conv1Src src[2] = {conv1_src(*b, false), conv1_src(*b, true)}, src2[2] = {conv1_src(cur2, false), conv1_src(cur2, true)};
             const bool tail_fused = enc_tail_fusable();
-            if (tail_fused) enc_tail_bwd_both(N);
-            enc_bwd_both(src, pair ? src2 : nullptr, N, tail_fused);
+            // ragged pass: the gradients of a window's duplicate rows are summed into its last real row first (fixed order), the backward then runs on N' frames
+            const int Nenc = enc_frames(N);
+            if (ragged()) launch_rows_reduce(st, demb, rg_lens(), rg_off(), B, S, EMB, demb_c);
+            if (tail_fused) enc_tail_bwd_both(Nenc);
+            enc_bwd_both(src, pair ? src2 : nullptr, Nenc, tail_fused);
             flush_unpacks();
         }
         if (bucket_ready(4)) return 1;       // perceptual_encoder.* final

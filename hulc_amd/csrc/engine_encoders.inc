@@ -3,7 +3,7 @@
 // forward and backward pass.  The driver is a list of stages (enc_fwd_stages, enc_bwd_stages).  Each stage has a single-camera function (conv1_fwd, conv_fwd, head_fwd;
 // head_bwd, conv_wgrad, conv_dgrad, conv1_wgrad) and, where the 16-bit engines run both cameras as jobs of one launch, a *_both function that returns false when it
 // launched nothing; the list then calls the single-camera function once per camera.  Weight-gradient slabs are queued (queue_unpack) and reduced by one launch
-// (flush_unpacks).  The rest of the engine calls conv1_src / conv1_src_f32, window_len_expand, store_args_bad, actions_of, enc_fwd_both, enc_tail_fusable,
+// (flush_unpacks).  The rest of the engine calls conv1_src / conv1_src_f32, window_tables (+ enc_frames, ragged: the ragged encoder pass), store_args_bad, actions_of, enc_fwd_both, enc_tail_fusable,
 // enc_tail_fwd_both, enc_tail_bwd_both, enc_bwd_both and flush_unpacks.
     ConvGeom geom(int Nf, int IH, int C, int K, int S) const {
         ConvGeom g; g.Nf = Nf; g.IH = g.IW = IH; g.C = C; g.KH = g.KW = K; g.S = S; g.OH = g.OW = (IH - K) / S + 1; return g;
@@ -19,7 +19,7 @@
         // exactly like the reference (ingest_u8_kernel)
         s.fold = (s.u8 && std::is_same<T, h16_t>::value && u8_fold_mode) ? 1 : 0;
         if (s.u8 && b.window_start) { s.wstart = reinterpret_cast<const long long*>(b.window_start); s.S = b.S; s.nstore = b.store_frames; }      // windows gathered from the frame store
-        if (s.wstart && b.window_len) {      // variable-length padded windows: the per-frame table of window_len_expand, read as one-frame windows
+        if (s.wstart && (b.window_len || b.window_len_host)) {      // variable-length padded windows: the per-frame table of window_len_expand (ragged pass: the compact table of window_tables), read as one-frame windows
             const int set = &b == &cur2 ? 1 : 0;
             s.wstart = wl_frame[set]; s.S = 1;
             if (s.shift) s.shift = wl_shift[set][gripper ? 1 : 0];
@@ -31,23 +31,69 @@
     // hulc_batch::window_len, expanded once per forward / validation (conv_wgrad.h window_expand_kernel); set 0 = the batch of the pass, 1 = the paired pass's lang batch (cur2)
     long long* wl_frame[2] = {nullptr, nullptr};
     int* wl_shift[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    int window_len_expand(const hulc_batch& b, int nB, int set) {
-        if (!b.window_len) return 0;
+    int wl_alloc(int set) {
         if (!wl_frame[set]) {
             wl_frame[set] = alloc<long long>((int64_t)maxN); wl_shift[set][0] = alloc<int>((int64_t)maxN * 2); wl_shift[set][1] = alloc<int>((int64_t)maxN * 2);
             if (alloc_failed) { hulc_set_error("window_len: workspace allocation failed"); return 1; }
         }
+        return 0;
+    }
+    int window_len_expand(const hulc_batch& b, int nB, int set) {
+        if (!b.window_len) return 0;
+        if (wl_alloc(set)) return 1;
         hipLaunchKernelGGL(window_expand_kernel, dim3(cdiv(nB * b.S, 256)), dim3(256), 0, st, reinterpret_cast<const long long*>(b.window_start), b.window_len, nB, b.S,
                            (long long)b.store_frames, b.shift_static, b.shift_gripper, wl_frame[set], wl_shift[set][0], wl_shift[set][1]);
+        return 0;
+    }
+    // ---- ragged encoder pass (hulc_batch::window_len_host): the encoders run on the N' real frames of the pass, their output is expanded to the (B,S,EMB) rows the
+    // rest of the engine reads (rows_expand_kernel) and the embedding gradient is reduced to compact rows before the encoder backward (rows_reduce_kernel).
+    // rg_host / rg_dev: [off (nJ + 1) | lens (nJ)] over the nJ windows of the pass (the paired pass: vis then lang), clamped and summed on the host — every table,
+    // grid and frame count below comes from this one array.  rg_n1 = the frames of the first conv1 source (the whole pass unless paired), rg_N = N'.
+    // The state of a pass is cur.window_len_host (ragged()): the rollout paths set cur to a zeroed batch.
+    std::vector<int> rg_host;
+    int* rg_dev = nullptr;
+    T* emb_c = nullptr; float* demb_c = nullptr;
+    int rg_nJ = 0, rg_n1 = 0, rg_N = 0;
+    long long enc_frames_last = 0;
+    bool ragged() const { return cur.window_len_host != nullptr; }
+    const int* rg_off() const { return rg_dev; }
+    const int* rg_lens() const { return rg_dev + rg_nJ + 1; }
+    int enc_frames(int N) const { return ragged() ? rg_N : N; }      // the frame count of the encoder stages of this pass
+    T* enc_emb() { return ragged() ? emb_c : emb; }                  // where the encoders' tails write / read their rows
+    float* enc_demb() { return ragged() ? demb_c : demb; }
+    // frames of conv1 source h of a two-source (paired) pass over Nf frames
+    int src_frames(int Nf, int h) const { return ragged() ? (h ? Nf - rg_n1 : rg_n1) : Nf / 2; }
+    // the per-frame tables of the pass, once per forward / validation: b (nB windows) and, in the paired pass, b2
+    int window_tables(const hulc_batch& b, int nB, const hulc_batch* b2) {
+        if (!b.window_len_host) return (window_len_expand(b, nB, 0) || (b2 && window_len_expand(*b2, b2->B, 1))) ? 1 : 0;
+        const int nJ = nB + (b2 ? b2->B : 0);
+        if (!rg_dev) { rg_dev = alloc<int>((int64_t)2 * maxB + 1); emb_c = alloc<T>((int64_t)maxN * EMB); demb_c = alloc<float>((int64_t)maxN * EMB); }
+        if (alloc_failed || wl_alloc(0) || (b2 && wl_alloc(1))) { hulc_set_error("window_len_host: workspace allocation failed"); return 1; }
+        rg_host.resize((size_t)2 * nJ + 1);
+        int *off = rg_host.data(), *len = off + nJ + 1;
+        off[0] = 0;
+        for (int i = 0; i < nJ; ++i) {
+            const hulc_batch& s = i < nB ? b : *b2;
+            const int lmax = (int)std::min<long long>(s.S, s.store_frames);
+            len[i] = std::min(std::max(s.window_len_host[i < nB ? i : i - nB], 1), lmax);
+            off[i + 1] = off[i] + len[i];
+        }
+        rg_nJ = nJ; rg_n1 = off[nB]; rg_N = off[nJ];
+        HIP_CHECK(hipMemcpyAsync(rg_dev, rg_host.data(), sizeof(int) * rg_host.size(), hipMemcpyHostToDevice, st));
+        launch_window_compact(st, reinterpret_cast<const long long*>(b.window_start), rg_lens(), rg_off(), 0, nB, b.S, (long long)b.store_frames, b.shift_static, b.shift_gripper,
+                              wl_frame[0], wl_shift[0][0], wl_shift[0][1]);
+        if (b2) launch_window_compact(st, reinterpret_cast<const long long*>(b2->window_start), rg_lens() + nB, rg_off() + nB, rg_n1, b2->B, b2->S, (long long)b2->store_frames,
+                                      b2->shift_static, b2->shift_gripper, wl_frame[1], wl_shift[1][0], wl_shift[1][1]);
         return 0;
     }
     // argument check of the frame-store fields, before any launch (hulc_forward_loss / _pair, hulc_validate): true = error set
     static bool store_args_bad(const hulc_batch* b) {
         if (b->window_len && !b->window_start) { hulc_set_error("window_len (variable-length windows) needs window_start (the frame store)"); return true; }
+        if (b->window_len_host && !b->window_start) { hulc_set_error("window_len_host (ragged encoder pass) needs window_start (the frame store)"); return true; }
         if (!b->window_start) return false;
         if (b->store_frames < 1) { hulc_set_error("window_start (frame store) needs store_frames >= 1 (got %lld)", (long long)b->store_frames); return true; }
         // fixed windows need S frames in the store; with window_len a window may be as short as one frame
-        if (!b->frames_u8 || (!b->window_len && b->store_frames < b->S)) { hulc_set_error("window_start (frame store) needs frames_u8 and store_frames >= S (got frames_u8=%d, store_frames=%lld, S=%d)", b->frames_u8, (long long)b->store_frames, b->S); return true; }
+        if (!b->frames_u8 || (!b->window_len && !b->window_len_host && b->store_frames < b->S)) { hulc_set_error("window_start (frame store) needs frames_u8 and store_frames >= S (got frames_u8=%d, store_frames=%lld, S=%d)", b->frames_u8, (long long)b->store_frames, b->S); return true; }
         return false;
     }
     // b - sum_k W16 of the two conv1 layers (Conv1Src::fold), recomputed after every weight refresh, only when a uint8 batch asks for it
@@ -108,14 +154,15 @@
     static double conv_wgrad_bytes(const ConvW& c, const ConvGeom& g, int xbytes) { return (double)g.Nf * g.IH * g.IW * c.I * xbytes + (double)g.Nf * g.OH * g.OW * c.O * 2; }
 
     float* pend_zero[2] = {nullptr, nullptr};   // loss accumulators the next conv1 forward launch clears (16-bit engines)
-    // conv1 forward of one camera.  Paired pass (src2): frames [0, Nf/2) come from src, [Nf/2, Nf) from src2 — one launch per source, the later stages run on all Nf frames
+    // conv1 forward of one camera.  Paired pass (src2): the first src_frames(Nf, 0) frames (Nf/2; the ragged pass: the vis batch's N') come from src, the rest from
+    // src2 — one launch per source, the later stages run on all Nf frames
     void conv1_fwd(int k, const Conv1Src& src, int Nf, const Conv1Src* src2) {
         const EncW& e = encw(k); EncA& a = enca(k);
-        const int nf = src2 ? Nf / 2 : Nf;
-        const ConvGeom g = geom(nf, e.IH, 3, 8, 4);
         for (int h = 0; h < (src2 ? 2 : 1); ++h) {
+            const int nf = src2 ? src_frames(Nf, h) : Nf;
+            const ConvGeom g = geom(nf, e.IH, 3, 8, 4);
             const Conv1Src& sh = h ? *src2 : src;
-            const long long foff = h ? nf : 0, poff = foff * g.OH * g.OW;
+            const long long foff = h ? src_frames(Nf, 0) : 0, poff = foff * g.OH * g.OW;
             if constexpr (std::is_same<T, h16_t>::value) {
                 const double px = (double)nf * g.OH * g.OW;
                 TimerScope ts(this, "conv1_fwd", "hbm", 2.0 * px * 32 * 192, (double)nf * 3 * e.IH * e.IH * (sh.u8 ? 1 : 4) + px * 32 * 2);
@@ -166,7 +213,7 @@
         if (defer_tail) return;
         { EpiP ep = epi(a.f1, false); ep.relu = 1; lin_fwd(fin, 128, Nf, e.fc1, ep, 512); }
         { EpiP ep = epi(a.f2, true); lin_fwd(a.f1, 512, Nf, e.fc2, ep, 64); }
-        ln_fwd(a.f2, 64, Nf, 64, e.lng, e.lnb, emb + k * 64, EMB, nullptr, 0, a.lnst);
+        ln_fwd(a.f2, 64, Nf, 64, e.lng, e.lnb, enc_emb() + k * 64, EMB, nullptr, 0, a.lnst);
     }
     // conv2 / conv3 forward of BOTH cameras as one launch (conv_reg.h launch_conv_reg_jobs): the gripper camera's job runs in the static camera's 8-wave form on its
     // share of the persistent workgroups, its prologue and tail under the static job's throughput.  false = nothing launched (shape-decided); the timer accounts
@@ -216,7 +263,7 @@
                 c.x = e.gripper ? a.g0 : a.ss; c.W1 = e.fc1.W; c.W2 = e.fc2.W; c.b1 = e.fc1.b32; c.b2 = e.fc2.b32;
                 c.lng = e.lng; c.lnb = e.lnb; c.f1 = a.f1; c.f2 = a.f2; c.lnst = a.lnst; c.col0 = k * 64;
             }
-            q.emb = emb; q.Nf = Nf; q.ldemb = EMB;
+            q.emb = enc_emb(); q.Nf = Nf; q.ldemb = EMB;
             launch_enc_tail_fwd(st, q);
         }
     }
@@ -255,7 +302,7 @@
                 c.xmask = a.g0; c.dlng = e.dlng; c.dlnb = e.dlnb;       // g0 is fc7's ReLU output; the static camera's tail input (ss) has no mask
                 c.d_f2 = a.d_f2t; c.d_f1 = a.d_f1; c.dx_f32 = a.d_ss; c.dx_t = a.d_g0; c.col0 = k * 64;
             }
-            q.demb = demb; q.Nf = Nf; q.ldemb = EMB;
+            q.demb = enc_demb(); q.Nf = Nf; q.ldemb = EMB;
             launch_enc_tail_bwd(st, q);
             // weight / bias gradients of the four Linear layers: one launch, frames split over blockIdx.y, operands read as they lie.  Every row chunk writes its own
             // slab; the slabs are summed into the gradient by the encoders' one unpack launch (no per-element atomics here: 1.5 M of them made this launch 39 us).
@@ -328,12 +375,12 @@
     void conv1_wgrad(int k, const Conv1Src& src, int Nf, const Conv1Src* src2) {
         const EncW& e = encw(k); EncA& a = enca(k);
         const ConvW& c = e.c1;
-        const int nf = src2 ? Nf / 2 : Nf;
-        const ConvGeom g = geom(nf, e.IH, 3, 8, 4);
-        const long long npix = (long long)nf * g.OH * g.OW;
         for (int h = 0; h < (src2 ? 2 : 1); ++h) {
+            const int nf = src2 ? src_frames(Nf, h) : Nf;
+            const ConvGeom g = geom(nf, e.IH, 3, 8, 4);
+            const long long npix = (long long)nf * g.OH * g.OW;
             const Conv1Src& sh = h ? *src2 : src;
-            const long long foff = h ? nf : 0;
+            const long long foff = h ? src_frames(Nf, 0) : 0;
             const T* dy = a.dact1 + foff * g.OH * g.OW * 32;
             const float* x = nullptr;
             if constexpr (std::is_same<T, float>::value) x = sh.u8 ? x32[k] + foff * 3 * e.IH * e.IH : reinterpret_cast<const float*>(sh.X);
@@ -385,13 +432,14 @@
             const int Kc = cS.I * cS.KH * cS.KW;
             if (cS.O != 32 || cG.O != 32 || Kc != 192 || cG.I * cG.KH * cG.KW != 192) return false;
             if (!unpack_room(2, 1024 * (int64_t)cS.O * Kc)) return false;      // (at most max_blocks = 1024 slabs)
-            const int ns_src = src2 ? 2 : 1, nf = src2 ? Nf / 2 : Nf;
+            const int ns_src = src2 ? 2 : 1;
             Wgrad1Job J[4]; int nj = 0;
             double fl = 0, by = 0;
             for (int k = 0; k < 2; ++k) {
-                const ConvGeom g = geom(nf, encw(k).IH, 3, 8, 4);
                 for (int h = 0; h < ns_src; ++h) {
-                    Wgrad1Job q{}; q.S = h ? src2[k] : src[k]; q.work_ctr = next_ctr(); q.dY = enca(k).dact1 + (long long)h * nf * g.OH * g.OW * 32; q.bias_part = encw(k).c1.db;
+                    const int nf = src2 ? src_frames(Nf, h) : Nf;
+                    const ConvGeom g = geom(nf, encw(k).IH, 3, 8, 4);
+                    Wgrad1Job q{}; q.S = h ? src2[k] : src[k]; q.work_ctr = next_ctr(); q.dY = enca(k).dact1 + (long long)(h ? src_frames(Nf, 0) : 0) * g.OH * g.OW * 32; q.bias_part = encw(k).c1.db;
                     q.Nf = nf; q.IH = g.IH; q.IW = g.IW; q.OH = g.OH; q.OW = g.OW;
                     J[nj++] = q;
                     fl += conv_wgrad_flops(cS, g); by += conv_wgrad_bytes(cS, g, q.S.u8 ? 1 : 4);
@@ -498,7 +546,7 @@
     void head_bwd(int k, int Nf, bool tail_done) {
         const EncW& e = encw(k); EncA& a = enca(k);
         if (!tail_done) {
-            ln_bwd(demb + k * 64, EMB, a.f2, 64, a.lnst, e.lng, Nf, 64, nullptr, 0, 0, a.d_f2t, 64, e.dlng, e.dlnb);
+            ln_bwd(enc_demb() + k * 64, EMB, a.f2, 64, a.lnst, e.lng, Nf, 64, nullptr, 0, 0, a.d_f2t, 64, e.dlng, e.dlnb);
             { EpiP ep = epi(a.d_f1, false); ep.mask = a.f1; lin_dgrad(a.d_f2t, Nf, e.fc2, ep, dense_out(512)); }
             lin_wgrad(a.d_f2t, a.f1, 512, Nf, 64, 512, e.fc2.dW, 512, e.fc2.db);
         }

@@ -76,9 +76,14 @@
         {
             const Conv1Src src[2] = {conv1_src(*b, false), conv1_src(*b, true)}, src2[2] = {conv1_src(cur2, false), conv1_src(cur2, true)};
             const bool tail_fused = enc_tail_fusable();
-            enc_fwd_both(src, pair ? src2 : nullptr, N, tail_fused);
+            // ragged pass (window_len_host): the encoders run on the N' real frames and write compact rows, which are then expanded to the (B,S,EMB) rows everything
+            // below reads; the transformer input is a function of the batch row, so pr_fwd writes it with its own launch (x0_done stays false)
+            const int Nenc = enc_frames(N);
+            enc_fwd_both(src, pair ? src2 : nullptr, Nenc, tail_fused);
             x0_done = false;
-            if (tail_fused) enc_tail_fwd_both(N, !mcil && tr_fused_mode && S <= 64 && EMB == 128, S, dp);
+            if (tail_fused) enc_tail_fwd_both(Nenc, !ragged() && !mcil && tr_fused_mode && S <= 64 && EMB == 128, S, dp);
+            if (ragged()) launch_rows_expand<T>(st, emb_c, rg_lens(), rg_off(), B, S, EMB, emb);
+            enc_frames_last = Nenc;
         }
         // ---- goal encoder (goal_encoders.py:31-36 / 64-69)
         if (pair) {       // rows [0, Bv): visual goal = emb[:, -1]; rows [Bv, B): language goal
@@ -220,6 +225,8 @@
             if (store_args_bad(b)) return 1;
             if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
         }
+        if ((vb->window_len_host != nullptr) != (lb->window_len_host != nullptr)) {
+            hulc_set_error("hulc_forward_loss_pair: window_len_host (ragged encoder pass) must be given for both modalities or for neither"); return 1; }
         if (vb->frames_u8 != lb->frames_u8 || vb->actions_absolute != lb->actions_absolute || vb->max_rel_pos != lb->max_rel_pos || vb->max_rel_orn != lb->max_rel_orn) {
             hulc_set_error("hulc_forward_loss_pair: both modalities must use the same ingest options"); return 1; }
         if ((vb->plan_idx != nullptr) != (lb->plan_idx != nullptr) || (vb->plan_eps != nullptr) != (lb->plan_eps != nullptr)) {
@@ -280,7 +287,7 @@
         if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
         if (cfg.kind == HULC_KIND_HULC && b->plan_idx && plan_idx_bad(b->plan_idx, b->B * NCAT, "hulc_forward_loss")) return 1;
         cur = *b; cur_lw = lw; cur_cw = cw; have_fwd = false; val_clip_n = 0;
-        if (window_len_expand(*b, pair ? pairBv : b->B, 0) || (pair && window_len_expand(cur2, cur2.B, 1))) return 1;
+        if (window_tables(*b, pair ? pairBv : b->B, pair ? &cur2 : nullptr)) return 1;
         const int B = b->B, S = b->S, N = B * S, SB = S * B;
         const bool hulc = cfg.kind == HULC_KIND_HULC;
         const float dp = cfg.dropout_p;

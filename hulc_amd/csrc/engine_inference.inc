@@ -48,7 +48,7 @@
         if (hulc && ((nz->plan_idx_pr && plan_idx_bad(nz->plan_idx_pr, b->B * NCAT, "hulc_validate (plan_idx_pr)")) ||
                      (nz->plan_idx_pp && plan_idx_bad(nz->plan_idx_pp, b->B * NCAT, "hulc_validate (plan_idx_pp)")))) return 1;
         cur = *b; have_fwd = false; pair = false; val_clip_n = 0;
-        if (window_len_expand(*b, b->B, 0)) return 1;
+        if (window_tables(*b, b->B, nullptr)) return 1;
         const int B = b->B, S = b->S, SB = S * B;
         HIP_CHECK(hipMemsetAsync(valm, 0, 32 * sizeof(float), st));
         trunk_fwd(b, 0.f);

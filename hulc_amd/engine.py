@@ -94,13 +94,17 @@ class StepEngine:
         `window_start` (B,) int64 selects the FRAME STORE form (hulc_batch::window_start): rgb_static / rgb_gripper are then the device-resident
         stores (F,H,W,3) uint8 and window b = store frames [window_start[b], window_start[b] + S) — nothing is materialised per step.
         `window_len` (B,) int32 on the device next to it: window b holds that many real frames and is padded to S by repeating its last one
-        (hulc_batch::window_len)."""
+        (hulc_batch::window_len).
+        `window_len_host` (B,) int32 numpy array or CPU tensor, valid only with window_start: the same lengths on the HOST select the ragged encoder
+        pass (hulc_batch::window_len_host) — the perceptual encoders run on the real frames only; `window_len` is then ignored by the library.  It
+        stays on the host: a device tensor is a ValueError."""
+        wlh = StepEngine._host_lens(mb)
         rel = {}
         if mb.get("actions_absolute"):        # RelativeActions (transforms.py:32-56) applied on the device
             rel = dict(actions_absolute=1, max_rel_pos=float(mb.get("max_rel_pos", 0.02)), max_rel_orn=float(mb.get("max_rel_orn", 0.05)))
         if mb["rgb_static"].dtype != torch.uint8:
-            if mb.get("window_len") is not None:
-                raise ValueError("window_len needs the frame store form: uint8 stores and window_start")
+            if mb.get("window_len") is not None or wlh is not None:
+                raise ValueError("window_len / window_len_host need the frame store form: uint8 stores and window_start")
             return rel
         if mb["rgb_gripper"].dtype != torch.uint8 or mb["rgb_static"].shape[-1] != 3 or mb["rgb_gripper"].shape[-1] != 3:
             raise ValueError("uint8 ingest expects both cameras as uint8 (B,S,H,W,3) tensors")
@@ -121,7 +125,25 @@ class StepEngine:
             if not torch.is_tensor(wl) or not wl.is_cuda or wl.dtype != torch.int32 or wl.dim() != 1 or wl.shape[0] != mb["actions"].shape[0]:
                 raise ValueError("frame store: window_len must be a (B,) int32 tensor on the device")
             f["window_len"] = ptr(wl)
+        if wlh is not None:      # without window_start the library reports the error (hulc_last_error)
+            f["window_len_host"] = ptr(wlh)
         return f
+
+    @staticmethod
+    def _host_lens(mb: Dict) -> Optional[torch.Tensor]:
+        """The batch's `window_len_host` as a contiguous (B,) int32 CPU tensor, or None; raises for a device tensor or a wrong shape."""
+        wl = mb.get("window_len_host")
+        if wl is None:
+            return None
+        if torch.is_tensor(wl):
+            if wl.device.type != "cpu":
+                raise ValueError(f"window_len_host must stay on the host (numpy array or CPU tensor), got a tensor on {wl.device}")
+            wl = wl.to(torch.int32)
+        else:
+            wl = torch.from_numpy(np.ascontiguousarray(wl, np.int32))
+        if wl.dim() != 1 or wl.shape[0] != mb["actions"].shape[0]:
+            raise ValueError("window_len_host must be a (B,) int32 array")
+        return wl.contiguous()
 
     def _batch_struct(self, mb: Dict, is_lang: bool, step: int, keep: list):
         B, S = mb["actions"].shape[:2]
@@ -613,6 +635,11 @@ class StepEngine:
         v = C.c_int64()
         L.check(self.lib.hulc_get_option(self.ctx, name.encode(), C.byref(v)))
         return int(v.value)
+
+    def encoder_frames(self) -> int:
+        """Frames the perceptual encoders ran on in the last forward_loss / forward_loss_pair / validate: B*S (the pair: both batches), or the
+        number of real frames N' of a batch with `window_len_host` (hulc_get_option "encoder_frames")."""
+        return self.get_option("encoder_frames")
 
     def allreduce_grads(self, bucket_dtype: str = "fp32"):
         """One SUM all-reduce of the whole gradient buffer (after backward()); stream-ordered, no host sync."""

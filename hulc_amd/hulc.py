@@ -591,6 +591,8 @@ class Hulc(torch.nn.Module):
             mb["window_start"] = dataset_batch["window_start"].to(device=device, dtype=torch.int64)
         if dataset_batch.get("window_len") is not None:        # variable-length windows padded to S by repetition (hulc_batch::window_len)
             mb["window_len"] = dataset_batch["window_len"].to(device=device, dtype=torch.int32)
+        if dataset_batch.get("window_len_host") is not None:   # ragged encoder pass (hulc_batch::window_len_host): the lengths stay on the HOST, as they are
+            mb["window_len_host"] = dataset_batch["window_len_host"]
         if dataset_batch.get("staged") is not None:            # two-tier frame store: the engine marks the handle once the slots' last reader is enqueued
             mb["staged"] = dataset_batch["staged"]
         for k in ("shift_static", "shift_gripper", "pad_static", "pad_gripper"):       # optional RandomShiftsAug draws of the ingest path

@@ -24,7 +24,8 @@ class HulcBatch(C.Structure):
                 ("plan_idx", C.c_void_p), ("aux_rows", C.c_void_p), ("n_aux", C.c_int32), ("step", C.c_uint64),
                 ("frames_u8", C.c_int32), ("pad_static", C.c_int32), ("pad_gripper", C.c_int32), ("shift_static", C.c_void_p),
                 ("shift_gripper", C.c_void_p), ("plan_eps", C.c_void_p), ("actions_absolute", C.c_int32), ("max_rel_pos", C.c_float),
-                ("max_rel_orn", C.c_float), ("window_start", C.c_void_p), ("store_frames", C.c_int64), ("window_len", C.c_void_p)]
+                ("max_rel_orn", C.c_float), ("window_start", C.c_void_p), ("store_frames", C.c_int64), ("window_len", C.c_void_p),
+                ("window_len_host", C.c_void_p)]      # HOST (B) int32: the ragged encoder pass
 
 
 class HulcStoreTables(C.Structure):
@@ -99,7 +100,8 @@ EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_s
            "hulc_bind_params", "hulc_prepare_weights", "hulc_zero_grads", "hulc_flush_grads", "hulc_forward_loss", "hulc_forward_loss_pair", "hulc_backward", "hulc_backward_part",
            "hulc_adam_step", "hulc_optimizer_step", "hulc_comm_unique_id", "hulc_comm_prepare", "hulc_comm_init", "hulc_comm_destroy", "hulc_comm_buckets", "hulc_comm_stats", "hulc_comm_size", "hulc_comm_timeline", "hulc_allreduce_grads", "hulc_backward_allreduce", "hulc_scaler_enable", "hulc_scaler_get", "hulc_scaler_set", "hulc_grad_clip_set", "hulc_grad_norm_get", "hulc_validate", "hulc_store_gather", "hulc_store_stage", "hulc_store_stage_join", "hulc_store_stage_stats", "hulc_clip_gt_encode", "hulc_clip_gt_scores", "hulc_aux_heads_enable", "hulc_aux_weights_set", "hulc_aux_losses_get", "hulc_rollout_reset", "hulc_rollout_plan", "hulc_rollout_act", "hulc_rollout_get_goal", "hulc_rollout_set_state", "hulc_rollout_envs_init", "hulc_rollout_envs_reset", "hulc_rollout_envs_plan", "hulc_rollout_envs_act", "hulc_rollout_envs_get_state", "hulc_rollout_envs_set_state", "hulc_sbert_create", "hulc_sbert_destroy", "hulc_sbert_set_stream", "hulc_sbert_bind", "hulc_sbert_encode", "hulc_set_kl_beta", "hulc_set_dropout", "hulc_set_option", "hulc_get_option", "hulc_timers_enable", "hulc_timers_read", "hulc_get_tensor", "hulc_get_plan_idx", "hulc_k_gemm_nt", "hulc_k_cast", "hulc_k_trread_probe", "hulc_k_conv_wgrad", "hulc_k_conv1_wgrad_u8", "hulc_k_conv1_interior_groups", "hulc_k_conv_tile", "hulc_k_camera_split", "hulc_k_conv_pair", "hulc_k_skinny", "hulc_k_attention", "hulc_k_rnn_persist", "hulc_k_rnn_persist_flag_words", "hulc_k_clip_loss", "hulc_k_clip_loss_fp32", "hulc_k_mia_head", "hulc_k_cosine_dist", "hulc_k_spatial_softmax64", "hulc_k_enc_tail_fwd", "hulc_k_enc_tail_bwd", "hulc_k_logistic_loss",
            "hulc_k_plan_kl_sample", "hulc_k_st_softmax_bwd", "hulc_k_plan_gather", "hulc_k_plan_scatter_grad", "hulc_k_normal_kl_sample", "hulc_k_normal_rsample_bwd",
-           "hulc_k_layernorm_fwd", "hulc_k_layernorm_bwd", "hulc_k_layernorm_mean", "hulc_k_tr_layer_fwd", "hulc_k_tr_ffn_bwd", "hulc_k_tr_attn_bwd"]
+           "hulc_k_layernorm_fwd", "hulc_k_layernorm_bwd", "hulc_k_layernorm_mean", "hulc_k_tr_layer_fwd", "hulc_k_tr_ffn_bwd", "hulc_k_tr_attn_bwd",
+           "hulc_k_window_compact", "hulc_k_rows_expand", "hulc_k_rows_reduce"]
 
 _lib = None
 
@@ -240,6 +242,11 @@ def load():
         lib.hulc_k_tr_layer_fwd.argtypes = [C.c_int32, C.POINTER(HulcTrLayerJob), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
         lib.hulc_k_tr_ffn_bwd.argtypes = [C.c_int32, C.POINTER(HulcTrFfnBwdJob), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]
         lib.hulc_k_tr_attn_bwd.argtypes = [C.c_int32, C.POINTER(HulcTrAttnBwdJob), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_void_p]
+    if hasattr(lib, "hulc_k_rows_reduce") or not os.environ.get("HULC_LIB_PATH"):
+        P, I, Q = C.c_void_p, C.c_int32, C.c_int64
+        lib.hulc_k_window_compact.argtypes = [P, P, P, I, I, I, Q, P, P, P, P, P, P]
+        lib.hulc_k_rows_expand.argtypes = [I, P, P, P, I, I, I, P, P]
+        lib.hulc_k_rows_reduce.argtypes = [P, P, P, I, I, I, P, P]
     _lib = lib
     return lib
 

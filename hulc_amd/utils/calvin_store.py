@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .frame_store import FrameStore
+from .frame_store import FrameStore, ragged_plan
 
 
 class _LangDatasetInfo:
@@ -102,12 +102,14 @@ class CalvinStoreDataModule:
     resident_gb (None: every split wholly on the device): GiB of device memory for the resident frames of both splits (split_budget) — validation resident
     first, training gets the rest; the episodes beyond a store's cut live in pinned host memory and their windows are staged into a ring of
     2 x batch_size x len(modalities) slots of max_window_size frames.  train_dataloader stages batch n + 1 before it yields batch n, so the copies
-    wait only for step n - 1 and run under step n.  The windows drawn are the same as without a budget (same seed, same rng stream)."""
+    wait only for step n - 1 and run under step n.  The windows drawn are the same as without a budget (same seed, same rng stream).
+    ragged_encoders (default false): the batches carry `window_len_host`, so the perceptual encoders run on the real frames of the windows only
+    (INTEGRATION.md 4f); the windows drawn and everything else in the batch are the same."""
 
     def __init__(self, root_data_dir: str, batch_size: int = 32, min_window_size: int = 20, max_window_size: int = 32, lang_folder: str = "lang_annotations",
                  aux_lang_loss_window: int = 8, modalities: Sequence[str] = ("vis", "lang"), pad_static: int = 10, pad_gripper: int = 4, val_batches: int = 1,
                  device: str = "cuda:0", seed: int = 0, rank: Optional[int] = None, world: Optional[int] = None, training_dir: str = "training",
-                 validation_dir: str = "validation", resident_gb: Optional[float] = None, **_unused):
+                 validation_dir: str = "validation", resident_gb: Optional[float] = None, ragged_encoders: bool = False, **_unused):
         if not root_data_dir or not os.path.isdir(str(root_data_dir)):
             raise FileNotFoundError(f"datamodule.root_data_dir={root_data_dir!r} is not a directory")
         if rank is None or world is None:
@@ -123,6 +125,7 @@ class CalvinStoreDataModule:
         self.stores: Dict[str, FrameStore] = {}
         self.train_datasets, self.val_datasets = {}, {}
         self.resident_gb = None if resident_gb is None else float(resident_gb)
+        self.ragged_encoders = bool(ragged_encoders)      # every batch carries the host lens of its draw as window_len_host: the ragged encoder pass
         stage_slots = 2 * self.batch_size * len(self.modalities)      # two batches: the one the step reads and the one staged ahead
         budget = {"train": None, "val": None}
         if self.resident_gb is not None:
@@ -177,7 +180,7 @@ class CalvinStoreDataModule:
                 (starts, lens, (hs, hl)), rows, aux = st.sample_windows(self.batch_size, self.min_window, self.S, rng, return_host=True), None, None
             if self.record_windows:
                 self.window_log.append(dict(split=split, modality=m, starts=hs.copy(), lens=hl.copy()))
-            drawn[m] = dict(starts=starts, lens=lens, rows=rows, aux=aux, staged=st.stage(hs, self.S, hl) if st.tiered else None)
+            drawn[m] = dict(starts=starts, lens=lens, host_lens=hl, rows=rows, aux=aux, staged=st.stage(hs, self.S, hl) if st.tiered else None)
         return drawn
 
     def _assemble(self, split: str, drawn: Dict, tg: Optional[torch.Generator]):
@@ -188,6 +191,8 @@ class CalvinStoreDataModule:
                 d["idx"] = w["rows"].to(torch.int64)          # annotation index: lang_lookup is the identity
             else:
                 d = st.batch(w["starts"], self.S, lens=w["lens"], shifts=tg is not None, generator=tg, staged=w["staged"])
+            if self.ragged_encoders:      # the host array of the draw, clamped as batch() clamps the device lens: no read-back
+                d["window_len_host"] = ragged_plan(w["host_lens"], self.S, st.F)[0]
             out[m] = d
         return out
 

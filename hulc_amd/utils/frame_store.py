@@ -41,6 +41,19 @@ def plan_tiers(episode_ends: Sequence[int], resident_frames: int) -> int:
     return int(fit[-1]) if fit.size else 0
 
 
+def ragged_plan(lens, S: int, store_frames: int):
+    """The host arithmetic of the ragged encoder pass (include/hulc_hip.h hulc_batch::window_len_host), restated: -> (L, offsets, n_real) with
+    L[b] = clamp(lens[b], 1, min(S, store_frames)) (B,) int32, offsets[b] = sum of L[:b] (B + 1,) int32 and n_real = offsets[B] = N', the number of
+    frames the perceptual encoders run on.  Compact frame offsets[b] + t (t < L[b]) is frame t of window b; batch row (b, t) reads compact row
+    offsets[b] + min(t, L[b] - 1).  Plain host arithmetic."""
+    if int(S) < 1 or int(store_frames) < 1:
+        raise ValueError(f"ragged_plan needs S >= 1 and store_frames >= 1 (got {S}, {store_frames})")
+    ln = np.asarray(lens.detach().cpu().numpy() if torch.is_tensor(lens) else lens).astype(np.int64).reshape(-1)
+    L = np.clip(ln, 1, min(int(S), int(store_frames))).astype(np.int32)
+    offsets = np.concatenate([[0], np.cumsum(L, dtype=np.int64)]).astype(np.int32)
+    return L, offsets, int(offsets[-1])
+
+
 class StagedWindows:
     """What `FrameStore.stage` hands back for one batch of windows: `frame_starts` (B,) int64, the starts to put into `window_start` — resident windows
     keep theirs, host-tier windows name their staging slot —, `table_starts` the original ones for the per-frame tables, `lens`, the `ticket` of the
@@ -344,12 +357,16 @@ class FrameStore:
     def batch(self, starts: Optional[torch.Tensor], S: int, actions: Optional[torch.Tensor] = None, robot_obs: Optional[torch.Tensor] = None, shifts: bool = False,
               generator: Optional[torch.Generator] = None, lang: Optional[torch.Tensor] = None, use_for_aux: Optional[torch.Tensor] = None,
               lens: Optional[torch.Tensor] = None, lang_rows: Optional[torch.Tensor] = None, absolute: bool = False, engine=None,
-              staged: Optional[StagedWindows] = None) -> Dict:
+              staged: Optional[StagedWindows] = None, ragged: bool = False) -> Dict:
         """The reference-shaped batch dict of one modality (hulc/models/hulc.py:395-414) for `Hulc.training_step` / `validation_step`: the stores stand in
         for rgb_obs, `window_start` names the windows.  actions / robot_obs: (B,S,7) / (B,S,15) tensors, or None to gather them from the store's own
         per-frame tables.  shifts=True draws the per-frame RandomShiftsAug offsets (transforms.py:8-29) on the device.
         lens (B,) int32: variable-length windows padded to S (`window_len`).  lang_rows (B,) int32: rows of the store's lang table (instead of `lang`).
         absolute: the actions table holds absolute targets, padding repeats all seven dims.
+        ragged=True (needs lens): the clamped lens also go into the dict on the HOST, as `window_len_host` (B,) int32 numpy — the engine then runs the
+        perceptual encoders on the real frames of the windows only (hulc_batch::window_len_host; `ragged_plan` restates its arithmetic).  lens given as
+        a numpy array or CPU tensor are taken as they are; a device tensor costs one .cpu() (a synchronisation — `sample_windows(return_host=True)`
+        hands out the host arrays of its draw).  Works with `staged=`: staging rewrites only the starts.
         With an engine (argument, or attach()) the tables are gathered by hulc_store_gather — required for `lens`, whose padding rules live there;
         without one, fixed windows are gathered by torch indexing.  The starts are clamped ONCE here, so frames and tables always name the same rows.
         Tiered stores: `staged` = the handle `stage` returned for these windows (starts / lens are then taken from it); without one the windows are
@@ -357,6 +374,14 @@ class FrameStore:
         starts rewritten to the staging slots, the tables are gathered with the original starts, and the dict carries the handle as `staged`."""
         engine = engine if engine is not None else self.engine
         table_starts = None
+        lens_host = None
+        if ragged and not self.tiered:
+            if lens is None:
+                raise ValueError("ragged=True needs lens (the windows' real frame counts)")
+            lens_host = np.asarray(lens.detach().cpu().numpy() if torch.is_tensor(lens) else lens).astype(np.int64).reshape(-1)
+            lens_host = np.clip(lens_host, 1, min(int(S), self.F)).astype(np.int32)
+        if lens is not None and not torch.is_tensor(lens):
+            lens = torch.from_numpy(np.ascontiguousarray(lens, np.int32))
         if self.tiered:
             if staged is None:
                 staged = self.stage(starts, S, lens, engine=engine)
@@ -366,6 +391,10 @@ class FrameStore:
             starts = torch.from_numpy(staged.frame_starts).to(self.device)
             table_starts = torch.from_numpy(staged.table_starts).to(self.device)
             lens = None if staged.lens is None else torch.from_numpy(staged.lens).to(self.device)
+            if ragged:
+                if staged.lens is None:
+                    raise ValueError("ragged=True needs lens (the windows' real frame counts)")
+                lens_host = staged.lens.astype(np.int32)      # clamped by stage()
         elif staged is not None:
             raise ValueError("staged= belongs to a tiered store (resident_frames=...)")
         starts = starts.to(self.device, torch.int64)
@@ -406,6 +435,8 @@ class FrameStore:
                  pad_static=self.pad_static, pad_gripper=self.pad_gripper)
         if lens is not None:
             d["window_len"] = lens
+        if lens_host is not None:
+            d["window_len_host"] = lens_host
         if staged is not None:
             d["staged"] = staged
         if shifts:

@@ -103,6 +103,20 @@ typedef struct hulc_batch {
      * t >= L are ignored).  A short window may therefore start closer to the end of the store than S frames; store_frames >= 1 is all it needs.
      * Nothing downstream changes: the model sees S frames, the visual goal emb[:, -1] is the last real frame, nothing is masked (as in the reference). */
     const int32_t* window_len;
+    /* ---- ragged encoder pass: the perceptual encoders run on the REAL frames of variable-length windows only (hulc_forward_loss, hulc_forward_loss_pair,
+     * hulc_validate; the rollout calls ignore it).
+     * window_len_host: (B) int32 in HOST memory, read during the call only; requires window_start.  NULL = everything above, bit for bit and launch for launch.
+     * The lengths mean what window_len means, and window_len is IGNORED when this is given: the engine clamps L_b = clamp(len_b, 1, min(S, store_frames)) on the
+     * host, computes off_b = sum_{i<b} L_i and N' = sum_b L_b, uploads them and derives every table and grid from that one array (a host pointer because the
+     * host must know N' to size the launches).  The encoders run forward and backward on N' compact frames: compact frame off_b + t (t < L_b) is store frame
+     * clamp(window_start[b], 0, store_frames - L_b) + t with the RandomShiftsAug shift row b * S + t.  Row (b, t) of the (B,S,128) embedding is then the copy
+     * of compact row off_b + min(t, L_b - 1) — the same values the padded pass computes S - L_b more times — and nothing downstream of the embedding changes.
+     * Backward: the embedding gradient is accumulated as always, then compact row off_b + t takes row (b, t) for t < L_b - 1 and row off_b + L_b - 1 the sum
+     * ((g[b, L_b-1] + g[b, L_b]) + ...) + g[b, S-1], in fp32 in ascending t without atomics (two runs give the same bits), and the encoder backward runs on N'
+     * frames.  Forward results are bit-identical to the padded pass; encoder gradients differ by the order of the sums over a window's duplicates (and, in the
+     * 16-bit engines, by rounding the summed gradient once instead of once per duplicate).  In hulc_forward_loss_pair both batches give it or neither does.
+     * hulc_get_option "encoder_frames" reports the frame count of the last pass. */
+    const int32_t* window_len_host;
 } hulc_batch;
 
 /* out_losses (device or host pointer, see `losses_on_host`): [total_mod, kl_scaled, action, clip] of this modality,
@@ -448,7 +462,9 @@ int hulc_set_option(hulc_ctx* ctx, const char* name, int64_t value);
  * timed out — the context then runs one launch per time step; a failed launch never reaches the weights: its optimizer step skips itself on the
  * device, and calls that end in a synchronisation are run again), "persistent_rnn_fallbacks" counts such events.  More settable names:
  * "persist_under_comm" (default 0: recurrences that follow an issued bucket of hulc_backward_allreduce run one launch per step, because RCCL's
- * kernels hold CUs), "comm_timing" (hulc_comm_timeline), "debug_poison_partials" (tests). */
+ * kernels hold CUs), "comm_timing" (hulc_comm_timeline), "debug_poison_partials" (tests).  Read-only: "encoder_frames" = the number of frames the
+ * perceptual encoders ran on in the last hulc_forward_loss / _pair or hulc_validate: B * S (the pair: both batches' sum), or N' with
+ * hulc_batch::window_len_host. */
 int hulc_get_option(hulc_ctx* ctx, const char* name, int64_t* value);
 
 /* HIP-event timers around the launches of each kernel class, recorded on the context's stream (bench.py's roofline leg).
@@ -627,6 +643,19 @@ int hulc_k_layernorm_bwd(int32_t dtype, const float* dy, int64_t lddy, const flo
 /* layernorm_mean_kernel: x [B][S][n] fp32 -> yout [B][S][n] = LayerNorm(x), stats [B*S][2], out [B][n] T = mean over S of yout. */
 int hulc_k_layernorm_mean(int32_t dtype, const float* x, int32_t B, int32_t S, int32_t n, const float* g, const float* b, float* stats, void* out, float* yout,
                           void* hip_stream);
+/* ---- the row kernels of the ragged encoder pass (hulc_batch::window_len_host; csrc/conv_wgrad.h), launched with the engine's grid and block.  lens (B) int32
+ * holds CLAMPED lengths 1 <= lens[b] <= min(S, store_frames), off (B + 1) int32 their exclusive prefix sum; both on the device.  N' = off[B].
+ * hulc_k_window_compact: window_compact_kernel.  frame_out [N'] int64: frame_out[off[b] - off_base + t] = clamp(window_start[b], 0, store_frames - lens[b]) + t for
+ *   t < lens[b]; shift_*_out [N'][2] = shift_*[b * S + t] (each pair optional). */
+int hulc_k_window_compact(const int64_t* window_start, const int32_t* lens, const int32_t* off, int32_t off_base, int32_t B, int32_t S, int64_t store_frames,
+                          const int32_t* shift_static, const int32_t* shift_gripper, int64_t* frame_out, int32_t* shift_static_out, int32_t* shift_gripper_out,
+                          void* hip_stream);
+/* hulc_k_rows_expand: rows_expand_kernel.  dst [B*S][n] = src [N'][n] rows off[b] + min(t, lens[b] - 1), copied in 16-byte pieces; elem_bytes 2 or 4,
+ *   n * elem_bytes a multiple of 16, both pointers 16-byte aligned. */
+int hulc_k_rows_expand(int32_t elem_bytes, const void* src, const int32_t* lens, const int32_t* off, int32_t B, int32_t S, int32_t n, void* dst, void* hip_stream);
+/* hulc_k_rows_reduce: rows_reduce_kernel.  src [B*S][n] fp32 -> dst [N'][n] fp32: dst[off[b] + t] = src[b, t] for t < lens[b] - 1, dst[off[b] + lens[b] - 1] =
+ *   ((src[b, lens[b]-1] + src[b, lens[b]]) + ...) + src[b, S-1] in fp32, ascending t, no atomics.  n a multiple of 4, both pointers 16-byte aligned. */
+int hulc_k_rows_reduce(const float* src, const int32_t* lens, const int32_t* off, int32_t B, int32_t S, int32_t n, float* dst, void* hip_stream);
 
 /* ---- the fused plan-recognition transformer layer kernels (csrc/tr_fused.h), launched as the engine launches them.  dtype = HULC_DTYPE_BF16 or HULC_DTYPE_F16
  * (the kernels exist in the 16-bit units only; HULC_DTYPE_F32 is refused).  d_model 128, 8 heads of 16, 2048 hidden units; N = B * S rows, window b = rows

@@ -168,6 +168,9 @@ val_batches: 1
 # GiB of device memory for the frames of both splits, or null = every split wholly in HBM.  With a budget, validation is resident first and
 # training gets the rest; the episodes beyond the cut stay in pinned host memory and are staged one step ahead (INTEGRATION.md 4e)
 resident_gb: null
+# true = the batches carry the host lens of their draws (window_len_host): the perceptual encoders run on the real frames of the padded windows only
+# (INTEGRATION.md 4f).  Same windows, same model inputs; encoder gradients differ by summation order
+ragged_encoders: false
 """)
 w("callbacks/default.yaml", """defaults:
   - kl_schedule: constant

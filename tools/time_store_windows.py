@@ -6,6 +6,12 @@ timed steps, each step timed with its own pair of events.
     HULC_LIB_PATH=<older libhulc_hip.so> python tools/time_store_windows.py --modes fixed      # the same fixed-window run on another build
 
     python tools/time_store_windows.py --modes padded --host-share 0,0.25,1.0      # two-tier store: that share of the frames in pinned host memory
+    python tools/time_store_windows.py --modes padded,ragged,ragged_full [--pair]  # the ragged encoder pass (hulc_batch::window_len_host) against the padded one
+
+Modes: `fixed` (window_start alone), `padded` (+ window_len, lens uniform min_window..S), `ragged` (the same lens also as window_len_host: the encoders
+run on the real frames only), `ragged_full` (window_len_host with every len = S: the ragged pass's own overhead at an unchanged frame count).
+--pair: the vis + lang paired pass (hulc_forward_loss_pair) on 2 x batch windows, each modality with its own windows and lens.
+profiles/ragged_windows.txt records the numbers of the commit that added window_len_host.
 
 Prints one JSON line per mode.  profiles/store_windows.txt records the numbers of the commit that added window_len, profiles/store_tiers.txt those
 of the two-tier store.
@@ -40,11 +46,12 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--modes", default="fixed,padded")
     ap.add_argument("--repeat", type=int, default=1, help="timed passes per mode (run-to-run spread inside one process)")
+    ap.add_argument("--pair", action="store_true", help="time the paired vis + lang pass (2 x batch windows) instead of one modality")
     ap.add_argument("--host-share", default="", help="comma-separated shares of the store kept in pinned host memory (two-tier store; padded windows)")
     args = ap.parse_args()
     B, S, F, dev = args.batch, args.seq, args.store, torch.device("cuda:0")
     dims = spec.ModelDims(kind="hulc", max_window=max(32, S), use_clip=False)
-    eng = StepEngine(dims, B, S, dtype=args.dtype, device=str(dev), dropout_p=0.1, seed=42, num_classes=dims.mix_classes)
+    eng = StepEngine(dims, 2 * B if args.pair else B, S, dtype=args.dtype, device=str(dev), dropout_p=0.1, seed=42, num_classes=dims.mix_classes)
     eng.load_numpy(spec.init_all(dims, seed=0))
     g = torch.Generator(device=dev)
     g.manual_seed(1)
@@ -57,13 +64,27 @@ def main():
               shift_gripper=torch.randint(0, 9, (B * S, 2), device=dev, generator=g, dtype=torch.int32))
     starts = torch.randint(0, F - S + 1, (64, B), device=dev, generator=g, dtype=torch.int64)
     lens = torch.randint(args.min_window, S + 1, (64, B), device=dev, generator=g, dtype=torch.int32)
+    full = torch.full((B,), S, device=dev, dtype=torch.int32)
+    lens_host, full_host = lens.cpu().numpy(), np.full(B, S, np.int32)      # the host arrays a datamodule holds of its own draws
+    lang = torch.nn.functional.normalize(torch.randn(B, 384, device=dev, generator=g), dim=-1)
+    mb_l = dict(mb, lang=lang, shift_static=mb["shift_static"].flip(0).contiguous(), shift_gripper=mb["shift_gripper"].flip(0).contiguous())
 
-    def step(i, padded):
-        d = dict(mb, window_start=starts[i % 64])
-        if padded:
+    def windows(d, i, mode):
+        d = dict(d, window_start=starts[i % 64])
+        if mode in ("padded", "ragged"):
             d["window_len"] = lens[i % 64]
+        if mode == "ragged":
+            d["window_len_host"] = lens_host[i % 64]
+        if mode == "ragged_full":
+            d["window_len"], d["window_len_host"] = full, full_host
+        return d
+
+    def step(i, mode):
         eng.zero_grads()
-        eng.forward_loss(d, False, 1.0, 3.0, step=i, sync_losses=False)
+        if args.pair:      # the lang modality draws the windows of another step
+            eng.forward_loss_pair(windows(mb, i, mode), windows(mb_l, i + 17, mode), 0.5, 3.0, step=i, sync_losses=False)
+        else:
+            eng.forward_loss(windows(mb, i, mode), False, 1.0, 3.0, step=i, sync_losses=False)
         eng.backward()
         eng.adam_step(lr=2e-4)
 
@@ -72,19 +93,21 @@ def main():
         eng.close()
         return
     for mode in args.modes.split(","):
-        padded = mode == "padded"
+        if mode not in ("fixed", "padded", "ragged", "ragged_full"):
+            raise SystemExit(f"unknown mode {mode!r}")
+        padded = mode in ("padded", "ragged")
         for rep in range(args.repeat):
             for i in range(args.warmup):
-                step(i, padded)
+                step(i, mode)
             torch.cuda.synchronize()
             ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
             for i, (a, b) in enumerate(ev):
                 a.record()
-                step(args.warmup + i, padded)
+                step(args.warmup + i, mode)
                 b.record()
             torch.cuda.synchronize()
             ms = np.array([a.elapsed_time(b) for a, b in ev])
-            print(json.dumps(dict(mode=mode, rep=rep, lib=os.environ.get("HULC_LIB_PATH") or "in-tree", B=B, S=S, store_frames=F, dtype=args.dtype, steps=args.steps,
+            print(json.dumps(dict(mode=mode, pair=bool(args.pair), encoder_frames=eng.encoder_frames() if hasattr(eng.lib, "hulc_k_rows_reduce") else None, rep=rep, lib=os.environ.get("HULC_LIB_PATH") or "in-tree", B=B, S=S, store_frames=F, dtype=args.dtype, steps=args.steps,
                                   median_ms=round(float(np.median(ms)), 4), mean_ms=round(float(ms.mean()), 4), p10_ms=round(float(np.percentile(ms, 10)), 4),
                                   p90_ms=round(float(np.percentile(ms, 90)), 4), mean_window_len=round(float(lens.float().mean()), 2) if padded else float(S))), flush=True)
     eng.close()
