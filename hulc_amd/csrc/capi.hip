@@ -350,7 +350,24 @@ int hulc_k_tr_ffn_bwd(int32_t dtype, const hulc_tr_ffn_bwd_job* job, int32_t B, 
 int hulc_k_tr_attn_bwd(int32_t dtype, const hulc_tr_attn_bwd_job* job, int32_t B, int32_t S, int32_t nparts, int64_t part_stride, float dp, void* stream) {
     HULC_K_16BIT("hulc_k_tr_attn_bwd", k_tr_attn_bwd(job, B, S, nparts, (long long)part_stride, dp, stream));
 }
+int hulc_k_gemm_multi(int32_t dtype, int32_t form, const hulc_gemm_epi_job* jobs, int32_t n, int32_t sh, int32_t* ran, void* stream) {
+    HULC_K_16BIT("hulc_k_gemm_multi", k_gemm_multi(form, jobs, n, sh, ran, stream));
+}
 #undef HULC_K_16BIT
+// the GEMM core with its epilogue (k_entries.h): fp32 and bf16 instances in this unit, fp16 in the other
+int hulc_k_gemm_epi(int32_t dtype, const hulc_gemm_epi_job* job, int32_t kernel, int32_t* ran, void* stream) {
+    if (dtype == HULC_DTYPE_F16) return hulc_f16::k_gemm_epi(1, job, kernel, ran, stream);
+    if (dtype != HULC_DTYPE_F32 && dtype != HULC_DTYPE_BF16) { hulc_set_error("hulc_k_gemm_epi: unknown dtype %d", (int)dtype); return 1; }
+    return hulc_bf16::k_gemm_epi(dtype == HULC_DTYPE_BF16 ? 1 : 0, job, kernel, ran, stream);
+}
+int hulc_k_gemm_pick(int32_t dtype, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int32_t* pick, int32_t* bk) {
+    if (dtype != HULC_DTYPE_F32 && dtype != HULC_DTYPE_BF16 && dtype != HULC_DTYPE_F16) { hulc_set_error("hulc_k_gemm_pick: unknown dtype %d", (int)dtype); return 1; }
+    return hulc_bf16::k_gemm_pick(dtype != HULC_DTYPE_F32, M, N, K, (long long)lda, (long long)ldb, pick, bk);      // the routing does not depend on which 16-bit type
+}
+int hulc_k_gemm_wgrad_nsplit(int32_t dtype, int32_t M, int32_t N, int32_t K, int32_t* nsplit, int32_t* big) {
+    if (dtype != HULC_DTYPE_F32 && dtype != HULC_DTYPE_BF16 && dtype != HULC_DTYPE_F16) { hulc_set_error("hulc_k_gemm_wgrad_nsplit: unknown dtype %d", (int)dtype); return 1; }
+    return hulc_bf16::k_gemm_wgrad_nsplit(dtype != HULC_DTYPE_F32, M, N, K, nsplit, big);
+}
 int hulc_k_logistic_loss(int32_t dtype, int32_t wide, const float* heads, int32_t ldh, const float* actions, const float* robot_obs, int32_t B, int32_t S,
                          int32_t n_mix, int32_t n_dim, int32_t num_classes, float log_scale_min, float gripper_alpha, int32_t gripper_control,
                          int32_t discrete_gripper, float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* stream) {

@@ -660,38 +660,16 @@ struct Engine : IEngine {
             }
         }
         const double fl = 2.0 * M * N * K, by = ((double)M * K + (double)N * K + (double)M * N) * sizeof(T);
-        if constexpr (std::is_same<T, h16_t>::value) {
-            if (a.R1 == 0x7fffffff && b.R1 == 0x7fffffff && ep.z_stride == 0 && skinny_ok(M, N, K, a.s1, b.s1, a.p, b.p)) {
-                // two roles share the skinny kernels: M <= 64 layers stream a whole weight matrix per launch (weight-bound), many-row GEMMs
-                // (small-N heads / weight gradients with K = 2048) stream activations
-                TimerScope ts(this, M <= 64 ? "skinny_gemm_m64" : "skinny_gemm_rows", "hbm", fl, by);
-                launch_skinny(st, a.p, a.s1, b.p, b.s1, M, N, K, om, ep);
-                return;
-            }
-        }
-        // largest tile that still yields >= 128 workgroups (small-N transformer / encoder GEMMs are latency-bound otherwise)
-        const long long w128 = (long long)cdiv(M, 128) * cdiv(N, 128), w64 = (long long)cdiv(M, 64) * cdiv(N, 64);
-        if (M >= 512 && N >= 128 && w128 >= 128) {
+        const GemmPick pick = gemm_pick<T>(a, b, ep, M, N, K, gemm_use_glds);      // gemm.h: the tile and kernel decision
+        if (pick == GEMM_PICK_SKINNY) {
+            // two roles share the skinny kernels: M <= 64 layers stream a whole weight matrix per launch (weight-bound), many-row GEMMs
+            // (small-N heads / weight gradients with K = 2048) stream activations
+            TimerScope ts(this, M <= 64 ? "skinny_gemm_m64" : "skinny_gemm_rows", "hbm", fl, by);
+            gemm_launch_picked<T>(st, pick, a, b, om, ep, M, N, K);
+        } else if (gemm_pick_tile(pick) == 128) {
             TimerScope ts(this, "gemm_128x128", "mfma", fl, by);
-            if constexpr (std::is_same<T, h16_t>::value) {
-                if (gemm_use_glds && gemm_glds_ok(a, b, ep, M, N, K)) { launch_gemm_glds(st, a, b, om, ep, M, N, K); return; }
-                if (K >= 128) { launch_gemm<T, 128, 128, DenseLoader<T>, DenseLoader<T>, DenseOut, 64>(st, a, b, om, ep, M, N, K); return; }   // BK = 64: half the barriers per flop
-            }
-            launch_gemm<T, 128, 128>(st, a, b, om, ep, M, N, K);
-        }
-        else {
-            // small-N / short-K GEMMs (transformer, encoder heads) are bound by the exposed L2 latency of each k-step: a deeper BK means fewer of them
-            const bool t64 = w64 >= 128 || (M <= 64 && N <= 64);
-            if constexpr (std::is_same<T, h16_t>::value) {
-                if (K >= 128) {        // BK = 128 (the default 32 only for K < 128)
-                    if (t64) launch_gemm<T, 64, 64, DenseLoader<T>, DenseLoader<T>, DenseOut, 128>(st, a, b, om, ep, M, N, K);
-                    else launch_gemm<T, 32, 32, DenseLoader<T>, DenseLoader<T>, DenseOut, 128>(st, a, b, om, ep, M, N, K);
-                    return;
-                }
-            }
-            if (t64) launch_gemm<T, 64, 64>(st, a, b, om, ep, M, N, K);
-            else launch_gemm<T, 32, 32>(st, a, b, om, ep, M, N, K);
-        }
+            gemm_launch_picked<T>(st, pick, a, b, om, ep, M, N, K);
+        } else gemm_launch_picked<T>(st, pick, a, b, om, ep, M, N, K);
     }
     // dW[M][N] += A[M][K] B[N][K]^T with fp32 accumulate; few output tiles + long K -> split K across workgroups (atomics)
     void gemm_wgrad(const DenseLoader<T>& a, const DenseLoader<T>& b, float* dW, long long lddw, int M, int N, int K) {
@@ -699,11 +677,8 @@ struct Engine : IEngine {
         if constexpr (std::is_same<T, h16_t>::value) {
             if (a.R1 == 0x7fffffff && b.R1 == 0x7fffffff && skinny_ok(M, N, K, a.s1, b.s1, a.p, b.p)) { gemm(a, b, dense_out(lddw), ep, M, N, K); return; }
         }
-        const long long t128 = (long long)cdiv(M, 128) * cdiv(N, 128), t64 = (long long)cdiv(M, 64) * cdiv(N, 64);
-        const bool big = M >= 128 && N >= 128;
-        const long long tiles = big ? t128 : t64;
-        int nsplit = 1;
-        if (!std::is_same<T, float>::value && tiles < 128 && K >= 512) nsplit = (int)std::min<long long>(std::min<long long>(256 / tiles, K / 256), 32);
+        bool big = false;
+        const int nsplit = gemm_wgrad_nsplit<T>(M, N, K, &big);      // gemm.h
         if (nsplit <= 1) { gemm(a, b, dense_out(lddw), ep, M, N, K); return; }
         ep.atomic = 1;
         TimerScope ts(this, big ? "gemm_128x128" : "gemm_64x64_splitk", "mfma", 2.0 * M * N * K, ((double)M * K + (double)N * K) * sizeof(T) + 4.0 * M * N);

@@ -291,7 +291,11 @@ DEVI void epi_store(const EpiP& ep, float accv, int rrow, int col, long long o) 
 // 4 consecutive output columns of one row (the MFMA is issued as D^T = B A^T, so a lane owns C[row][col..col+3]):
 // vector bias / residual / mask loads and one 16-byte (fp32) or 8-byte (T = bf16) store when aligned, else the scalar path.
 // The vector path is split in two so that a kernel can issue the operand loads early (skinny_lds_kernel: before it waits for
-// its A/W stream) and apply them after the reduction.
+// its A/W stream) and apply them after the reduction.  One difference in order from the scalar path: the vector paths (here and epi_fast16_pre) add
+// bias + bias2 FIRST and then that sum to acc * alpha, epi_store adds the two biases to the accumulator one after the other — with both biases set the two
+// round differently (within the epilogue's rounding bound).  And one in contraction, fp32 engine only: 1 - m * m of the tanh mask is fused into one FMA on one
+// path and not on the other (measured: the scalar and the vector result differ in the last bit of about one element in ten); with a 16-bit mask m * m is exact
+// in fp32 and the two agree.  Everywhere else — at most one bias, alpha == 1, no dropout — the paths agree bit for bit (tests/test_gpu_gemm_epilogue.py).
 struct EpiPre4 {
     bool vec;
     float b[4], rv[4], mk[4];
@@ -1414,10 +1418,14 @@ __global__ void __launch_bounds__(NW * 64) skinny_lds_kchunk_kernel(const h16_t*
         } else epi_apply4<h16_t>(ep, pre, v4, errow, ecol, N, eo);
     }
 }
+// what launch_skinny_lds_kchunk covers (A2: the second problem's A, or null)
+static inline bool skinny_lds_kchunk_ok(const h16_t* A, long long lda, int M, int N, int K, const h16_t* A2 = nullptr) {
+    if (K % 2048 != 0 || K <= 2048 || M > 64 || (lda % 64) != 0 || ((uintptr_t)A % 128) != 0 || (N % 16) != 0) return false;
+    return !(A2 && ((uintptr_t)A2 % 128) != 0);
+}
 static inline bool launch_skinny_lds_kchunk(hipStream_t st, const h16_t* A, long long lda, const h16_t* W, long long ldw, int M, int N, int K, const DenseOut& om,
                                             const EpiP& ep, const GruBwdP& gb = GruBwdP{}, const KChunk2* p2 = nullptr) {
-    if (K % 2048 != 0 || K <= 2048 || M > 64 || (lda % 64) != 0 || ((uintptr_t)A % 128) != 0 || (N % 16) != 0) return false;
-    if (p2 && ((uintptr_t)p2->A % 128) != 0) return false;
+    if (!skinny_lds_kchunk_ok(A, lda, M, N, K, p2 ? p2->A : nullptr)) return false;
     static bool attr = false;
     if (!attr) { hipFuncSetAttribute((const void*)skinny_lds_kchunk_kernel<2, 4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
     hipLaunchKernelGGL((skinny_lds_kchunk_kernel<2, 4, 16>), dim3(N / 16, (M + 31) / 32, p2 ? 2 : 1), dim3(1024), (size_t)16 * 2 * 2 * 2 * 1024, st, A, lda, W, ldw, M, N, K, om, ep, gb,
@@ -1462,10 +1470,13 @@ static inline bool launch_skinny_lds(hipStream_t st, const h16_t* A, long long l
     return true;
 }
 // two independent [M <= 64] x [N] x [K = 2048] recurrent steps in ONE launch of skinny_lds_kernel<2, 4, 16> (grid.z = 2); false: shape not covered
+static inline bool skinny_lds_dual_ok(const h16_t* A0, const h16_t* W0, const h16_t* A1, const h16_t* W1, long long lda, long long ldw, int M, int N, int K) {
+    return !(K != 2048 || M <= 32 || M > 64 || (N % 16) != 0 || (lda % 64) != 0 || ((uintptr_t)A0 % 128) != 0 || ((uintptr_t)A1 % 128) != 0 ||
+             ((uintptr_t)W0 % 16) != 0 || ((uintptr_t)W1 % 16) != 0 || (ldw % 8) != 0);
+}
 static inline bool launch_skinny_lds_dual(hipStream_t st, const h16_t* A0, const h16_t* W0, const EpiP& ep0, const h16_t* A1, const h16_t* W1, const EpiP& ep1, long long lda,
                                           long long ldw, int M, int N, int K, const DenseOut& om) {
-    if (!skinny_use_lds || K != 2048 || M <= 32 || M > 64 || (N % 16) != 0 || (lda % 64) != 0 || ((uintptr_t)A0 % 128) != 0 || ((uintptr_t)A1 % 128) != 0 ||
-        ((uintptr_t)W0 % 16) != 0 || ((uintptr_t)W1 % 16) != 0 || (ldw % 8) != 0) return false;
+    if (!skinny_use_lds || !skinny_lds_dual_ok(A0, W0, A1, W1, lda, ldw, M, N, K)) return false;
     static bool attr16 = false;
     if (!attr16) { hipFuncSetAttribute((const void*)skinny_lds_kernel<2, 4, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr16 = true; }
     Skinny2 p2; p2.A = A1; p2.W = W1; p2.ep = ep1;
@@ -1503,6 +1514,74 @@ static inline bool skinny_ok(int M, int N, int K, long long lda, long long ldw, 
     // and K >= 512 (at shorter K the kernel is shorter per launch but the step measured slower)
     const bool shape = M <= 64 || (K >= 512 && (long long)M * N <= 524288 && (long long)((M + 63) / 64) * (N / 16) >= 16);
     return shape && (K % 32) == 0 && K >= 128 && (N % 16) == 0 && (lda % 8) == 0 && (ldw % 8) == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Routing of a dense NT product, as a pure host decision (Engine::gemm launches what gemm_pick names; the test entries of k_entries.h and the host tests ask
+// the same function).  16-bit types: the skinny family when skinny_ok says so, else by workgroup count — the largest tile that still yields >= 128 workgroups
+// (small-N transformer / encoder GEMMs are latency-bound otherwise): 128x128 through the LDS-DMA kernel where gemm_glds_ok allows (else BK = 64 from K = 128 up:
+// half the barriers per flop), 64x64 against 32x32 with BK = 128 from K = 128 up (bound by the exposed L2 latency of each k-step: a deeper BK means fewer of them).
+// fp32: the register-staged kernel with BK = 32 at the same tile.
+// ---------------------------------------------------------------------------------------------------------
+enum GemmPick { GEMM_PICK_SKINNY = 0, GEMM_PICK_GLDS, GEMM_PICK_128_BK64, GEMM_PICK_128_BK32, GEMM_PICK_64_BK128, GEMM_PICK_64_BK32, GEMM_PICK_32_BK128, GEMM_PICK_32_BK32 };
+static inline int gemm_pick_tile(GemmPick p) {
+    switch (p) {
+        case GEMM_PICK_SKINNY: return 0;
+        case GEMM_PICK_GLDS: case GEMM_PICK_128_BK64: case GEMM_PICK_128_BK32: return 128;
+        case GEMM_PICK_64_BK128: case GEMM_PICK_64_BK32: return 64;
+        default: return 32;
+    }
+}
+template <typename T>
+static inline GemmPick gemm_pick(const DenseLoader<T>& a, const DenseLoader<T>& b, const EpiP& ep, int M, int N, int K, bool use_glds) {
+    constexpr bool H16 = sizeof(T) == 2;
+    if constexpr (H16) {
+        if (a.R1 == 0x7fffffff && b.R1 == 0x7fffffff && ep.z_stride == 0 && skinny_ok(M, N, K, a.s1, b.s1, a.p, b.p)) return GEMM_PICK_SKINNY;
+    }
+    const long long w128 = (long long)((M + 127) / 128) * ((N + 127) / 128), w64 = (long long)((M + 63) / 64) * ((N + 63) / 64);
+    if (M >= 512 && N >= 128 && w128 >= 128) {
+        if constexpr (H16) {
+            if (use_glds && gemm_glds_ok(a, b, ep, M, N, K)) return GEMM_PICK_GLDS;
+            if (K >= 128) return GEMM_PICK_128_BK64;
+        }
+        return GEMM_PICK_128_BK32;
+    }
+    const bool t64 = w64 >= 128 || (M <= 64 && N <= 64);
+    if (H16 && K >= 128) return t64 ? GEMM_PICK_64_BK128 : GEMM_PICK_32_BK128;
+    return t64 ? GEMM_PICK_64_BK32 : GEMM_PICK_32_BK32;
+}
+// launches exactly the kernel `pick` names; a pick that the type has no kernel for (skinny / LDS-DMA / deep BK with fp32) returns false without launching
+template <typename T>
+static inline bool gemm_launch_picked(hipStream_t st, GemmPick pick, const DenseLoader<T>& a, const DenseLoader<T>& b, const DenseOut& om, const EpiP& ep, int M, int N, int K) {
+    typedef DenseLoader<T> DL;
+    if constexpr (sizeof(T) == 2) {
+        switch (pick) {
+            case GEMM_PICK_SKINNY: launch_skinny(st, a.p, a.s1, b.p, b.s1, M, N, K, om, ep); return true;
+            case GEMM_PICK_GLDS: launch_gemm_glds(st, a, b, om, ep, M, N, K); return true;
+            case GEMM_PICK_128_BK64: launch_gemm<T, 128, 128, DL, DL, DenseOut, 64>(st, a, b, om, ep, M, N, K); return true;
+            case GEMM_PICK_64_BK128: launch_gemm<T, 64, 64, DL, DL, DenseOut, 128>(st, a, b, om, ep, M, N, K); return true;
+            case GEMM_PICK_32_BK128: launch_gemm<T, 32, 32, DL, DL, DenseOut, 128>(st, a, b, om, ep, M, N, K); return true;
+            default: break;
+        }
+    }
+    switch (pick) {
+        case GEMM_PICK_128_BK32: launch_gemm<T, 128, 128>(st, a, b, om, ep, M, N, K); return true;
+        case GEMM_PICK_64_BK32: launch_gemm<T, 64, 64>(st, a, b, om, ep, M, N, K); return true;
+        case GEMM_PICK_32_BK32: launch_gemm<T, 32, 32>(st, a, b, om, ep, M, N, K); return true;
+        default: return false;
+    }
+}
+// split-K factor of a weight gradient dW[M][N] += A[M][K] B[N][K]^T (Engine::gemm_wgrad): few output tiles + long K -> K split across workgroups that add with
+// fp32 atomics.  16-bit types only (fp32 stays bit-reproducible); 1 = no split.  *big: the 128x128 tile (else 64x64)
+template <typename T>
+static inline int gemm_wgrad_nsplit(int M, int N, int K, bool* big = nullptr) {
+    const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128), t64 = (long long)((M + 63) / 64) * ((N + 63) / 64);
+    const bool b128 = M >= 128 && N >= 128;
+    if (big) *big = b128;
+    const long long tiles = b128 ? t128 : t64;
+    if (sizeof(T) == 4 || tiles >= 128 || K < 512) return 1;
+    const long long ns = (256 / tiles) < (K / 256) ? (256 / tiles) : (K / 256);
+    return (int)(ns < 32 ? ns : 32);
 }
 
 }  // namespace HULC_NS

@@ -213,6 +213,10 @@ struct IEngine {
                          void* stream);                                                                                                         \
     int k_tr_layer_fwd(const hulc_tr_layer_job* j, int B, int S, int ln_in, float dp, void* stream);                                            \
     int k_tr_ffn_bwd(const hulc_tr_ffn_bwd_job* j, int B, int S, int bcast, float bdiv, float dp, void* stream);                                \
-    int k_tr_attn_bwd(const hulc_tr_attn_bwd_job* j, int B, int S, int nparts, long long part_stride, float dp, void* stream);
+    int k_tr_attn_bwd(const hulc_tr_attn_bwd_job* j, int B, int S, int nparts, long long part_stride, float dp, void* stream);                  \
+    int k_gemm_epi(int t16, const hulc_gemm_epi_job* j, int kernel, int* ran, void* stream);                                                    \
+    int k_gemm_multi(int form, const hulc_gemm_epi_job* jobs, int n, int sh, int* ran, void* stream);                                           \
+    int k_gemm_pick(int t16, int M, int N, int K, long long lda, long long ldb, int* pick, int* bk);                                            \
+    int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big);
 namespace hulc_bf16 { HULC_TU_DECLS }   // capi.hip: HULC_DTYPE_F32 / HULC_DTYPE_BF16
 namespace hulc_f16 { HULC_TU_DECLS }    // engine_f16.hip: HULC_DTYPE_F16

@@ -1,7 +1,8 @@
 // hulc_amd/csrc/k_entries.h — per-kernel test entries of the 16-bit encoder head and of the action loss (include/hulc_hip.h: hulc_k_spatial_softmax64,
 // hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss), of the latent-plan kernels (hulc_k_plan_*, hulc_k_st_softmax_bwd, hulc_k_normal_*), of
 // the LayerNorm family (hulc_k_layernorm_*; launched through plan_ln_launch.h, which the engine calls too) and of the fused transformer layer kernels
-// (hulc_k_tr_layer_fwd, hulc_k_tr_ffn_bwd, hulc_k_tr_attn_bwd; launched through tr_fused.h's helpers).  Included by engine.h inside each translation unit, so every entry exists once per
+// (hulc_k_tr_layer_fwd, hulc_k_tr_ffn_bwd, hulc_k_tr_attn_bwd; launched through tr_fused.h's helpers), and of the GEMM core with its runtime epilogue
+// (hulc_k_gemm_epi, hulc_k_gemm_multi, hulc_k_gemm_pick, hulc_k_gemm_wgrad_nsplit; launched through gemm.h's launchers and routing).  Included by engine.h inside each translation unit, so every entry exists once per
 // 16-bit type (hulc_bf16 / hulc_f16; iengine.h declares them).  Nothing here restates a kernel: each entry checks its arguments, then launches through the
 // helper the engine calls (enc_tail.h) or with the grid and block of the engine's launch site (engine_encoders.inc, engine_forward.inc).
 #pragma once
@@ -400,6 +401,206 @@ int k_tr_attn_bwd(const hulc_tr_attn_bwd_job* j, int B, int S, int nparts, long 
     q.B = B; q.S = S; q.dp = dp; q.seed_o = j->seed_o; q.seed_att = j->seed_att;
     launch_tr_attn_bwd(st, q);
     return fs.finish(who, st);
+}
+
+// ---------------------------------------------------------------------------------------------------- the GEMM core with its runtime epilogue (gemm.h)
+// hulc_k_gemm_epi / hulc_k_gemm_multi: a job mirrors EpiP field for field.  Everything is checked first — with the predicates the engine's routing uses (gemm_pick,
+// gemm_glds_ok, gemm_glds_pair_ok, skinny_ok, skinny_lds_kchunk_ok, skinny_lds_dual_ok) — and only then launched, through the launchers the engine calls.
+// esz = bytes of the storage type T
+static int k_gemm_job_bad(const char* who, int idx, const hulc_gemm_epi_job* jp, int esz) {
+    if (!jp) { hulc_set_error("%s: null job", who); return 1; }
+    const hulc_gemm_epi_job& j = *jp;
+    if (!j.A || !j.B || !j.out) { hulc_set_error("%s: job %d: null pointer (A, B, out are required)", who, idx); return 1; }
+    if (j.M < 1 || j.N < 1 || j.K < 1 || (long long)j.M * j.N > (1ll << 30) || j.lda < j.K || j.ldb < j.K || j.ldc < j.N) {
+        hulc_set_error("%s: job %d: shape M=%d N=%d K=%d lda=%lld ldb=%lld ldc=%lld (need M, N, K >= 1, M * N <= 2^30, lda, ldb >= K, ldc >= N)", who, idx, j.M, j.N, j.K, (long long)j.lda,
+                       (long long)j.ldb, (long long)j.ldc); return 1;
+    }
+    if ((j.out_s0 == 0) != (j.out_R1 == 0) || j.out_R1 < 0 || j.out_s0 < 0) {
+        hulc_set_error("%s: job %d: output map out_R1=%d out_s0=%lld (both 0 = plain rows, or both > 0)", who, idx, j.out_R1, (long long)j.out_s0); return 1;
+    }
+    if (!(j.drop_p >= 0.f && j.drop_p < 1.f)) { hulc_set_error("%s: job %d: drop_p=%g outside [0, 1)", who, idx, (double)j.drop_p); return 1; }
+    if (!(j.alpha == j.alpha) || j.alpha - j.alpha != 0.f) { hulc_set_error("%s: job %d: alpha is not finite", who, idx); return 1; }
+    auto flag = [](int v) { return v == 0 || v == 1; };
+    if (j.relu < 0 || j.relu > 2 || !flag(j.out_f32) || !flag(j.accumulate) || !flag(j.atomic) || !flag(j.res_f32) || !flag(j.res_late) || !flag(j.mask_tanh) || !flag(j.out2_relu) ||
+        !flag(j.generic_only) || !flag(j.wfrag)) { hulc_set_error("%s: job %d: relu must be 0, 1 or 2 and every flag 0 or 1", who, idx); return 1; }
+    if (j.res && (j.res_ld < j.N || j.res_rowmod < 0)) { hulc_set_error("%s: job %d: res_ld=%lld res_rowmod=%d (need res_ld >= N, res_rowmod >= 0)", who, idx, (long long)j.res_ld, j.res_rowmod); return 1; }
+    if ((j.out2_lo & 3) || (j.out2_hi & 3) || j.out2_lo < 0 || j.out2_hi < j.out2_lo) {
+        hulc_set_error("%s: job %d: out2_lo=%lld out2_hi=%lld must be multiples of 4 with 0 <= lo <= hi", who, idx, (long long)j.out2_lo, (long long)j.out2_hi); return 1;
+    }
+    if (j.out2 && (j.accumulate || j.atomic)) { hulc_set_error("%s: job %d: accumulate / atomic is never combined with out2", who, idx); return 1; }
+    if (j.out2_mask && !j.out2) { hulc_set_error("%s: job %d: out2_mask without out2", who, idx); return 1; }
+    if (j.atomic && !j.out_f32) { hulc_set_error("%s: job %d: atomic needs an fp32 output", who, idx); return 1; }
+    if (j.nsplit < 1 || j.nsplit > 64 || j.z_stride < 0 || (j.z_stride & 3)) { hulc_set_error("%s: job %d: nsplit=%d z_stride=%lld (need 1 <= nsplit <= 64, z_stride >= 0 and a multiple of 4)", who, idx, j.nsplit, (long long)j.z_stride); return 1; }
+    if (k_misaligned(j.A, esz) || k_misaligned(j.B, esz)) { hulc_set_error("%s: job %d: A, B are not aligned to their element type", who, idx); return 1; }
+    if (k_misaligned16(j.bias) || k_misaligned16(j.bias2)) { hulc_set_error("%s: job %d: bias, bias2 must be 16-byte aligned (read as float4)", who, idx); return 1; }
+    if (k_misaligned(j.out, 4 * (j.out_f32 ? 4 : esz)) || k_misaligned(j.res, 4 * (j.res_f32 ? 4 : esz)) || k_misaligned(j.mask, 4 * esz) || k_misaligned(j.out2, 4 * esz) ||
+        k_misaligned(j.out2_mask, 4 * esz)) { hulc_set_error("%s: job %d: out, res, mask, out2, out2_mask must be aligned to four of their elements", who, idx); return 1; }
+    return 0;
+}
+static EpiP k_gemm_job_epi(const hulc_gemm_epi_job& j) {
+    EpiP e;
+    e.out = j.out; e.out_f32 = j.out_f32; e.accumulate = j.accumulate; e.atomic = j.atomic; e.z_stride = j.z_stride; e.bias = j.bias; e.bias2 = j.bias2; e.res = j.res; e.res_f32 = j.res_f32;
+    e.res_ld = j.res_ld; e.res_rowmod = j.res_rowmod; e.res_late = j.res_late; e.mask = j.mask; e.mask_tanh = j.mask_tanh; e.relu = j.relu; e.alpha = j.alpha; e.drop_p = j.drop_p;
+    e.drop_seed = j.drop_seed; e.out2 = j.out2; e.out2_lo = j.out2_lo; e.out2_hi = j.out2_hi; e.out2_mask = j.out2_mask; e.out2_relu = j.out2_relu; e.generic_only = j.generic_only;
+    return e;
+}
+static DenseOut k_gemm_job_om(const hulc_gemm_epi_job& j) { return j.out_s0 ? dense_out_map(j.out_R1, j.out_s0, j.ldc) : dense_out(j.ldc); }
+// gemm_kernel at tile 32 / 64 / 128 with BK by the engine's rule (gemm_pick), nsplit K slabs
+template <typename T>
+static void k_gemm_tile(hipStream_t st, int tile, const DenseLoader<T>& a, const DenseLoader<T>& b, const DenseOut& om, const EpiP& ep, int M, int N, int K, int nsplit, bool bk32) {
+    typedef DenseLoader<T> DL;
+    if constexpr (sizeof(T) == 2) {
+        if (K >= 128 && !bk32) {
+            if (tile == 32) launch_gemm<T, 32, 32, DL, DL, DenseOut, 128>(st, a, b, om, ep, M, N, K, 1, nsplit);
+            else if (tile == 64) launch_gemm<T, 64, 64, DL, DL, DenseOut, 128>(st, a, b, om, ep, M, N, K, 1, nsplit);
+            else launch_gemm<T, 128, 128, DL, DL, DenseOut, 64>(st, a, b, om, ep, M, N, K, 1, nsplit);
+            return;
+        }
+    }
+    if (tile == 32) launch_gemm<T, 32, 32>(st, a, b, om, ep, M, N, K, 1, nsplit);
+    else if (tile == 64) launch_gemm<T, 64, 64>(st, a, b, om, ep, M, N, K, 1, nsplit);
+    else launch_gemm<T, 128, 128>(st, a, b, om, ep, M, N, K, 1, nsplit);
+}
+template <typename T>
+static int k_gemm_epi_t(const hulc_gemm_epi_job& j, int kernel, int* ran, hipStream_t st) {
+    static const char* who = "hulc_k_gemm_epi";
+    const DenseLoader<T> a = dense<T>((const T*)j.A, j.M, j.lda), b = dense<T>((const T*)j.B, j.N, j.ldb);
+    const DenseOut om = k_gemm_job_om(j);
+    const EpiP ep = k_gemm_job_epi(j);
+    const int M = j.M, N = j.N, K = j.K;
+    if (kernel != 8 && j.atomic) { hulc_set_error("%s: atomic goes with kernel 8 (split K) only", who); return 1; }
+    if (kernel != 7 && j.wfrag) { hulc_set_error("%s: wfrag goes with kernel 7 (the K-chunked kernel) only", who); return 1; }
+    if ((kernel < 1 || kernel > 3) && kernel != 8 && (j.nsplit != 1 || j.z_stride != 0)) { hulc_set_error("%s: kernel %d takes nsplit = 1 and z_stride = 0", who, kernel); return 1; }
+    if (kernel >= 1 && kernel <= 3 && (j.nsplit > 1) != (j.z_stride > 0)) { hulc_set_error("%s: kernels 1 .. 3: nsplit > 1 goes with z_stride > 0 (partial slabs) and the reverse", who); return 1; }
+    if (kernel == 0) {
+        const GemmPick pick = gemm_pick<T>(a, b, ep, M, N, K, gemm_use_glds);
+        if (!gemm_launch_picked<T>(st, pick, a, b, om, ep, M, N, K)) { hulc_set_error("%s: gemm_pick chose a kernel this type does not have", who); return 1; }
+        *ran = pick == GEMM_PICK_SKINNY ? HULC_GEMM_RAN_SKINNY_ROUTER : pick == GEMM_PICK_GLDS ? HULC_GEMM_RAN_GLDS : gemm_pick_tile(pick) == 128 ? HULC_GEMM_RAN_128 :
+               gemm_pick_tile(pick) == 64 ? HULC_GEMM_RAN_64 : HULC_GEMM_RAN_32;
+        return k_launched(who);
+    }
+    if (kernel >= 1 && kernel <= 3) {
+        k_gemm_tile<T>(st, 16 << kernel, a, b, om, ep, M, N, K, j.nsplit, false);
+        *ran = kernel;
+        return k_launched(who);
+    }
+    if (kernel == 8) {
+        if (!j.atomic || !j.out_f32 || j.nsplit < 2 || j.z_stride != 0) { hulc_set_error("%s: kernel 8 (split K) needs atomic = 1, out_f32 = 1, nsplit >= 2, z_stride = 0", who); return 1; }
+        bool big = false;
+        gemm_wgrad_nsplit<T>(M, N, K, &big);
+        k_gemm_tile<T>(st, big ? 128 : 64, a, b, om, ep, M, N, K, j.nsplit, true);      // Engine::gemm_wgrad: BK = 32
+        *ran = big ? HULC_GEMM_RAN_SPLITK_128 : HULC_GEMM_RAN_SPLITK_64;
+        return k_launched(who);
+    }
+    if constexpr (sizeof(T) == 2) {
+        const h16_t* A = (const h16_t*)j.A; const h16_t* W = (const h16_t*)j.B;
+        if (kernel == 4) {
+            if (!gemm_glds_ok(a, b, ep, M, N, K)) { hulc_set_error("%s: kernel 4: gemm_glds_ok refuses (K >= 64, K %% 32 == 0, rows 16-byte aligned, z_stride 0)", who); return 1; }
+            launch_gemm_glds(st, a, b, om, ep, M, N, K);
+            *ran = HULC_GEMM_RAN_GLDS;
+            return k_launched(who);
+        }
+        if (kernel >= 5 && kernel <= 7 && !skinny_ok(M, N, K, j.lda, j.ldb, A, W)) {
+            hulc_set_error("%s: kernel %d: skinny_ok refuses (M <= 64 or few rows of tiles, K %% 32 == 0, K >= 128, N %% 16 == 0, rows 16-byte aligned)", who, kernel); return 1;
+        }
+        if (kernel == 5 || kernel == 6) {
+            const bool saved = skinny_use_lds;
+            if (kernel == 6) skinny_use_lds = false;
+            launch_skinny(st, A, j.lda, W, j.ldb, M, N, K, om, ep);
+            skinny_use_lds = saved;
+            *ran = kernel;
+            return k_launched(who);
+        }
+        if (kernel == 7) {
+            if (!skinny_lds_kchunk_ok(A, j.lda, M, N, K)) { hulc_set_error("%s: kernel 7: shape not covered by the K-chunked kernel (K = n x 2048 > 2048, M <= 64, lda %% 64 == 0, A 128-byte aligned)", who); return 1; }
+            if (j.wfrag && (j.ldb != K || k_misaligned16(W))) { hulc_set_error("%s: kernel 7: wfrag repacks a dense B (ldb == K, 16-byte aligned)", who); return 1; }
+            KFragScratch fs;
+            if (j.wfrag) { fs.add(W, N, K); if (fs.alloc_and_pack(who, st)) return 1; }
+            if (!launch_skinny_lds_kchunk(st, A, j.lda, j.wfrag ? fs.at(0) : W, j.wfrag ? 0ll : (long long)j.ldb, M, N, K, om, ep)) { hulc_set_error("%s: kernel 7: the launcher refused", who); return 1; }
+            *ran = HULC_GEMM_RAN_KCHUNK;
+            return j.wfrag ? fs.finish(who, st) : k_launched(who);
+        }
+    }
+    hulc_set_error("%s: kernel %d is unknown, or a 16-bit kernel asked of fp32", who, kernel);
+    return 1;
+}
+// t16: 0 = float, 1 = this translation unit's 16-bit type
+int k_gemm_epi(int t16, const hulc_gemm_epi_job* j, int kernel, int* ran, void* stream) {
+    int dummy = 0;
+    if (!ran) ran = &dummy;
+    *ran = HULC_GEMM_RAN_NONE;
+    if (k_gemm_job_bad("hulc_k_gemm_epi", 0, j, t16 ? 2 : 4)) return 1;
+    if (t16) return k_gemm_epi_t<h16_t>(*j, kernel, ran, (hipStream_t)stream);
+#ifdef HULC_HALF_F16
+    hulc_set_error("hulc_k_gemm_epi: the fp32 instances live in the bf16 translation unit"); return 1;
+#else
+    return k_gemm_epi_t<float>(*j, kernel, ran, (hipStream_t)stream);
+#endif
+}
+int k_gemm_multi(int form, const hulc_gemm_epi_job* jobs, int n, int sh, int* ran, void* stream) {
+    static const char* who = "hulc_k_gemm_multi";
+    hipStream_t st = (hipStream_t)stream;
+    int dummy = 0;
+    if (!ran) ran = &dummy;
+    *ran = HULC_GEMM_RAN_NONE;
+    if (!jobs) { hulc_set_error("%s: null jobs", who); return 1; }
+    if (form < 0 || form > 2 || n < 2 || n > (form == 0 ? 3 : 2)) { hulc_set_error("%s: form=%d n=%d (form 0: n = 2 or 3; forms 1, 2: n = 2)", who, form, n); return 1; }
+    DenseLoader<h16_t> a[3], b[3]; DenseOut om[3]; EpiP ep[3];
+    for (int i = 0; i < n; ++i) {
+        const hulc_gemm_epi_job& j = jobs[i];
+        if (k_gemm_job_bad(who, i, &j, 2)) return 1;
+        if (j.nsplit != 1 || j.z_stride != 0 || j.atomic || j.wfrag) { hulc_set_error("%s: job %d: nsplit = 1, z_stride = 0, no atomic, no wfrag", who, i); return 1; }
+        a[i] = dense<h16_t>((const h16_t*)j.A, j.M, j.lda); b[i] = dense<h16_t>((const h16_t*)j.B, j.N, j.ldb); om[i] = k_gemm_job_om(j); ep[i] = k_gemm_job_epi(j);
+    }
+    const hulc_gemm_epi_job &j0 = jobs[0], &j1 = jobs[1];
+    if (form == 0) {
+        GemmGroupP g{};
+        g.n = n;
+        for (int i = 0; i < n; ++i) {
+            if (!gemm_glds_ok(a[i], b[i], ep[i], jobs[i].M, jobs[i].N, jobs[i].K)) { hulc_set_error("%s: job %d: gemm_glds_ok refuses (K >= 64, K %% 32 == 0, rows 16-byte aligned)", who, i); return 1; }
+            g.a[i] = a[i]; g.b[i] = b[i]; g.om[i] = om[i]; g.ep[i] = ep[i]; g.M[i] = jobs[i].M; g.N[i] = jobs[i].N; g.K[i] = jobs[i].K;
+        }
+        launch_gemm_glds_group(st, g);
+        *ran = HULC_GEMM_RAN_GROUP;
+        return k_launched(who);
+    }
+    if (j0.M != j1.M || j0.N != j1.N || j0.K != j1.K || j0.lda != j1.lda || j0.ldb != j1.ldb || j0.ldc != j1.ldc || j0.out_R1 != j1.out_R1 || j0.out_s0 != j1.out_s0) {
+        hulc_set_error("%s: forms 1 and 2: the two jobs share M, N, K, the leading dimensions and the output map", who); return 1;
+    }
+    if (form == 1) {
+        if (j0.A != j1.A) { hulc_set_error("%s: form 1: the two jobs share A", who); return 1; }
+        if (!gemm_glds_pair_ok(a[0], b[0], b[1], ep[0], ep[1], j0.M, j0.N, j0.K, sh)) {
+            hulc_set_error("%s: form 1: gemm_glds_pair_ok refuses (K >= 192, K, sh multiples of 64, 0 < sh < K, M, N multiples of 128, plain fp32 epilogues, 16-byte aligned)", who); return 1;
+        }
+        launch_gemm_glds_pair(st, a[0], b[0], b[1], om[0], ep[0], ep[1], j0.M, j0.N, j0.K, sh);
+        *ran = HULC_GEMM_RAN_PAIR;
+        return k_launched(who);
+    }
+    if (!skinny_use_lds || !skinny_lds_dual_ok(a[0].p, b[0].p, a[1].p, b[1].p, j0.lda, j0.ldb, j0.M, j0.N, j0.K)) {
+        hulc_set_error("%s: form 2: shape not covered by the dual launch (32 < M <= 64, K = 2048, N %% 16 == 0, lda %% 64 == 0, A 128-byte aligned, W 16-byte aligned)", who); return 1;
+    }
+    if (!launch_skinny_lds_dual(st, a[0].p, b[0].p, ep[0], a[1].p, b[1].p, ep[1], j0.lda, j0.ldb, j0.M, j0.N, j0.K, om[0])) { hulc_set_error("%s: form 2: the launcher refused", who); return 1; }
+    *ran = HULC_GEMM_RAN_DUAL;
+    return k_launched(who);
+}
+// host arithmetic only: the routing functions of gemm.h behind a C entry (tests/test_gemm_epi_ref_host.py)
+int k_gemm_pick(int t16, int M, int N, int K, long long lda, long long ldb, int* pick, int* bk) {
+    if (!pick || !bk || M < 1 || N < 1 || K < 1 || lda < K || ldb < K) { hulc_set_error("hulc_k_gemm_pick: null argument or bad shape"); return 1; }
+    EpiP ep;
+    GemmPick p;
+    const void* al = (const void*)(uintptr_t)0x10000;       // never dereferenced: stands for an aligned operand
+    if (t16) p = gemm_pick<h16_t>(dense<h16_t>((const h16_t*)al, M, lda), dense<h16_t>((const h16_t*)al, N, ldb), ep, M, N, K, gemm_use_glds);
+    else p = gemm_pick<float>(dense<float>((const float*)al, M, lda), dense<float>((const float*)al, N, ldb), ep, M, N, K, gemm_use_glds);
+    *pick = p == GEMM_PICK_SKINNY ? HULC_GEMM_RAN_SKINNY_ROUTER : p == GEMM_PICK_GLDS ? HULC_GEMM_RAN_GLDS : gemm_pick_tile(p) == 128 ? HULC_GEMM_RAN_128 : gemm_pick_tile(p) == 64 ? HULC_GEMM_RAN_64 : HULC_GEMM_RAN_32;
+    *bk = (p == GEMM_PICK_SKINNY || p == GEMM_PICK_GLDS) ? 0 : (p == GEMM_PICK_64_BK128 || p == GEMM_PICK_32_BK128) ? 128 : p == GEMM_PICK_128_BK64 ? 64 : 32;
+    return 0;
+}
+int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big) {
+    if (!nsplit || !big || M < 1 || N < 1 || K < 1) { hulc_set_error("hulc_k_gemm_wgrad_nsplit: null argument or bad shape"); return 1; }
+    bool b = false;
+    *nsplit = t16 ? gemm_wgrad_nsplit<h16_t>(M, N, K, &b) : gemm_wgrad_nsplit<float>(M, N, K, &b);
+    *big = b ? 1 : 0;
+    return 0;
 }
 
 }  // namespace HULC_NS

@@ -701,6 +701,46 @@ typedef struct hulc_tr_attn_bwd_job {
 } hulc_tr_attn_bwd_job;
 int hulc_k_tr_attn_bwd(int32_t dtype, const hulc_tr_attn_bwd_job* job, int32_t B, int32_t S, int32_t nparts, int64_t part_stride, float dp, void* hip_stream);
 
+/* ---- the GEMM core (csrc/gemm.h) with its whole runtime epilogue, launched through the launchers the engine calls.  dtype = HULC_DTYPE_BF16 / F16 / F32 (storage
+ * type T of A, B, res (unless res_f32), mask, out (unless out_f32), out2, out2_mask; the LDS-DMA and skinny kernels exist for the 16-bit types only).
+ * A job = one product out = epilogue(A[M][K] B[N][K]^T): A, B row-major with leading dimensions lda, ldb; output row r starts at element r * ldc (out_s0 == 0) or
+ * (r / out_R1) * out_s0 + (r % out_R1) * ldc (the two-level row map); the epilogue fields are EpiP's, one for one, applied in this order: v = acc * alpha;
+ * + bias[col] + bias2[col]; + res[rrow][col] when !res_late (rrow = row % res_rowmod when res_rowmod > 0); relu 1: max(v, 0), 2: tanh(v); mask (T, at the output's
+ * element offsets): v = mask > 0 ? v : 0, or with mask_tanh v *= 1 - mask^2; drop_p > 0: v = hash_uniform(drop_seed, element offset) < drop_p ? 0 : v / (1 - drop_p);
+ * + res when res_late; accumulate: + what the output held; stored as fp32 (out_f32) or T.  out2: the elements whose offset o lies in [out2_lo, out2_hi) are stored
+ * a second time, as T, at out2[o - out2_lo]: max(v, 0) with out2_relu, and zeroed where out2_mask[o - out2_lo] <= 0.  atomic: fp32 atomic adds (split K).
+ * z_stride: element offset between the split-K partial slabs of a non-atomic launch with nsplit > 1.  wfrag (kernel 7): B is repacked into the fragment order in
+ * scratch first (frag_pack_kernel, as the engine's weight preparation does) and read with a zero leading dimension; the call then synchronises.
+ * Refused before any launch: null job / A / B / out, M, N, K < 1, leading dimensions shorter than a row, drop_p outside [0, 1), out2_lo / out2_hi not multiples of
+ * 4 or out of order, accumulate or atomic together with out2, relu not 0 / 1 / 2, pointers not aligned to their element type, bias / bias2 not 16-byte aligned, res / mask /
+ * out / out2 / out2_mask not aligned to four of their elements (the vector paths read and write them that way; every buffer the engine passes is), and every
+ * shape or alignment the chosen kernel's own predicate (skinny_ok, gemm_glds_ok, gemm_glds_pair_ok, the launch_skinny_lds* launchers) does not accept. */
+typedef struct hulc_gemm_epi_job {
+    const void* A; const void* B; int32_t M, N, K; int64_t lda, ldb;
+    int64_t ldc; int32_t out_R1; int64_t out_s0;
+    int32_t nsplit, wfrag;
+    void* out; int32_t out_f32, accumulate, atomic; int64_t z_stride;
+    const float* bias; const float* bias2;
+    const void* res; int32_t res_f32; int64_t res_ld; int32_t res_rowmod, res_late;
+    const void* mask; int32_t mask_tanh, relu; float alpha, drop_p; uint64_t drop_seed;
+    void* out2; int64_t out2_lo, out2_hi; const void* out2_mask; int32_t out2_relu, generic_only;
+} hulc_gemm_epi_job;
+/* kernel: 0 = what gemm_pick (the engine's routing) chooses; 1 / 2 / 3 = gemm_kernel at 32x32 / 64x64 / 128x128 with BK by the engine's rule (16 bit: 128 / 128 / 64
+ * from K = 128 up, else 32; fp32: 32), nsplit > 1 with z_stride = split-K slabs; 4 = gemm_glds_kernel; 5 = launch_skinny, the production skinny router; 6 = the
+ * register-fragment skinny_gemm_kernel (the LDS forms switched off for the call); 7 = skinny_lds_kchunk_kernel; 8 = atomic split K (atomic = 1, out_f32 = 1,
+ * nsplit >= 2) through gemm_kernel at the tile Engine::gemm_wgrad takes.  *ran (may be NULL) receives what was launched: HULC_GEMM_RAN_*. */
+enum { HULC_GEMM_RAN_NONE = 0, HULC_GEMM_RAN_32 = 1, HULC_GEMM_RAN_64 = 2, HULC_GEMM_RAN_128 = 3, HULC_GEMM_RAN_GLDS = 4, HULC_GEMM_RAN_SKINNY_ROUTER = 5, HULC_GEMM_RAN_SKINNY_REG = 6,
+       HULC_GEMM_RAN_KCHUNK = 7, HULC_GEMM_RAN_SPLITK_64 = 8, HULC_GEMM_RAN_SPLITK_128 = 9, HULC_GEMM_RAN_GROUP = 10, HULC_GEMM_RAN_PAIR = 11, HULC_GEMM_RAN_DUAL = 12 };
+int hulc_k_gemm_epi(int32_t dtype, const hulc_gemm_epi_job* job, int32_t kernel, int32_t* ran, void* hip_stream);
+/* form 0: launch_gemm_glds_group over n = 2 or 3 independent jobs; form 1: launch_gemm_glds_pair, two jobs that share A (and M, N, K, the output map): job 0 is
+ * C1 = sum_{k >= sh} A[m][k] B1[n][k - sh], job 1 is C2 = A B2^T; form 2: launch_skinny_lds_dual, two jobs of one shape (32 < M <= 64, K = 2048).  16-bit types only. */
+int hulc_k_gemm_multi(int32_t dtype, int32_t form, const hulc_gemm_epi_job* jobs, int32_t n, int32_t sh, int32_t* ran, void* hip_stream);
+/* host arithmetic only (no device is touched): the engine's routing.  hulc_k_gemm_pick: *pick = the HULC_GEMM_RAN_* kernel family (32 / 64 / 128 / GLDS /
+ * SKINNY_ROUTER) gemm_pick chooses for a dense product with 256-byte aligned operands, leading dimensions lda, ldb and z_stride = 0, *bk = its k-step (0 for
+ * the skinny and LDS-DMA kernels).  hulc_k_gemm_wgrad_nsplit: Engine::gemm_wgrad's split-K factor (1 = none), *big = 1: the 128x128 tile. */
+int hulc_k_gemm_pick(int32_t dtype, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int32_t* pick, int32_t* bk);
+int hulc_k_gemm_wgrad_nsplit(int32_t dtype, int32_t M, int32_t N, int32_t K, int32_t* nsplit, int32_t* big);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,14 +49,15 @@ def test_ctypes_struct_layout_matches_header(tmp_path):
     src = tmp_path / "layout.c"
     fields = {"hulc_batch": [f[0] for f in lib.HulcBatch._fields_], "hulc_val_noise": [f[0] for f in lib.HulcValNoise._fields_],
               "hulc_rollout_obs": [f[0] for f in lib.HulcRolloutObs._fields_], "hulc_config": [f[0] for f in lib.HulcConfig._fields_],
-              "hulc_optim": [f[0] for f in lib.HulcOptim._fields_]}
+              "hulc_optim": [f[0] for f in lib.HulcOptim._fields_], "hulc_gemm_epi_job": [f[0] for f in lib.HulcGemmEpiJob._fields_]}
     body = "".join(f'printf("{st} %zu\\n", sizeof({st}));' + "".join(f'printf("{st}.{fl} %zu\\n", offsetof({st}, {fl}));' for fl in fls)
                    for st, fls in fields.items())
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hulc_hip.h"\nint main(void) {' + body + "return 0; }\n")
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    mirrors = {"hulc_batch": lib.HulcBatch, "hulc_val_noise": lib.HulcValNoise, "hulc_rollout_obs": lib.HulcRolloutObs, "hulc_config": lib.HulcConfig, "hulc_optim": lib.HulcOptim}
+    mirrors = {"hulc_batch": lib.HulcBatch, "hulc_val_noise": lib.HulcValNoise, "hulc_rollout_obs": lib.HulcRolloutObs, "hulc_config": lib.HulcConfig, "hulc_optim": lib.HulcOptim,
+               "hulc_gemm_epi_job": lib.HulcGemmEpiJob}
     for st, cls in mirrors.items():
         assert ctypes.sizeof(cls) == int(out[st]), st
         for fl in fields[st]:
@@ -280,6 +281,107 @@ def test_fused_transformer_entries_refuse_bad_arguments_before_touching_the_devi
         refused(ab(**{name: A + 8}), e, "16-byte aligned")
     for name, off in (("parts", 2), ("y1", 2), ("st1", 1), ("n1g", 2), ("dg1", 2), ("db1", 2), ("Pat", 2), ("b_d", 1)):
         refused(ab(**{name: A + off}), e, "element type")
+
+
+def test_gemm_epilogue_entries_refuse_bad_arguments_before_touching_the_device():
+    """hulc_k_gemm_epi / hulc_k_gemm_multi check every argument, and the preconditions of the kernel asked for with the predicates the engine's routing uses, before
+    anything is launched: the pointers here are made-up addresses that are never dereferenced (without a GPU a launch would report a HIP failure instead of
+    naming the argument; with one, an LDS-DMA kernel outside its preconditions would read out of bounds)."""
+    import ctypes as C
+    from hulc_amd import lib as L
+    lib = L.load()
+    BF, F16, F32 = L.DTYPE["bf16"], L.DTYPE["fp16"], L.DTYPE["fp32"]
+    A = 0x100000          # a 256-byte aligned made-up address
+
+    def refused(rc, entry, word):
+        err = lib.hulc_last_error().decode()
+        assert rc != 0 and entry in err and word in err, (entry, word, rc, err)
+
+    def mk(**over):
+        j = L.HulcGemmEpiJob(A=A, B=A + 0x100000, out=A + 0x200000, M=64, N=64, K=2048, lda=2048, ldb=2048, ldc=64, nsplit=1, alpha=1.0)
+        for k, v in over.items():
+            setattr(j, k, v)
+        return j
+
+    e = "hulc_k_gemm_epi"
+    ran = C.c_int32(99)
+    ep = lambda dt=BF, kernel=2, **over: lib.hulc_k_gemm_epi(dt, C.byref(mk(**over)), kernel, C.byref(ran), None)
+    refused(lib.hulc_k_gemm_epi(BF, None, 0, None, None), e, "null job")
+    assert lib.hulc_k_gemm_epi(7, C.byref(mk()), 0, None, None) != 0 and b"unknown dtype" in lib.hulc_last_error()
+    for name in ("A", "B", "out"):
+        refused(ep(**{name: None}), e, "null pointer")
+    for kw in (dict(M=0), dict(N=0), dict(K=0), dict(lda=2047), dict(ldb=100), dict(ldc=63), dict(M=1 << 20, N=1 << 20, ldc=1 << 20)):
+        refused(ep(**kw), e, "shape")
+    for kw in (dict(out_R1=4), dict(out_s0=64), dict(out_R1=-1, out_s0=8)):
+        refused(ep(**kw), e, "output map")
+    for p in (1.0, 1.5, -0.1, float("nan")):
+        refused(ep(drop_p=p), e, "outside [0, 1)")
+    refused(ep(alpha=float("inf")), e, "alpha")
+    for kw in (dict(relu=3), dict(relu=-1), dict(out_f32=2), dict(accumulate=5), dict(res_late=-1), dict(generic_only=2)):
+        refused(ep(**kw), e, "relu must be")
+    refused(ep(res=A, res_ld=63), e, "res_ld")
+    for kw in (dict(out2=A, out2_lo=2, out2_hi=8), dict(out2=A, out2_lo=0, out2_hi=6), dict(out2=A, out2_lo=8, out2_hi=4), dict(out2_lo=-4)):
+        refused(ep(**kw), e, "multiples of 4")
+    refused(ep(out2=A, out2_hi=64, accumulate=1), e, "never combined with out2")
+    refused(ep(out2_mask=A), e, "out2_mask without out2")
+    refused(ep(kernel=8, atomic=1, nsplit=2), e, "atomic needs an fp32 output")
+    for kw in (dict(nsplit=0), dict(nsplit=65), dict(z_stride=-4), dict(z_stride=6)):
+        refused(ep(**kw), e, "nsplit")
+    for name in ("A", "B"):
+        refused(ep(**{name: A + 1}), e, "element type")
+        refused(ep(dt=F32, **{name: A + 2}), e, "element type")
+    for name in ("bias", "bias2"):
+        refused(ep(**{name: A + 8}), e, "16-byte aligned")
+    for name, off16, off32 in (("out", 4, 8), ("res", 2, 8), ("mask", 4, 8), ("out2", 6, 12), ("out2_mask", 4, 4)):
+        kw = dict(res_ld=64) if name == "res" else dict(out2=A, out2_hi=64) if name == "out2_mask" else dict(out2_hi=64) if name == "out2" else {}
+        refused(ep(**{name: A + off16}, **kw), e, "four of their elements")
+        refused(ep(dt=F32, **{name: A + off32}, **kw), e, "four of their elements")
+    refused(ep(out=A + 8, out_f32=1), e, "four of their elements")          # an fp32 output is stored as float4
+    assert ep(res=A + 8, res_f32=1, res_ld=64, dt=F16) != 0 and b"four of their elements" in lib.hulc_last_error()
+    # kernel choice
+    refused(ep(kernel=9), e, "unknown")
+    for k in (4, 5, 6, 7):
+        refused(ep(dt=F32, kernel=k), e, "asked of fp32")
+    refused(ep(kernel=2, atomic=1, out_f32=1), e, "kernel 8")
+    refused(ep(kernel=2, wfrag=1), e, "kernel 7")
+    refused(ep(kernel=0, nsplit=2, z_stride=4096), e, "nsplit = 1")
+    refused(ep(kernel=2, nsplit=2), e, "z_stride > 0")
+    refused(ep(kernel=3, z_stride=4096), e, "z_stride > 0")
+    for kw in (dict(atomic=0, out_f32=1, nsplit=2), dict(atomic=1, out_f32=1, nsplit=1), dict(atomic=1, out_f32=1, nsplit=2, z_stride=4096)):
+        refused(ep(kernel=8, **kw), e, "kernel 8 (split K) needs")
+    # the kernels' own predicates
+    for kw in (dict(K=32, lda=32, ldb=32), dict(K=72, lda=72, ldb=72), dict(lda=2052), dict(A=A + 8)):
+        refused(ep(kernel=4, **kw), e, "gemm_glds_ok")
+    for k in (5, 6, 7):
+        for kw in (dict(N=40, ldc=40), dict(K=96, lda=96, ldb=96), dict(K=136, lda=136, ldb=136), dict(ldb=2052), dict(B=A + 8), dict(M=65, N=16, ldc=16, K=256, lda=256, ldb=256)):
+            refused(ep(kernel=k, **kw), e, "skinny_ok")
+    for kw in (dict(), dict(K=4096, lda=4096, ldb=4096, A=A + 64), dict(K=4096, lda=4096 + 8, ldb=4096), dict(K=3072, lda=3072, ldb=3072)):
+        refused(ep(kernel=7, **kw), e, "K-chunked")
+    refused(ep(kernel=7, K=4096, lda=4096, ldb=4104, wfrag=1), e, "wfrag repacks a dense B")
+    assert ran.value == 0, "nothing ran"
+
+    e = "hulc_k_gemm_multi"
+    def multi(form, jobs, n=None, sh=0, dt=BF):
+        arr = (L.HulcGemmEpiJob * len(jobs))(*jobs)
+        return lib.hulc_k_gemm_multi(dt, form, arr, len(jobs) if n is None else n, sh, C.byref(ran), None)
+    pj = lambda **over: mk(**{**dict(M=128, N=128, K=192, lda=192, ldb=192, ldc=128, out_f32=1), **over})
+    refused(lib.hulc_k_gemm_multi(BF, 0, None, 2, 0, None, None), e, "null jobs")
+    refused(multi(0, [mk(), mk()], dt=F32), e, "not a 16-bit type")
+    for form, n in ((3, 2), (-1, 2), (0, 1), (0, 4), (1, 3), (2, 3)):
+        refused(multi(form, [mk(), mk(), mk(), mk()], n=n), e, "form=")
+    refused(multi(0, [mk(), mk(drop_p=1.0)]), e, "job 1: drop_p")
+    refused(multi(0, [mk(nsplit=2, z_stride=64), mk()]), e, "job 0: nsplit = 1")
+    refused(multi(0, [mk(), mk(), mk(K=40, lda=40, ldb=40)]), e, "job 2: gemm_glds_ok")
+    refused(multi(1, [pj(), pj(M=256)], sh=64), e, "share M, N, K")
+    refused(multi(1, [pj(), pj(A=A + 0x400000)], sh=64), e, "share A")
+    for sh, kw in ((0, {}), (32, {}), (192, {}), (64, dict(K=128, lda=128, ldb=128)), (64, dict(M=130)), (64, dict(N=120, ldc=120)), (64, dict(out_f32=0)), (64, dict(bias=A)),
+                   (64, dict(alpha=2.0)), (64, dict(relu=1)), (64, dict(generic_only=1)), (64, dict(lda=196))):
+        refused(multi(1, [pj(**kw), pj(**kw)], sh=sh), e, "gemm_glds_pair_ok")
+    dj = lambda **over: mk(**{**dict(M=64, N=48, ldc=48), **over})
+    for kw in (dict(M=32), dict(M=65), dict(K=1024, lda=1024, ldb=1024), dict(N=40, ldc=40), dict(lda=2048 + 8), dict(A=A + 64), dict(B=A + 8), dict(ldb=2052)):
+        refused(multi(2, [dj(**kw), dj(**kw)]), e, "dual launch")
+    refused(multi(2, [dj(), dj(ldc=64)]), e, "share M, N, K")
+    assert ran.value == 0, "nothing ran"
 
 
 def test_dropout_probability_outside_the_half_open_unit_interval_is_refused():

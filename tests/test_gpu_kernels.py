@@ -126,6 +126,22 @@ def test_conv_wgrad_tr(which, IH, CI, KH, S):
         assert np.abs(out.cpu().numpy() - ref).max() / np.abs(ref).max() < 1e-4
 
 
+def _product_per_element(got, A, B, what, out16=True, bias=None, relu=0):
+    """every element of `got` against the float64 product of the device's own bf16 operands (+ bias, ReLU): gemm_epi_ref.product's accumulation bound
+    (K + 2) 2^-24 sum |a||b|, the epilogue's derived bound, and one bf16 ulp where the output is stored in 16 bit — beside the max-norm gates kept below"""
+    import gemm_epi_ref as G
+    import plan_ln_inputs as PI
+    from plan_ln_gpu_util import check_tol
+    acc, bnd = G.product(A, B)
+    ref, tol = acc, bnd
+    if bias is not None or relu:
+        ref, _, ebnd, _ = G.epilogue(acc, dict(bias=bias, relu=relu))
+        tol = bnd * (1 + 1e-6) + ebnd          # ReLU is a contraction: the product's error carries; the epilogue bound is taken at the reference accumulator
+    if out16:
+        tol = tol + np.maximum(PI.ULP["bf16"] * np.abs(ref), 2.0 ** -133)
+    return check_tol(np.abs(got - ref), tol, got, ref, what)
+
+
 # variants 20x: the LDS-DMA kernel with MT = x row tiles per workgroup (201: the 16-row blocks of the M <= 32 recurrent step; 202 with a
 # ragged last block and many rows: the K = 2048 many-row routing)
 @pytest.mark.parametrize("M,N,K,variant", [(64, 2048, 2048, 82), (64, 2048, 2048, 84), (37, 256, 512, 82), (5, 32, 128, 41), (16, 1024, 4096, 81),
@@ -142,6 +158,7 @@ def test_skinny_gemm(M, N, K, variant):
     torch.cuda.synchronize()
     ref = f64(A) @ f64(W).T
     assert np.abs(f64(out) - ref).max() / np.abs(ref).max() < 6e-3
+    _product_per_element(f64(out), f64(A), f64(W), f"skinny {M}x{N}x{K} variant {variant}")
 
 
 @pytest.mark.parametrize("N,K", [(384, 128), (128, 384), (2048, 128), (128, 2048), (96, 6144)])
@@ -172,6 +189,7 @@ def test_skinny_kchunk_reads_fragment_ordered_weights(M, N, K):
     torch.cuda.synchronize()
     ref = f64(A) @ f64(W).T
     assert np.abs(f64(out) - ref).max() / np.abs(ref).max() < 6e-3
+    _product_per_element(f64(out), f64(A), f64(W), f"kchunk on fragment-ordered W {M}x{N}x{K}")
 
 
 @pytest.mark.parametrize("M", [40, 64])
@@ -188,6 +206,7 @@ def test_skinny_dual_launch(M):
     for z in range(2):
         ref = f64(A[z]) @ f64(W[z]).T
         assert np.abs(f64(out[z]) - ref).max() / np.abs(ref).max() < 6e-3, z
+        _product_per_element(f64(out[z]), f64(A[z]), f64(W[z]), f"dual launch M={M} problem {z}")
 
 
 def test_tr_read_lane_mapping():
@@ -222,6 +241,8 @@ def test_gemm_glds_matches_fp64(M, N, K):
     err = ((c.double() - ref).abs().max() / ref.abs().max()).item()
     assert err < 2e-5, err                       # fp32 accumulation of exact bf16 products
     assert (c - c_old).abs().max().item() <= 2e-5 * ref.abs().max().item()
+    for got, name in ((c, "LDS-DMA"), (c_old, "register-staged")):
+        _product_per_element(f64(got), f64(a), f64(b), f"gemm {name} {M}x{N}x{K}", out16=False, bias=f64(bias), relu=1)
 
 
 @pytest.mark.parametrize("variant,S", [(0, 5), (0, 32), (0, 47), (1, 1), (1, 5), (1, 8), (1, 16), (1, 17), (1, 20), (1, 32), (2, 33), (2, 47), (2, 64), (2, 9)])
