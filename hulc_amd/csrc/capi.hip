@@ -125,6 +125,10 @@ int hulc_aux_heads_enable(hulc_ctx* ctx, int32_t bc_z, int32_t mia) {
     if (!ctx) { hulc_set_error("hulc_aux_heads_enable: null context"); return 1; }
     return ctx->e->aux_heads_enable(bc_z, mia);
 }
+int hulc_decoder_select(hulc_ctx* ctx, int32_t decoder, int32_t criterion) {
+    if (!ctx) { hulc_set_error("hulc_decoder_select: null context"); return 1; }
+    return ctx->e->decoder_select(decoder, criterion);
+}
 int hulc_aux_weights_set(hulc_ctx* ctx, float bc_z_weight, float mia_weight) {
     if (!ctx) { hulc_set_error("hulc_aux_weights_set: null context"); return 1; }
     return ctx->e->aux_weights_set(bc_z_weight, mia_weight);
@@ -406,6 +410,17 @@ int hulc_k_normal_kl_sample(int32_t dtype, const float* pr_state, const float* p
 }
 int hulc_k_normal_rsample_bwd(int32_t dtype, const float* dplan, const float* eps, const float* pr_state, const float* dpr_kl, int32_t B, int32_t n, void* out, void* stream) {
     HULC_K_ANY("hulc_k_normal_rsample_bwd", k_normal_rsample_bwd, dplan, eps, pr_state, dpr_kl, B, n, out, stream);
+}
+// the deterministic decoder's head (det_head.h)
+int hulc_k_det_head_loss(int32_t dtype, const void* H1, const void* W, const float* bias, const float* actions, const float* robot_obs, int32_t B, int32_t S,
+                         int32_t criterion, int32_t frame, float grad_scale, const float* lscale, float* row_loss, float* pred, float* dpre, void* stream) {
+    HULC_K_ANY("hulc_k_det_head_loss", k_det_head_loss, H1, W, bias, actions, robot_obs, B, S, criterion, frame, grad_scale, lscale, row_loss, pred, dpre, stream);
+}
+int hulc_k_det_head_bwd(int32_t dtype, const float* dpre, const void* W, const void* H1, int32_t B, int32_t S, void* dH1, void* dZ1, float* dW, float* db, void* stream) {
+    HULC_K_ANY("hulc_k_det_head_bwd", k_det_head_bwd, dpre, W, H1, B, S, dH1, dZ1, dW, db, stream);
+}
+int hulc_k_det_head_act(int32_t dtype, const void* h1, const void* W, const float* bias, const float* robot_obs, int32_t n, float* out, void* stream) {
+    HULC_K_ANY("hulc_k_det_head_act", k_det_head_act, h1, W, bias, robot_obs, n, out, stream);
 }
 int hulc_k_layernorm_fwd(int32_t dtype, const float* x, int64_t ldx, int32_t rows, int32_t n, const float* g, const float* b, void* out, int64_t ldo, float* out_f32, int64_t ldf,
                          float* stats, void* stream) {

@@ -21,6 +21,7 @@
 #include "rollout_step.h"
 #include "aux_heads.h"
 #include "aux_rows.h"
+#include "det_head.h"
 
 namespace HULC_NS {
 
@@ -56,11 +57,12 @@ struct Engine : IEngine {
         if (hipMalloc(&p, bytes) != hipSuccess) { alloc_failed = true; return nullptr; }
         hipMemsetAsync(p, 0, bytes, st);
         allocs.push_back(p);
-        ws_bytes += bytes;
+        ws_bytes += bytes; alloc_sz[p] = bytes;
         if (name) named[name] = Named{p, n, kind >= 0 ? kind : (std::is_same<U, float>::value ? 0 : (std::is_same<U, int>::value ? 2 : 1))};
         return (U*)p;
     }
     bool alloc_failed = false;
+    std::map<void*, int64_t> alloc_sz;      // bytes of every block of the arena (release() gives a block back)
 
     // ---- weights
     struct LinW {
@@ -196,6 +198,12 @@ struct Engine : IEngine {
     int bcz_n = 0, mia_n = 0;                                // rows the heads of the last forward ran on (0: not launched, loss 0)
     float *clip_rows_ws = nullptr, *mia_rows_ws = nullptr;   // aux_rows.h workspaces of the n > 64 kernels: only a context with max_batch > 64 has them
     int aux_rows_last = 0;                                   // rows of the last forward / validate, for hulc_aux_losses_get
+    // deterministic action decoder (det_head.h; hulc_decoder_select): off unless selected before the bind — then the packed mixture heads are neither allocated,
+    // bound nor launched, and action_decoder.actions.0.* is read straight from the bound parameters (16-bit engines: from their shadow)
+    bool det = false, dec_selected = false; int det_crit = HULC_CRIT_HUBER;
+    const float *det_w32 = nullptr, *det_b32 = nullptr; float *det_dw = nullptr, *det_db = nullptr;
+    const T* det_w = nullptr;
+    float* dpre = nullptr;                                   // [S B][8]: gradient of the head's pre-activation
     // ---- state of the last forward
     hulc_batch cur{}; float cur_lw = 0, cur_cw = 0; bool have_fwd = false;
 
@@ -328,6 +336,32 @@ struct Engine : IEngine {
         if (mia && B > AUX_ROWS_SINGLE) mia_rows_ws = alloc<float>(mia_rows_ws_floats(B));
         if (alloc_failed) { hulc_set_error("hulc_aux_heads_enable: workspace allocation failed"); return 1; }
         aux_bcz = bc_z != 0; aux_mia = mia != 0;
+        return 0;
+    }
+    // ---------------------------------------------------------------- deterministic action decoder (include/hulc_hip.h: hulc_decoder_select)
+    template <typename U> void release(U*& p) {
+        if (!p) return;
+        for (auto it = named.begin(); it != named.end();) { if (it->second.p == (void*)p) it = named.erase(it); else ++it; }
+        allocs.erase(std::remove(allocs.begin(), allocs.end(), (void*)p), allocs.end());
+        ws_bytes -= alloc_sz[(void*)p]; alloc_sz.erase((void*)p);
+        hipFree((void*)p); p = nullptr;
+    }
+    int decoder_select(int decoder, int criterion) override {
+        if (bound) { hulc_set_error("hulc_decoder_select after hulc_bind_params (the head's tensors are bound by name: select the decoder first)"); return 1; }
+        if (decoder != HULC_DECODER_LOGISTIC && decoder != HULC_DECODER_DETERMINISTIC) { hulc_set_error("hulc_decoder_select: unknown decoder %d", decoder); return 1; }
+        if (dec_selected) { hulc_set_error("hulc_decoder_select: the decoder of this context is already selected"); return 1; }
+        if (decoder == HULC_DECODER_LOGISTIC) { dec_selected = true; return 0; }
+        if (cfg.kind == HULC_KIND_GCBC) { hulc_set_error("hulc_decoder_select: HULC_KIND_GCBC with the deterministic decoder has no reference behaviour (GCBC.forward raises: torch.cat of a (B,0) plan with (B,S,.) tensors)"); return 1; }
+        if (mcil) { hulc_set_error("hulc_decoder_select: the deterministic decoder is not built for HULC_KIND_MCIL* (gripper_control false, 128-wide embedding slice)"); return 1; }
+        if (criterion != HULC_CRIT_HUBER && criterion != HULC_CRIT_MSE) { hulc_set_error("hulc_decoder_select: criterion %d (HULC_CRIT_HUBER or HULC_CRIT_MSE)", criterion); return 1; }
+        static_assert(HID == DET_HID, "det_head.h is built for the 2048-wide decoder");
+        HIP_CHECK(hipStreamSynchronize(st));      // the buffers' clearing memsets
+        const int64_t SB = (int64_t)maxS * maxB;
+        release(heads); release(dheads); release(wheads); release(wheadsT);
+        dpre = alloc<float>(SB * DET_LD, "det_dpre");
+        if (alloc_failed) { hulc_set_error("hulc_decoder_select: workspace allocation failed"); return 1; }
+        for (int i = 0; i < 4; ++i) head_rows[i] = 0;
+        det = true; det_crit = criterion; dec_selected = true;
         return 0;
     }
     int aux_weights_set(float bc_z_weight, float mia_weight) override { aux_w_bcz = bc_z_weight; aux_w_mia = mia_weight; return 0; }
@@ -519,10 +553,16 @@ struct Engine : IEngine {
             bind_lin(whh0, ad + "rnn.weight_hh_l0", HID, HID, false);
             bind_lin(wih1, ad + "rnn.weight_ih_l1", HID, HID, false);
             bind_lin(whh1, ad + "rnn.weight_hh_l1", HID, HID, false);
-            add_tr_packed(wheads, wheadsT, NHEAD, HID);      // the packed heads' transposed copy rides on the batched transpose as well
+            if (!det) add_tr_packed(wheads, wheadsT, NHEAD, HID);      // the packed heads' transposed copy rides on the batched transpose as well
             const char* hn[4] = {"prob_fc", "mean_fc", "log_scale_fc", "gripper_fc"};
             for (int i = 0; i < 4; ++i) { head_w32[i] = head_b32[i] = nullptr; head_dw[i] = head_db[i] = nullptr; }
-            for (int i = 0; i < (mcil ? 3 : 4); ++i) {
+            if (det) {
+                det_w32 = pw(ad + "actions.0.weight"); det_b32 = pw(ad + "actions.0.bias"); det_dw = gw(ad + "actions.0.weight"); det_db = gw(ad + "actions.0.bias");
+                if (tab.at(ad + "actions.0.weight").n != (int64_t)DET_OUT * HID || tab.at(ad + "actions.0.bias").n != DET_OUT) {
+                    hulc_set_error("hulc_bind_params: action_decoder.actions.0 must be Linear(2048, 7)"); return 1; }
+                det_w = std::is_same<T, float>::value ? (const T*)det_w32 : (const T*)(wshadow + (det_w32 - P));
+            }
+            for (int i = 0; i < (det ? 0 : (mcil ? 3 : 4)); ++i) {
                 head_w32[i] = pw(ad + hn[i] + ".weight"); head_b32[i] = pw(ad + hn[i] + ".bias");
                 head_dw[i] = gw(ad + hn[i] + ".weight"); head_db[i] = gw(ad + hn[i] + ".bias");
             }

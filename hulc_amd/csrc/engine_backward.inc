@@ -207,6 +207,11 @@
         {
             // heads
             const long long lastBH = (long long)(S - 1) * BH;          // the BPTT's first step (t = S-1) needs no multiplication: written by the GEMM that produces dH
+            if (det) {      // dH1 (+ dZ1 of the last step) and the head's weight / bias gradients (det_head.h): slabs in the idle convolution slab arena, summed in order
+                if (part_cur + (int64_t)det_head_slabs(SB) * DET_SLAB > this->partcap) { hulc_set_error("hulc_backward: no room for the deterministic head's gradient slabs"); return 1; }
+                launch_det_head_dgrad<T>(st, dpre, det_w, H1, B, S, dH1, dZ1 + lastBH);
+                launch_det_head_wgrad<T>(st, dpre, H1, SB, this->part + part_cur, det_dw, det_db);
+            } else {
             { EpiP ep = epi(dH1, false); ep.out2 = dZ1 + lastBH; ep.out2_lo = lastBH; ep.out2_hi = lastBH + BH; ep.out2_mask = H1 + lastBH;
               gemm(dense<T>(dheads, SB, NHEAD), dense<T>(wheadsT, HID, NHEAD), dense_out(HID), ep, SB, HID, NHEAD); }
             {
@@ -230,6 +235,7 @@
                     lin_wgrad(dheads, H1, HID, SB, NHEAD, HID, dwheads_tmp, HID, dbheads_tmp);
                     hipLaunchKernelGGL(unpack_heads_grad_kernel, dim3(cdiv((long long)rows * HID, 256)), dim3(256), 0, st, hp, dwheads_tmp, dbheads_tmp, HID, 1, 0ll);
                 }
+            }
             }
             // layer 1 BPTT
             rnn_bwd(dH1, H1, dZ1, whh1, B, S, 1, false, false, true);

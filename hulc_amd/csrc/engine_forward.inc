@@ -199,6 +199,7 @@
               if (!h0_1) { ep.out2 = H1; ep.out2_lo = 0; ep.out2_hi = BH; ep.out2_relu = 1; }
               gemm(dense<T>(H0, SB, HID), dense<T>(wih1.W, HID, HID), dense_out(HID), ep, SB, HID, HID); }
             rnn_fwd(Zx1, H1, whh1, B, S, h0_1, 1, false, !h0_1);
+            if (det) return;      // the deterministic head reads H1 itself (det_head.h): no heads GEMM
             { EpiP ep = epi(heads, true); ep.bias = bheads;
               gemm(dense<T>(H1, SB, HID), dense<T>(wheads, NHEAD, HID), dense_out(NHEAD), ep, SB, NHEAD, HID); }
     }
@@ -332,7 +333,9 @@
             // mcil_default.yaml: gripper_control false (no tcp-frame transform), discrete_gripper false (7th mixture dimension instead of the CE head)
             constexpr int ll_block = 64;     // one wave per workgroup: 256 CUs x 1 wave instead of 64 CUs x 4 (the kernel is one long serial chain per thread)
             // 16-bit engines: one lane per mixture component (kernels.h logistic_loss_wide_kernel: 17.9 -> ~6 us); the fp32 parity engine keeps the serial kernel's summation order
-            if (!std::is_same<T, float>::value && NMIX <= 16 && NDIM <= 7)
+            if (det)      // tanh head + Huber / MSE against the world-frame actions (deterministic_decoder.py:82-94) + the pre-activation gradient, one launch
+                launch_det_head_loss<T>(st, H1, det_w, det_b32, actions_of(*b), b->robot_obs, B, S, det_crit, 0, lw / (float)(S * Bm), lscale(), rowloss, 8, nullptr, dpre);
+            else if (!std::is_same<T, float>::value && NMIX <= 16 && NDIM <= 7)
                 hipLaunchKernelGGL((logistic_loss_wide_kernel<T>), dim3(SB), dim3(128), 0, st, heads, NHEAD, actions_of(*b), b->robot_obs, B, S, NMIX, NDIM,
                                    cfg.num_classes, cfg.log_scale_min, cfg.gripper_alpha, mcil ? 0 : 1, lw / (float)(S * Bm), rowloss, a_tcp, dheads, mcil ? 0 : 1, lscale());
             else

@@ -75,6 +75,12 @@
                 if (po) HIP_CHECK(hipMemcpyAsync(po, plan_f, sizeof(float) * B * (PLAN / 2), hipMemcpyDefault, st));
             }
             dec_fwd(pass == 0 ? pidx_pp : pidx, B, S, nullptr, nullptr);
+            if (det) {      // loss_and_act (deterministic_decoder.py:63-80): the criterion in the tcp frame, the prediction in the world frame; no noise (u_mix / u_act ignored)
+                launch_det_head_loss<T>(st, H1, det_w, det_b32, acts, b->robot_obs, B, S, det_crit, 1, 0.f, nullptr, rowloss, 8, nullptr, dpre);
+                hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, rowloss, SB * 8, 1.f / SB, valm + pass);
+                launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, b->robot_obs, acts, B, S, pass == 0 ? pred_pp : pred_pr, valm + 8 + 8 * pass);
+                continue;
+            }
             hipLaunchKernelGGL((logistic_loss_kernel<T, NMIX>), dim3(cdiv(SB * 8, 256)), dim3(256), 0, st, heads, NHEAD, acts, b->robot_obs, B, S, NMIX, NDIM,
                                cfg.num_classes, cfg.log_scale_min, cfg.gripper_alpha, mcil ? 0 : 1, 0.f, rowloss, a_tcp, dheads, mcil ? 0 : 1);
             hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, rowloss, SB * 8, 1.f / SB, valm + pass);
@@ -281,9 +287,10 @@
         HIP_CHECK(hipMemcpyAsync(roll_h1, H1, sizeof(T) * HID, hipMemcpyDeviceToDevice, st));
         roll_has_h = true;
         HIP_CHECK(hipMemcpyAsync(roll_ro, obs->robot_obs_raw, sizeof(float) * 15, hipMemcpyDefault, st));
+        if (det) { u_mix = u_act = nullptr; launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, roll_ro, nullptr, 1, 1, roll_pred, nullptr); }      // deterministic head: the noise is ignored
         if (u_mix) { HIP_CHECK(hipMemcpyAsync(nz_mix, u_mix, sizeof(float) * NDIM * NMIX, hipMemcpyDefault, st)); u_mix = nz_mix; }
         if (u_act) { HIP_CHECK(hipMemcpyAsync(nz_act, u_act, sizeof(float) * NDIM, hipMemcpyDefault, st)); u_act = nz_act; }
-        hipLaunchKernelGGL(logistic_sample_kernel, dim3(1), dim3(64), 0, st, heads, NHEAD, roll_ro, (const float*)nullptr, u_mix, u_act, 1, 1, NMIX, NDIM,
+        if (!det) hipLaunchKernelGGL(logistic_sample_kernel, dim3(1), dim3(64), 0, st, heads, NHEAD, roll_ro, (const float*)nullptr, u_mix, u_act, 1, 1, NMIX, NDIM,
                            cfg.log_scale_min, mcil ? 0 : 1, site_seed(51), roll_pred, (float*)nullptr, mcil ? 0 : 1);
         HIP_CHECK(hipMemcpyAsync(action_out, roll_pred, sizeof(float) * 7, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));

@@ -170,6 +170,7 @@
         bb.B = n; bb.S = 1; bb.step = env_counter++;
         cur = bb;
         HIP_CHECK(hipMemcpyAsync(env_ro, obs->robot_obs_raw, sizeof(float) * 15 * n, hipMemcpyDefault, st));
+        if (det) u_mix = u_act = nullptr;      // deterministic head: the noise is ignored
         if (u_mix) { HIP_CHECK(hipMemcpyAsync(nz_mix, u_mix, sizeof(float) * n * NDIM * NMIX, hipMemcpyDefault, st)); u_mix = nz_mix; }
         if (u_act) { HIP_CHECK(hipMemcpyAsync(nz_act, u_act, sizeof(float) * n * NDIM, hipMemcpyDefault, st)); u_act = nz_act; }
         const Conv1Src src[2] = {conv1_src_f32(obs->rgb_static), conv1_src_f32(obs->rgb_gripper)};
@@ -187,12 +188,15 @@
             l1.Wx = wih1.W; l1.wx_ld = HID; l1.Whh = whh1.W; l1.h = env_h1; l1.ctab = nullptr; l1.b1 = bih1; l1.b2 = bhh1;
             l1.w16 = a16(l1.Wx) && a16(l1.Whh);
             hipLaunchKernelGGL(env_rnn_layer_kernel, dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l1);
+            if (det) launch_det_head_act<T>(st, env_h1, env_rows, env_cap, det_w, det_b32, env_ro, nullptr, n, 1, env_pred, nullptr);      // the new layer-1 state of every row's slot
+            else {
             EnvHeadsP hp{};
             hp.rowdesc = env_rows; hp.n = n; hp.max_envs = env_cap; hp.h1 = env_h1; hp.W = wheads; hp.bias = bheads; hp.robot_obs = env_ro; hp.u_mix = u_mix; hp.u_act = u_act;
             hp.NMIX = NMIX; hp.NDIM = NDIM; hp.log_scale_min = cfg.log_scale_min; hp.gripper_control = mcil ? 0 : 1; hp.discrete_gripper = mcil ? 0 : 1;
             hp.seed = site_seed(53); hp.pred = env_pred;
             if (NHEAD == 192) hipLaunchKernelGGL((env_heads_sample_kernel<12>), dim3(cdiv(n, 16)), dim3(ENV_WAVES * 64), 0, st, hp);
             else hipLaunchKernelGGL((env_heads_sample_kernel<14>), dim3(cdiv(n, 16)), dim3(ENV_WAVES * 64), 0, st, hp);
+            }
         } else {
             // the fp32 parity engine composes the generic path: slot state -> rows, dec_fwd at B = n, S = 1, rows -> slots, the validation sampler
             EnvGatherP g{}; g.rowdesc = env_rows; g.n = n; g.max_envs = env_cap; g.NCAT = env_ncat(); g.PC = env_pc();
@@ -201,7 +205,8 @@
             hipLaunchKernelGGL((env_gather_kernel<T>), dim3(n), dim3(256), 0, st, g);
             dec_fwd(env_pidx, n, 1, env_ha, env_hb);
             hipLaunchKernelGGL((env_scatter_hidden_kernel<T>), dim3(n), dim3(256), 0, st, env_rows, env_cap, H0, H1, env_h0, env_h1);
-            hipLaunchKernelGGL(logistic_sample_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, heads, NHEAD, env_ro, (const float*)nullptr, u_mix, u_act, n, 1, NMIX, NDIM,
+            if (det) launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, env_ro, nullptr, n, 1, env_pred, nullptr);
+            else hipLaunchKernelGGL(logistic_sample_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, heads, NHEAD, env_ro, (const float*)nullptr, u_mix, u_act, n, 1, NMIX, NDIM,
                                cfg.log_scale_min, mcil ? 0 : 1, site_seed(53), env_pred, (float*)nullptr, mcil ? 0 : 1);
         }
         HIP_CHECK(hipMemcpyAsync(actions_out, env_pred, sizeof(float) * 7 * n, hipMemcpyDeviceToHost, st));

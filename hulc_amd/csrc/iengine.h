@@ -28,6 +28,7 @@ struct IEngine {
     virtual int clip_gt_scores(int slot, float* out_host, int64_t cap, int32_t* n_out, int32_t* m_out) = 0;
     // ---- BC-Z / MIA language auxiliary heads (engine.h, aux_heads.h)
     virtual int aux_heads_enable(int bc_z, int mia) = 0;
+    virtual int decoder_select(int decoder, int criterion) = 0;
     virtual int aux_weights_set(float bc_z_weight, float mia_weight) = 0;
     virtual int aux_losses_get(float* out_host4) = 0;
     virtual int rollout_reset() = 0;
@@ -190,6 +191,10 @@ struct IEngine {
     int k_logistic_loss(int t16, int wide, const float* heads, int ldh, const float* actions, const float* robot_obs, int B, int S, int nmix,   \
                         int ndim, int num_classes, float log_scale_min, float gripper_alpha, int gripper_control, int discrete_gripper,         \
                         float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* stream);                  \
+    int k_det_head_loss(int t16, const void* H1, const void* W, const float* bias, const float* actions, const float* robot_obs, int B, int S, int criterion,     \
+                        int frame, float grad_scale, const float* lscale, float* row_loss, float* pred, float* dpre, void* stream);                              \
+    int k_det_head_bwd(int t16, const float* dpre, const void* W, const void* H1, int B, int S, void* dH1, void* dZ1, float* dW, float* db, void* stream);        \
+    int k_det_head_act(int t16, const void* h1, const void* W, const float* bias, const float* robot_obs, int n, float* out, void* stream);                       \
     int k_plan_kl_sample(const float* pr_logits, const float* pp_logits, int B, int NCAT, int NCLS, const int* idx_in, int* idx_out, float* probs,  \
                          float* kl_cat, float* dpp, float* dpr, float w_pp, float w_pr, unsigned long long seed, const float* lscale, void* stream); \
     int k_st_softmax_bwd(int t16, const float* probs, const float* dplan, const float* dpr_kl, const float* dpp_kl, int rows, int NCLS, float* out,  \

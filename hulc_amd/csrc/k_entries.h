@@ -12,6 +12,7 @@
 #include "plan_ln_launch.h"
 #include "gemm.h"
 #include "tr_fused.h"
+#include "det_head.h"
 #include <vector>
 
 namespace HULC_NS {
@@ -132,6 +133,61 @@ static int k_idx_out_of_range(const char* who, const int* idx, long long count, 
     for (long long i = 0; i < count; ++i)
         if (h[i] < 0 || h[i] >= NCLS) { hulc_set_error("%s: plan index %d at position %lld is outside [0, %d)", who, h[i], i, NCLS); return 1; }
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- deterministic decoder head (det_head.h)
+static inline bool k_det_shape_bad(const char* who, int B, int S) {
+    if (B < 1 || S < 1 || (long long)B * S > (1 << 22)) { hulc_set_error("%s: B=%d S=%d (need B, S >= 1 and B*S <= 2^22)", who, B, S); return true; }
+    return false;
+}
+int k_det_head_loss(int t16, const void* H1, const void* W, const float* bias, const float* actions, const float* robot_obs, int B, int S, int criterion, int frame,
+                    float grad_scale, const float* lscale, float* row_loss, float* pred, float* dpre, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (k_det_shape_bad("hulc_k_det_head_loss", B, S)) return 1;
+    if ((criterion != HULC_CRIT_HUBER && criterion != HULC_CRIT_MSE) || (frame != 0 && frame != 1)) { hulc_set_error("hulc_k_det_head_loss: criterion=%d frame=%d (both 0 or 1)", criterion, frame); return 1; }
+    if (!H1 || !W || !bias || !actions || !robot_obs || !row_loss || !pred || !dpre) { hulc_set_error("hulc_k_det_head_loss: null argument"); return 1; }
+    if (k_misaligned(H1, 16) || k_misaligned(W, 16) || k_misaligned(dpre, 16) || k_misaligned(bias, 4) || k_misaligned(actions, 4) || k_misaligned(robot_obs, 4) ||
+        k_misaligned(lscale, 4) || k_misaligned(row_loss, 4) || k_misaligned(pred, 4)) { hulc_set_error("hulc_k_det_head_loss: misaligned pointer (H1, W, dpre: 16 bytes; the rest: 4)"); return 1; }
+#define HULC_K_L(TT) launch_det_head_loss<TT>(st, (const TT*)H1, (const TT*)W, bias, actions, robot_obs, B, S, criterion, frame, grad_scale, lscale, row_loss, 1, pred, dpre)
+    HULC_K_T("hulc_k_det_head_loss", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_det_head_loss");
+}
+int k_det_head_bwd(int t16, const float* dpre, const void* W, const void* H1, int B, int S, void* dH1, void* dZ1, float* dW, float* db, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (k_det_shape_bad("hulc_k_det_head_bwd", B, S)) return 1;
+    if (!dpre || !W || !H1 || !dH1 || !dZ1 || !dW || !db) { hulc_set_error("hulc_k_det_head_bwd: null argument"); return 1; }
+    if (k_misaligned(dpre, 16) || k_misaligned(W, 16) || k_misaligned(H1, 16) || k_misaligned(dH1, 16) || k_misaligned(dZ1, 16) || k_misaligned(dW, 4) || k_misaligned(db, 4)) {
+        hulc_set_error("hulc_k_det_head_bwd: misaligned pointer (dpre, W, H1, dH1, dZ1: 16 bytes; dW, db: 4)"); return 1; }
+    float* part = nullptr;
+    if (hipMalloc((void**)&part, sizeof(float) * (size_t)det_head_slabs(B * S) * DET_SLAB) != hipSuccess) { hulc_set_error("hulc_k_det_head_bwd: hipMalloc failed"); return 1; }
+#define HULC_K_L(TT)                                                                                                     \
+    do {                                                                                                                 \
+        launch_det_head_dgrad<TT>(st, dpre, (const TT*)W, (const TT*)H1, B, S, (TT*)dH1, (TT*)dZ1);                       \
+        launch_det_head_wgrad<TT>(st, dpre, (const TT*)H1, B * S, part, dW, db);                                         \
+    } while (0)
+#ifdef HULC_HALF_F16
+    if (!t16) { hipFree(part); hulc_set_error("hulc_k_det_head_bwd: the fp32 instances live in the bf16 translation unit"); return 1; }
+    HULC_K_L(h16_t);
+#else
+    if (t16) HULC_K_L(h16_t); else HULC_K_L(float);
+#endif
+#undef HULC_K_L
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);
+    hipFree(part);
+    if (e1 != hipSuccess || e2 != hipSuccess) { hulc_set_error("hulc_k_det_head_bwd: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); return 1; }
+    return 0;
+}
+int k_det_head_act(int t16, const void* h1, const void* W, const float* bias, const float* robot_obs, int n, float* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (k_det_shape_bad("hulc_k_det_head_act", n, 1)) return 1;
+    if (!h1 || !W || !bias || !robot_obs || !out) { hulc_set_error("hulc_k_det_head_act: null argument"); return 1; }
+    if (k_misaligned(h1, 16) || k_misaligned(W, 16) || k_misaligned(bias, 4) || k_misaligned(robot_obs, 4) || k_misaligned(out, 4)) {
+        hulc_set_error("hulc_k_det_head_act: misaligned pointer (h1, W: 16 bytes; the rest: 4)"); return 1; }
+#define HULC_K_L(TT) launch_det_head_act<TT>(st, (const TT*)h1, nullptr, 0, (const TT*)W, bias, robot_obs, nullptr, n, 1, out, nullptr)
+    HULC_K_T("hulc_k_det_head_act", HULC_K_L);
+#undef HULC_K_L
+    return k_launched("hulc_k_det_head_act");
 }
 
 int k_plan_kl_sample(const float* pr_logits, const float* pp_logits, int B, int NCAT, int NCLS, const int* idx_in, int* idx_out, float* probs, float* kl_cat, float* dpp,

@@ -42,6 +42,8 @@ class StepEngine:
         self.aux_heads = bool(dims.use_bc_z or dims.use_mia)
         if self.aux_heads:      # before the bind: the heads' tensors are then required by name (include/hulc_hip.h: hulc_aux_heads_enable)
             L.check(self.lib.hulc_aux_heads_enable(self.ctx, int(dims.use_bc_z), int(dims.use_mia)))
+        if dims.decoder == "deterministic":      # before the bind as well: action_decoder.actions.0.* replaces the mixture heads (hulc_decoder_select)
+            L.check(self.lib.hulc_decoder_select(self.ctx, L.DECODER["deterministic"], L.CRITERION[dims.criterion]))
         names = list(self.layout.keys())
         self._names = (C.c_char_p * len(names))(*[n.encode() for n in names])
         self._offs = (C.c_int64 * len(names))(*[self.layout[n][0] for n in names])

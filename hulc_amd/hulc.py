@@ -242,6 +242,31 @@ class Hulc(torch.nn.Module):
         ad = action_decoder
         self.kind = self.KIND
         rnn_type = "nn.RNN"
+        # model/action_decoder=deterministic (deterministic_decoder.py): the same rnn_decoder, then Linear(2048, 7) + tanh and nn.HuberLoss / nn.MSELoss
+        det = "DeterministicDecoder" in str(_get(ad, "_target_", ""))
+        criterion = "HuberLoss"
+        if det:
+            criterion = str(_get(ad, "criterion", "HuberLoss"))
+            if criterion not in ("HuberLoss", "MSELoss"):
+                raise NotImplementedError(f"action_decoder.criterion {criterion!r}: the built criteria are HuberLoss and MSELoss")
+            if self.KIND != "hulc":
+                raise NotImplementedError("model=gcbc with the deterministic decoder: the reference raises inside forward (torch.cat of a (B,0) plan with (B,S,.) tensors), "
+                                          "there is no behaviour to reproduce")
+            if _get(distribution, "dist", "discrete") == "continuous" or "BiRNN" in str(_get(pr, "_target_", "Transformers")):
+                raise NotImplementedError("the deterministic decoder is not built for the mcil option group (continuous distribution / BiRNN plan recognition)")
+            if not _get(ad, "gripper_control", True):
+                raise NotImplementedError("action_decoder.gripper_control false: the deterministic head is built with the tcp-frame transforms of gripper_control true "
+                                          "(conf/model/action_decoder/deterministic.yaml)")
+            for key, want, why in (("hidden_size", 2048, "the head reads the 2048-wide decoder state"), ("num_layers", 2, "the decoder recurrence has two layers"),
+                                   ("rnn_model", "rnn_decoder", "gru_decoder / lstm_decoder / mlp_decoder have no engine path"),
+                                   ("policy_rnn_dropout_p", 0.0, "the decoder recurrence has no dropout"), ("out_features", 7, "the head has 7 outputs (6 + gripper)")):
+                v = _get(ad, key, want)
+                if not isinstance(v, str) or key == "rnn_model":
+                    if (str(v) if key == "rnn_model" else float(v)) != (want if key == "rnn_model" else float(want)):
+                        raise NotImplementedError(f"action_decoder.{key} {v!r} with the deterministic decoder: {why} (built: {want!r})")
+            sl = _get(ad, "perceptual_emb_slice", [64, 128])
+            if sl is None or (not isinstance(sl, str) and [int(x) for x in sl] != [64, 128]):
+                raise NotImplementedError(f"action_decoder.perceptual_emb_slice {sl!r}: the decoder is built on the gripper half [64, 128]")
         # conf/model/mcil.yaml: the same Hulc class with a BiRNN plan recognition net, a continuous plan distribution
         # and the mcil decoder options; the three go together (any other mix has no built engine path)
         mcil_flags = [_get(distribution, "dist", "discrete") == "continuous", "BiRNN" in str(_get(pr, "_target_", "Transformers")),
@@ -306,7 +331,7 @@ class Hulc(torch.nn.Module):
         mw = _get(pr, "max_position_embeddings", 32) or 32
         max_window = 32 if isinstance(mw, str) else int(mw)      # a dangling ${...} (vision_only datasets) falls back to 32
         self.dims = spec.ModelDims(kind=self.kind, max_window=max_window, use_clip=self.use_clip_auxiliary_loss, use_bc_z=self.use_bc_z_auxiliary_loss, use_mia=self.use_mia_auxiliary_loss,
-                                   rnn_type="gru" if (self.kind == "mcil" and rnn_type == "nn.GRU") else "rnn")
+                                   rnn_type="gru" if (self.kind == "mcil" and rnn_type == "nn.GRU") else "rnn", decoder="deterministic" if det else "logistic", criterion=criterion)
         # Lightning precision flags: 16 / "16-mixed" = native AMP fp16 + GradScaler (the reference's conf/trainer/play_trainer.yaml:3) ->
         # the fp16 engine with its on-device loss scaler; bf16 needs none; 32 = the fp32 parity engine
         pmap = {"16": "fp16", "fp16": "fp16", "16-mixed": "fp16", "bf16": "bf16", "bf16-mixed": "bf16", "32": "fp32", "fp32": "fp32", "32-true": "fp32"}
@@ -356,6 +381,8 @@ class Hulc(torch.nn.Module):
         ad = "action_decoder."
         ss = "perceptual_encoder.rgb_static_encoder.spatial_softmax."
         nd = self.dims.mix_dims                       # logistic_decoder_rnn.py:61: out_features - 1 with the discrete gripper head
+        if self.dims.decoder == "deterministic":      # DeterministicDecoder registers no buffers
+            return {ss + "x_map": lin.repeat_interleave(21), ss + "y_map": lin.repeat(21), ss + "temperature": torch.ones(1)}
         buf = {ss + "x_map": lin.repeat_interleave(21), ss + "y_map": lin.repeat(21), ss + "temperature": torch.ones(1),
                ad + "one_hot_embedding_eye": torch.eye(10), ad + "ones": torch.ones(1, 1, 10),
                ad + "action_max_bound": torch.ones(1, 1, nd, 10), ad + "action_min_bound": -torch.ones(1, 1, nd, 10)}

@@ -37,6 +37,9 @@ class ModelDims:
     act_dims: int = 6             # out_features - 1 (discrete gripper)
     num_classes: int = 10
 
+    decoder: str = "logistic"     # "logistic" (LogisticDecoderRNN) | "deterministic" (DeterministicDecoder: Linear(hidden, 7) + tanh; kind "hulc" only)
+    criterion: str = "HuberLoss"  # deterministic decoder: "HuberLoss" | "MSELoss" (torch.nn, reduction "mean")
+
     cont_plan: int = 256          # mcil: distribution.plan_features (conf/model/distribution/continuous.yaml)
     rnn_type: str = "rnn"         # mcil: plan_recognition.rnn_type — "rnn" = nn.RNN (tanh; birnn.yaml default), "gru" = nn.GRU (BASELINE config 4)
 
@@ -152,12 +155,21 @@ def param_table(d: ModelDims) -> List[Tuple[str, Tuple[int, ...], tuple]]:
         t.append((f"{ad}rnn.weight_hh_l{l}", (H, H), ("u", H)))
         t.append((f"{ad}rnn.bias_ih_l{l}", (H,), ("u", H)))
         t.append((f"{ad}rnn.bias_hh_l{l}", (H,), ("u", H)))
-    no = d.mix_dims * d.n_mix
-    lin(ad + "mean_fc", no, H)
-    lin(ad + "log_scale_fc", no, H)
-    lin(ad + "prob_fc", no, H)
-    if d.kind != "mcil":
-        lin(ad + "gripper_fc", 2, H)
+    if d.decoder == "deterministic":      # deterministic_decoder.py:35: nn.Sequential(nn.Linear(hidden_size, out_features), nn.Tanh())
+        if d.kind != "hulc":
+            raise ValueError(f"the deterministic decoder is built for kind 'hulc' only (got {d.kind!r})")
+        if d.criterion not in ("HuberLoss", "MSELoss"):
+            raise ValueError(f"criterion {d.criterion!r}: 'HuberLoss' or 'MSELoss'")
+        lin(ad + "actions.0", d.act_dims + 1, H)
+    elif d.decoder != "logistic":
+        raise ValueError(f"decoder {d.decoder!r}: 'logistic' or 'deterministic'")
+    else:
+        no = d.mix_dims * d.n_mix
+        lin(ad + "mean_fc", no, H)
+        lin(ad + "log_scale_fc", no, H)
+        lin(ad + "prob_fc", no, H)
+        if d.kind != "mcil":
+            lin(ad + "gripper_fc", 2, H)
 
     if d.use_clip or d.use_mia:
         lin("proj_vis_lang.mlp_im.0", 128, d.fc_hidden)

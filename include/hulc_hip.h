@@ -358,6 +358,22 @@ int hulc_aux_heads_enable(hulc_ctx* ctx, int32_t bc_z, int32_t mia);
 int hulc_aux_weights_set(hulc_ctx* ctx, float bc_z_weight, float mia_weight);
 int hulc_aux_losses_get(hulc_ctx* ctx, float* out_host /* (4) */);
 
+/* ---- Deterministic action decoder (hulc/models/decoders/deterministic_decoder.py; conf/model/action_decoder/deterministic.yaml): the same two-layer
+ * rnn_decoder, then Linear(2048, 7) + tanh in place of the logistic-mixture heads, trained with nn.HuberLoss (HULC_CRIT_HUBER) or nn.MSELoss (HULC_CRIT_MSE),
+ * reduction "mean" over (B, S, 7).  hulc_decoder_select(ctx, HULC_DECODER_DETERMINISTIC, criterion): after hulc_ctx_create and BEFORE hulc_bind_params (later: an
+ * error), HULC_KIND_HULC only (the reference's GCBC raises inside forward with this decoder; the mcil option group is not built), once per context (a second
+ * call: an error).  The bound table must then name action_decoder.actions.0.{weight (7,2048), bias (7)} and need not name mean_fc / log_scale_fc / prob_fc /
+ * gripper_fc; the packed-head buffers are released.  HULC_DECODER_LOGISTIC is accepted and changes nothing.  A context that never calls it allocates, binds and
+ * launches exactly what it did before.
+ * The TRAINING loss compares the tanh output with the WORLD-frame actions: DeterministicDecoder.loss computes the tcp-frame criterion and discards it
+ * (deterministic_decoder.py:91-94); hulc_validate (loss_and_act) compares in the tcp frame.  Predictions are mapped tcp -> world everywhere.  The noise
+ * arguments of hulc_validate / hulc_rollout_act / hulc_rollout_envs_act (u_mix, u_act) are accepted and ignored: the head is deterministic. */
+#define HULC_DECODER_LOGISTIC 0
+#define HULC_DECODER_DETERMINISTIC 1
+#define HULC_CRIT_HUBER 0
+#define HULC_CRIT_MSE 1
+int hulc_decoder_select(hulc_ctx* ctx, int32_t decoder, int32_t criterion);
+
 /* ---- Rollout (Hulc.reset / step, hulc/models/hulc.py:843-957; stateful LogisticDecoderRNN.act, logistic_decoder_rnn.py:102-116).
  * hulc_rollout_plan  = get_pp_plan_vision (:905-927: obs and goal frame encoded as one 2-frame window) or get_pp_plan_lang
  *                      (:929-948): latent goal + a plan sampled from the plan proposal; clears the decoder's hidden state.
@@ -596,6 +612,22 @@ int hulc_k_enc_tail_bwd(int32_t dtype, int32_t Nf, int32_t ldemb, const hulc_enc
 int hulc_k_logistic_loss(int32_t dtype, int32_t wide, const float* heads, int32_t ldh, const float* actions, const float* robot_obs, int32_t B, int32_t S,
                          int32_t n_mix, int32_t n_dim, int32_t num_classes, float log_scale_min, float gripper_alpha, int32_t gripper_control,
                          int32_t discrete_gripper, float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out, void* dheads, void* hip_stream);
+
+/* ---- the deterministic decoder's head, one kernel per entry (csrc/det_head.h; launched through the helpers the engine calls).  dtype = the engine type T of
+ * H1 / W / dH1 / dZ1: HULC_DTYPE_F32, HULC_DTYPE_BF16 or HULC_DTYPE_F16.  Rows are time-major (r = t*B + b); actions [B][S][7], robot_obs [B][S][15] and pred
+ * [B][S][7] are batch-major fp32 like the batch.  Every entry refuses null or misaligned (16 bytes; 4 for bias / actions / robot_obs / lscale) pointers and
+ * B, S, n < 1 or B*S, n > 2^22 without launching.
+ * hulc_k_det_head_loss: pre = H1 W^T + bias, p = tanh(pre), d = p - target with target = actions (frame 0, training) or world_to_tcp_frame(actions, robot_obs)
+ *   (frame 1, validation).  row_loss [S*B] = sum_j l(d_j) / 7, l = Huber (delta 1) or the squared error; pred = tcp_to_world_frame(p, robot_obs);
+ *   dpre [S*B][8] fp32 = grad_scale (* lscale[0] when the device float is given) l'(d) (1 - p^2) / 7, column 7 zero.
+ * hulc_k_det_head_bwd: dH1 [S*B][2048] = dpre W (type T), dZ1 [B][2048] = dH1 (H1 > 0) of the rows of time step S-1; dW [7][2048] and db [7] fp32 ACCUMULATE
+ *   sum_r dpre[r][j] H1[r][k] and sum_r dpre[r][j]: per 256-row slabs summed in slab order (the same bits on every run).  Synchronises (it owns the slab scratch).
+ * hulc_k_det_head_act: n rows h1 [n][2048] -> out [n][7] = tcp_to_world_frame(tanh(h1 W^T + bias), robot_obs [n][15]). */
+int hulc_k_det_head_loss(int32_t dtype, const void* H1, const void* W, const float* bias, const float* actions, const float* robot_obs, int32_t B, int32_t S,
+                         int32_t criterion, int32_t frame, float grad_scale, const float* lscale, float* row_loss, float* pred, float* dpre, void* hip_stream);
+int hulc_k_det_head_bwd(int32_t dtype, const float* dpre, const void* W, const void* H1, int32_t B, int32_t S, void* dH1, void* dZ1, float* dW, float* db,
+                        void* hip_stream);
+int hulc_k_det_head_act(int32_t dtype, const void* h1, const void* W, const float* bias, const float* robot_obs, int32_t n, float* out, void* hip_stream);
 
 /* ---- the latent-plan kernels and the LayerNorm family, one kernel per entry (csrc/kernels.h; launched as the engine launches them, csrc/plan_ln_launch.h).
  * dtype = the engine type T of the kernel instance: HULC_DTYPE_F32, HULC_DTYPE_BF16 or HULC_DTYPE_F16; "T" below is float or the 16-bit type.  Every entry

@@ -110,6 +110,12 @@ w("model/action_decoder/hulc_default.yaml", dict(
     act_max_bound="${datamodule.action_max}", act_min_bound="${datamodule.action_min}", dataset_dir="${datamodule.root_data_dir}",
     latent_goal_features="${model.visual_goal.latent_goal_features}", plan_features="???", perceptual_features="???"),
   H.format("action_decoder/hulc_default.yaml"))
+# model/action_decoder=deterministic: the plain behaviour-cloning head (Linear + tanh, nn.HuberLoss / nn.MSELoss) on the same rnn_decoder
+w("model/action_decoder/deterministic.yaml", dict(
+    _target_="hulc.models.decoders.deterministic_decoder.DeterministicDecoder", criterion="HuberLoss", hidden_size=2048, num_layers=2,
+    rnn_model="rnn_decoder", policy_rnn_dropout_p=0.0, gripper_control=True, perceptual_emb_slice=[64, 128], out_features="${datamodule.action_space}",
+    latent_goal_features="${model.visual_goal.latent_goal_features}", plan_features="???", perceptual_features="???"),
+  H.format("action_decoder/deterministic.yaml"))
 w("model/optimizer/adam.yaml", dict(_target_="torch.optim.Adam", lr="${training.lr}"), H.format("optimizer/adam.yaml"))
 w("model/optimizer/adamw.yaml", dict(_target_="torch.optim.AdamW", lr="${training.lr}", weight_decay=1.0e-6), H.format("optimizer/adamw.yaml"))
 w("model/optimizer/sgd.yaml", dict(_target_="torch.optim.SGD", lr="${training.lr}", momentum=0.9), H.format("optimizer/sgd.yaml"))
