@@ -536,28 +536,19 @@ int hulc_k_attention(int32_t variant, const float* qkv, float* P, float* ao, con
     return 0;
 }
 
+// The encoder's convolution family (k_entries.h: k_conv_wgrad, k_conv1_wgrad_u8, k_conv_tile, k_conv_pair, k_conv_plan).  The entries without a dtype are the bf16
+// wrappers; the _t entries take HULC_DTYPE_BF16 or HULC_DTYPE_F16 and refuse anything else before anything is allocated or launched
+#define HULC_K_CONV_T(name, call)                                                                                          \
+    if (dtype == HULC_DTYPE_F16) return hulc_f16::call;                                                                    \
+    if (dtype == HULC_DTYPE_BF16) return hulc_bf16::call;                                                                  \
+    hulc_set_error(name ": dtype %d is not a 16-bit type (HULC_DTYPE_BF16 or HULC_DTYPE_F16)", (int)dtype);                \
+    return 1
 // conv wgrad unit-test entry (bf16 NHWC): out[CO][KH*KW*CI] (packed (kh,kw,ci) order, fp32, overwritten)
 int hulc_k_conv_wgrad(int32_t which, const void* X, const void* dY, float* out, int32_t Nf, int32_t IH, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    float* part = nullptr;
-    static float* bias_tmp = nullptr;
-    if (!bias_tmp && hipMalloc(&bias_tmp, sizeof(float) * 512 * 64) != hipSuccess) { hulc_set_error("hulc_k_conv_wgrad: hipMalloc failed"); return 1; }
-    const int KC = which == 3 ? 576 : (which == 2 ? 512 : 192);
-    const int CO = which == 1 ? 32 : 64;
-    if (hipMalloc(&part, sizeof(float) * 512ll * 64 * KC) != hipSuccess) { hulc_set_error("hulc_k_conv_wgrad: hipMalloc failed"); return 1; }
-    int ns;
-    static h16_t* zp = nullptr;                   // zero page of the LDS-DMA kernel (pad slots, columns / rows beyond the frame)
-    if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_wgrad: hipMalloc failed"); return 1; } hipMemset(zp, 0, 256); }
-    if (which == 3) { const int OH = IH - 2; ns = launch_conv_wgrad_tr<64, 64, 3, 3, 1>(st, (const h16_t*)X, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512, nullptr, zp); }
-    else if (which == 2) { const int OH = (IH - 4) / 2 + 1; ns = launch_conv_wgrad_tr<32, 64, 4, 4, 2>(st, (const h16_t*)X, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512, nullptr, zp); }
-    else if (which == 1) { const int OH = (IH - 8) / 4 + 1; ns = launch_conv1_wgrad_tr(st, Conv1Src{X, nullptr, 0, 0}, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512); }
-    else { hipFree(part); hulc_set_error("hulc_k_conv_wgrad: which must be 1, 2 or 3"); return 1; }
-    hipMemsetAsync(out, 0, sizeof(float) * CO * KC, st);
-    hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((CO * KC + 1023) / 1024), dim3(256), 0, st, part, ns, (long long)CO * KC, out, CO, KC, 1, 1, 0);
-    hipError_t e = hipStreamSynchronize(st);
-    hipFree(part);
-    if (e != hipSuccess) { hulc_set_error("hulc_k_conv_wgrad: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return hulc_bf16::k_conv_wgrad("hulc_k_conv_wgrad", 0, which, X, dY, out, nullptr, Nf, IH, nullptr, stream);
+}
+int hulc_k_conv_wgrad_t(int32_t dtype, int32_t which, const void* X, const void* dY, float* out, float* db_out, int32_t Nf, int32_t IH, int32_t* slabs, void* stream) {
+    HULC_K_CONV_T("hulc_k_conv_wgrad_t", k_conv_wgrad("hulc_k_conv_wgrad_t", 1, which, X, dY, out, db_out, Nf, IH, slabs, stream));
 }
 
 // host arithmetic only (no device needed): the interior group range the uint8 conv1 kernels convert without clamps (conv_wgrad.h::conv1_interior_groups)
@@ -568,89 +559,27 @@ int hulc_k_conv1_interior_groups(int32_t IW, int32_t pad, int32_t cap, int32_t* 
     return 0;
 }
 
-// conv1's weight gradient from uint8 (Nf,IH,IH,3) frames alone (tests): dW (32,192) [torch (o, c, kh, kw) order] and db (32) of the frames after ScaleImageTensor / Normalize /
-// RandomShiftsAug — form 1: conversion from the prefetch registers (conv1_wgrad_tr2r_kernel), 2: the same with interior / row-end slots (the engine's); fold = Conv1Src::fold
+// conv1's weight gradient from uint8 (Nf,IH,IH,3) frames alone (tests): dW (32,192) [torch (o, c, kh, kw) order] and db (32)
 int hulc_k_conv1_wgrad_u8(const void* X, const int32_t* shifts, int32_t pad, const void* dY, float* dw_out, float* db_out, int32_t Nf, int32_t IH, int32_t form, int32_t fold, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (form != 1 && form != 2) { hulc_set_error("hulc_k_conv1_wgrad_u8: form must be 1 or 2 (got %d)", (int)form); return 1; }      // before any device call
-    float *part = nullptr, *bias = nullptr;
-    if (hipMalloc(&part, sizeof(float) * 512ll * 32 * 192) != hipSuccess || hipMalloc(&bias, sizeof(float) * 64) != hipSuccess) { hulc_set_error("hulc_k_conv1_wgrad_u8: hipMalloc failed"); return 1; }
-    hipMemsetAsync(bias, 0, sizeof(float) * 64, st);
-    Conv1Src src{}; src.X = X; src.shift = shifts; src.u8 = 1; src.pad = pad; src.fold = fold != 0;
-    const int OH = (IH - 8) / 4 + 1;
-    const int keep = g_conv1_wgrad_u8reg;
-    g_conv1_wgrad_u8reg = form;
-    const int ns = launch_conv1_wgrad_tr(st, src, (const h16_t*)dY, part, bias, Nf, IH, IH, OH, OH, 512);
-    g_conv1_wgrad_u8reg = keep;
-    hipMemsetAsync(dw_out, 0, sizeof(float) * 32 * 192, st);
-    hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((32 * 192 + 1023) / 1024), dim3(256), 0, st, part, ns, (long long)32 * 192, dw_out, 32, 192, 1, 1, 0);
-    hipMemcpyAsync(db_out, bias, sizeof(float) * 32, hipMemcpyDeviceToDevice, st);
-    hipError_t e = hipStreamSynchronize(st);
-    hipFree(part); hipFree(bias);
-    if (e != hipSuccess) { hulc_set_error("hulc_k_conv1_wgrad_u8: %s", hipGetErrorString(e)); return 1; }
-    return 0;
+    return hulc_bf16::k_conv1_wgrad_u8("hulc_k_conv1_wgrad_u8", 0, X, shifts, pad, dY, dw_out, db_out, Nf, IH, form, fold, nullptr, stream);
+}
+int hulc_k_conv1_wgrad_u8_t(int32_t dtype, const void* X, const int32_t* shifts, int32_t pad, const void* dY, float* dw_out, float* db_out, int32_t Nf, int32_t IH, int32_t form,
+                            int32_t fold, int32_t* slabs, void* stream) {
+    HULC_K_CONV_T("hulc_k_conv1_wgrad_u8_t", k_conv1_wgrad_u8("hulc_k_conv1_wgrad_u8_t", 1, X, shifts, pad, dY, dw_out, db_out, Nf, IH, form, fold, slabs, stream));
 }
 
-// raw-tile conv kernels alone (bf16 NHWC): mode 0 fwd 3x3/s1 64->64, 1 fwd 4x4/s2 32->64, 2 dgrad of (0), 3 dgrad of (1)
+// raw-tile conv kernels alone (bf16 NHWC): mode 0 fwd 3x3/s1 64->64, 1 fwd 4x4/s2 32->64, 2 dgrad of (0), 3 dgrad of (1); the other modes: include/hulc_hip.h
 int hulc_k_conv_tile(int32_t mode, const void* img, const void* w, const float* bias, const void* mask, void* out, int32_t Nf, int32_t IMH,
                      int32_t OUTH, int32_t relu, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    // every argument is checked before anything is allocated or launched.  relu: bit 0 = ReLU, bit 5 (32) = dynamic work claiming, bit 8 (256, modes 5 / 6) = the
-    // register-staged uint8 conv1 forward (conv1_fwd_kernel<4, true>, the cross-check of the LDS-DMA kernel)
-    if (mode < 0 || mode > 29 || (mode >= 14 && mode <= 16) || (mode >= 24 && mode <= 26)) { hulc_set_error("hulc_k_conv_tile: unsupported mode %d", (int)mode); return 1; }
-    if ((relu & ~(1 | 32 | 256)) || ((relu & 256) && mode != 5 && mode != 6)) { hulc_set_error("hulc_k_conv_tile: unknown bits in relu (%d) for mode %d", (int)relu, (int)mode); return 1; }
-    ConvTileP p{}; p.img = (const h16_t*)img; p.IMH = p.IMW = IMH; p.w = (const h16_t*)w; p.out = (h16_t*)out; p.OUTH = p.OUTW = OUTH;
-    p.bias = bias; p.mask = (const h16_t*)mask; p.relu = relu & 1; p.Nf = Nf;
-    // modes 7..9 = the production forms: 7 = mode 1 that also EMITS the ReLU bitmask of its output into `mask` (unsigned[Nf][OUTH][OUTW][2]);
-    // 8 / 9 = modes 2 / 3 with `mask` = ReLU bitmask words (2 / 1 per output pixel) staged through LDS.  relu bit 5 (32): dynamic work claiming.
-    if (mode == 7) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 1; }
-    else if (mode == 8 || mode == 9) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode -= 6; }
-    if (relu & 32) {
-        static int* ctr = nullptr;
-        if (!ctr && hipMalloc(&ctr, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_tile: hipMalloc failed"); return 1; }
-        hipMemsetAsync(ctr, 0, 256, st);
-        p.work_ctr = ctr;
-    }
-    {   // conv_reg.h pipelined-epilogue forms (modes 28 / 29 and what falls back from them): a scratch page for the stores of pixels that must not be written
-        static void* dp = nullptr;
-        if (!dp && hipMalloc(&dp, 8192) != hipSuccess) { hulc_set_error("hulc_k_conv_tile: hipMalloc failed"); return 1; }
-        p.dump = (h16_t*)dp;
-    }
-    bool ok = false;
-    // modes 10 / 11 / 17: modes 0 / 1 / 7 on the weights-in-registers kernels (conv_reg.h); 12 / 18: modes 2 / 8 (conv3 data gradient, 16-bit mask / bitmask)
-    if (mode == 17) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 11; }
-    if (mode == 18) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 12; }
-    if (mode == 19) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 13; }      // 13 / 19: modes 3 / 9 (conv2 data gradient, four parity classes)
-    // modes 20 / 21 / 27 / 22 / 28 / 23 / 29: modes 10 .. 19 in the form with two 256-thread workgroups per CU (conv_reg.h, NWV = 4)
-    if (mode == 27) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 21; }
-    if (mode == 28) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 22; }
-    if (mode == 29) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 23; }
-    if (mode == 12 || mode == 13 || mode == 22 || mode == 23) {      // the data-gradient forms stage their zero border from a zero page
-        static void* zp = nullptr;
-        if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_tile: hipMalloc failed"); return 1; } hipMemset(zp, 0, 256); }
-        p.zeros = (const h16_t*)zp;
-    }
-    if (mode == 20) ok = launch_conv_reg<64, 3, 3, 1, false, 1, 4>(st, p);
-    else if (mode == 21) ok = launch_conv_reg<32, 4, 4, 2, false, 1, 4, true>(st, p);         // the production form for small maps: slot decode in registers (conv_reg.h PKR)
-    else if (mode == 22) ok = launch_conv_reg<64, 3, 3, 1, true, 1, 4, true, 1>(st, p);       // the production forms: PKR + pipelined epilogue (EPI; 16-bit mask values
-    else if (mode == 23) ok = launch_conv_reg<64, 2, 2, 1, true, 2, 4, true, 1>(st, p);       // = modes 22 / 23 fall back to the pair form inside launch_conv_reg)
-    else if (mode == 10) ok = launch_conv_reg_fwd<64, 3, 3, 1>(st, p);
-    else if (mode == 11) ok = launch_conv_reg_fwd<32, 4, 4, 2>(st, p);
-    else if (mode == 12) ok = launch_conv_reg<64, 3, 3, 1, true>(st, p);
-    else if (mode == 13) ok = launch_conv_reg<64, 2, 2, 1, true, 2>(st, p);
-    else if (mode == 0) ok = launch_conv_tile<64, 64, 3, 3, 1, 1, false>(st, p);
-    else if (mode == 1) ok = launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p);
-    else if (mode == 2) ok = launch_conv_tile<64, 64, 3, 3, 1, 1, true>(st, p);
-    else if (mode == 3) ok = launch_conv_tile<64, 32, 2, 2, 1, 2, true>(st, p);
-    else if (mode == 4) { launch_conv1_fwd(st, Conv1Src{img, nullptr, 0, 0}, (const h16_t*)w, bias, (h16_t*)out, Nf, IMH, IMH, OUTH, OUTH); ok = true; }
-    else if (mode == 5 || mode == 6) {      // conv1 forward from uint8 NHWC frames; mode 6: `mask` = (Nf,2) int32 RandomShiftsAug shifts, pad 10 (IMH >= 100) or 4
-        launch_conv1_fwd(st, Conv1Src{img, mode == 6 ? (const int*)mask : nullptr, 1, IMH >= 100 ? 10 : 4}, (const h16_t*)w, bias, (h16_t*)out, Nf, IMH, IMH, OUTH,
-                         OUTH, (relu & 256) != 0);
-        ok = true;
-    }
-    if (!ok) { hulc_set_error("hulc_k_conv_tile: unsupported mode/shape"); return 1; }
-    if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_conv_tile: launch failed"); return 1; }
-    return 0;
+    return hulc_bf16::k_conv_tile("hulc_k_conv_tile", 0, mode, img, w, bias, mask, out, nullptr, Nf, IMH, OUTH, relu, 0, stream);
+}
+int hulc_k_conv_tile_t(int32_t dtype, int32_t mode, const void* img, const void* w, const float* bias, const void* mask, void* out, uint32_t* bits1_out, int32_t Nf, int32_t IMH,
+                       int32_t OUTH, int32_t relu, int32_t wgs, void* stream) {
+    HULC_K_CONV_T("hulc_k_conv_tile_t", k_conv_tile("hulc_k_conv_tile_t", 1, mode, img, w, bias, mask, out, bits1_out, Nf, IMH, OUTH, relu, wgs, stream));
+}
+// host arithmetic only (no device needed): plan_conv_reg's band / stack geometry of a weights-in-registers form (the same for both 16-bit types)
+int hulc_k_conv_plan(int32_t form, int32_t frames, int32_t in_side, int32_t out_side, int32_t wgs, int32_t* nbands, int32_t* rows_per_band, int32_t* frames_per_band, int32_t* items) {
+    return hulc_bf16::k_conv_plan(form, frames, in_side, out_side, wgs, nbands, rows_per_band, frames_per_band, items);
 }
 
 // host arithmetic only (no device needed): the division of a launch's persistent workgroups between the two cameras' jobs (conv_wgrad.h::camera_split)
@@ -661,101 +590,14 @@ int hulc_k_camera_split(int32_t grid, double work_static, double work_gripper, i
     return 0;
 }
 
-// One stage of both encoders as ONE launch (conv_reg.h launch_conv_reg_jobs, conv_wgrad.h launch_conv_wgrad_pair /
-// launch_conv1_wgrad_jobs) in the forms the engine runs, dynamic claiming on (one zeroed counter per job, as the engine's next_ctr()); b == NULL: job a alone through the same entry
+// One stage of both encoders as ONE launch, in the forms the engine runs (k_entries.h: k_conv_pair); b == NULL: job a alone through the same entry
 int hulc_k_conv_pair(int32_t stage, const hulc_conv_job* a, const hulc_conv_job* b, int32_t wg_a, int32_t wg_b, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const bool fwd = stage == HULC_PAIR_CONV2_FWD || stage == HULC_PAIR_CONV3_FWD, dgr = stage == HULC_PAIR_CONV3_DGRAD || stage == HULC_PAIR_CONV2_DGRAD;
-    const bool wgr = stage == HULC_PAIR_CONV3_WGRAD || stage == HULC_PAIR_CONV2_WGRAD || stage == HULC_PAIR_CONV1_WGRAD;
-    // every argument is checked before anything is allocated or written
-    if (!fwd && !dgr && !wgr) { hulc_set_error("hulc_k_conv_pair: unknown stage %d", (int)stage); return 1; }
-    if (!a) { hulc_set_error("hulc_k_conv_pair: job a is required"); return 1; }
-    if (wg_a < 1 || (b && wg_b < 1)) { hulc_set_error("hulc_k_conv_pair: every job needs at least one workgroup"); return 1; }
-    if (wgr && !b) { hulc_set_error("hulc_k_conv_pair: the weight-gradient stages need both jobs"); return 1; }
-    {
-        const hulc_conv_job* src[2] = {a, b};
-        for (int k = 0; k < (b ? 2 : 1); ++k)
-            if (!src[k]->in || !src[k]->w || !src[k]->out || src[k]->frames < 1 || src[k]->in_side < 1 || src[k]->out_side < 1 || (wgr && !src[k]->bits)) { hulc_set_error("hulc_k_conv_pair: incomplete job"); return 1; }
-    }
-    if (wgr) {
-        const int KH = stage == HULC_PAIR_CONV1_WGRAD ? 8 : (stage == HULC_PAIR_CONV3_WGRAD ? 3 : 4), S = stage == HULC_PAIR_CONV1_WGRAD ? 4 : (stage == HULC_PAIR_CONV3_WGRAD ? 1 : 2);
-        if (a->in_side < KH || b->in_side < KH || a->out_side != (a->in_side - KH) / S + 1 || b->out_side != (b->in_side - KH) / S + 1) { hulc_set_error("hulc_k_conv_pair: out_side does not belong to in_side"); return 1; }
-    }
-    static void *dp = nullptr, *zp = nullptr;
-    static int* ctr = nullptr;
-    if (!dp && hipMalloc(&dp, 8192) != hipSuccess) { hulc_set_error("hulc_k_conv_pair: hipMalloc failed"); return 1; }
-    if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_pair: hipMalloc failed"); return 1; } hipMemset(zp, 0, 256); }
-    if (!ctr && hipMalloc(&ctr, 256) != hipSuccess) { hulc_set_error("hulc_k_conv_pair: hipMalloc failed"); return 1; }
-    hipMemsetAsync(ctr, 0, 256, st);      // job k claims through ctr + 16 k
-    if (wgr) {
-        // weight gradients: the launch writes one slab per workgroup, each job's slabs are then summed into its own output as hulc_k_conv_wgrad does.  Synchronises
-        const bool c1 = stage == HULC_PAIR_CONV1_WGRAD, c3 = stage == HULC_PAIR_CONV3_WGRAD;
-        const int KC = c1 ? 192 : (c3 ? 576 : 512), CO = c1 ? 32 : 64;
-        float* part = nullptr;
-        if (hipMalloc(&part, sizeof(float) * (size_t)(wg_a + wg_b) * CO * KC) != hipSuccess) { hulc_set_error("hulc_k_conv_pair: hipMalloc failed"); return 1; }
-        const hulc_conv_job* src[2] = {a, b};
-        const int wg[2] = {wg_a, wg_b};
-        int ns[2] = {0, 0};
-        bool okw = false;
-        if (c1) {      // fp32 NCHW frames (the headline boundary): both jobs on conv1_wgrad_tr2_kernel<6, 2>
-            Wgrad1Job J[2];
-            for (int k = 0; k < 2; ++k) {
-                Wgrad1Job q{}; q.S = Conv1Src{src[k]->in, nullptr, 0, 0}; q.work_ctr = ctr + 16 * k; q.dY = (const h16_t*)src[k]->w; q.bias_part = (float*)src[k]->bits;
-                q.Nf = src[k]->frames; q.IH = q.IW = src[k]->in_side; q.OH = q.OW = src[k]->out_side;
-                J[k] = q;
-            }
-            J[0].part = part;
-            size_t l0 = 0, l1 = 0; int r, nb;
-            okw = conv1_wgrad_plan(J[0].S, J[0].IH, J[0].IW, J[0].OH, J[0].OW, r, nb, l0) == conv1_wgrad_plan(J[1].S, J[1].IH, J[1].IW, J[1].OH, J[1].OW, r, nb, l1);
-            if (okw) {
-                for (int k = 0; k < 2; ++k) { hipMemsetAsync(src[k]->bits, 0, sizeof(float) * CO, st); hipMemsetAsync(src[k]->out, 0, sizeof(float) * CO * KC, st); }
-                okw = launch_conv1_wgrad_jobs(st, J, 2, 1024, wg, ns);
-            }
-        } else {
-            WgradJob J[2];
-            for (int k = 0; k < 2; ++k) {
-                WgradJob q{}; q.X = (const h16_t*)src[k]->in; q.dY = (const h16_t*)src[k]->w; q.bias_part = (float*)src[k]->bits; q.zeros = (const h16_t*)zp; q.work_ctr = ctr + 16 * k;
-                q.Nf = src[k]->frames; q.IH = q.IW = src[k]->in_side; q.OH = q.OW = src[k]->out_side; q.FPB = 1;
-                J[k] = q;
-            }
-            J[0].part = part;
-            using W3 = WgradCamW<64, 3>; using W2 = WgradCamW<32, 4>;
-            okw = c3 ? (a->in_side == W3::stat && b->in_side == W3::gripper) : (a->in_side == W2::stat && b->in_side == W2::gripper);      // the shapes the launch takes: nothing is written otherwise
-            if (okw) {
-                for (int k = 0; k < 2; ++k) { hipMemsetAsync(src[k]->bits, 0, sizeof(float) * CO, st); hipMemsetAsync(src[k]->out, 0, sizeof(float) * CO * KC, st); }
-                okw = c3 ? launch_conv_wgrad_pair<64, 64, 3, 3, 1>(st, J[0], J[1], 512, wg, ns) : launch_conv_wgrad_pair<32, 64, 4, 4, 2>(st, J[0], J[1], 512, wg, ns);
-            }
-        }
-        if (okw) {
-            hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((CO * KC + 1023) / 1024), dim3(256), 0, st, part, ns[0], (long long)CO * KC, (float*)a->out, CO, KC, 1, 1, 0);
-            hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((CO * KC + 1023) / 1024), dim3(256), 0, st, part + (long long)ns[0] * CO * KC, ns[1], (long long)CO * KC, (float*)b->out, CO, KC, 1, 1, 0);
-        }
-        const hipError_t e = hipStreamSynchronize(st);
-        hipFree(part);
-        if (!okw) { hulc_set_error("hulc_k_conv_pair: unsupported shape (the two cameras' maps only)"); return 1; }
-        if (e != hipSuccess) { hulc_set_error("hulc_k_conv_pair: %s", hipGetErrorString(e)); return 1; }
-        return 0;
-    }
-    ConvTileP j[2]; int wg[2] = {wg_a, wg_b};
-    const hulc_conv_job* src[2] = {a, b};
-    const int n = b ? 2 : 1;
-    for (int k = 0; k < n; ++k) {
-        ConvTileP p{}; p.img = (const h16_t*)src[k]->in; p.IMH = p.IMW = src[k]->in_side; p.w = (const h16_t*)src[k]->w; p.out = (h16_t*)src[k]->out; p.OUTH = p.OUTW = src[k]->out_side;
-        p.Nf = src[k]->frames; p.dump = (h16_t*)dp;
-        if (fwd) { p.bias = src[k]->bias; p.relu = 1; p.bits_out = (unsigned*)src[k]->bits; }
-        else { p.maskbits = (const unsigned*)src[k]->bits; p.zeros = (const h16_t*)zp; }
-        p.work_ctr = ctr + 16 * k;
-        j[k] = p;
-    }
-    bool ok = false;
-    if (stage == HULC_PAIR_CONV2_FWD) ok = launch_conv_reg_fwd_jobs<32, 4, 4, 2>(st, j, n, wg);
-    else if (stage == HULC_PAIR_CONV3_FWD) ok = launch_conv_reg_fwd_jobs<64, 3, 3, 1>(st, j, n, wg);
-    else if (stage == HULC_PAIR_CONV3_DGRAD) ok = launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, true, 1>(st, j, n, wg);
-    else ok = launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, true, 1>(st, j, n, wg);
-    if (!ok) { hulc_set_error("hulc_k_conv_pair: unsupported shape"); return 1; }
-    if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_conv_pair: launch failed"); return 1; }
-    return 0;
+    return hulc_bf16::k_conv_pair("hulc_k_conv_pair", 0, stage, a, b, wg_a, wg_b, nullptr, stream);
 }
+int hulc_k_conv_pair_t(int32_t dtype, int32_t stage, const hulc_conv_job* a, const hulc_conv_job* b, int32_t wg_a, int32_t wg_b, int32_t* slabs, void* stream) {
+    HULC_K_CONV_T("hulc_k_conv_pair_t", k_conv_pair("hulc_k_conv_pair_t", 1, stage, a, b, wg_a, wg_b, slabs, stream));
+}
+#undef HULC_K_CONV_T
 
 // skinny GEMM alone (bf16): out[M][N] (bf16) = A[M][K] W[N][K]^T ; variant = NW*10 + MT (e.g. 82 = 8 waves, 32-row blocks)
 int hulc_k_skinny(const void* A, const void* W, void* out, int32_t M, int32_t N, int32_t K, int32_t variant, void* stream) {

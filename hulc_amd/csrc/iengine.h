@@ -222,6 +222,15 @@ struct IEngine {
     int k_gemm_epi(int t16, const hulc_gemm_epi_job* j, int kernel, int* ran, void* stream);                                                    \
     int k_gemm_multi(int form, const hulc_gemm_epi_job* jobs, int n, int sh, int* ran, void* stream);                                           \
     int k_gemm_pick(int t16, int M, int N, int K, long long lda, long long ldb, int* pick, int* bk);                                            \
-    int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big);
+    int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big);                                                               \
+    int k_conv_wgrad(const char* who, int typed, int which, const void* X, const void* dY, float* out, float* db_out, int Nf, int IH, int* slabs, \
+                     void* stream);                                                                                                             \
+    int k_conv1_wgrad_u8(const char* who, int typed, const void* X, const int* shifts, int pad, const void* dY, float* dw_out, float* db_out,   \
+                         int Nf, int IH, int form, int fold, int* slabs, void* stream);                                                         \
+    int k_conv_tile(const char* who, int typed, int mode, const void* img, const void* w, const float* bias, const void* mask, void* out,       \
+                    unsigned* bits1_out, int Nf, int IMH, int OUTH, int relu, int wgs, void* stream);                                           \
+    int k_conv_pair(const char* who, int typed, int stage, const hulc_conv_job* a, const hulc_conv_job* b, int wg_a, int wg_b, int* slabs,      \
+                    void* stream);                                                                                                              \
+    int k_conv_plan(int form, int frames, int in_side, int out_side, int wgs, int* nbands, int* rows_per_band, int* frames_per_band, int* items);
 namespace hulc_bf16 { HULC_TU_DECLS }   // capi.hip: HULC_DTYPE_F32 / HULC_DTYPE_BF16
 namespace hulc_f16 { HULC_TU_DECLS }    // engine_f16.hip: HULC_DTYPE_F16

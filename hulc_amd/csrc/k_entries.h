@@ -2,7 +2,9 @@
 // hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss), of the latent-plan kernels (hulc_k_plan_*, hulc_k_st_softmax_bwd, hulc_k_normal_*), of
 // the LayerNorm family (hulc_k_layernorm_*; launched through plan_ln_launch.h, which the engine calls too) and of the fused transformer layer kernels
 // (hulc_k_tr_layer_fwd, hulc_k_tr_ffn_bwd, hulc_k_tr_attn_bwd; launched through tr_fused.h's helpers), and of the GEMM core with its runtime epilogue
-// (hulc_k_gemm_epi, hulc_k_gemm_multi, hulc_k_gemm_pick, hulc_k_gemm_wgrad_nsplit; launched through gemm.h's launchers and routing).  Included by engine.h inside each translation unit, so every entry exists once per
+// (hulc_k_gemm_epi, hulc_k_gemm_multi, hulc_k_gemm_pick, hulc_k_gemm_wgrad_nsplit; launched through gemm.h's launchers and routing), and of the encoder's convolution family
+// (hulc_k_conv_tile, hulc_k_conv_pair, hulc_k_conv_wgrad, hulc_k_conv1_wgrad_u8 and their per-type forms; launched through the launchers of conv_tile.h, conv_reg.h and
+// conv_wgrad.h).  Included by engine.h inside each translation unit, so every entry exists once per
 // 16-bit type (hulc_bf16 / hulc_f16; iengine.h declares them).  Nothing here restates a kernel: each entry checks its arguments, then launches through the
 // helper the engine calls (enc_tail.h) or with the grid and block of the engine's launch site (engine_encoders.inc, engine_forward.inc).
 #pragma once
@@ -656,6 +658,297 @@ int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big) {
     bool b = false;
     *nsplit = t16 ? gemm_wgrad_nsplit<h16_t>(M, N, K, &b) : gemm_wgrad_nsplit<float>(M, N, K, &b);
     *big = b ? 1 : 0;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- the encoder's convolution family (conv_tile.h, conv_reg.h, conv_wgrad.h)
+// hulc_k_conv_wgrad, hulc_k_conv1_wgrad_u8, hulc_k_conv_tile, hulc_k_conv_pair (the bf16 wrappers: typed == 0) and their per-type forms hulc_k_*_t (typed == 1), launched
+// through the launchers engine_encoders.inc calls.  who = the C entry's name (error messages).  typed: the bench-only forms no launch site of engine_encoders.inc names
+// are refused — the 8-wave data-gradient forms (modes 12 / 13 / 18 / 19), the register-staged uint8 conv1 forward (relu bit 256) and the uint8 conv1 weight-gradient
+// form 1 — and out_side must belong to in_side and a data-gradient form must come with its mask; the fp16 unit does not instantiate the 8-wave data-gradient kernels at all.
+// slabs (may be null): the number of partial slabs that were summed into the weight gradient (the pair entry: two numbers)
+static inline int k_conv_fwd_side(int in_side, int K, int S) { return in_side < K ? -1 : (in_side - K) / S + 1; }
+static inline bool k_conv_mode_bench_only(int mode) { return mode == 12 || mode == 13 || mode == 18 || mode == 19; }
+// which = 1: conv1 from fp32 NCHW frames, out [32][192] in (c,kh,kw) order; 2 / 3: conv2 / conv3 from 16-bit NHWC, out [64][KH*KW*CI] in packed (kh,kw,ci) order
+int k_conv_wgrad(const char* who, int typed, int which, const void* X, const void* dY, float* out, float* db_out, int Nf, int IH, int* slabs, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (slabs) *slabs = 0;
+    if (typed) {      // every argument is checked before anything is allocated or launched
+        if (which < 1 || which > 3) { hulc_set_error("%s: which must be 1, 2 or 3", who); return 1; }
+        const int KH = which == 3 ? 3 : (which == 2 ? 4 : 8);
+        if (!X || !dY || !out || Nf < 1 || IH < KH || IH > 4096 || (long long)Nf * IH * IH * 64 >= (1ll << 31)) { hulc_set_error("%s: null argument, or Nf=%d, IH=%d out of range", who, Nf, IH); return 1; }
+    }
+    float* part = nullptr;
+    static float* bias_tmp = nullptr;
+    if (!bias_tmp && hipMalloc(&bias_tmp, sizeof(float) * 512 * 64) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; }
+    const int KC = which == 3 ? 576 : (which == 2 ? 512 : 192);
+    const int CO = which == 1 ? 32 : 64;
+    if (hipMalloc(&part, sizeof(float) * 512ll * 64 * KC) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; }
+    int ns;
+    static h16_t* zp = nullptr;                   // zero page of the LDS-DMA kernel (pad slots, columns / rows beyond the frame)
+    if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; } hipMemset(zp, 0, 256); }
+    if (db_out) hipMemsetAsync(bias_tmp, 0, sizeof(float) * 64, st);      // the kernels add their bias partials to bias_tmp[0 .. CO)
+    if (which == 3) { const int OH = IH - 2; ns = launch_conv_wgrad_tr<64, 64, 3, 3, 1>(st, (const h16_t*)X, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512, nullptr, zp); }
+    else if (which == 2) { const int OH = (IH - 4) / 2 + 1; ns = launch_conv_wgrad_tr<32, 64, 4, 4, 2>(st, (const h16_t*)X, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512, nullptr, zp); }
+    else if (which == 1) { const int OH = (IH - 8) / 4 + 1; ns = launch_conv1_wgrad_tr(st, Conv1Src{X, nullptr, 0, 0}, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512); }
+    else { hipFree(part); hulc_set_error("%s: which must be 1, 2 or 3", who); return 1; }
+    hipMemsetAsync(out, 0, sizeof(float) * CO * KC, st);
+    hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((CO * KC + 1023) / 1024), dim3(256), 0, st, part, ns, (long long)CO * KC, out, CO, KC, 1, 1, 0);
+    if (db_out) hipMemcpyAsync(db_out, bias_tmp, sizeof(float) * CO, hipMemcpyDeviceToDevice, st);
+    hipError_t e = hipStreamSynchronize(st);
+    hipFree(part);
+    if (e != hipSuccess) { hulc_set_error("%s: %s", who, hipGetErrorString(e)); return 1; }
+    if (slabs) *slabs = ns;
+    return 0;
+}
+
+// conv1's weight gradient from uint8 (Nf,IH,IH,3) frames alone: dW (32,192) [torch (o, c, kh, kw) order] and db (32) of the frames after ScaleImageTensor / Normalize /
+// RandomShiftsAug — form 1: conversion from the prefetch registers (conv1_wgrad_tr2r_kernel), 2: the same with interior / row-end slots (the engine's); fold = Conv1Src::fold
+int k_conv1_wgrad_u8(const char* who, int typed, const void* X, const int* shifts, int pad, const void* dY, float* dw_out, float* db_out, int Nf, int IH, int form, int fold, int* slabs,
+                     void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (slabs) *slabs = 0;
+    if (form != 1 && form != 2) { hulc_set_error("%s: form must be 1 or 2 (got %d)", who, form); return 1; }      // before any device call
+    if (typed) {
+        if (form != 2) { hulc_set_error("%s: form %d is a bench-only form (the engine runs form 2)", who, form); return 1; }
+        if (!X || !dY || !dw_out || !db_out || Nf < 1 || IH < 8 || IH > 4096 || pad < 0 || pad > CONV1_RAW_MARGIN) { hulc_set_error("%s: null argument, or Nf=%d, IH=%d, pad=%d out of range", who, Nf, IH, pad); return 1; }
+    }
+    float *part = nullptr, *bias = nullptr;
+    if (hipMalloc(&part, sizeof(float) * 512ll * 32 * 192) != hipSuccess || hipMalloc(&bias, sizeof(float) * 64) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; }
+    hipMemsetAsync(bias, 0, sizeof(float) * 64, st);
+    Conv1Src src{}; src.X = X; src.shift = shifts; src.u8 = 1; src.pad = pad; src.fold = fold != 0;
+    const int OH = (IH - 8) / 4 + 1;
+    const int keep = g_conv1_wgrad_u8reg;
+    g_conv1_wgrad_u8reg = form;
+    const int ns = launch_conv1_wgrad_tr(st, src, (const h16_t*)dY, part, bias, Nf, IH, IH, OH, OH, 512);
+    g_conv1_wgrad_u8reg = keep;
+    hipMemsetAsync(dw_out, 0, sizeof(float) * 32 * 192, st);
+    hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((32 * 192 + 1023) / 1024), dim3(256), 0, st, part, ns, (long long)32 * 192, dw_out, 32, 192, 1, 1, 0);
+    hipMemcpyAsync(db_out, bias, sizeof(float) * 32, hipMemcpyDeviceToDevice, st);
+    hipError_t e = hipStreamSynchronize(st);
+    hipFree(part); hipFree(bias);
+    if (e != hipSuccess) { hulc_set_error("%s: %s", who, hipGetErrorString(e)); return 1; }
+    if (slabs) *slabs = ns;
+    return 0;
+}
+
+// raw-tile / weights-in-registers conv kernels alone (16-bit NHWC): the modes of include/hulc_hip.h.  bits1_out (typed, modes 4 .. 6): conv1's ReLU bit words, one per pixel
+// wgs (typed, the weights-in-registers modes 10 .. 29): the persistent workgroups of the launch (several items per workgroup, stacks sized for them); 0 = the launcher's own
+int k_conv_tile(const char* who, int typed, int mode, const void* img, const void* w, const float* bias, const void* mask, void* out, unsigned* bits1_out, int Nf, int IMH, int OUTH,
+                int relu, int wgs, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    // every argument is checked before anything is allocated or launched.  relu: bit 0 = ReLU, bit 5 (32) = dynamic work claiming, bit 8 (256, modes 5 / 6) = the
+    // register-staged uint8 conv1 forward (conv1_fwd_kernel<4, true>, the cross-check of the LDS-DMA kernel)
+    if (mode < 0 || mode > 29 || (mode >= 14 && mode <= 16) || (mode >= 24 && mode <= 26)) { hulc_set_error("%s: unsupported mode %d", who, mode); return 1; }
+    if ((relu & ~(1 | 32 | 256)) || ((relu & 256) && mode != 5 && mode != 6)) { hulc_set_error("%s: unknown bits in relu (%d) for mode %d", who, relu, mode); return 1; }
+#ifdef HULC_HALF_F16
+    if (k_conv_mode_bench_only(mode)) { hulc_set_error("%s: mode %d is a bench-only form: bf16 only", who, mode); return 1; }
+#endif
+    if (typed) {
+        if (k_conv_mode_bench_only(mode) || (relu & 256)) { hulc_set_error("%s: mode %d, relu %d is a bench-only form no launch site of the engine names", who, mode, relu); return 1; }
+        const int m10 = mode % 10;
+        const bool c1 = mode >= 4 && mode <= 6, dg = !c1 && (m10 == 2 || m10 == 3 || m10 == 8 || m10 == 9), k3 = !c1 && (m10 == 0 || m10 == 2 || m10 == 8);
+        if (!img || !w || !out || (!dg && !bias) || Nf < 1 || IMH < 1 || OUTH < 1 || IMH > 4096 || OUTH > 4096) { hulc_set_error("%s: null argument, or Nf=%d, IMH=%d, OUTH=%d out of range", who, Nf, IMH, OUTH); return 1; }
+        const int want = c1 ? k_conv_fwd_side(IMH, 8, 4) : (k3 ? k_conv_fwd_side(dg ? OUTH : IMH, 3, 1) : k_conv_fwd_side(dg ? OUTH : IMH, 4, 2));
+        if (want < 1 || want != (dg ? IMH : OUTH)) { hulc_set_error("%s: mode %d: out_side %d does not belong to in_side %d", who, mode, OUTH, IMH); return 1; }
+        if (dg && !mask) { hulc_set_error("%s: mode %d is a data-gradient form and needs its mask", who, mode); return 1; }
+        if (mode == 6 && !mask) { hulc_set_error("%s: mode 6 needs the shifts in mask", who); return 1; }
+        if (!c1 && !dg && !(relu & 1)) { hulc_set_error("%s: mode %d: the forward forms run with ReLU (relu bit 0)", who, mode); return 1; }
+        if (wgs < 0 || wgs > 512 || (wgs && mode < 10)) { hulc_set_error("%s: wgs=%d (0 .. 512; the weights-in-registers modes 10 .. 29 only)", who, wgs); return 1; }
+        if (bits1_out && !c1) { hulc_set_error("%s: bits1_out goes with the conv1 forward (modes 4 .. 6); the conv2 forms emit their bit words into mask", who); return 1; }
+    }
+    ConvTileP p{}; p.img = (const h16_t*)img; p.IMH = p.IMW = IMH; p.w = (const h16_t*)w; p.out = (h16_t*)out; p.OUTH = p.OUTW = OUTH;
+    p.bias = bias; p.mask = (const h16_t*)mask; p.relu = relu & 1; p.Nf = Nf;
+    // modes 7..9 = the production forms: 7 = mode 1 that also EMITS the ReLU bitmask of its output into `mask` (unsigned[Nf][OUTH][OUTW][2]);
+    // 8 / 9 = modes 2 / 3 with `mask` = ReLU bitmask words (2 / 1 per output pixel) staged through LDS.  relu bit 5 (32): dynamic work claiming.
+    if (mode == 7) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 1; }
+    else if (mode == 8 || mode == 9) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode -= 6; }
+    if (relu & 32) {
+        static int* ctr = nullptr;
+        if (!ctr && hipMalloc(&ctr, 256) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; }
+        hipMemsetAsync(ctr, 0, 256, st);
+        p.work_ctr = ctr;
+    }
+    {   // conv_reg.h pipelined-epilogue forms (modes 28 / 29 and what falls back from them): a scratch page for the stores of pixels that must not be written
+        static void* dp = nullptr;
+        if (!dp && hipMalloc(&dp, 8192) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; }
+        p.dump = (h16_t*)dp;
+    }
+    bool ok = false;
+    const int* const wgp = (typed && wgs > 0) ? &wgs : nullptr;
+    // modes 10 / 11 / 17: modes 0 / 1 / 7 on the weights-in-registers kernels (conv_reg.h); 12 / 18: modes 2 / 8 (conv3 data gradient, 16-bit mask / bitmask)
+    if (mode == 17) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 11; }
+    if (mode == 18) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 12; }
+    if (mode == 19) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 13; }      // 13 / 19: modes 3 / 9 (conv2 data gradient, four parity classes)
+    // modes 20 / 21 / 27 / 22 / 28 / 23 / 29: modes 10 .. 19 in the form with two 256-thread workgroups per CU (conv_reg.h, NWV = 4)
+    if (mode == 27) { p.mask = nullptr; p.bits_out = (unsigned*)mask; mode = 21; }
+    if (mode == 28) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 22; }
+    if (mode == 29) { p.mask = nullptr; p.maskbits = (const unsigned*)mask; mode = 23; }
+    if (mode == 12 || mode == 13 || mode == 22 || mode == 23) {      // the data-gradient forms stage their zero border from a zero page
+        static void* zp = nullptr;
+        if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; } hipMemset(zp, 0, 256); }
+        p.zeros = (const h16_t*)zp;
+    }
+    if (mode == 20) ok = launch_conv_reg_jobs<64, 3, 3, 1, false, 1, 4>(st, &p, 1, wgp);
+    else if (mode == 21) ok = launch_conv_reg_jobs<32, 4, 4, 2, false, 1, 4, true>(st, &p, 1, wgp);         // the production form for small maps: slot decode in registers (conv_reg.h PKR)
+    else if (mode == 22) ok = launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, true, 1>(st, &p, 1, wgp);       // the production forms: PKR + pipelined epilogue (EPI; 16-bit mask values
+    else if (mode == 23) ok = launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, true, 1>(st, &p, 1, wgp);       // = modes 22 / 23 fall back to the pair form inside launch_conv_reg)
+    else if (mode == 10) ok = launch_conv_reg_fwd_jobs<64, 3, 3, 1>(st, &p, 1, wgp);
+    else if (mode == 11) ok = launch_conv_reg_fwd_jobs<32, 4, 4, 2>(st, &p, 1, wgp);
+#ifndef HULC_HALF_F16
+    else if (mode == 12) ok = launch_conv_reg<64, 3, 3, 1, true>(st, p);
+    else if (mode == 13) ok = launch_conv_reg<64, 2, 2, 1, true, 2>(st, p);
+#endif
+    else if (mode == 0) ok = launch_conv_tile<64, 64, 3, 3, 1, 1, false>(st, p);
+    else if (mode == 1) ok = launch_conv_tile<32, 64, 4, 4, 2, 1, false>(st, p);
+    else if (mode == 2) ok = launch_conv_tile<64, 64, 3, 3, 1, 1, true>(st, p);
+    else if (mode == 3) ok = launch_conv_tile<64, 32, 2, 2, 1, 2, true>(st, p);
+    else if (mode == 4) { launch_conv1_fwd(st, Conv1Src{img, nullptr, 0, 0}, (const h16_t*)w, bias, (h16_t*)out, Nf, IMH, IMH, OUTH, OUTH, false, bits1_out); ok = true; }
+    else if (mode == 5 || mode == 6) {      // conv1 forward from uint8 NHWC frames; mode 6: `mask` = (Nf,2) int32 RandomShiftsAug shifts, pad 10 (IMH >= 100) or 4
+        launch_conv1_fwd(st, Conv1Src{img, mode == 6 ? (const int*)mask : nullptr, 1, IMH >= 100 ? 10 : 4}, (const h16_t*)w, bias, (h16_t*)out, Nf, IMH, IMH, OUTH,
+                         OUTH, (relu & 256) != 0, bits1_out);
+        ok = true;
+    }
+    if (!ok) { hulc_set_error("%s: unsupported mode/shape", who); return 1; }
+    if (hipGetLastError() != hipSuccess) { hulc_set_error("%s: launch failed", who); return 1; }
+    return 0;
+}
+
+// One stage of both encoders as ONE launch (conv_reg.h launch_conv_reg_jobs, conv_wgrad.h launch_conv_wgrad_pair /
+// launch_conv1_wgrad_jobs) in the forms the engine runs, dynamic claiming on (one zeroed counter per job, as the engine's next_ctr()); b == NULL: job a alone through the same entry
+int k_conv_pair(const char* who, int typed, int stage, const hulc_conv_job* a, const hulc_conv_job* b, int wg_a, int wg_b, int* slabs, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const bool fwd = stage == HULC_PAIR_CONV2_FWD || stage == HULC_PAIR_CONV3_FWD, dgr = stage == HULC_PAIR_CONV3_DGRAD || stage == HULC_PAIR_CONV2_DGRAD;
+    const bool wgr = stage == HULC_PAIR_CONV3_WGRAD || stage == HULC_PAIR_CONV2_WGRAD || stage == HULC_PAIR_CONV1_WGRAD;
+    if (slabs) slabs[0] = slabs[1] = 0;
+    // every argument is checked before anything is allocated or written
+    if (!fwd && !dgr && !wgr) { hulc_set_error("%s: unknown stage %d", who, stage); return 1; }
+    if (!a) { hulc_set_error("%s: job a is required", who); return 1; }
+    if (wg_a < 1 || (b && wg_b < 1)) { hulc_set_error("%s: every job needs at least one workgroup", who); return 1; }
+    if (wgr && !b) { hulc_set_error("%s: the weight-gradient stages need both jobs", who); return 1; }
+    {
+        const hulc_conv_job* src[2] = {a, b};
+        for (int k = 0; k < (b ? 2 : 1); ++k)
+            if (!src[k]->in || !src[k]->w || !src[k]->out || src[k]->frames < 1 || src[k]->in_side < 1 || src[k]->out_side < 1 || (wgr && !src[k]->bits)) { hulc_set_error("%s: incomplete job", who); return 1; }
+    }
+    if (wgr) {
+        const int KH = stage == HULC_PAIR_CONV1_WGRAD ? 8 : (stage == HULC_PAIR_CONV3_WGRAD ? 3 : 4), S = stage == HULC_PAIR_CONV1_WGRAD ? 4 : (stage == HULC_PAIR_CONV3_WGRAD ? 1 : 2);
+        if (a->in_side < KH || b->in_side < KH || a->out_side != (a->in_side - KH) / S + 1 || b->out_side != (b->in_side - KH) / S + 1) { hulc_set_error("%s: out_side does not belong to in_side", who); return 1; }
+    } else if (typed) {
+        const bool k3 = stage == HULC_PAIR_CONV3_FWD || stage == HULC_PAIR_CONV3_DGRAD;
+        const hulc_conv_job* src[2] = {a, b};
+        for (int k = 0; k < (b ? 2 : 1); ++k) {
+            const int big = dgr ? src[k]->out_side : src[k]->in_side, small = dgr ? src[k]->in_side : src[k]->out_side;
+            if (big > 4096 || k_conv_fwd_side(big, k3 ? 3 : 4, k3 ? 1 : 2) != small) { hulc_set_error("%s: out_side does not belong to in_side", who); return 1; }
+            if (dgr && !src[k]->bits) { hulc_set_error("%s: a data-gradient job needs its mask (the ReLU bit words in bits)", who); return 1; }
+            if (fwd && !src[k]->bias) { hulc_set_error("%s: a forward job needs its bias", who); return 1; }
+        }
+    }
+    static void *dp = nullptr, *zp = nullptr;
+    static int* ctr = nullptr;
+    if (!dp && hipMalloc(&dp, 8192) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; }
+    if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; } hipMemset(zp, 0, 256); }
+    if (!ctr && hipMalloc(&ctr, 256) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; }
+    hipMemsetAsync(ctr, 0, 256, st);      // job k claims through ctr + 16 k
+    if (wgr) {
+        // weight gradients: the launch writes one slab per workgroup, each job's slabs are then summed into its own output as hulc_k_conv_wgrad does.  Synchronises
+        const bool c1 = stage == HULC_PAIR_CONV1_WGRAD, c3 = stage == HULC_PAIR_CONV3_WGRAD;
+        const int KC = c1 ? 192 : (c3 ? 576 : 512), CO = c1 ? 32 : 64;
+        float* part = nullptr;
+        if (hipMalloc(&part, sizeof(float) * (size_t)(wg_a + wg_b) * CO * KC) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; }
+        const hulc_conv_job* src[2] = {a, b};
+        const int wg[2] = {wg_a, wg_b};
+        int ns[2] = {0, 0};
+        bool okw = false;
+        if (c1) {      // fp32 NCHW frames (the headline boundary): both jobs on conv1_wgrad_tr2_kernel<6, 2>
+            Wgrad1Job J[2];
+            for (int k = 0; k < 2; ++k) {
+                Wgrad1Job q{}; q.S = Conv1Src{src[k]->in, nullptr, 0, 0}; q.work_ctr = ctr + 16 * k; q.dY = (const h16_t*)src[k]->w; q.bias_part = (float*)src[k]->bits;
+                q.Nf = src[k]->frames; q.IH = q.IW = src[k]->in_side; q.OH = q.OW = src[k]->out_side;
+                J[k] = q;
+            }
+            J[0].part = part;
+            size_t l0 = 0, l1 = 0; int r, nb;
+            okw = conv1_wgrad_plan(J[0].S, J[0].IH, J[0].IW, J[0].OH, J[0].OW, r, nb, l0) == conv1_wgrad_plan(J[1].S, J[1].IH, J[1].IW, J[1].OH, J[1].OW, r, nb, l1);
+            if (okw) {
+                for (int k = 0; k < 2; ++k) { hipMemsetAsync(src[k]->bits, 0, sizeof(float) * CO, st); hipMemsetAsync(src[k]->out, 0, sizeof(float) * CO * KC, st); }
+                okw = launch_conv1_wgrad_jobs(st, J, 2, 1024, wg, ns);
+            }
+        } else {
+            WgradJob J[2];
+            for (int k = 0; k < 2; ++k) {
+                WgradJob q{}; q.X = (const h16_t*)src[k]->in; q.dY = (const h16_t*)src[k]->w; q.bias_part = (float*)src[k]->bits; q.zeros = (const h16_t*)zp; q.work_ctr = ctr + 16 * k;
+                q.Nf = src[k]->frames; q.IH = q.IW = src[k]->in_side; q.OH = q.OW = src[k]->out_side; q.FPB = 1;
+                J[k] = q;
+            }
+            J[0].part = part;
+            using W3 = WgradCamW<64, 3>; using W2 = WgradCamW<32, 4>;
+            okw = c3 ? (a->in_side == W3::stat && b->in_side == W3::gripper) : (a->in_side == W2::stat && b->in_side == W2::gripper);      // the shapes the launch takes: nothing is written otherwise
+            if (okw) {
+                for (int k = 0; k < 2; ++k) { hipMemsetAsync(src[k]->bits, 0, sizeof(float) * CO, st); hipMemsetAsync(src[k]->out, 0, sizeof(float) * CO * KC, st); }
+                okw = c3 ? launch_conv_wgrad_pair<64, 64, 3, 3, 1>(st, J[0], J[1], 512, wg, ns) : launch_conv_wgrad_pair<32, 64, 4, 4, 2>(st, J[0], J[1], 512, wg, ns);
+            }
+        }
+        if (okw) {
+            hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((CO * KC + 1023) / 1024), dim3(256), 0, st, part, ns[0], (long long)CO * KC, (float*)a->out, CO, KC, 1, 1, 0);
+            hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((CO * KC + 1023) / 1024), dim3(256), 0, st, part + (long long)ns[0] * CO * KC, ns[1], (long long)CO * KC, (float*)b->out, CO, KC, 1, 1, 0);
+        }
+        const hipError_t e = hipStreamSynchronize(st);
+        hipFree(part);
+        if (!okw) { hulc_set_error("%s: unsupported shape (the two cameras' maps only)", who); return 1; }
+        if (e != hipSuccess) { hulc_set_error("%s: %s", who, hipGetErrorString(e)); return 1; }
+        if (slabs) { slabs[0] = ns[0]; slabs[1] = ns[1]; }
+        return 0;
+    }
+    ConvTileP j[2]; int wg[2] = {wg_a, wg_b};
+    const hulc_conv_job* src[2] = {a, b};
+    const int n = b ? 2 : 1;
+    for (int k = 0; k < n; ++k) {
+        ConvTileP p{}; p.img = (const h16_t*)src[k]->in; p.IMH = p.IMW = src[k]->in_side; p.w = (const h16_t*)src[k]->w; p.out = (h16_t*)src[k]->out; p.OUTH = p.OUTW = src[k]->out_side;
+        p.Nf = src[k]->frames; p.dump = (h16_t*)dp;
+        if (fwd) { p.bias = src[k]->bias; p.relu = 1; p.bits_out = (unsigned*)src[k]->bits; }
+        else { p.maskbits = (const unsigned*)src[k]->bits; p.zeros = (const h16_t*)zp; }
+        p.work_ctr = ctr + 16 * k;
+        j[k] = p;
+    }
+    bool ok = false;
+    if (stage == HULC_PAIR_CONV2_FWD) ok = launch_conv_reg_fwd_jobs<32, 4, 4, 2>(st, j, n, wg);
+    else if (stage == HULC_PAIR_CONV3_FWD) ok = launch_conv_reg_fwd_jobs<64, 3, 3, 1>(st, j, n, wg);
+    else if (stage == HULC_PAIR_CONV3_DGRAD) ok = launch_conv_reg_jobs<64, 3, 3, 1, true, 1, 4, true, 1>(st, j, n, wg);
+    else ok = launch_conv_reg_jobs<64, 2, 2, 1, true, 2, 4, true, 1>(st, j, n, wg);
+    if (!ok) { hulc_set_error("%s: unsupported shape", who); return 1; }
+    if (hipGetLastError() != hipSuccess) { hulc_set_error("%s: launch failed", who); return 1; }
+    return 0;
+}
+
+// host arithmetic only: what plan_conv_reg decides for a weights-in-registers form (the modes of hulc_k_conv_tile: 10 / 11 / 17, 20 / 21 / 27, 22 / 23 / 28 / 29 and the
+// bf16-only 12 / 13 / 18 / 19), a frame count, the map sides (in_side / out_side as hulc_k_conv_tile takes them) and the workgroups of the job (wgs < 1: the grid a single
+// launch takes).  The geometry does not depend on the 16-bit type.  Non-zero where the form does not take the shape; no device call
+int k_conv_plan(int form, int frames, int in_side, int out_side, int wgs, int* nbands, int* rows_per_band, int* frames_per_band, int* items) {
+    static const char* who = "hulc_k_conv_plan";
+    if (!nbands || !rows_per_band || !frames_per_band || !items || frames < 1 || in_side < 1 || out_side < 1 || in_side > 4096 || out_side > 4096) { hulc_set_error("%s: null argument or frames=%d, in_side=%d, out_side=%d out of range", who, frames, in_side, out_side); return 1; }
+    const int m10 = form % 10;
+    const bool known = (form >= 10 && form <= 13) || (form >= 17 && form <= 23) || (form >= 27 && form <= 29);
+    if (!known) { hulc_set_error("%s: form %d is not a weights-in-registers form", who, form); return 1; }
+    const bool dg = m10 == 2 || m10 == 3 || m10 == 8 || m10 == 9, k3 = m10 == 0 || m10 == 2 || m10 == 8, bitsf = m10 == 8 || m10 == 9;
+    if (k_conv_fwd_side(dg ? out_side : in_side, k3 ? 3 : 4, k3 ? 1 : 2) != (dg ? in_side : out_side)) { hulc_set_error("%s: form %d: out_side %d does not belong to in_side %d", who, form, out_side, in_side); return 1; }
+    const h16_t* al = reinterpret_cast<const h16_t*>((uintptr_t)0x10000);       // never dereferenced: stands for an operand that is present
+    ConvTileP p{}; p.IMH = p.IMW = in_side; p.OUTH = p.OUTW = out_side; p.Nf = frames;
+    if (!dg) p.relu = 1;
+    else { p.zeros = al; if (bitsf) p.maskbits = reinterpret_cast<const unsigned*>(al); else p.mask = al; }
+    size_t lds = 0; int it = 0; double work = 0;
+    bool ok = false;
+    const int w8 = wgs > 0 ? wgs : 256, w4 = wgs > 0 ? wgs : 512;
+    if (form == 10) ok = plan_conv_reg<64, 3, 3, 1, false, 1, 8, true>(p, w8, lds, it, work);
+    else if (form == 11 || form == 17) ok = plan_conv_reg<32, 4, 4, 2, false, 1, 8, true>(p, w8, lds, it, work);
+    else if (form == 20) ok = plan_conv_reg<64, 3, 3, 1, false, 1, 4>(p, w4, lds, it, work);
+    else if (form == 21 || form == 27) ok = plan_conv_reg<32, 4, 4, 2, false, 1, 4, true>(p, w4, lds, it, work);
+    else if (form == 22 || form == 28) ok = plan_conv_reg<64, 3, 3, 1, true, 1, 4, true, 1>(p, w4, lds, it, work);
+    else if (form == 23 || form == 29) ok = plan_conv_reg<64, 2, 2, 1, true, 2, 4, true, 1>(p, w4, lds, it, work);
+    else if (form == 12 || form == 18) ok = plan_conv_reg<64, 3, 3, 1, true>(p, w8, lds, it, work);
+    else ok = plan_conv_reg<64, 2, 2, 1, true, 2>(p, w8, lds, it, work);
+    if (!ok) { hulc_set_error("%s: form %d does not take frames=%d, in_side=%d, out_side=%d", who, form, frames, in_side, out_side); return 1; }
+    *nbands = p.FPB > 1 ? 1 : p.nbands; *rows_per_band = p.RB; *frames_per_band = p.FPB; *items = it;
     return 0;
 }
 

@@ -117,7 +117,8 @@ EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_s
            "hulc_k_plan_kl_sample", "hulc_k_st_softmax_bwd", "hulc_k_plan_gather", "hulc_k_plan_scatter_grad", "hulc_k_normal_kl_sample", "hulc_k_normal_rsample_bwd",
            "hulc_k_layernorm_fwd", "hulc_k_layernorm_bwd", "hulc_k_layernorm_mean", "hulc_k_tr_layer_fwd", "hulc_k_tr_ffn_bwd", "hulc_k_tr_attn_bwd",
            "hulc_k_window_compact", "hulc_k_rows_expand", "hulc_k_rows_reduce", "hulc_k_gemm_epi", "hulc_k_gemm_multi", "hulc_k_gemm_pick", "hulc_k_gemm_wgrad_nsplit",
-           "hulc_k_det_head_loss", "hulc_k_det_head_bwd", "hulc_k_det_head_act"]
+           "hulc_k_det_head_loss", "hulc_k_det_head_bwd", "hulc_k_det_head_act",
+           "hulc_k_conv_wgrad_t", "hulc_k_conv1_wgrad_u8_t", "hulc_k_conv_tile_t", "hulc_k_conv_pair_t", "hulc_k_conv_plan"]
 
 _lib = None
 
@@ -275,6 +276,13 @@ def load():
         lib.hulc_k_det_head_loss.argtypes = [I, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P]
         lib.hulc_k_det_head_bwd.argtypes = [I, P, P, P, I, I, P, P, P, P, P]
         lib.hulc_k_det_head_act.argtypes = [I, P, P, P, P, I, P, P]
+    if hasattr(lib, "hulc_k_conv_plan") or not os.environ.get("HULC_LIB_PATH"):
+        P, I, PI = C.c_void_p, C.c_int32, C.POINTER(C.c_int32)
+        lib.hulc_k_conv_wgrad_t.argtypes = [I, I, P, P, P, P, I, I, PI, P]
+        lib.hulc_k_conv1_wgrad_u8_t.argtypes = [I, P, P, I, P, P, P, I, I, I, I, PI, P]
+        lib.hulc_k_conv_tile_t.argtypes = [I, I, P, P, P, P, P, P, I, I, I, I, I, P]
+        lib.hulc_k_conv_pair_t.argtypes = [I, I, C.POINTER(HulcConvJob), C.POINTER(HulcConvJob), I, I, PI, P]
+        lib.hulc_k_conv_plan.argtypes = [I, I, I, I, I, PI, PI, PI, PI]
     _lib = lib
     return lib
 

@@ -495,7 +495,8 @@ int hulc_get_plan_idx(hulc_ctx* ctx, int32_t* host_out, int64_t cap);
 
 /* Per-kernel test entry points (device pointers).  Entries with a `dtype` argument run the build of the kernels for that 16-bit type: HULC_DTYPE_BF16 or
  * HULC_DTYPE_F16 (hulc_k_gemm_nt, hulc_k_spatial_softmax64, hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss; HULC_DTYPE_F32 where noted).
- * The half-precision entries without one run the bf16 build; the fp16 build of their kernels is covered by the fp16 step tests.
+ * The half-precision entries without one run the bf16 build.  The encoder's convolution family has both: the entries without a dtype are bf16 wrappers that keep their
+ * behaviour, the _t entries below them run either 16-bit build.
  * hulc_k_gemm_nt: dtype selects fp32 / bf16 / fp16 storage of A, B. */
 int hulc_k_gemm_nt(int32_t dtype, const void* A, const void* B, float* C, int32_t M, int32_t N, int32_t K, int64_t lda,
                    int64_t ldb, int64_t ldc, const float* bias, int32_t relu, void* hip_stream);
@@ -536,6 +537,26 @@ typedef struct hulc_conv_job {
 } hulc_conv_job;
 enum { HULC_PAIR_CONV2_FWD = 2, HULC_PAIR_CONV3_FWD = 3, HULC_PAIR_CONV2_DGRAD = 12, HULC_PAIR_CONV3_DGRAD = 13, HULC_PAIR_CONV1_WGRAD = 21, HULC_PAIR_CONV2_WGRAD = 22, HULC_PAIR_CONV3_WGRAD = 23 };
 int hulc_k_conv_pair(int32_t stage, const hulc_conv_job* a, const hulc_conv_job* b, int32_t wg_a, int32_t wg_b, void* hip_stream);
+/* The conv entries per 16-bit type: a leading dtype = HULC_DTYPE_BF16 or HULC_DTYPE_F16 (anything else, HULC_DTYPE_F32 included, is refused before anything is allocated or
+ * launched, with the entry's name in the message); the other arguments as in the entry without _t, plus:
+ *  - the typed entries refuse, in both types, the bench-only forms that no launch site of the engine names: modes 12 / 13 / 18 / 19 (the 8-wave data-gradient forms), relu bit
+ *    256 and the uint8 conv1 weight-gradient form 1; an out_side that does not belong to in_side; a data-gradient form without its mask.  The fp16 build does not contain
+ *    the bench-only kernels;
+ *  - bits1_out (modes 4 .. 6; may be NULL): the ReLU bit words of conv1's output, uint32 [Nf][OUTH][OUTH], bit c = (channel c > 0): what conv2's data gradient reads;
+ *  - wgs (modes 10 .. 29; 0 = the launcher's own grid): the persistent workgroups of the launch, so that a handful of frames gives several items per workgroup and
+ *    stacks sized for them;
+ *  - db_out (may be NULL): the bias gradient fp32 [64] ([32] for which = 1), overwritten;
+ *  - slabs (may be NULL): the number of partial slabs the entry summed into the weight gradient (the pair entry: two numbers, job a's and job b's; 0, 0 for the other stages). */
+int hulc_k_conv_wgrad_t(int32_t dtype, int32_t which, const void* X, const void* dY, float* out, float* db_out, int32_t Nf, int32_t IH, int32_t* slabs, void* hip_stream);
+int hulc_k_conv1_wgrad_u8_t(int32_t dtype, const void* X, const int32_t* shifts, int32_t pad, const void* dY, float* dw_out, float* db_out, int32_t Nf, int32_t IH, int32_t form,
+                            int32_t fold, int32_t* slabs, void* hip_stream);
+int hulc_k_conv_tile_t(int32_t dtype, int32_t mode, const void* img, const void* w, const float* bias, const void* mask, void* out, uint32_t* bits1_out, int32_t Nf, int32_t IMH,
+                       int32_t OUTH, int32_t relu, int32_t wgs, void* hip_stream);
+int hulc_k_conv_pair_t(int32_t dtype, int32_t stage, const hulc_conv_job* a, const hulc_conv_job* b, int32_t wg_a, int32_t wg_b, int32_t* slabs, void* hip_stream);
+/* host arithmetic only (no device call): the band / stack geometry the launcher decides for a weights-in-registers form (a mode 10 .. 13, 17 .. 23, 27 .. 29 of the conv
+ * tile entry), a frame count, the map sides as that entry takes them and the workgroups of the job (wgs < 1: the grid a single launch takes): bands per frame, output rows
+ * (class rows for the conv2 data gradient) per band, frames stacked to a band, work items.  The same for both 16-bit types.  Non-zero where the form does not take the shape. */
+int hulc_k_conv_plan(int32_t form, int32_t frames, int32_t in_side, int32_t out_side, int32_t wgs, int32_t* nbands, int32_t* rows_per_band, int32_t* frames_per_band, int32_t* items);
 /* skinny GEMM kernel alone (bf16 in / bf16 out), variant = waves*10 + row-tiles-per-workgroup; 300 = the production router; 400 = TWO
  * independent problems in one launch (second one at A + M*K, W + N*K, out + M*N; 32 < M <= 64, K = 2048); 500 = W repacked into the
  * fragment order first (every 16-row x 32-column block = 1 KB in MFMA lane order) and read that way by the K-chunked kernel (K = n x 2048,
