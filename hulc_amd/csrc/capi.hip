@@ -129,6 +129,10 @@ int hulc_decoder_select(hulc_ctx* ctx, int32_t decoder, int32_t criterion) {
     if (!ctx) { hulc_set_error("hulc_decoder_select: null context"); return 1; }
     return ctx->e->decoder_select(decoder, criterion);
 }
+int hulc_decoder_body_select(hulc_ctx* ctx, int32_t body) {
+    if (!ctx) { hulc_set_error("hulc_decoder_body_select: null context"); return 1; }
+    return ctx->e->decoder_body_select(body);
+}
 int hulc_aux_weights_set(hulc_ctx* ctx, float bc_z_weight, float mia_weight) {
     if (!ctx) { hulc_set_error("hulc_aux_weights_set: null context"); return 1; }
     return ctx->e->aux_weights_set(bc_z_weight, mia_weight);

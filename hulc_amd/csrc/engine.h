@@ -204,6 +204,12 @@ struct Engine : IEngine {
     const float *det_w32 = nullptr, *det_b32 = nullptr; float *det_dw = nullptr, *det_db = nullptr;
     const T* det_w = nullptr;
     float* dpre = nullptr;                                   // [S B][8]: gradient of the head's pre-activation
+    // feed-forward decoder body (hulc_decoder_body_select, rnn_model = mlp_decoder): off unless selected before the bind.  Layer 0 keeps the recurrence's
+    // decomposition (wih0 / bih0 are rnn.0.*, the second bias reads a zero vector and has no gradient), layers 1 / 2 are mlp1 / mlp2.  a0 lives in H0, a1 in H1, y in
+    // Zx1, dy in dH1 and the two masked data gradients in dZ1 / dZ0; Zx0 and dH0 are released, the recurrences (engine_recurrent.inc) are never launched
+    bool mlp = false, body_selected = false;
+    LinW mlp1, mlp2;
+    float* zbias = nullptr;                                  // [HID] zeros
     // ---- state of the last forward
     hulc_batch cur{}; float cur_lw = 0, cur_cw = 0; bool have_fwd = false;
 
@@ -353,6 +359,7 @@ struct Engine : IEngine {
         if (decoder == HULC_DECODER_LOGISTIC) { dec_selected = true; return 0; }
         if (cfg.kind == HULC_KIND_GCBC) { hulc_set_error("hulc_decoder_select: HULC_KIND_GCBC with the deterministic decoder has no reference behaviour (GCBC.forward raises: torch.cat of a (B,0) plan with (B,S,.) tensors)"); return 1; }
         if (mcil) { hulc_set_error("hulc_decoder_select: the deterministic decoder is not built for HULC_KIND_MCIL* (gripper_control false, 128-wide embedding slice)"); return 1; }
+        if (mlp) { hulc_set_error("hulc_decoder_select: the deterministic decoder is not built on the feed-forward body (HULC_BODY_MLP is selected)"); return 1; }
         if (criterion != HULC_CRIT_HUBER && criterion != HULC_CRIT_MSE) { hulc_set_error("hulc_decoder_select: criterion %d (HULC_CRIT_HUBER or HULC_CRIT_MSE)", criterion); return 1; }
         static_assert(HID == DET_HID, "det_head.h is built for the 2048-wide decoder");
         HIP_CHECK(hipStreamSynchronize(st));      // the buffers' clearing memsets
@@ -362,6 +369,24 @@ struct Engine : IEngine {
         if (alloc_failed) { hulc_set_error("hulc_decoder_select: workspace allocation failed"); return 1; }
         for (int i = 0; i < 4; ++i) head_rows[i] = 0;
         det = true; det_crit = criterion; dec_selected = true;
+        return 0;
+    }
+    // ---------------------------------------------------------------- feed-forward decoder body (include/hulc_hip.h: hulc_decoder_body_select)
+    int decoder_body_select(int body) override {
+        if (bound) { hulc_set_error("hulc_decoder_body_select after hulc_bind_params (the body's tensors are bound by name: select the body first)"); return 1; }
+        if (body != HULC_BODY_RNN && body != HULC_BODY_MLP) { hulc_set_error("hulc_decoder_body_select: unknown body %d", body); return 1; }
+        if (body_selected) { hulc_set_error("hulc_decoder_body_select: the decoder body of this context is already selected"); return 1; }
+        if (body == HULC_BODY_RNN) { body_selected = true; return 0; }
+        if (mcil) { hulc_set_error("hulc_decoder_body_select: the feed-forward body is not built for HULC_KIND_MCIL* (continuous plan, 128-wide embedding slice)"); return 1; }
+        if (det) { hulc_set_error("hulc_decoder_body_select: the feed-forward body is not built under the deterministic decoder (HULC_DECODER_DETERMINISTIC is selected)"); return 1; }
+        HIP_CHECK(hipStreamSynchronize(st));      // the buffers' clearing memsets
+        release(Zx0); release(dH0);
+        zbias = alloc<float>(HID);
+        if (alloc_failed) { hulc_set_error("hulc_decoder_body_select: workspace allocation failed"); return 1; }
+        const int64_t n = (int64_t)maxS * maxB * HID;
+        named["dec_a0"] = Named{H0, n, 1}; named["dec_a1"] = Named{H1, n, 1}; named["dec_y"] = Named{Zx1, n, 1};
+        named["dec_dy"] = Named{dH1, n, 1}; named["dec_da1"] = Named{dZ1, n, 1}; named["dec_da0"] = Named{dZ0, n, 1};
+        mlp = true; body_selected = true;
         return 0;
     }
     int aux_weights_set(float bc_z_weight, float mia_weight) override { aux_w_bcz = bc_z_weight; aux_w_mia = mia_weight; return 0; }
@@ -544,15 +569,31 @@ struct Engine : IEngine {
             }
             bind_lin(pr_fs, pr + "fc_state.0", PLAN, FCH);
             const std::string ad = "action_decoder.";
+            if (mlp) {      // rnn.0 takes the place of weight_ih_l0 / bias_ih_l0; there is no second bias (zbias) and nothing recurrent
+                wih0_32 = pw(ad + "rnn.0.weight"); dwih0 = gw(ad + "rnn.0.weight");
+                bih0 = pw(ad + "rnn.0.bias"); dbih0 = gw(ad + "rnn.0.bias"); bhh0 = zbias; dbhh0 = nullptr;
+                bih1 = bhh1 = nullptr; dbih1 = dbhh1 = nullptr;
+                for (const char* l : {"rnn.2", "rnn.4"})
+                    if (tab.at(ad + l + ".weight").n != (int64_t)HID * HID || tab.at(ad + l + ".bias").n != HID) {
+                        hulc_set_error("hulc_bind_params: action_decoder.%s must be Linear(2048, 2048)", l); return 1; }
+                if (tab.at(ad + "rnn.0.weight").n != (int64_t)HID * KIN || tab.at(ad + "rnn.0.bias").n != HID) {
+                    hulc_set_error("hulc_bind_params: action_decoder.rnn.0 must be Linear(%d, 2048)", KIN); return 1; }
+            } else {
             wih0_32 = pw(ad + "rnn.weight_ih_l0"); dwih0 = gw(ad + "rnn.weight_ih_l0");
             bih0 = pw(ad + "rnn.bias_ih_l0"); bhh0 = pw(ad + "rnn.bias_hh_l0"); bih1 = pw(ad + "rnn.bias_ih_l1"); bhh1 = pw(ad + "rnn.bias_hh_l1");
             dbih0 = gw(ad + "rnn.bias_ih_l0"); dbhh0 = gw(ad + "rnn.bias_hh_l0"); dbih1 = gw(ad + "rnn.bias_ih_l1"); dbhh1 = gw(ad + "rnn.bias_hh_l1");
+            }
             wih0 = std::is_same<T, float>::value ? (T*)wih0_32 : wshadow + (wih0_32 - P);
             if (!wih0T) wih0T = alloc<T>((int64_t)HID * KIN);
             add_tr(wih0_32, wih0, wih0T, HID, KIN);
+            if (mlp) {
+                bind_lin(mlp1, ad + "rnn.2", HID, HID);
+                bind_lin(mlp2, ad + "rnn.4", HID, HID);
+            } else {
             bind_lin(whh0, ad + "rnn.weight_hh_l0", HID, HID, false);
             bind_lin(wih1, ad + "rnn.weight_ih_l1", HID, HID, false);
             bind_lin(whh1, ad + "rnn.weight_hh_l1", HID, HID, false);
+            }
             if (!det) add_tr_packed(wheads, wheadsT, NHEAD, HID);      // the packed heads' transposed copy rides on the batched transpose as well
             const char* hn[4] = {"prob_fc", "mean_fc", "log_scale_fc", "gripper_fc"};
             for (int i = 0; i < 4; ++i) { head_w32[i] = head_b32[i] = nullptr; head_dw[i] = head_db[i] = nullptr; }
@@ -586,7 +627,8 @@ struct Engine : IEngine {
         // the weight gradients every writer of which can STORE (see LazyG): the M = B MLPs and the decoder's 2048^2 recurrent / layer-1 input weights
         for (int i = 0; i < 5; ++i) lazy_register(pp[i]);
         for (int i = 0; i < 3; ++i) { lazy_register(vg[i]); lazy_register(lg[i]); }
-        lazy_register(pr_fs); lazy_register(whh0); lazy_register(whh1); lazy_register(wih1);
+        lazy_register(pr_fs); lazy_register(whh0); lazy_register(whh1); lazy_register(wih1);      // feed-forward body: the three are unbound (dW null) and lazy_register skips them
+        if (mlp) { lazy_register(mlp1); lazy_register(mlp2); }      // their only writer is lin_wgrad
         std::sort(lazy.begin(), lazy.end(), [](const LazyG& a, const LazyG& b) { return a.off < b.off; });
         for (size_t i = 0; i + 1 < lazy.size(); ++i) if (lazy[i].off + lazy[i].n > lazy[i + 1].off) { lazy.clear(); break; }      // overlapping views: no lazy set
         if (blk2desc_dev) { hipFree(blk2desc_dev); blk2desc_dev = nullptr; }

@@ -212,11 +212,13 @@
                 launch_det_head_dgrad<T>(st, dpre, det_w, H1, B, S, dH1, dZ1 + lastBH);
                 launch_det_head_wgrad<T>(st, dpre, H1, SB, this->part + part_cur, det_dw, det_db);
             } else {
-            { EpiP ep = epi(dH1, false); ep.out2 = dZ1 + lastBH; ep.out2_lo = lastBH; ep.out2_hi = lastBH + BH; ep.out2_mask = H1 + lastBH;
+            { EpiP ep = epi(dH1, false);
+              if (!mlp) { ep.out2 = dZ1 + lastBH; ep.out2_lo = lastBH; ep.out2_hi = lastBH + BH; ep.out2_mask = H1 + lastBH; }      // feed-forward body: dH1 is dy, no BPTT step to seed
               gemm(dense<T>(dheads, SB, NHEAD), dense<T>(wheadsT, HID, NHEAD), dense_out(HID), ep, SB, HID, NHEAD); }
             {
                 const HeadPack hp = head_pack();
                 const int rows = head_rows[0] + head_rows[1] + head_rows[2] + head_rows[3];
+                const T* const hx = mlp ? Zx1 : H1;      // what the heads read: y of the feed-forward body, else the layer-1 state
                 bool slabs = false;
                 if constexpr (std::is_same<T, h16_t>::value) {
                     // row-split weight gradient (see tr_wgrads_flush): one slab per 256 rows in the (idle) convolution slab arena, summed by the unpack launch
@@ -224,7 +226,7 @@
                     if (SB > 64 && part_cur + (int64_t)nz * NHEAD * HID <= this->partcap) {
                         LinBwdBatch bt{}; bt.M = SB; bt.store = 0; bt.mchunk = 256; bt.n = 1;
                         LinBwdJob& J = bt.j[0];
-                        J.dY = dheads; J.X = H1; J.dW = nullptr; J.db = dbheads_tmp; J.ldx = HID; J.lddw = HID; J.N = NHEAD; J.K = HID; J.nx = cdiv(NHEAD, 64); J.blk0 = 0;
+                        J.dY = dheads; J.X = hx; J.dW = nullptr; J.db = dbheads_tmp; J.ldx = HID; J.lddw = HID; J.N = NHEAD; J.K = HID; J.nx = cdiv(NHEAD, 64); J.blk0 = 0;
                         J.part = this->part + part_cur;
                         hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(J.nx * cdiv(HID, 128), nz), dim3(256), 0, st, bt);
                         hipLaunchKernelGGL(unpack_heads_grad_kernel, dim3(cdiv((long long)rows * HID, 256)), dim3(256), 0, st, hp, J.part, dbheads_tmp, HID, nz, (long long)NHEAD * HID);
@@ -232,11 +234,23 @@
                     }
                 }
                 if (!slabs) {
-                    lin_wgrad(dheads, H1, HID, SB, NHEAD, HID, dwheads_tmp, HID, dbheads_tmp);
+                    lin_wgrad(dheads, hx, HID, SB, NHEAD, HID, dwheads_tmp, HID, dbheads_tmp);
                     hipLaunchKernelGGL(unpack_heads_grad_kernel, dim3(cdiv((long long)rows * HID, 256)), dim3(256), 0, st, hp, dwheads_tmp, dbheads_tmp, HID, 1, 0ll);
                 }
             }
             }
+            if (mlp) {
+                // feed-forward body: y = W2 a1 + b2, a1 = relu(W1 a0 + b1) — weight and bias gradients through the transposes (lin_wgrad), data gradients under the ReLU masks
+                lin_wgrad(dH1, H1, HID, SB, HID, HID, mlp2.dW, HID, mlp2.db);
+                { EpiP ep = epi(dZ1, false); ep.mask = H1; lin_dgrad(dH1, SB, mlp2, ep, dense_out(HID)); }
+                lin_wgrad(dZ1, H0, HID, SB, HID, HID, mlp1.dW, HID, mlp1.db);
+                { EpiP ep = epi(dZ0, false); ep.mask = H0; lin_dgrad(dZ1, SB, mlp1, ep, dense_out(HID)); }
+                // layer 0: the gripper-half columns of W0; the 16-bit engines take the bias gradient (the column sums of dZ0) from the same transpose, the fp32 engine from dC below
+                const int mp = ldpad(SB);
+                transpose_pair(dZ0, HID, tA, SB, HID, embg, DE, tB, SB, DE, mp, std::is_same<T, h16_t>::value ? dbih0 : nullptr, nullptr);
+                h0t_valid = false;
+                { EpiP ep = epi(dwih0 + dec_plan, true); ep.accumulate = 1; gemm(dense<T>(tA, HID, mp), dense<T>(tB, DE, mp), dense_out(KIN), ep, HID, DE, SB); }
+            } else {
             // layer 1 BPTT
             rnn_bwd(dH1, H1, dZ1, whh1, B, S, 1, false, false, true);
             {
@@ -299,11 +313,12 @@
                 }
                 { EpiP ep = epi(dwih0 + dec_plan, true); ep.accumulate = 1; gemm(dense<T>(tA, HID, mp), dense<T>(tB, DE, mp), dense_out(KIN), ep, HID, DE, SB); }
             }
+            }
             // d emb (gripper half), scattered back to (B,S,128)[..., 64:128]
             { EpiP ep = epi(demb + (EMB - DE), true); ep.accumulate = 1;
               gemm(dense<T>(dZ0, SB, HID), dense<T>(wih0T + (long long)dec_plan * HID, DE, HID), dense_out_map(B, EMB, (long long)S * EMB), ep, SB, DE, HID); }
             hipLaunchKernelGGL((sum_over_t_kernel<T>), dim3(cdiv(BH, 256)), dim3(256), 0, st, dZ0, S, BH, dC);
-            if constexpr (!std::is_same<T, h16_t>::value) colsum(dC, HID, B, HID, dbih0, dbhh0);
+            if constexpr (!std::is_same<T, h16_t>::value) colsum(dC, HID, B, HID, dbih0, dbhh0);      // feed-forward body: dbhh0 is null (one bias), colsum's second output is optional
             { EpiP ep = epi(dgoal, true); ep.accumulate = 1;
               gemm(dense<T>(dC, B, HID), dense<T>(wih0T + (long long)(dec_plan + DE) * HID, GOAL, HID), dense_out(GOAL), ep, B, GOAL, HID); }
             {

@@ -190,6 +190,15 @@
                                bhh0, Cplan, emb, embg, S, DE, goal_t, GOAL, dec_plan + DE, cb_fused ? Cb : (T*)nullptr);
             if (!cb_fused) { EpiP ep = epi(Cb, false); ep.res = Cplan; ep.res_f32 = 1; ep.res_ld = HID;
               gemm(dense<T>(goal_t, B, GOAL), dense<T>(wih0 + dec_plan + DE, HID, KIN), dense_out(HID), ep, B, HID, GOAL); }
+            if (mlp) {      // feed-forward body (rnn.py mlp_decoder): a0 = relu(W0 x + b0) with the time-invariant term as the broadcast residual, a1 = relu(W1 a0 + b1), y = W2 a1 + b2
+                { EpiP ep = epi(H0, false); ep.res = Cb; ep.res_ld = HID; ep.res_rowmod = B; ep.relu = 1;
+                  gemm(dense<T>(embg, SB, DE), dense<T>(wih0 + dec_plan, HID, KIN), dense_out(HID), ep, SB, HID, DE); }
+                { EpiP ep = epi(H1, false); ep.relu = 1; lin_fwd(H0, HID, SB, mlp1, ep, HID); }
+                { EpiP ep = epi(Zx1, false); lin_fwd(H1, HID, SB, mlp2, ep, HID); }
+                { EpiP ep = epi(heads, true); ep.bias = bheads;
+                  gemm(dense<T>(Zx1, SB, HID), dense<T>(wheads, NHEAD, HID), dense_out(NHEAD), ep, SB, NHEAD, HID); }
+                return;
+            }
             const long long BH = (long long)B * HID;
             { EpiP ep = epi(Zx0, false); ep.res = Cb; ep.res_ld = HID; ep.res_rowmod = B;
               if (!h0_0) { ep.out2 = H0; ep.out2_lo = 0; ep.out2_hi = BH; ep.out2_relu = 1; }      // h_{-1} = 0: H0[0] = relu(Zx0[0]) written here

@@ -195,7 +195,8 @@
     void roll_alloc() {
         if (roll_plan) return;
         val_alloc();
-        roll_plan = alloc<int>(NCAT); roll_plan_c = alloc<T>(PLAN); roll_goal = alloc<T>(GOAL); roll_h0 = alloc<T>(HID); roll_h1 = alloc<T>(HID);
+        roll_plan = alloc<int>(NCAT); roll_plan_c = alloc<T>(PLAN); roll_goal = alloc<T>(GOAL);
+        if (!mlp) { roll_h0 = alloc<T>(HID); roll_h1 = alloc<T>(HID); }
         roll_fs = alloc<float>(2ll * 3 * encS.IH * encS.IH); roll_fg = alloc<float>(2ll * 3 * encG.IH * encG.IH);
         roll_ro = alloc<float>(16); roll_pred = alloc<float>(8); roll_pred_goal = alloc<float>(GOAL);
     }
@@ -282,10 +283,13 @@
         enc_fwd_both(src, nullptr, 1, false);
         HIP_CHECK(hipMemcpyAsync(goal_t, roll_goal, sizeof(T) * GOAL, hipMemcpyDeviceToDevice, st));
         if (mcil) HIP_CHECK(hipMemcpyAsync(plan_t, roll_plan_c, sizeof(T) * (PLAN / 2), hipMemcpyDeviceToDevice, st));
+        if (mlp) dec_fwd(roll_plan, 1, 1, nullptr, nullptr);      // feed-forward body: h_n is None (rnn.py mlp_decoder), nothing is kept between steps
+        else {
         dec_fwd(roll_plan, 1, 1, roll_has_h ? roll_h0 : nullptr, roll_has_h ? roll_h1 : nullptr);
         HIP_CHECK(hipMemcpyAsync(roll_h0, H0, sizeof(T) * HID, hipMemcpyDeviceToDevice, st));
         HIP_CHECK(hipMemcpyAsync(roll_h1, H1, sizeof(T) * HID, hipMemcpyDeviceToDevice, st));
         roll_has_h = true;
+        }
         HIP_CHECK(hipMemcpyAsync(roll_ro, obs->robot_obs_raw, sizeof(float) * 15, hipMemcpyDefault, st));
         if (det) { u_mix = u_act = nullptr; launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, roll_ro, nullptr, 1, 1, roll_pred, nullptr); }      // deterministic head: the noise is ignored
         if (u_mix) { HIP_CHECK(hipMemcpyAsync(nz_mix, u_mix, sizeof(float) * NDIM * NMIX, hipMemcpyDefault, st)); u_mix = nz_mix; }

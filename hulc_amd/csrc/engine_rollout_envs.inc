@@ -22,9 +22,10 @@
         if (max_envs > env_cap) {       // a larger table: new blocks (the old ones stay until the engine goes, like every workspace block)
             const int64_t S = max_envs;
             env_plan_i = alloc<int>(S * NCAT); env_plan_f = alloc<float>(S * 256); env_goal = alloc<T>(S * GOAL);
-            env_h0 = alloc<T>(2 * S * HID); env_h1 = alloc<T>(2 * S * HID); env_cache = alloc<float>(S * HID);
+            if (!mlp) { env_h0 = alloc<T>(2 * S * HID); env_h1 = alloc<T>(2 * S * HID); }      // the feed-forward body has no per-slot hidden state
+            env_cache = alloc<float>(S * HID);
             env_rows = alloc<int>(S); env_pidx = alloc<int>(S * NCAT); env_ro = alloc<float>(S * 16); env_pred = alloc<float>(S * 8); env_goal_f = alloc<float>(S * GOAL);
-            if constexpr (std::is_same<T, float>::value) { env_ha = alloc<T>(S * HID); env_hb = alloc<T>(S * HID); }
+            if (std::is_same<T, float>::value && !mlp) { env_ha = alloc<T>(S * HID); env_hb = alloc<T>(S * HID); }
             if (maxS >= 2) { env_fs = alloc<float>(2 * S * 3 * encS.IH * encS.IH); env_fg = alloc<float>(2 * S * 3 * encG.IH * encG.IH); }
             if (env_rows_host) { hipHostFree(env_rows_host); env_rows_host = nullptr; }
             if (hipHostMalloc((void**)&env_rows_host, sizeof(int) * S, hipHostMallocDefault) != hipSuccess) alloc_failed = true;
@@ -33,8 +34,10 @@
         }
         env_max = max_envs;
         env_has_plan.assign(env_max, 0); env_par.assign(env_max, 0);
+        if (!mlp) {
         HIP_CHECK(hipMemsetAsync(env_h0, 0, sizeof(T) * 2 * env_cap * HID, st));
         HIP_CHECK(hipMemsetAsync(env_h1, 0, sizeof(T) * 2 * env_cap * HID, st));
+        }
         env_counter = 0;
         return 0;
     }
@@ -74,7 +77,7 @@
     int rollout_envs_reset(int n, const int32_t* slots, int clear_hidden) override {
         if (env_check("hulc_rollout_envs_reset", n, slots, true, false)) return 1;
         n = (int)env_desc.size();
-        const bool zero = cfg.kind != HULC_KIND_GCBC || clear_hidden != 0;      // GCBC.reset drops the goal only (gcbc.py:281-285)
+        const bool zero = !mlp && (cfg.kind != HULC_KIND_GCBC || clear_hidden != 0);      // feed-forward body: only the plans are dropped      // GCBC.reset drops the goal only (gcbc.py:281-285)
         if (zero) {
             if (env_upload_rows()) return 1;
             hipLaunchKernelGGL((env_zero_hidden_kernel<T>), dim3(n), dim3(256), 0, st, env_rows, env_cap, env_h0, env_h1);
@@ -117,7 +120,7 @@
             hipLaunchKernelGGL(plan_kl_sample_kernel, dim3(n * NCAT), dim3(64), 0, st, pp_logits, (const float*)nullptr, n, NCAT, NCLS, inj, env_pidx, probs, klcat, dpp_kl,
                                dpr_kl, 0.f, 0.f, site_seed(52));
         }
-        env_store(n, env_pidx, mcil ? plan_f : nullptr, !gcbc);       // action_decoder.clear_hidden_state() per planned slot (hulc.py:925 / :946); GCBC.step never clears it
+        env_store(n, env_pidx, mcil ? plan_f : nullptr, !gcbc && !mlp);       // action_decoder.clear_hidden_state() per planned slot (hulc.py:925 / :946); GCBC.step never clears it
         if (plan_out && mcil) HIP_CHECK(hipMemcpyAsync(plan_out, plan_f, sizeof(float) * n * (PLAN / 2), hipMemcpyDefault, st));
         if (plan_out && !mcil && !gcbc) {      // what the slots hold (an injected index comes back clamped into [0, NCLS))
             EnvGatherP g{}; g.rowdesc = env_rows; g.n = n; g.max_envs = env_cap; g.NCAT = NCAT; g.s_plan_i = env_plan_i; g.s_goal = env_goal; g.pidx = env_pidx;
@@ -175,19 +178,47 @@
         if (u_act) { HIP_CHECK(hipMemcpyAsync(nz_act, u_act, sizeof(float) * n * NDIM, hipMemcpyDefault, st)); u_act = nz_act; }
         const Conv1Src src[2] = {conv1_src_f32(obs->rgb_static), conv1_src_f32(obs->rgb_gripper)};
         enc_fwd_both(src, nullptr, n, false);
-        if constexpr (std::is_same<T, h16_t>::value) {
+        if (mlp && std::is_same<T, h16_t>::value) {
+            if constexpr (std::is_same<T, h16_t>::value) {
+            // feed-forward body, 16 bit: embedding -> actions in four launches, the recurrence-free forms of the row kernels (rollout_step.h).  a0 / a1 / y are rows
+            // 0..n-1 of the decoder's forward workspace (H0 / H1 / Zx1, n <= max_batch rows); nothing goes back to the slots and no parity is read
+            auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+            EnvLayerP l{};
+            l.rowdesc = env_rows; l.n = n; l.max_envs = env_cap; l.x = emb + (EMB - DE); l.x_ld = EMB; l.Kx = DE;
+            l.Wx = wih0 + dec_plan; l.wx_ld = KIN; l.h = H0; l.ctab = env_cache; l.w16 = a16(l.Wx) && (KIN % 8) == 0;
+            hipLaunchKernelGGL((env_rnn_layer_kernel<false, true>), dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l);
+            l.x = H0; l.x_ld = HID; l.Kx = HID; l.Wx = mlp1.W; l.wx_ld = HID; l.h = H1; l.ctab = nullptr; l.b1 = mlp1.b32; l.w16 = a16(l.Wx);
+            hipLaunchKernelGGL((env_rnn_layer_kernel<false, true>), dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l);
+            l.x = H1; l.Wx = mlp2.W; l.h = Zx1; l.b1 = mlp2.b32; l.w16 = a16(l.Wx);
+            hipLaunchKernelGGL((env_rnn_layer_kernel<false, false>), dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l);
+            EnvHeadsP hp{};
+            hp.rowdesc = env_rows; hp.n = n; hp.max_envs = env_cap; hp.h1 = Zx1; hp.W = wheads; hp.bias = bheads; hp.robot_obs = env_ro; hp.u_mix = u_mix; hp.u_act = u_act;
+            hp.NMIX = NMIX; hp.NDIM = NDIM; hp.log_scale_min = cfg.log_scale_min; hp.gripper_control = 1; hp.discrete_gripper = 1;
+            hp.seed = site_seed(53); hp.pred = env_pred;
+            if (NHEAD == 192) hipLaunchKernelGGL((env_heads_sample_kernel<12, true>), dim3(cdiv(n, 16)), dim3(ENV_WAVES * 64), 0, st, hp);
+            else hipLaunchKernelGGL((env_heads_sample_kernel<14, true>), dim3(cdiv(n, 16)), dim3(ENV_WAVES * 64), 0, st, hp);
+            }
+        } else if (mlp) {
+            // feed-forward body, fp32 engine: slot plan / goal -> rows, dec_fwd at B = n, S = 1, the validation sampler; no state goes back to the slots
+            EnvGatherP g{}; g.rowdesc = env_rows; g.n = n; g.max_envs = env_cap; g.NCAT = env_ncat(); g.PC = 0;
+            g.s_plan_i = env_plan_i; g.s_plan_f = env_plan_f; g.s_goal = env_goal; g.pidx = env_ncat() ? env_pidx : nullptr; g.goal_t = goal_t;
+            hipLaunchKernelGGL((env_gather_kernel<T>), dim3(n), dim3(256), 0, st, g);
+            dec_fwd(env_pidx, n, 1, nullptr, nullptr);
+            hipLaunchKernelGGL(logistic_sample_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, heads, NHEAD, env_ro, (const float*)nullptr, u_mix, u_act, n, 1, NMIX, NDIM,
+                               cfg.log_scale_min, 1, site_seed(53), env_pred, (float*)nullptr, 1);
+        } else if constexpr (std::is_same<T, h16_t>::value) {
             // embedding -> actions: three launches, no copy (rollout_step.h)
             auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
             EnvLayerP l0{};
             l0.rowdesc = env_rows; l0.n = n; l0.max_envs = env_cap; l0.x = emb + (EMB - DE); l0.x_ld = EMB; l0.x_by_slot = 0; l0.Kx = DE;
             l0.Wx = wih0 + dec_plan; l0.wx_ld = KIN; l0.Whh = whh0.W; l0.h = env_h0; l0.ctab = env_cache;
             l0.w16 = a16(l0.Wx) && a16(l0.Whh) && (KIN % 8) == 0;
-            hipLaunchKernelGGL(env_rnn_layer_kernel, dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l0);
+            hipLaunchKernelGGL((env_rnn_layer_kernel<true, true>), dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l0);
             EnvLayerP l1{};
             l1.rowdesc = env_rows; l1.n = n; l1.max_envs = env_cap; l1.x = env_h0; l1.x_ld = HID; l1.x_by_slot = 1; l1.Kx = HID;
             l1.Wx = wih1.W; l1.wx_ld = HID; l1.Whh = whh1.W; l1.h = env_h1; l1.ctab = nullptr; l1.b1 = bih1; l1.b2 = bhh1;
             l1.w16 = a16(l1.Wx) && a16(l1.Whh);
-            hipLaunchKernelGGL(env_rnn_layer_kernel, dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l1);
+            hipLaunchKernelGGL((env_rnn_layer_kernel<true, true>), dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l1);
             if (det) launch_det_head_act<T>(st, env_h1, env_rows, env_cap, det_w, det_b32, env_ro, nullptr, n, 1, env_pred, nullptr);      // the new layer-1 state of every row's slot
             else {
             EnvHeadsP hp{};

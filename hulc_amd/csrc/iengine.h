@@ -29,6 +29,7 @@ struct IEngine {
     // ---- BC-Z / MIA language auxiliary heads (engine.h, aux_heads.h)
     virtual int aux_heads_enable(int bc_z, int mia) = 0;
     virtual int decoder_select(int decoder, int criterion) = 0;
+    virtual int decoder_body_select(int body) = 0;
     virtual int aux_weights_set(float bc_z_weight, float mia_weight) = 0;
     virtual int aux_losses_get(float* out_host4) = 0;
     virtual int rollout_reset() = 0;

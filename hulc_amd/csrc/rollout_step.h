@@ -5,6 +5,12 @@
 //   env_heads_sample_kernel         heads = h1'[slot] W_heads^T + b, logistic-mixture sample, gripper argmax, tcp -> world frame
 // and no copy.  `cache` is the time-invariant decoder input term (plan embedding gather + goal W_ih0[:, goal cols]^T + b_ih0 + b_hh0), written per slot by
 // env_plan_store_kernel when the slot is planned (or its state installed) — it only changes at a replan.
+// The feed-forward body (hulc_decoder_body_select, rnn_model = mlp_decoder) runs the same kernels in their recurrence-free forms (REC = false), FOUR launches:
+//   env_rnn_layer_kernel<false, true>   a0[row] = relu(emb_gripper[row] W_0[:, emb cols]^T + cache[slot])
+//   env_rnn_layer_kernel<false, true>   a1[row] = relu(a0[row] W_1^T + b_1)
+//   env_rnn_layer_kernel<false, false>  y[row]  = a1[row] W_2^T + b_2
+//   env_heads_sample_kernel<NT, true>   heads = y[row] W_heads^T + b, ...
+// a0 / a1 / y are ROW buffers [n][2048] of the call (the decoder's forward workspace): there is no per-slot hidden state, no parity, and `cache` holds one bias.
 //
 // State layout (device memory, owned by the engine; S = max_envs):
 //   plan_i [S][32] int32 (hulc) / plan_f [S][256] fp32 (mcil) / goal [S][32] T / cache [S][2048] fp32 (16-bit engines) /
@@ -37,10 +43,10 @@ struct EnvLayerP {
     const int* rowdesc; int n, max_envs;
     const h16_t* x; long long x_ld; int x_by_slot, Kx;      // x_by_slot 0: row r of the call at x + r x_ld; 1: the NEW state of the layer below, x[(1 - parity) S + slot]
     const h16_t* Wx; long long wx_ld;                        // [2048][wx_ld], the first Kx columns of every row are used
-    const h16_t* Whh;                                        // [2048][2048]
-    h16_t* h;                                                // [2][S][2048] of this layer
+    const h16_t* Whh;                                        // [2048][2048]; REC = false: unused
+    h16_t* h;                                                // [2][S][2048] of this layer; REC = false: the output ROW buffer [n][2048]
     const float* ctab;                                       // [S][2048] per-slot constant (layer 0) or null
-    const float *b1, *b2;                                    // ctab == null: c = b1 + b2
+    const float *b1, *b2;                                    // ctab == null: c = b1 + b2 (REC = false: c = b1)
     int w16;                                                 // Wx and Whh rows are 16-byte aligned
 };
 
@@ -52,6 +58,9 @@ struct EnvLayerP {
 // into the MFMA fragments (A = 16 weight rows, B = 16 state rows: each lane's 8 k-elements are 16 contiguous bytes) — no LDS staging, no LDS-DMA.
 // Why two buffers: every workgroup reads WHOLE h rows while the other 127 write their 16 columns of the new state; in place a late workgroup would read
 // columns of step t + 1.  No grid barrier, no flags: the dependent layer is the next launch on the stream.
+// REC = false (feed-forward body): no h segment, one bias, the output goes to row r of p.h (a row buffer no workgroup of this launch reads); RELU = false: the
+// body's third layer.  <true, true> is the recurrent layer.
+template <bool REC, bool RELU>
 __global__ void __launch_bounds__(ENV_WAVES * 64) env_rnn_layer_kernel(EnvLayerP p) {
     __shared__ float4 red[ENV_WAVES][4][64];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -65,11 +74,11 @@ __global__ void __launch_bounds__(ENV_WAVES * 64) env_rnn_layer_kernel(EnvLayerP
         ok[t] = r < p.n;
         const int d = ok[t] ? p.rowdesc[r] : 0;
         const long long cur = (long long)env_par(d) * p.max_envs + env_slot(d), nxt = (long long)(1 - env_par(d)) * p.max_envs + env_slot(d);
-        hr[t] = p.h + cur * ENV_HID + kq;
+        hr[t] = REC ? p.h + cur * ENV_HID + kq : nullptr;
         xr[t] = (p.x_by_slot ? p.x + nxt * p.x_ld : p.x + (long long)r * p.x_ld) + kq;
     }
     const h16_t* wxr = p.Wx + (long long)(c0 + lr) * p.wx_ld + kq;
-    const h16_t* whr = p.Whh + (long long)(c0 + lr) * ENV_HID + kq;
+    const h16_t* whr = REC ? p.Whh + (long long)(c0 + lr) * ENV_HID + kq : nullptr;
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -86,6 +95,7 @@ __global__ void __launch_bounds__(ENV_WAVES * 64) env_rnn_layer_kernel(EnvLayerP
         for (int t = 0; t < 4; ++t) if (t < ntile) acc[t] = MFMA_16x16x32_H(wf, xf[t], acc[t], 0, 0, 0);      // D^T: lane = state row, registers = 4 consecutive output columns
     }
     // h segment: 64 steps, 8 per wave
+    if constexpr (REC) {
 #pragma unroll 4
     for (int i = 0; i < ENV_HID / 32 / ENV_WAVES; ++i) {
         const int k = (wave + i * ENV_WAVES) * 32;
@@ -95,6 +105,7 @@ __global__ void __launch_bounds__(ENV_WAVES * 64) env_rnn_layer_kernel(EnvLayerP
         for (int t = 0; t < 4; ++t) xf[t] = (t < ntile && ok[t]) ? *reinterpret_cast<const h16x8_t*>(hr[t] + k) : zero8v;
 #pragma unroll
         for (int t = 0; t < 4; ++t) if (t < ntile) acc[t] = MFMA_16x16x32_H(wf, xf[t], acc[t], 0, 0, 0);
+    }
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) if (t < ntile) red[wave][t][lane] = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
@@ -109,11 +120,15 @@ __global__ void __launch_bounds__(ENV_WAVES * 64) env_rnn_layer_kernel(EnvLayerP
     const int c = c0 + (lane >> 4) * 4;
     float4 cc;
     if (p.ctab) cc = *reinterpret_cast<const float4*>(p.ctab + (long long)slot * ENV_HID + c);
-    else { const float4 a = *reinterpret_cast<const float4*>(p.b1 + c), b = *reinterpret_cast<const float4*>(p.b2 + c); cc = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+    else if constexpr (REC) { const float4 a = *reinterpret_cast<const float4*>(p.b1 + c), b = *reinterpret_cast<const float4*>(p.b2 + c); cc = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+    else cc = *reinterpret_cast<const float4*>(p.b1 + c);
+    s.x += cc.x; s.y += cc.y; s.z += cc.z; s.w += cc.w;
+    if constexpr (RELU) { s.x = fmaxf(s.x, 0.f); s.y = fmaxf(s.y, 0.f); s.z = fmaxf(s.z, 0.f); s.w = fmaxf(s.w, 0.f); }
     uint2 o;
-    o.x = pack2h(fmaxf(s.x + cc.x, 0.f), fmaxf(s.y + cc.y, 0.f));
-    o.y = pack2h(fmaxf(s.z + cc.z, 0.f), fmaxf(s.w + cc.w, 0.f));
-    *reinterpret_cast<uint2*>(p.h + ((long long)(1 - env_par(d)) * p.max_envs + slot) * ENV_HID + c) = o;
+    o.x = pack2h(s.x, s.y);
+    o.y = pack2h(s.z, s.w);
+    const long long orow = REC ? (long long)(1 - env_par(d)) * p.max_envs + slot : (long long)r;
+    *reinterpret_cast<uint2*>(p.h + orow * ENV_HID + c) = o;
 }
 
 DEVI void env_euler_xyz(float a, float b, float c, float (&R)[9]) {
@@ -126,7 +141,7 @@ DEVI void env_euler_xyz(float a, float b, float c, float (&R)[9]) {
 
 struct EnvHeadsP {
     const int* rowdesc; int n, max_envs;
-    const h16_t* h1;                  // [2][S][2048]: the NEW layer-1 state h1[1 - parity][slot] is read
+    const h16_t* h1;                  // [2][S][2048]: the NEW layer-1 state h1[1 - parity][slot] is read; BYROW: [n][2048], row r of the call
     const h16_t* W;                   // packed heads [NHEAD][2048]: prob | mean | log_scale | gripper | zero pad
     const float* bias;                // [NHEAD]
     const float* robot_obs;           // [n][15]
@@ -139,7 +154,8 @@ struct EnvHeadsP {
 // Heads GEMM (K = 2048, NT * 16 packed head columns) + the sampler of logistic_sample_kernel (kernels.h; logistic_decoder_rnn.py:234-258) + the tcp -> world map
 // (gripper_control.py:39-63) for one 16-row tile per workgroup: a workgroup owns COMPLETE rows of heads, so sampling needs no second pass.  The 8 waves split K
 // (256 each, NT accumulator tiles per wave), the partial tiles are summed through LDS in two rounds (waves 4..7 into 0..3, then 0..3 in order): a fixed order again.
-template <int NT>
+// BYROW (feed-forward body): the heads read row r of a row buffer, not a slot's state.
+template <int NT, bool BYROW = false>
 __global__ void __launch_bounds__(ENV_WAVES * 64) env_heads_sample_kernel(EnvHeadsP p) {
     __shared__ float4 red[4][NT][64];
     __shared__ float act_s[16][8];
@@ -148,7 +164,7 @@ __global__ void __launch_bounds__(ENV_WAVES * 64) env_heads_sample_kernel(EnvHea
     const int r0 = blockIdx.x * 16;
     const bool ok = r0 + lr < p.n;
     const int d = ok ? p.rowdesc[r0 + lr] : 0;
-    const h16_t* hrow = p.h1 + ((long long)(1 - env_par(d)) * p.max_envs + env_slot(d)) * ENV_HID + kq;
+    const h16_t* hrow = p.h1 + (BYROW ? (long long)(ok ? r0 + lr : 0) : (long long)(1 - env_par(d)) * p.max_envs + env_slot(d)) * ENV_HID + kq;
     const h16_t* wrow = p.W + (long long)lr * ENV_HID + kq;
     f32x4 acc[NT];
 #pragma unroll

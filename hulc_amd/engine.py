@@ -44,6 +44,8 @@ class StepEngine:
             L.check(self.lib.hulc_aux_heads_enable(self.ctx, int(dims.use_bc_z), int(dims.use_mia)))
         if dims.decoder == "deterministic":      # before the bind as well: action_decoder.actions.0.* replaces the mixture heads (hulc_decoder_select)
             L.check(self.lib.hulc_decoder_select(self.ctx, L.DECODER["deterministic"], L.CRITERION[dims.criterion]))
+        if dims.decoder_body == "mlp":      # before the bind: action_decoder.rnn.{0,2,4}.* replace the recurrence's eight tensors (hulc_decoder_body_select)
+            L.check(self.lib.hulc_decoder_body_select(self.ctx, L.BODY["mlp"]))
         names = list(self.layout.keys())
         self._names = (C.c_char_p * len(names))(*[n.encode() for n in names])
         self._offs = (C.c_int64 * len(names))(*[self.layout[n][0] for n in names])

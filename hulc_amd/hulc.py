@@ -245,6 +245,14 @@ class Hulc(torch.nn.Module):
         # model/action_decoder=deterministic (deterministic_decoder.py): the same rnn_decoder, then Linear(2048, 7) + tanh and nn.HuberLoss / nn.MSELoss
         det = "DeterministicDecoder" in str(_get(ad, "_target_", ""))
         criterion = "HuberLoss"
+        # action_decoder.rnn_model=mlp_decoder (decoders/utils/rnn.py): Linear-ReLU-Linear-ReLU-Linear in place of the recurrence, no hidden state
+        mlp = str(_get(ad, "rnn_model", "rnn_decoder")) == "mlp_decoder"
+        if mlp and det:
+            raise NotImplementedError("action_decoder.rnn_model 'mlp_decoder' with the deterministic decoder: the feed-forward body is built under the logistic decoder only")
+        if mlp and (_get(distribution, "dist", "discrete") == "continuous" or "BiRNN" in str(_get(pr, "_target_", "Transformers"))
+                    or not _get(ad, "gripper_control", True) or not _get(ad, "discrete_gripper", True)):
+            raise NotImplementedError("action_decoder.rnn_model 'mlp_decoder' is not built for the mcil option group (continuous distribution / BiRNN plan recognition / "
+                                      "mcil decoder options)")
         if det:
             criterion = str(_get(ad, "criterion", "HuberLoss"))
             if criterion not in ("HuberLoss", "MSELoss"):
@@ -258,7 +266,7 @@ class Hulc(torch.nn.Module):
                 raise NotImplementedError("action_decoder.gripper_control false: the deterministic head is built with the tcp-frame transforms of gripper_control true "
                                           "(conf/model/action_decoder/deterministic.yaml)")
             for key, want, why in (("hidden_size", 2048, "the head reads the 2048-wide decoder state"), ("num_layers", 2, "the decoder recurrence has two layers"),
-                                   ("rnn_model", "rnn_decoder", "gru_decoder / lstm_decoder / mlp_decoder have no engine path"),
+                                   ("rnn_model", "rnn_decoder", "gru_decoder / lstm_decoder have no engine path"),
                                    ("policy_rnn_dropout_p", 0.0, "the decoder recurrence has no dropout"), ("out_features", 7, "the head has 7 outputs (6 + gripper)")):
                 v = _get(ad, key, want)
                 if not isinstance(v, str) or key == "rnn_model":
@@ -295,8 +303,9 @@ class Hulc(torch.nn.Module):
                    (_get(pr, "num_heads", 8), 8), (_get(pr, "num_layers", 2), 2), (_get(pr, "encoder_hidden_size", 2048), 2048),
                    (_get(pr, "fc_hidden_size", 4096), 4096), (_get(distribution, "category_size", 32), 32),
                    (_get(distribution, "class_size", 32), 32)]
-        chk += [(_get(ad, "n_mixtures", 10), 10), (_get(ad, "hidden_size", 2048), 2048), (_get(ad, "num_layers", 2), 2),
-                (_get(ad, "rnn_model", "rnn_decoder"), "rnn_decoder"), (_get(ad, "policy_rnn_dropout_p", 0.0), 0.0),
+        # (mlp_decoder accepts num_layers and policy_rnn_dropout_p and uses neither, rnn.py)
+        chk += [(_get(ad, "n_mixtures", 10), 10), (_get(ad, "hidden_size", 2048), 2048), (2 if mlp else _get(ad, "num_layers", 2), 2),
+                ("rnn_decoder" if mlp else _get(ad, "rnn_model", "rnn_decoder"), "rnn_decoder"), (0.0 if mlp else _get(ad, "policy_rnn_dropout_p", 0.0), 0.0),
                 (_get(visual_goal, "latent_goal_features", 32), 32),
                 # options that change the maths and have no built path: action bounds other than +-1 (the engine's bin width is
                 # 1/(num_classes-1), logistic_decoder_rnn.py:157-182), loaded statistics.yaml bounds, the plan-recognition normalisation flags
@@ -331,7 +340,8 @@ class Hulc(torch.nn.Module):
         mw = _get(pr, "max_position_embeddings", 32) or 32
         max_window = 32 if isinstance(mw, str) else int(mw)      # a dangling ${...} (vision_only datasets) falls back to 32
         self.dims = spec.ModelDims(kind=self.kind, max_window=max_window, use_clip=self.use_clip_auxiliary_loss, use_bc_z=self.use_bc_z_auxiliary_loss, use_mia=self.use_mia_auxiliary_loss,
-                                   rnn_type="gru" if (self.kind == "mcil" and rnn_type == "nn.GRU") else "rnn", decoder="deterministic" if det else "logistic", criterion=criterion)
+                                   rnn_type="gru" if (self.kind == "mcil" and rnn_type == "nn.GRU") else "rnn", decoder="deterministic" if det else "logistic", criterion=criterion,
+                                   decoder_body="mlp" if mlp else "rnn")
         # Lightning precision flags: 16 / "16-mixed" = native AMP fp16 + GradScaler (the reference's conf/trainer/play_trainer.yaml:3) ->
         # the fp16 engine with its on-device loss scaler; bf16 needs none; 32 = the fp32 parity engine
         pmap = {"16": "fp16", "fp16": "fp16", "16-mixed": "fp16", "bf16": "bf16", "bf16-mixed": "bf16", "32": "fp32", "fp32": "fp32", "32-true": "fp32"}

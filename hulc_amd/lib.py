@@ -59,6 +59,7 @@ class HulcOptim(C.Structure):
 
 DECODER = {"logistic": 0, "deterministic": 1}      # HULC_DECODER_*
 CRITERION = {"HuberLoss": 0, "MSELoss": 1}         # HULC_CRIT_*
+BODY = {"rnn": 0, "mlp": 1}                        # HULC_BODY_*
 OPTIM = {"adam": 0, "adamw": 1, "sgd": 2}
 CLIP = {"off": 0, "norm": 1, "value": 2}      # HULC_CLIP_*
 
@@ -118,7 +119,8 @@ EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_s
            "hulc_k_layernorm_fwd", "hulc_k_layernorm_bwd", "hulc_k_layernorm_mean", "hulc_k_tr_layer_fwd", "hulc_k_tr_ffn_bwd", "hulc_k_tr_attn_bwd",
            "hulc_k_window_compact", "hulc_k_rows_expand", "hulc_k_rows_reduce", "hulc_k_gemm_epi", "hulc_k_gemm_multi", "hulc_k_gemm_pick", "hulc_k_gemm_wgrad_nsplit",
            "hulc_k_det_head_loss", "hulc_k_det_head_bwd", "hulc_k_det_head_act",
-           "hulc_k_conv_wgrad_t", "hulc_k_conv1_wgrad_u8_t", "hulc_k_conv_tile_t", "hulc_k_conv_pair_t", "hulc_k_conv_plan"]
+           "hulc_k_conv_wgrad_t", "hulc_k_conv1_wgrad_u8_t", "hulc_k_conv_tile_t", "hulc_k_conv_pair_t", "hulc_k_conv_plan",
+           "hulc_decoder_body_select"]
 
 _lib = None
 
@@ -276,6 +278,8 @@ def load():
         lib.hulc_k_det_head_loss.argtypes = [I, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P]
         lib.hulc_k_det_head_bwd.argtypes = [I, P, P, P, I, I, P, P, P, P, P]
         lib.hulc_k_det_head_act.argtypes = [I, P, P, P, P, I, P, P]
+    if hasattr(lib, "hulc_decoder_body_select") or not os.environ.get("HULC_LIB_PATH"):
+        lib.hulc_decoder_body_select.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(lib, "hulc_k_conv_plan") or not os.environ.get("HULC_LIB_PATH"):
         P, I, PI = C.c_void_p, C.c_int32, C.POINTER(C.c_int32)
         lib.hulc_k_conv_wgrad_t.argtypes = [I, I, P, P, P, P, I, I, PI, P]

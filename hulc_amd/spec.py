@@ -39,6 +39,7 @@ class ModelDims:
 
     decoder: str = "logistic"     # "logistic" (LogisticDecoderRNN) | "deterministic" (DeterministicDecoder: Linear(hidden, 7) + tanh; kind "hulc" only)
     criterion: str = "HuberLoss"  # deterministic decoder: "HuberLoss" | "MSELoss" (torch.nn, reduction "mean")
+    decoder_body: str = "rnn"     # "rnn" (rnn_decoder: 2-layer ReLU nn.RNN) | "mlp" (mlp_decoder: Linear-ReLU-Linear-ReLU-Linear, no state; hulc / gcbc, logistic decoder)
 
     cont_plan: int = 256          # mcil: distribution.plan_features (conf/model/distribution/continuous.yaml)
     rnn_type: str = "rnn"         # mcil: plan_recognition.rnn_type — "rnn" = nn.RNN (tanh; birnn.yaml default), "gru" = nn.GRU (BASELINE config 4)
@@ -150,7 +151,15 @@ def param_table(d: ModelDims) -> List[Tuple[str, Tuple[int, ...], tuple]]:
     ln("language_goal.ln", d.goal)
 
     ad = "action_decoder."
-    for l, kin in ((0, d.dec_in), (1, H)):
+    if d.decoder_body == "mlp":           # decoders/utils/rnn.py mlp_decoder: nn.Linear defaults, so rnn.0 draws from 1/sqrt(dec_in), not the RNN's 1/sqrt(hidden)
+        if d.kind == "mcil" or d.decoder != "logistic":
+            raise ValueError(f"decoder_body 'mlp' is built for kinds 'hulc' / 'gcbc' with the logistic decoder (got kind {d.kind!r}, decoder {d.decoder!r})")
+        lin(ad + "rnn.0", H, d.dec_in)
+        lin(ad + "rnn.2", H, H)
+        lin(ad + "rnn.4", H, H)
+    elif d.decoder_body != "rnn":
+        raise ValueError(f"decoder_body {d.decoder_body!r}: 'rnn' or 'mlp'")
+    for l, kin in ((0, d.dec_in), (1, H)) if d.decoder_body == "rnn" else ():
         t.append((f"{ad}rnn.weight_ih_l{l}", (H, kin), ("u", H)))
         t.append((f"{ad}rnn.weight_hh_l{l}", (H, H), ("u", H)))
         t.append((f"{ad}rnn.bias_ih_l{l}", (H,), ("u", H)))

@@ -120,7 +120,7 @@ def save_checkpoint(path, module, optimizer, epoch, global_step, lr_scheduler=No
                 "optimizer_states": [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in optimizer.state_dict().items()}],
                 "lr_schedulers": [lr_scheduler.state_dict()] if lr_scheduler is not None and hasattr(lr_scheduler, "state_dict") else [],
                 "hyper_parameters": {"kind": module.kind, "use_clip_auxiliary_loss": module.use_clip_auxiliary_loss, "precision": module.precision,
-                                     "rnn_type": module.dims.rnn_type, "max_window": module.dims.max_window}}, path)
+                                     "rnn_type": module.dims.rnn_type, "max_window": module.dims.max_window, "decoder_body": module.dims.decoder_body}}, path)
 
 
 def get_last_checkpoint(log_dir: str) -> Optional[str]:
@@ -277,6 +277,10 @@ class Trainer:
             if hp.get("kind", module.kind) != module.kind or hp.get("rnn_type", module.dims.rnn_type) != module.dims.rnn_type:
                 raise RuntimeError(f"checkpoint {ckpt_path} holds a {hp.get('kind')!r} ({hp.get('rnn_type')}) model, this run builds {module.kind!r} "
                                    f"({module.dims.rnn_type}): refusing to resume (pass a fresh log_dir or the matching model= option)")
+            ck_body = hp.get("decoder_body", "rnn")      # checkpoints from before the option hold the recurrence
+            if ck_body != module.dims.decoder_body:
+                raise RuntimeError(f"checkpoint {ckpt_path} holds the {ck_body!r} decoder body, this run builds {module.dims.decoder_body!r}: refusing to resume "
+                                   "(pass a fresh log_dir or the matching model.action_decoder.rnn_model= option)")
             if self.rank == 0:
                 print(f"[hulc_amd] resuming from {ckpt_path} (epoch {ck.get('epoch')}, global_step {ck.get('global_step')})", flush=True)
             module.load_state_dict(ck["state_dict"])

@@ -374,6 +374,21 @@ int hulc_aux_losses_get(hulc_ctx* ctx, float* out_host /* (4) */);
 #define HULC_CRIT_MSE 1
 int hulc_decoder_select(hulc_ctx* ctx, int32_t decoder, int32_t criterion);
 
+/* ---- Feed-forward decoder body (action_decoder.rnn_model = mlp_decoder; hulc/models/decoders/utils/rnn.py: Sequential(Linear(KIN, 2048), ReLU, Linear(2048, 2048),
+ * ReLU, Linear(2048, 2048)) in place of the two-layer recurrence): a0 = relu(W0 x + b0), a1 = relu(W1 a0 + b1), y = W2 a1 + b2 — no activation behind the third
+ * layer — and the mixture heads read y.  x[b,t] = [plan_b | emb[b,t,64:128] | goal_b] as for the recurrence, KIN = 1120 (hulc) / 96 (gcbc).  There is no hidden
+ * state: hulc_rollout_act and hulc_rollout_envs_act keep nothing between steps, hulc_rollout_reset / hulc_rollout_envs_reset only drop the plans.
+ * hulc_decoder_body_select(ctx, HULC_BODY_MLP): after hulc_ctx_create and BEFORE hulc_bind_params (later: an error), once per context (a second call: an error),
+ * not for HULC_KIND_MCIL*, not together with HULC_DECODER_DETERMINISTIC (an error in either call order).  The bound table must then name
+ * action_decoder.rnn.0.{weight (2048,KIN), bias}, rnn.2.{weight (2048,2048), bias}, rnn.4.{weight (2048,2048), bias} and need not name the eight rnn.*_l{0,1}
+ * tensors; the recurrence's buffers are released and its persistent-launch state is never created.  HULC_BODY_RNN is accepted and changes nothing.  A context
+ * that never calls it allocates, binds and launches exactly what it did before.
+ * hulc_get_tensor names of this body: dec_a0, dec_a1, dec_y [S*B][2048] (time-major rows r = t*B + b) and the gradients dec_dy (of y), dec_da1, dec_da0 (of the
+ * pre-activations of a1 / a0: the ReLU mask applied). */
+#define HULC_BODY_RNN 0
+#define HULC_BODY_MLP 1
+int hulc_decoder_body_select(hulc_ctx* ctx, int32_t body);
+
 /* ---- Rollout (Hulc.reset / step, hulc/models/hulc.py:843-957; stateful LogisticDecoderRNN.act, logistic_decoder_rnn.py:102-116).
  * hulc_rollout_plan  = get_pp_plan_vision (:905-927: obs and goal frame encoded as one 2-frame window) or get_pp_plan_lang
  *                      (:929-948): latent goal + a plan sampled from the plan proposal; clears the decoder's hidden state.
