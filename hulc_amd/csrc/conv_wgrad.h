@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_tr_kernel(const h16_t* __re
         const int cgrp = tid >> 3, e = tid & 7;
         float s = 0.f;
         for (int t = cgrp; t < 256; t += CH) s += red[t * 8 + e];
-        unsafeAtomicAdd(bias_part + tid, s);          // bias_part = the bias gradient itself (<= gridDim.x adds per channel)
+        if (bias_part) unsafeAtomicAdd(bias_part + tid, s);          // bias_part = the bias gradient itself (<= gridDim.x adds per channel); null: the caller sums dY's columns itself (reproducible mode)
     }
 }
 
@@ -369,7 +369,7 @@ DEVI void conv_wgrad_tr8_body(const WgradJob& J, const int bid, const int nwg) {
         const int cgrp = tid >> 3, e = tid & 7;
         float s = 0.f;
         for (int t = cgrp; t < NTH; t += CHY) s += red[t * 8 + e];
-        unsafeAtomicAdd(bias_part + tid, s);
+        if (bias_part) unsafeAtomicAdd(bias_part + tid, s);
     }
 }
 template <int CI, int CO, int KH, int KW, int S, int NWV, int D = 3, int IWC = 0>
@@ -580,7 +580,7 @@ DEVI void conv_wgrad_dma_body(const WgradJob& J, const int bid, const int nwg) {
         const int cgrp = tid >> 3, e = tid & 7;
         float s = 0.f;
         for (int t = cgrp; t < NTH; t += CHY) s += red[t * 8 + e];
-        unsafeAtomicAdd(bias_part + tid, s);
+        if (bias_part) unsafeAtomicAdd(bias_part + tid, s);
     }
 }
 template <int CI, int CO, int KH, int KW, int S, int IWC = 0>
@@ -1258,7 +1258,7 @@ DEVI void conv1_wgrad_tr_body(const Conv1Src& X, int* __restrict__ work_ctr, con
         const int cgrp = tid >> 3, e = tid & 7;
         float s = 0.f;
         for (int t = cgrp; t < 256; t += 4) s += red[t * 8 + e];
-        unsafeAtomicAdd(bias_part + tid, s);
+        if (bias_part) unsafeAtomicAdd(bias_part + tid, s);
     }
 }
 __global__ void __launch_bounds__(256, 2) conv1_wgrad_tr_kernel(Wgrad1Batch bt) {
@@ -1444,7 +1444,7 @@ DEVI void conv1_wgrad_tr2_body(const float* __restrict__ X, int* __restrict__ wo
         const int cgrp = tid >> 3, e = tid & 7;
         float sacc = 0.f;
         for (int t = cgrp; t < 512; t += 4) sacc += redf[t * 8 + e];
-        unsafeAtomicAdd(bias_part + tid, sacc);
+        if (bias_part) unsafeAtomicAdd(bias_part + tid, sacc);
     }
 }
 template <int PFX, int PFY>
@@ -1676,7 +1676,7 @@ DEVI void conv1_wgrad_tr2r_body(const Conv1Src& S, int* __restrict__ work_ctr, c
         const int cgrp = tid >> 3, e = tid & 7;
         float sacc = 0.f;
         for (int t = cgrp; t < 512; t += 4) sacc += redf[t * 8 + e];
-        unsafeAtomicAdd(bias_part + tid, sacc);
+        if (bias_part) unsafeAtomicAdd(bias_part + tid, sacc);
         dbw[tid] = sacc;
     }
     __syncthreads();

@@ -141,6 +141,7 @@ struct EncTailBwdCam {
     h16_t *d_f2, *d_f1;              // [Nf][64], [Nf][512]
     float* dx_f32; h16_t* dx_t;      // [Nf][128]: one of the two
     int col0;
+    float* pg_slab;                  // reproducible mode: [2][gridDim.x][64] — every workgroup STORES its gamma / beta partials, summed in block order by colsum_final_kernel; null: atomics
 };
 struct EncTailBwdP { EncTailBwdCam cam[2]; const float* demb; int Nf, ldemb; };
 constexpr int ET_DP = 64 * 2 + 16;
@@ -206,7 +207,8 @@ __global__ void __launch_bounds__(512) enc_tail_bwd_kernel(EncTailBwdP p) {
         float s = 0.f;
 #pragma unroll
         for (int w = 0; w < 8; ++w) s += *(lds_f32*)(red + (w * 128 + tid) * 4);
-        unsafeAtomicAdd((tid < 64 ? c.dlng : c.dlnb) + (tid & 63), s);
+        if (c.pg_slab) c.pg_slab[((tid < 64 ? 0ll : (long long)gridDim.x) + blockIdx.x) * 64 + (tid & 63)] = s;
+        else unsafeAtomicAdd((tid < 64 ? c.dlng : c.dlnb) + (tid & 63), s);
     }
     // ---- d_f1 = (d_f2 W2) masked by f1 > 0
     {

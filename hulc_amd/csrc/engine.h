@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "iengine.h"
+#include "repro_sites.h"
 #include "gemm.h"
 #include "kernels.h"
 #include "plan_ln_launch.h"
@@ -178,6 +179,15 @@ struct Engine : IEngine {
     float* zero_arena = nullptr; int64_t zero_n = 0; bool arena_clean = false;   // arena_clean: the forward's last launch has cleared it (only a backward writes it)
     int* work_ctrs = nullptr; int work_ctr_next = 0;
     int* next_ctr() { return work_ctrs ? work_ctrs + (work_ctr_next++ & 63) : nullptr; }
+    // ---- reproducible mode (iengine.h "reproducible", repro_sites.h).  repro is the LATCHED option: a forward and its backward run the same routing.
+    // Every scheduling-dependent launch site reports itself through nd(); the reproducible routing of a site never does.
+    bool repro = false;
+    unsigned long long nd_sites = 0;
+    void nd(unsigned bit) { nd_sites |= bit; }
+    void repro_latch() { repro = repro_opt != 0; }
+    // claim counter of a launch whose workgroups ACCUMULATE over the items they claim (the weight-gradient kernels): null = the strided assignment
+    int* claim_ctr(bool contended) { if (repro) return nullptr; int* c = next_ctr(); if (c && contended) nd(ND_CONV_CLAIM); return c; }
+    bool trf_on() const { return tr_fused_mode && !repro; }      // the fused transformer launches sum with float atomics (tr_fused.h): reproducible mode runs the unfused layer
     float *demb, *dgoal, *dseqf, *dplan, *dprl, *dppx, *dxa, *dxb, *dy_f, *dxm;
     T *dprl_t, *dppl_t, *dseq_t, *dt_a, *dt_b, *dt_c, *dgl3_t;
     T *tA, *tB; int64_t tcap;
@@ -668,6 +678,7 @@ struct Engine : IEngine {
                         float* cs = nullptr, float* cs2 = nullptr) {
         TrPair p;
         p.d[0].cs = cs; p.d[0].cs2 = cs2;
+        if (cs && Ra > TRT) nd(ND_TRANSPOSE_COLSUM);
         p.d[0].src = a; p.d[0].dst = at; p.d[0].lds = lda; p.d[0].ldt = ldt; p.d[0].R = Ra; p.d[0].C = Ca; p.d[0].tiles_x = cdiv(Ca, TRT); p.d[0].blk0 = 0;
         const int n0 = p.d[0].tiles_x * cdiv(Ra, TRT);
         p.d[1].src = b; p.d[1].dst = bt; p.d[1].lds = ldb; p.d[1].ldt = ldt; p.d[1].R = Rb; p.d[1].C = Cb; p.d[1].tiles_x = cdiv(Cb, TRT); p.d[1].blk0 = n0;
@@ -687,6 +698,7 @@ struct Engine : IEngine {
                 blk += m.d[i].tiles_x * cdiv(R[i], TRT);
             }
             m.d[0].cs = cs; m.d[0].cs2 = cs2;
+            if (cs && Ra > TRT) nd(ND_TRANSPOSE_COLSUM);
             hipLaunchKernelGGL(multi_transpose64_kernel, dim3(blk), dim3(256), 0, st, m);
         }
     }
@@ -703,12 +715,13 @@ struct Engine : IEngine {
         }
         const int nsplit = std::max(1, std::min(256, cdiv(M, 256)));
         const int rps = cdiv(M, nsplit);
-        if constexpr (std::is_same<T, float>::value) {
-            // fp32 (parity) mode stays bit-reproducible: two-stage, deterministic
+        if (std::is_same<T, float>::value || repro) {
+            // fp32 (parity) mode and the reproducible mode: two-stage, fixed order
             hipLaunchKernelGGL((colsum_kernel<T>), dim3(cdiv(N, 64), nsplit), dim3(256), 0, st, x, ld, M, N, cspart, rps, 0, 1.f, (float*)nullptr);
             hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(N, 64)), dim3(256), 0, st, cspart, nsplit, N, out, out2, scale);
         } else {
             // bf16 (bench) mode: one launch, each row chunk adds its column sums with fp32 atomics
+            if (nsplit > 1) nd(ND_COLSUM_ROWS);
             hipLaunchKernelGGL((colsum_kernel<T>), dim3(cdiv(N, 64), nsplit), dim3(256), 0, st, x, ld, M, N, out, rps, 2, scale, out2);
         }
     }
@@ -762,6 +775,21 @@ struct Engine : IEngine {
         bool big = false;
         const int nsplit = gemm_wgrad_nsplit<T>(M, N, K, &big);      // gemm.h
         if (nsplit <= 1) { gemm(a, b, dense_out(lddw), ep, M, N, K); return; }
+        if (repro) {
+            // the same K split, but every slice stores its own fp32 slab [M][N] (gemm_kernel's z_stride form) in the idle part of the slab arena and one
+            // launch adds the slabs to dW in slice order; without room for the slabs the product runs unsplit
+            const long long zs = ((long long)M * N + 3) / 4 * 4;
+            if (part_cur + zs * nsplit > this->partcap) { gemm(a, b, dense_out(lddw), ep, M, N, K); return; }
+            float* const slabs = this->part + part_cur;
+            EpiP es = epi(slabs, true); es.z_stride = zs;
+            TimerScope ts(this, big ? "gemm_128x128" : "gemm_64x64_splitk", "mfma", 2.0 * M * N * K, ((double)M * K + (double)N * K) * sizeof(T) + 4.0 * M * N * nsplit);
+            if (big) launch_gemm<T, 128, 128>(st, a, b, dense_out(N), es, M, N, K, 1, nsplit);
+            else launch_gemm<T, 64, 64>(st, a, b, dense_out(N), es, M, N, K, 1, nsplit);
+            const int vec = (N & 3) == 0 && (lddw & 3) == 0 && ((uintptr_t)slabs & 15) == 0 && ((uintptr_t)dW & 15) == 0;
+            hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv((long long)M * N, vec ? 1024 : 256)), dim3(256), 0, st, (const float*)slabs, nsplit, zs, M, N, dW, lddw, vec);
+            return;
+        }
+        nd(ND_GEMM_SPLITK);
         ep.atomic = 1;
         TimerScope ts(this, big ? "gemm_128x128" : "gemm_64x64_splitk", "mfma", 2.0 * M * N * K, ((double)M * K + (double)N * K) * sizeof(T) + 4.0 * M * N);
         if (big) launch_gemm<T, 128, 128>(st, a, b, dense_out(lddw), ep, M, N, K, 1, nsplit);
@@ -784,7 +812,7 @@ struct Engine : IEngine {
             grad_ensure_zero(dW);      // the paths below accumulate
         }
         const int mp = ldpad(M);
-        constexpr bool fuse_cs = std::is_same<T, h16_t>::value;     // bf16 (bench) mode: the dY transpose also adds its column sums into db (atomics)
+        const bool fuse_cs = std::is_same<T, h16_t>::value && !repro;     // bf16 (bench) mode: the dY transpose also adds its column sums into db (atomics)
         transpose_pair(dY, N, tA, M, N, X, ldx, tB, M, K, mp, fuse_cs ? db : nullptr, fuse_cs ? db2 : nullptr);
         gemm_wgrad(dense<T>(tA, N, mp), dense<T>(tB, K, mp), dW, lddw, N, K, M);
         if (db && !fuse_cs) colsum(dY, N, M, N, db, db2);
@@ -803,7 +831,8 @@ struct Engine : IEngine {
     void ln_bwd(const float* dy, long long lddy, const float* x, long long ldx, const float* stats, const float* g, int rows, int n, float* dxf,
                 long long ldd, int acc, T* dxt, long long ldt, float* dg, float* db, float drop_p = 0.f, unsigned long long drop_seed = 0,
                 int bcast_rows = 0, float bcast_div = 1.f, int dy_parts = 1, long long dy_part_stride = 0) {
-        launch_ln_bwd<T>(st, cspart, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt, dg, db, drop_p, drop_seed, bcast_rows, bcast_div, dy_parts, dy_part_stride);
+        if (ln_bwd_fused<T>() && !repro && dg && cdiv(rows, ln_bwd_rows_per_block(rows)) > 1) nd(ND_LN_PARAM);
+        launch_ln_bwd<T>(st, cspart, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt, dg, db, drop_p, drop_seed, bcast_rows, bcast_div, dy_parts, dy_part_stride, repro);
     }
 
     // ---------------------------------------------------------------- weight preparation
@@ -880,6 +909,7 @@ struct Engine : IEngine {
                 U.part = J.part; U.grad = J.dW; U.slab = (long long)J.N * J.K; U.nsplit = nz; U.O = J.N; U.I = J.K; U.KH = U.KW = 1; U.nhwc = 0; U.blk0 = ublocks; U.ysplit = 1;
                 ublocks += cdiv(J.N * J.K, 1024);
             }
+            if (nz > 1) nd(ND_LIN_BWD_ROWS);      // the jobs' bias gradients (and the weight gradients of a job without slabs) land with atomics
             hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(tr_wblocks, nz), dim3(256), 0, st, tr_wjobs);
             if (ub.n > 0) hipLaunchKernelGGL(unpack_conv_wgrad_batched_kernel, dim3(ublocks, 1), dim3(256), 0, st, ub);
             tr_wjobs.n = 0; tr_wblocks = 0;
@@ -938,6 +968,7 @@ struct Engine : IEngine {
     }
     int zero_grads() override {
         if (!bound) { hulc_set_error("hulc_zero_grads before hulc_bind_params"); return 1; }
+        if (!have_fwd) repro_latch();      // a pending forward keeps its routing for its backward
         if (lazy.empty() || !lazy_zero_mode) {
             HIP_CHECK(hipMemsetAsync(G, 0, numel * sizeof(float), st));
             for (LazyG& z : lazy) z.stale = false;

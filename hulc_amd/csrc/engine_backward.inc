@@ -162,6 +162,7 @@
         const bool hulc = cfg.kind == HULC_KIND_HULC;
         const float dp = cfg.dropout_p;
         const long long BH = (long long)B * HID;
+        const bool cs16 = std::is_same<T, h16_t>::value && !repro;      // the bias gradients ride on the dZ transposes (atomics); else the two-stage column sums of the fp32 engine
         if (part == 1) goto encoders;
         if (!arena_clean) HIP_CHECK(hipMemsetAsync(zero_arena, 0, sizeof(float) * zero_n, st));   // demb, dgoal, dseqf, heads / fc7 gradient temporaries, work counters
         arena_clean = false;
@@ -226,9 +227,12 @@
                     if (SB > 64 && part_cur + (int64_t)nz * NHEAD * HID <= this->partcap) {
                         LinBwdBatch bt{}; bt.M = SB; bt.store = 0; bt.mchunk = 256; bt.n = 1;
                         LinBwdJob& J = bt.j[0];
-                        J.dY = dheads; J.X = hx; J.dW = nullptr; J.db = dbheads_tmp; J.ldx = HID; J.lddw = HID; J.N = NHEAD; J.K = HID; J.nx = cdiv(NHEAD, 64); J.blk0 = 0;
+                        // the row chunks' bias sums land with atomics (nz > 1); reproducible mode takes the bias gradient from the two-stage column sum below
+                        if (nz > 1 && !repro) nd(ND_LIN_BWD_ROWS);
+                        J.dY = dheads; J.X = hx; J.dW = nullptr; J.db = (repro && nz > 1) ? nullptr : dbheads_tmp; J.ldx = HID; J.lddw = HID; J.N = NHEAD; J.K = HID; J.nx = cdiv(NHEAD, 64); J.blk0 = 0;
                         J.part = this->part + part_cur;
                         hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(J.nx * cdiv(HID, 128), nz), dim3(256), 0, st, bt);
+                        if (!J.db) colsum(dheads, NHEAD, SB, NHEAD, dbheads_tmp);
                         hipLaunchKernelGGL(unpack_heads_grad_kernel, dim3(cdiv((long long)rows * HID, 256)), dim3(256), 0, st, hp, J.part, dbheads_tmp, HID, nz, (long long)NHEAD * HID);
                         slabs = true;
                     }
@@ -247,7 +251,7 @@
                 { EpiP ep = epi(dZ0, false); ep.mask = H0; lin_dgrad(dZ1, SB, mlp1, ep, dense_out(HID)); }
                 // layer 0: the gripper-half columns of W0; the 16-bit engines take the bias gradient (the column sums of dZ0) from the same transpose, the fp32 engine from dC below
                 const int mp = ldpad(SB);
-                transpose_pair(dZ0, HID, tA, SB, HID, embg, DE, tB, SB, DE, mp, std::is_same<T, h16_t>::value ? dbih0 : nullptr, nullptr);
+                transpose_pair(dZ0, HID, tA, SB, HID, embg, DE, tB, SB, DE, mp, cs16 ? dbih0 : nullptr, nullptr);
                 h0t_valid = false;
                 { EpiP ep = epi(dwih0 + dec_plan, true); ep.accumulate = 1; gemm(dense<T>(tA, HID, mp), dense<T>(tB, DE, mp), dense_out(KIN), ep, HID, DE, SB); }
             } else {
@@ -255,13 +259,13 @@
             rnn_bwd(dH1, H1, dZ1, whh1, B, S, 1, false, false, true);
             {
                 const int mp = ldpad(SB);
-                constexpr bool fuse_cs = std::is_same<T, h16_t>::value;     // 16-bit engines: the dZ transpose adds its column sums (= both bias gradients) on the way
+                const bool fuse_cs = cs16;     // 16-bit engines: the dZ transpose adds its column sums (= both bias gradients) on the way
                 // 16-bit engines: H0^T is needed twice (dW_ih1 here, dW_hh0 below): transposed ONCE, by the same launch as dZ1^T and H1^T, into its own buffer
                 // (was: a cast_transpose launch here and a second transpose of H0 next to dZ0 below: 4 launches -> 2)
                 bool h0t_kept = false;
                 if constexpr (std::is_same<T, h16_t>::value) {
                     if (!tB2) tB2 = alloc<T>(tcap);
-                    if (tB2) { transpose_triple(dZ1, HID, tA, SB, HID, H1, HID, tB, SB, HID, H0, HID, tB2, SB, HID, mp, dbih1, dbhh1); h0t_kept = true; }
+                    if (tB2) { transpose_triple(dZ1, HID, tA, SB, HID, H1, HID, tB, SB, HID, H0, HID, tB2, SB, HID, mp, fuse_cs ? dbih1 : nullptr, fuse_cs ? dbhh1 : nullptr); h0t_kept = true; }
                 }
                 if (!h0t_kept)
                 transpose_pair(dZ1, HID, tA, SB, HID, H1, HID, tB, SB, HID, mp, fuse_cs ? dbih1 : nullptr, fuse_cs ? dbhh1 : nullptr);
@@ -284,7 +288,7 @@
                     }
                 }
                 // dW_hh1, dW_ih1 and (below) dH0 = dZ1 W_ih1 read dZ1 / dZ1^T, H1^T, H0^T, W_ih1^T and write three different buffers: one grouped launch
-                if (!paired && h0t_kept && fuse_cs) gemm_group_begin();
+                if (!paired && h0t_kept && std::is_same<T, h16_t>::value) gemm_group_begin();
                 if (!paired) {
                 if (S > 1) { EpiP ep = epi(whh1.dW, true); ep.accumulate = grad_first(whh1.dW) ? 0 : 1;
                   gemm(dense<T>(tA + B, HID, mp), dense<T>(tB, HID, mp), dense_out(HID), ep, HID, HID, (S - 1) * B); }
@@ -302,11 +306,11 @@
                 const int mp = ldpad(SB);
                 // the column sums of dZ0 over all (t, b) rows = those of dC = sum_t dZ0: both bias gradients of layer 0 ride on this transpose too
                 if (h0t_valid) {      // H0^T is still in tB2 (layer 1's launch above): dZ0^T and embg^T in one launch, no second transpose of H0
-                    transpose_pair(dZ0, HID, tA, SB, HID, embg, DE, tB, SB, DE, mp, dbih0, dbhh0);
+                    transpose_pair(dZ0, HID, tA, SB, HID, embg, DE, tB, SB, DE, mp, cs16 ? dbih0 : nullptr, cs16 ? dbhh0 : nullptr);
                     if (S > 1) { EpiP ep = epi(whh0.dW, true); ep.accumulate = grad_first(whh0.dW) ? 0 : 1;
                       gemm(dense<T>(tA + B, HID, mp), dense<T>(tB2, HID, mp), dense_out(HID), ep, HID, HID, (S - 1) * B); }
                 } else {
-                transpose_pair(dZ0, HID, tA, SB, HID, H0, HID, tB, SB, HID, mp, std::is_same<T, h16_t>::value ? dbih0 : nullptr, std::is_same<T, h16_t>::value ? dbhh0 : nullptr);
+                transpose_pair(dZ0, HID, tA, SB, HID, H0, HID, tB, SB, HID, mp, cs16 ? dbih0 : nullptr, cs16 ? dbhh0 : nullptr);
                 if (S > 1) { EpiP ep = epi(whh0.dW, true); ep.accumulate = grad_first(whh0.dW) ? 0 : 1;
                   gemm(dense<T>(tA + B, HID, mp), dense<T>(tB, HID, mp), dense_out(HID), ep, HID, HID, (S - 1) * B); }
                 cast_tr<T, T>(embg, DE, nullptr, 0, tB, mp, SB, DE);
@@ -318,7 +322,8 @@
             { EpiP ep = epi(demb + (EMB - DE), true); ep.accumulate = 1;
               gemm(dense<T>(dZ0, SB, HID), dense<T>(wih0T + (long long)dec_plan * HID, DE, HID), dense_out_map(B, EMB, (long long)S * EMB), ep, SB, DE, HID); }
             hipLaunchKernelGGL((sum_over_t_kernel<T>), dim3(cdiv(BH, 256)), dim3(256), 0, st, dZ0, S, BH, dC);
-            if constexpr (!std::is_same<T, h16_t>::value) colsum(dC, HID, B, HID, dbih0, dbhh0);      // feed-forward body: dbhh0 is null (one bias), colsum's second output is optional
+            if constexpr (!std::is_same<T, h16_t>::value) colsum(dC, HID, B, HID, dbih0, dbhh0);
+            else if (!cs16) colsum(dZ0, HID, SB, HID, dbih0, dbhh0);      // reproducible mode: from the unrounded rows, not from the 16-bit dC      // feed-forward body: dbhh0 is null (one bias), colsum's second output is optional
             { EpiP ep = epi(dgoal, true); ep.accumulate = 1;
               gemm(dense<T>(dC, B, HID), dense<T>(wih0T + (long long)(dec_plan + DE) * HID, GOAL, HID), dense_out(GOAL), ep, B, GOAL, HID); }
             {
@@ -382,7 +387,7 @@
                 // LN2 (16-bit engines: the last layer's incoming gradient dxm / S is broadcast over the window inside the kernel)
                 const bool bc = ln_bwd_can_bcast && l == 1;
                 bool ffn_fused = false;
-                if constexpr (std::is_same<T, h16_t>::value) ffn_fused = tr_fused_mode && S <= 64;       // row-wise: half windows for S > 32
+                if constexpr (std::is_same<T, h16_t>::value) ffn_fused = trf_on() && S <= 64;       // row-wise: half windows for S > 32
                 // 16-bit fused path: every incoming gradient of the layer's four Linear layers stays in its own buffer, and the eight weight / bias
                 // gradients of both layers run as ONE row-split launch after the loop (tr_wgrads_flush) instead of 16 transposes + GEMMs
                 T *b_c = dt_c, *b_a = dt_a, *b_d = dt_c, *b_b = dt_b;
@@ -403,6 +408,7 @@
                         q.seed_y = site_seed(4 + 4 * l);
                         {
                             TimerScope ts(this, "transformer_fused", "mfma", 2.0 * N * (2.0 * EMB * FF), (double)N * (2 * EMB + FF) * sizeof(T));
+                            if (B > 1) nd(ND_TR_LN_BWD);      // norm2's parameter gradients: one atomic per column and window
                             launch_tr_ffn_bwd(st, q);
                         }
                         tr_wgrad_add(b_c, hff[l], tr_l2[l]); tr_wgrad_add(b_a, x1t[l], tr_l1[l]);
@@ -455,7 +461,8 @@
             tr_wgrads_flush(N);
             // x0 = dropout(emb + pos): d(emb) += mask*dx ; dpos += sum_b
             {
-                const int bchunk = std::is_same<T, float>::value ? B : 8;       // fp32 (parity) engine: one deterministic pass over the windows
+                const int bchunk = (std::is_same<T, float>::value || repro) ? B : 8;       // fp32 (parity) engine, reproducible mode: one pass over the windows in order
+                if (cdiv(B, bchunk) > 1) nd(ND_POS_EMB);
                 hipLaunchKernelGGL(pr_input_bwd_kernel, dim3(cdiv(S * EMB, 256), cdiv(B, bchunk)), dim3(256), 0, st, dx, B, S, EMB, dp, site_seed(0), demb, dpos, bchunk);
             }
         }
@@ -494,9 +501,9 @@
         // ---- encoders backward
         {
             const Conv1Src src[2] = {conv1_src(*b, false), conv1_src(*b, true)}, src2[2] = {conv1_src(cur2, false), conv1_src(cur2, true)};
-            const bool tail_fused = enc_tail_fusable();
             // ragged pass: the gradients of a window's duplicate rows are summed into its last real row first (fixed order), the backward then runs on N' frames
             const int Nenc = enc_frames(N);
+            const bool tail_fused = enc_tail_fusable() && (!repro || enc_tail_bwd_room(Nenc));      // (reproducible mode without slab room: the unfused tail backward of head_bwd)
             if (ragged()) launch_rows_reduce(st, demb, rg_lens(), rg_off(), B, S, EMB, demb_c);
             if (tail_fused) enc_tail_bwd_both(Nenc);
             enc_bwd_both(src, pair ? src2 : nullptr, Nenc, tail_fused);

@@ -287,7 +287,10 @@
     }
     void flush_unpacks() {
         constexpr int yparts = 8;      // same-box: 4 / 8 / 16 / 32 parts = 60 / 55 / 59 / 86 us (with 8 slab quads in flight per thread)
-        if (unpack_jobs.n > 0) hipLaunchKernelGGL(unpack_conv_wgrad_batched_kernel, dim3(unpack_blocks, yparts), dim3(256), 0, st, unpack_jobs);
+        // a job with ysplit == 0 spreads its slabs over the grid.y parts, each landing with one atomic per element; reproducible mode: one part, slabs in order
+        if (repro) for (int i = 0; i < unpack_jobs.n; ++i) unpack_jobs.j[i].ysplit = 1;
+        else for (int i = 0; i < unpack_jobs.n; ++i) if (unpack_jobs.j[i].ysplit == 0 && unpack_jobs.j[i].nsplit > 1) nd(ND_CONV_UNPACK_SPLIT);
+        if (unpack_jobs.n > 0) hipLaunchKernelGGL(unpack_conv_wgrad_batched_kernel, dim3(unpack_blocks, repro ? 1 : yparts), dim3(256), 0, st, unpack_jobs);
         unpack_jobs.n = 0; part_cur = 0; unpack_blocks = 0;
     }
     // the data-gradient chain of both tails (LayerNorm, fc2, fc1) in one launch, then the weight / bias gradients of their Linear layers in one more
@@ -303,7 +306,17 @@
                 c.d_f2 = a.d_f2t; c.d_f1 = a.d_f1; c.dx_f32 = a.d_ss; c.dx_t = a.d_g0; c.col0 = k * 64;
             }
             q.demb = enc_demb(); q.Nf = Nf; q.ldemb = EMB;
+            const int nblk = cdiv(Nf, 16);
+            const bool slab_pg = repro && nblk > 1;      // reproducible mode: LayerNorm parameter partials stored per workgroup (cspart), summed in block order
+            if (slab_pg) for (int k = 0; k < 2; ++k) q.cam[k].pg_slab = cspart + (long long)k * 2 * nblk * 64;
+            if (!repro && Nf > 16) nd(ND_ENC_TAIL_LN);
+            if (!repro && Nf > 256) nd(ND_LIN_BWD_ROWS);      // the five jobs' bias gradients below: one atomic per column and row chunk
             launch_enc_tail_bwd(st, q);
+            if (slab_pg)
+                for (int k = 0; k < 2; ++k) {
+                    hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, st, (const float*)q.cam[k].pg_slab, nblk, 64, encw(k).dlng, (float*)nullptr, 1.f);
+                    hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, st, (const float*)q.cam[k].pg_slab + (long long)nblk * 64, nblk, 64, encw(k).dlnb, (float*)nullptr, 1.f);
+                }
             // weight / bias gradients of the four Linear layers: one launch, frames split over blockIdx.y, operands read as they lie.  Every row chunk writes its own
             // slab; the slabs are summed into the gradient by the encoders' one unpack launch (no per-element atomics here: 1.5 M of them made this launch 39 us).
             // A job without room for its slabs (part == nullptr) adds with fp32 atomics
@@ -311,9 +324,10 @@
             LinBwdBatch bt{}; bt.M = Nf; bt.store = 0; bt.mchunk = chunk;
             int blk = 0;
             const int nz = cdiv(Nf, chunk);
+            const bool cs_bias = repro && nz > 1;      // reproducible mode: the bias gradients are two-stage column sums behind the launch, not the row chunks' atomics
             auto add = [&](const T* dY, const T* X, const LinW& L, float* dW, float* slabs) {
                 LinBwdJob& J = bt.j[bt.n++];
-                J.dY = dY; J.X = X; J.dW = dW; J.db = L.db; J.ldx = L.K; J.lddw = L.K; J.N = L.N; J.K = L.K; J.nx = cdiv(L.N, 64); J.blk0 = blk; J.part = slabs;
+                J.dY = dY; J.X = X; J.dW = dW; J.db = cs_bias ? nullptr : L.db; J.ldx = L.K; J.lddw = L.K; J.N = L.N; J.K = L.K; J.nx = cdiv(L.N, 64); J.blk0 = blk; J.part = slabs;
                 blk += J.nx * cdiv(L.K, 128);
             };
             for (int k = 0; k < 2; ++k) {
@@ -328,7 +342,20 @@
             tail_fc7_done = slabs7 != nullptr;      // else head_bwd runs fc7's weight gradient
             if (slabs7) add(aG.d_g0, aG.a3, L, nullptr, slabs7);
             hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(blk, nz), dim3(256), 0, st, bt);
+            if (cs_bias) {
+                for (int k = 0; k < 2; ++k) {
+                    const EncW& e = encw(k); EncA& a = enca(k);
+                    colsum(a.d_f2t, e.fc2.N, Nf, e.fc2.N, e.fc2.db);
+                    colsum(a.d_f1, e.fc1.N, Nf, e.fc1.N, e.fc1.db);
+                }
+                if (slabs7) colsum(aG.d_g0, L.N, Nf, L.N, L.db);
+            }
         }
+    }
+    // reproducible mode runs the fused tail backward only when every job of its weight-gradient launch gets slabs (a job without slabs adds with atomics)
+    bool enc_tail_bwd_room(int Nf) const {
+        const int64_t nz = cdiv(Nf, 256);
+        return unpack_room(5, nz * (2 * (64ll * 512 + 512ll * 128) + 128ll * 3136));
     }
     h16_t* zero_page = nullptr;
     const h16_t* wgrad_zero_page() {
@@ -349,11 +376,14 @@
     // is one launch here.  bias_done: the kernel added the bias gradient itself (the tr kernels, atomics)
     void wgrad_unpack(const ConvW& c, const T* dy, long long npix, int nsplit, bool bias_done) {
         const bool many = std::is_same<T, h16_t>::value && nsplit >= 64;
+        const int yparts = many && !repro ? 16 : 1;
         // slab parts over grid.y, each landing with one fp32 atomic per element.  16 parts: more (21 / 24 / 64 for conv3 / conv2 / conv1) made
         // every launch slower (23 / 11.3 / 10.9 us against 18.6 / 9.5 / 9.6: the scattered atomics, not the slab stream, are the cost)
-        if (!(many && queue_unpack(c.dW, c.O, c.I, c.KH, c.KW, c.nhwc, nsplit, 0)))
-            hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3(cdiv(c.O * c.I * c.KH * c.KW, 1024), many ? 16 : 1), dim3(256), 0, st, this->part + part_cur, nsplit,   // fp32 (parity) mode: one deterministic pass, no atomics
+        if (!(many && queue_unpack(c.dW, c.O, c.I, c.KH, c.KW, c.nhwc, nsplit, 0))) {
+            if (yparts > 1) nd(ND_CONV_UNPACK_SPLIT);
+            hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3(cdiv(c.O * c.I * c.KH * c.KW, 1024), yparts), dim3(256), 0, st, this->part + part_cur, nsplit,   // fp32 (parity) mode: one deterministic pass, no atomics
                                (long long)c.O * c.I * c.KH * c.KW, c.dW, c.O, c.I, c.KH, c.KW, c.nhwc);
+        }
         if (!bias_done) colsum(dy, c.O, (int)npix, c.O, c.db);
     }
     // conv2's / conv3's weight gradient of one camera.  16-bit engines: raw-tile + transposing-LDS-read kernel (conv_wgrad.h); slabs = persistent workgroups
@@ -364,12 +394,15 @@
         int nsplit = 0;
         if constexpr (std::is_same<T, h16_t>::value) {
             TimerScope ts(this, "conv_wgrad_tr", "mfma", conv_wgrad_flops(c, g), conv_wgrad_bytes(c, g, 2));
-            if (c.I == 64 && c.KH == 3) nsplit = launch_conv_wgrad_tr<64, 64, 3, 3, 1>(st, s.x, s.dy, this->part + part_cur, c.db, g.Nf, g.IH, g.IW, g.OH, g.OW, 512, next_ctr(), wgrad_zero_page());
-            else if (c.I == 32 && c.KH == 4) nsplit = launch_conv_wgrad_tr<32, 64, 4, 4, 2>(st, s.x, s.dy, this->part + part_cur, c.db, g.Nf, g.IH, g.IW, g.OH, g.OW, 512, next_ctr(), wgrad_zero_page());
+            // reproducible mode: strided items (no claim counter) and no bias atomics — the bias gradient is the two-stage column sum of wgrad_unpack
+            float* const kb = repro ? nullptr : c.db;
+            if (c.I == 64 && c.KH == 3) nsplit = launch_conv_wgrad_tr<64, 64, 3, 3, 1>(st, s.x, s.dy, this->part + part_cur, kb, g.Nf, g.IH, g.IW, g.OH, g.OW, 512, claim_ctr(g.Nf > 1), wgrad_zero_page());
+            else if (c.I == 32 && c.KH == 4) nsplit = launch_conv_wgrad_tr<32, 64, 4, 4, 2>(st, s.x, s.dy, this->part + part_cur, kb, g.Nf, g.IH, g.IW, g.OH, g.OW, 512, claim_ctr(g.Nf > 1), wgrad_zero_page());
+            if (nsplit > 1 && !repro) nd(ND_CONV_BIAS);
         }
         const bool tr = nsplit > 0;
         if (!tr) nsplit = wgrad_gemm<64>(c, s.dy, ConvNHWCLoaderT<T>{s.x, g}, npix);
-        wgrad_unpack(c, s.dy, npix, nsplit, tr);
+        wgrad_unpack(c, s.dy, npix, nsplit, tr && !repro);
     }
     // conv1's weight gradient of one camera, once per frame source (paired pass: two, as conv1_fwd).  The fp32 engine reads the frames the forward materialised (conv1_f32)
     void conv1_wgrad(int k, const Conv1Src& src, int Nf, const Conv1Src* src2) {
@@ -387,11 +420,12 @@
             int nsplit = 0;
             if constexpr (std::is_same<T, h16_t>::value) {
                 TimerScope ts(this, "conv1_wgrad", "hbm", conv_wgrad_flops(c, g), conv_wgrad_bytes(c, g, sh.u8 ? 1 : 4));
-                nsplit = launch_conv1_wgrad_tr(st, sh, dy, this->part + part_cur, c.db, nf, g.IH, g.IW, g.OH, g.OW, 1024, next_ctr());
+                nsplit = launch_conv1_wgrad_tr(st, sh, dy, this->part + part_cur, repro ? (float*)nullptr : c.db, nf, g.IH, g.IW, g.OH, g.OW, 1024, claim_ctr(nf > 1));
+                if (nsplit > 1 && !repro) nd(ND_CONV_BIAS);
             }
             const bool tr = nsplit > 0;
             if (!tr) nsplit = wgrad_gemm<32>(c, dy, Conv1LoaderT<T>{x, g}, npix);
-            wgrad_unpack(c, dy, npix, nsplit, tr);
+            wgrad_unpack(c, dy, npix, nsplit, tr && !repro);
         }
     }
     // conv3's or conv2's weight gradient for BOTH cameras as one launch (conv_wgrad.h launch_conv_wgrad_pair); both jobs' slabs go into the one batched
@@ -403,7 +437,7 @@
             const int64_t slab = (int64_t)cS.O * cS.I * cS.KH * cS.KW;
             if (cG.I != cS.I || cG.KH != cS.KH || cG.O != cS.O || cS.O != 64 || !unpack_room(2, 256 * slab)) return false;
             auto job = [&](const Stage& s) {
-                WgradJob J{}; J.X = s.x; J.dY = s.dy; J.bias_part = s.c.db; J.zeros = wgrad_zero_page(); J.Nf = s.g.Nf; J.IH = s.g.IH; J.IW = s.g.IW; J.OH = s.g.OH; J.OW = s.g.OW; J.work_ctr = next_ctr(); J.FPB = 1;
+                WgradJob J{}; J.X = s.x; J.dY = s.dy; J.bias_part = repro ? nullptr : s.c.db; J.zeros = wgrad_zero_page(); J.Nf = s.g.Nf; J.IH = s.g.IH; J.IW = s.g.IW; J.OH = s.g.OH; J.OW = s.g.OW; J.work_ctr = claim_ctr(s.g.Nf > 1); J.FPB = 1;
                 return J;
             };
             WgradJob A = job(S), B = job(G);
@@ -419,6 +453,8 @@
             if (!ok) return false;
             queue_unpack(cS.dW, cS.O, cS.I, cS.KH, cS.KW, cS.nhwc, ns[0], 0);
             queue_unpack(cG.dW, cS.O, cS.I, cS.KH, cS.KW, cG.nhwc, ns[1], 0);
+            if (repro) { colsum(S.dy, cS.O, S.g.Nf * S.g.OH * S.g.OW, cS.O, cS.db); colsum(G.dy, cG.O, G.g.Nf * G.g.OH * G.g.OW, cG.O, cG.db); }
+            else if (ns[0] > 1 || ns[1] > 1) nd(ND_CONV_BIAS);
             return true;
         }
         return false;
@@ -439,7 +475,7 @@
                 for (int h = 0; h < ns_src; ++h) {
                     const int nf = src2 ? src_frames(Nf, h) : Nf;
                     const ConvGeom g = geom(nf, encw(k).IH, 3, 8, 4);
-                    Wgrad1Job q{}; q.S = h ? src2[k] : src[k]; q.work_ctr = next_ctr(); q.dY = enca(k).dact1 + (long long)(h ? src_frames(Nf, 0) : 0) * g.OH * g.OW * 32; q.bias_part = encw(k).c1.db;
+                    Wgrad1Job q{}; q.S = h ? src2[k] : src[k]; q.work_ctr = claim_ctr(nf > 1); q.dY = enca(k).dact1 + (long long)(h ? src_frames(Nf, 0) : 0) * g.OH * g.OW * 32; q.bias_part = repro ? nullptr : encw(k).c1.db;
                     q.Nf = nf; q.IH = g.IH; q.IW = g.IW; q.OH = g.OH; q.OW = g.OW;
                     J[nj++] = q;
                     fl += conv_wgrad_flops(cS, g); by += conv_wgrad_bytes(cS, g, q.S.u8 ? 1 : 4);
@@ -457,6 +493,9 @@
                 int nsl = 0;
                 for (int h = 0; h < ns_src; ++h) nsl += ns[k * ns_src + h];
                 queue_unpack(c.dW, c.O, c.I, c.KH, c.KW, c.nhwc, nsl, 0);
+                if (nsl > 1 && !repro) nd(ND_CONV_BIAS);
+                // reproducible mode: the bias gradient over all frames of the camera (both sources' rows of dact1 lie back to back)
+                if (repro) { const ConvGeom g = geom(Nf, encw(k).IH, 3, 8, 4); colsum(enca(k).dact1, c.O, Nf * g.OH * g.OW, c.O, c.db); }
             }
             return true;
         }

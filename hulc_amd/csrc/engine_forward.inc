@@ -81,7 +81,7 @@
             const int Nenc = enc_frames(N);
             enc_fwd_both(src, pair ? src2 : nullptr, Nenc, tail_fused);
             x0_done = false;
-            if (tail_fused) enc_tail_fwd_both(Nenc, !ragged() && !mcil && tr_fused_mode && S <= 64 && EMB == 128, S, dp);
+            if (tail_fused) enc_tail_fwd_both(Nenc, !ragged() && !mcil && trf_on() && S <= 64 && EMB == 128, S, dp);
             if (ragged()) launch_rows_expand<T>(st, emb_c, rg_lens(), rg_off(), B, S, EMB, emb);
             enc_frames_last = Nenc;
         }
@@ -125,7 +125,7 @@
         // ---- plan recognition transformer (plan_recognition_net.py:94-117)
         bool fused = false;
         if constexpr (std::is_same<T, h16_t>::value) {
-            fused = tr_fused_mode && S <= 64;          // 32 < S <= 64 (config 5): two 32-row halves per window, tr_fused.h WIDE
+            fused = trf_on() && S <= 64;          // 32 < S <= 64 (config 5): two 32-row halves per window, tr_fused.h WIDE
         }
         if (!(fused && x0_done))
         hipLaunchKernelGGL((posadd_kernel<T>), dim3(cdiv((long long)N * EMB, 256)), dim3(256), 0, st, emb, pos32, B, S, EMB, xf[0], xt[0], dp, site_seed(0),
@@ -143,6 +143,7 @@
                     q.seed_att = site_seed(1 + 4 * l); q.seed_o = site_seed(2 + 4 * l); q.seed_h = site_seed(3 + 4 * l); q.seed_y = site_seed(4 + 4 * l);
                     // per token: QKV 3 x 128 x 128, out projection 128 x 128, FFN 2 x 128 x 2048, attention 2 x S x 128 MACs (SURVEY §8(d))
                     TimerScope ts(this, "transformer_fused", "mfma", 2.0 * N * (4.0 * EMB * EMB + 2.0 * EMB * FF + 2.0 * S * EMB), (double)N * (4 * EMB + FF) * sizeof(T));
+                    nd(ND_TR_FFN_FWD);      // y2: four hidden quarters per element
                     launch_tr_layer_fwd(st, q);
                 }
                 // the last norm2 and the mean over the window in one launch (the normalised rows are kept for tests only)
@@ -287,6 +288,7 @@
     int forward_impl(const hulc_batch* b, float lw, float cw, float* out, int on_host) {
         if (!bound) { hulc_set_error("hulc_forward_loss before hulc_bind_params"); return 1; }
         persist_check("hulc_forward_loss", false);
+        repro_latch();
         if (b->B < 1 || b->S < 1 || b->B > maxB || b->S > maxS || b->S > cfg.max_window || b->S > 64) {
             hulc_set_error("batch (B=%d,S=%d) exceeds workspace (max_batch=%d,max_seq=%d,max_window=%d)", b->B, b->S, maxB, maxS, cfg.max_window);
             return 1;

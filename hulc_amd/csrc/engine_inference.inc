@@ -41,6 +41,7 @@
         if (b->actions_absolute && !(b->max_rel_pos > 0.f && b->max_rel_orn > 0.f)) { hulc_set_error("actions_absolute needs max_rel_pos > 0 and max_rel_orn > 0 (RelativeActions, transforms.py:35-37)"); return 1; }
         val_alloc();
         if (alloc_failed) { hulc_set_error("hulc_validate: workspace allocation failed"); return 1; }
+        repro_latch();
         if (store_args_bad(b)) return 1;
         if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
         static const hulc_val_noise none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -78,7 +79,10 @@
             if (det) {      // loss_and_act (deterministic_decoder.py:63-80): the criterion in the tcp frame, the prediction in the world frame; no noise (u_mix / u_act ignored)
                 launch_det_head_loss<T>(st, H1, det_w, det_b32, acts, b->robot_obs, B, S, det_crit, 1, 0.f, nullptr, rowloss, 8, nullptr, dpre);
                 hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, rowloss, SB * 8, 1.f / SB, valm + pass);
-                launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, b->robot_obs, acts, B, S, pass == 0 ? pred_pp : pred_pr, valm + 8 + 8 * pass);
+                // metrics: one atomic per row and component; reproducible mode sums the stored predictions in a fixed order instead (val_metrics_kernel)
+                if (!repro && SB > 1) nd(ND_VAL_METRICS);
+                launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, b->robot_obs, acts, B, S, pass == 0 ? pred_pp : pred_pr, repro ? (float*)nullptr : valm + 8 + 8 * pass);
+                if (repro) hipLaunchKernelGGL(val_metrics_kernel, dim3(1), dim3(256), 0, st, (const float*)(pass == 0 ? pred_pp : pred_pr), acts, SB, valm + 8 + 8 * pass);
                 continue;
             }
             hipLaunchKernelGGL((logistic_loss_kernel<T, NMIX>), dim3(cdiv(SB * 8, 256)), dim3(256), 0, st, heads, NHEAD, acts, b->robot_obs, B, S, NMIX, NDIM,
@@ -89,7 +93,9 @@
             if (um) { HIP_CHECK(hipMemcpyAsync(nz_mix, um, sizeof(float) * SB * NDIM * NMIX, hipMemcpyDefault, st)); um = nz_mix; }
             if (ua) { HIP_CHECK(hipMemcpyAsync(nz_act, ua, sizeof(float) * SB * NDIM, hipMemcpyDefault, st)); ua = nz_act; }
             hipLaunchKernelGGL(logistic_sample_kernel, dim3(cdiv(SB, 64)), dim3(64), 0, st, heads, NHEAD, b->robot_obs, acts, um, ua, B, S, NMIX, NDIM,
-                               cfg.log_scale_min, mcil ? 0 : 1, site_seed(42 + pass), pass == 0 ? pred_pp : pred_pr, valm + 8 + 8 * pass, mcil ? 0 : 1);
+                               cfg.log_scale_min, mcil ? 0 : 1, site_seed(42 + pass), pass == 0 ? pred_pp : pred_pr, repro ? (float*)nullptr : valm + 8 + 8 * pass, mcil ? 0 : 1);
+            if (!repro && SB > 1) nd(ND_VAL_METRICS);
+            if (repro) hipLaunchKernelGGL(val_metrics_kernel, dim3(1), dim3(256), 0, st, (const float*)(pass == 0 ? pred_pp : pred_pr), acts, SB, valm + 8 + 8 * pass);
         }
         // val/val_pred_clip_loss (hulc.py:804-808): the CLIP auxiliary loss of the lang modality on the masked rows, forward only
         if (b->is_lang && cfg.use_clip && b->n_aux > 0) {

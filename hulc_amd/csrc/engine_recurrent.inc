@@ -92,6 +92,8 @@
         if (name && !strcmp(name, "fused_transformer")) { *value = tr_fused_mode; return 0; }
         if (name && !strcmp(name, "persist_under_comm")) { *value = persist_under_comm; return 0; }
         if (name && !strcmp(name, "comm_timing")) { *value = comm_timing; return 0; }
+        if (name && !strcmp(name, "reproducible")) { *value = repro_opt; return 0; }
+        if (name && !strcmp(name, "nondeterministic_sites")) { *value = (long long)nd_sites; return 0; }      // cumulative since the context was created (repro_sites.h)
         if (name && !strcmp(name, "encoder_frames")) { *value = enc_frames_last; return 0; }      // frames the perceptual encoders ran on in the last forward / validate
         hulc_set_error("hulc_get_option: unknown option '%s'", name ? name : "(null)");
         return 1;

@@ -431,6 +431,59 @@ __global__ void __launch_bounds__(256) colsum_final_kernel(const float* __restri
     }
 }
 
+// Reproducible mode (repro_sites.h): dW[r][c] (leading dimension lddw) += sum_z part[z][r][c], z ascending, slabs [M][N] dense at distance zs (a multiple of 4).
+// A thread owns four consecutive elements of a row when vec (N % 4 == 0, 16-byte aligned slabs and rows): 16-byte slab loads, four slabs in flight.
+__global__ void __launch_bounds__(256) slab_sum_kernel(const float* __restrict__ part, int nparts, long long zs, int M, int N, float* __restrict__ dW, long long lddw, int vec) {
+    const long long total = (long long)M * N;
+    if (vec) {
+        const long long idx = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+        if (idx >= total) return;
+        float4 s = *reinterpret_cast<const float4*>(part + idx);
+        int z = 1;
+        for (; z + 3 < nparts; z += 4) {
+            float4 t[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const float4*>(part + (long long)(z + u) * zs + idx);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { s.x += t[u].x; s.y += t[u].y; s.z += t[u].z; s.w += t[u].w; }
+        }
+        for (; z < nparts; ++z) { const float4 t = *reinterpret_cast<const float4*>(part + (long long)z * zs + idx); s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w; }
+        float4* o = reinterpret_cast<float4*>(dW + (idx / N) * lddw + idx % N);
+        float4 v = *o;
+        v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w;
+        *o = v;
+        return;
+    }
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    float s = part[idx];
+    for (int z = 1; z < nparts; ++z) s += part[(long long)z * zs + idx];
+    dW[(idx / N) * lddw + idx % N] += s;
+}
+// Reproducible mode: the validation metrics of one decoder pass from its stored predictions — metrics[0..5] = mean |pred - gt|, metrics[6] = the share of rows
+// whose gripper sign matches (what logistic_sample_kernel / det_head_act_kernel add with one atomic per row).  One workgroup: thread t sums rows t, t + 256, ...
+// ascending, the 256 partials meet in a fixed tree.
+__global__ void __launch_bounds__(256) val_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int rows, float* __restrict__ metrics) {
+    __shared__ float red[7][256];
+    const float inv = 1.f / (float)rows;
+    float s[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int r = threadIdx.x; r < rows; r += 256) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) s[i] += fabsf(pred[r * 7 + i] - gt[r * 7 + i]) * inv;
+        s[6] += (((pred[r * 7 + 6] > 0.f) ? 1.f : -1.f) == gt[r * 7 + 6]) ? inv : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) red[i][threadIdx.x] = s[i];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+#pragma unroll
+            for (int i = 0; i < 7; ++i) red[i][threadIdx.x] += red[i][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 7) metrics[threadIdx.x] += red[threadIdx.x][0];
+}
+
 // =========================================================================================================
 // spatial softmax (vision_network.py:100-108) on NHWC features [N][HW][C]; one block per frame, 4 x C threads
 // out[n][2c] = sum p * lin[h], out[n][2c+1] = sum p * lin[w]; also saves (max, 1/sum) for backward
@@ -814,7 +867,10 @@ __global__ void __launch_bounds__(1024) layernorm_bwd_fused_kernel(const float* 
                                                                   int rows, int n, float* __restrict__ dx_f32, long long ldd, int accumulate,
                                                                   T* __restrict__ dx_t, long long ldt, float drop_p, unsigned long long seed,
                                                                   int rows_per_block, float* __restrict__ dg, float* __restrict__ db,
-                                                                  int dy_rowdiv = 0, float dy_div = 1.f, int dy_parts = 1, long long dy_part_stride = 0) {
+                                                                  int dy_rowdiv = 0, float dy_div = 1.f, int dy_parts = 1, long long dy_part_stride = 0,
+                                                                  float* __restrict__ pg_slab = nullptr) {
+    // pg_slab (reproducible mode): the block's gamma / beta partials are STORED at pg_slab[blockIdx.x][n] and pg_slab[gridDim.x + blockIdx.x][n] — the layout
+    // layernorm_param_grad_kernel writes — and colsum_final_kernel adds them in block order
     // dy_parts > 1: the incoming gradient is the sum of dy_parts arrays dy + i * dy_part_stride (the fused FFN backward's four partials)
     // dy_rowdiv > 0: the incoming gradient is a per-WINDOW vector broadcast over the window's dy_rowdiv rows and divided by dy_div
     // (the mean over S in front of plan_recognition.fc: bcast_over_s_kernel's job, read here instead of materialised)
@@ -857,7 +913,8 @@ __global__ void __launch_bounds__(1024) layernorm_bwd_fused_kernel(const float* 
     if (t < 256 && col < n) {
         float a = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
         for (int w = 4; w < nwv; w += 4) a += (red[w][t] + red[w + 1][t]) + (red[w + 2][t] + red[w + 3][t]);
-        unsafeAtomicAdd((t < 128 ? dg : db) + col, a);
+        if (pg_slab) pg_slab[((t < 128 ? 0ll : (long long)gridDim.x) + blockIdx.x) * n + col] = a;
+        else unsafeAtomicAdd((t < 128 ? dg : db) + col, a);
     }
 }
 // partial sums for dgamma[c] = sum_r dy*xhat and dbeta[c] = sum_r dy over a row chunk (grid.y); part = [2][nsplit][n]

@@ -24,11 +24,18 @@ inline long long ln_bwd_scratch_floats(int rows, int n) { return 2ll * ln_bwd_ns
 template <typename T>
 inline void launch_ln_bwd(hipStream_t st, float* scratch, const float* dy, long long lddy, const float* x, long long ldx, const float* stats, const float* g, int rows,
                           int n, float* dxf, long long ldd, int acc, T* dxt, long long ldt, float* dg, float* db, float drop_p = 0.f, unsigned long long drop_seed = 0,
-                          int bcast_rows = 0, float bcast_div = 1.f, int dy_parts = 1, long long dy_part_stride = 0) {
+                          int bcast_rows = 0, float bcast_div = 1.f, int dy_parts = 1, long long dy_part_stride = 0, bool fixed_order = false) {
     if constexpr (ln_bwd_fused<T>()) {
         const int rpb = ln_bwd_rows_per_block(rows);
-        hipLaunchKernelGGL((layernorm_bwd_fused_kernel<T>), dim3(cdiv(rows, rpb)), dim3(rpb == 16 ? 1024 : 256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt,
-                           drop_p, drop_seed, rpb, dg, db, bcast_rows, bcast_div, dy_parts, dy_part_stride);
+        const int nblk = cdiv(rows, rpb);
+        // fixed_order (reproducible mode): the blocks store their gamma / beta partials in `scratch` ([2][nblk][n]) and the fp32 pair's second stage adds them in block order
+        const bool slab = fixed_order && dg && nblk > 1;
+        hipLaunchKernelGGL((layernorm_bwd_fused_kernel<T>), dim3(nblk), dim3(rpb == 16 ? 1024 : 256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, dxt, ldt,
+                           drop_p, drop_seed, rpb, dg, db, bcast_rows, bcast_div, dy_parts, dy_part_stride, slab ? scratch : (float*)nullptr);
+        if (slab) {
+            hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, scratch, nblk, n, dg, (float*)nullptr, 1.f);
+            hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(n, 64)), dim3(256), 0, st, scratch + (long long)nblk * n, nblk, n, db, (float*)nullptr, 1.f);
+        }
     } else {        // fp32 (parity) mode: unfused and deterministic
         if ((drop_p > 0.f || drop_seed != 0) && dxt && dxf) {       // dx first, its copy through the dropout mask in a second launch
             hipLaunchKernelGGL((layernorm_bwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, lddy, x, ldx, stats, g, rows, n, dxf, ldd, acc, (T*)nullptr, 0);

@@ -175,7 +175,7 @@ class Trainer:
     def __init__(self, max_epochs: int = 1, max_steps: int = -1, log_dir: str = "./runs", callbacks: Optional[List] = None,
                  log_every: int = 10, limit_val_batches: Optional[int] = None, check_val_every_n_epoch: int = 1, limit_train_batches=None,
                  accumulate_grad_batches: int = 1, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: Optional[str] = "norm",
-                 track_grad_norm=-1, **_unused):
+                 track_grad_norm=-1, deterministic: bool = False, **_unused):
         self.max_epochs, self.max_steps, self.log_dir = int(max_epochs), int(max_steps), log_dir
         self.limit_train_batches, self.accumulate_grad_batches = limit_train_batches, max(1, int(accumulate_grad_batches or 1))
         if self.accumulate_grad_batches != 1:
@@ -201,6 +201,9 @@ class Trainer:
             # only the 2-norm comes out of the fused reduction; another norm type is rejected, not silently replaced
             raise NotImplementedError(f"track_grad_norm={track_grad_norm!r}: only the 2-norm (track_grad_norm=2) is supported by hulc_amd.trainer.Trainer")
         self.track_grad_norm = tg
+        # Lightning's Trainer(deterministic=True): here the engine's "reproducible" option (fixed summation order in every launch: same seed, same bits, on one rank)
+        self.deterministic = bool(deterministic)
+        self._fallback_warned = False
         self.datamodule = None
         self.limit_val_batches, self.check_val_every_n_epoch = limit_val_batches, max(1, int(check_val_every_n_epoch or 1))
         self.val_history: List[Dict[str, float]] = []
@@ -232,6 +235,25 @@ class Trainer:
             return False
         eng.set_grad_clip(self.gradient_clip_algorithm if self.clips_gradients else "off", self.gradient_clip_val, track=self.track_grad_norm == 2.0)
         return want_norm
+
+    def _configure_deterministic(self, module) -> None:
+        """Trainer(deterministic=True): set the engine's `reproducible` option before the first step."""
+        if not self.deterministic:
+            return
+        eng = getattr(module, "engine", None)
+        if eng is None or not hasattr(eng, "set_option"):
+            raise RuntimeError("deterministic=True needs a module that steps through hulc_amd.engine.StepEngine")
+        eng.set_option("reproducible", 1)
+
+    def _warn_persist_fallback(self, module) -> None:
+        """The one known exception to deterministic=True: a persistent recurrence that timed out switches the context to one launch per time step,
+        another kernel form and therefore other bits from that step on.  One rank-0 line the first time the engine's fallback counter moves."""
+        if not self.deterministic or self._fallback_warned or self.rank != 0:
+            return
+        if module.engine.get_option("persistent_rnn_fallbacks") > 0:
+            self._fallback_warned = True
+            print(f"[hulc_amd] warning: deterministic=true, but a persistent recurrence fell back to one launch per time step before step {self.global_step}: "
+                  "this run's bits differ from a run without the fallback from here on", flush=True)
 
     def validate(self, module, datamodule) -> Dict[str, float]:
         """Lightning's validation loop for this module: eval mode, validation_step over the val batches, mean of every `val*` metric."""
@@ -271,6 +293,7 @@ class Trainer:
         self.optimizer, sched = oc["optimizer"], oc["lr_scheduler"]["scheduler"]
         self.lr_scheduler = sched
         log_norms = self._configure_grad_clip(module)
+        self._configure_deterministic(module)
         if ckpt_path:
             ck = torch.load(ckpt_path, map_location="cpu", weights_only=False)
             hp = ck.get("hyper_parameters") or {}
@@ -312,6 +335,7 @@ class Trainer:
                 sched.step()
                 self.global_step += 1
                 if self.rank == 0 and self.global_step % self.log_every == 0:
+                    self._warn_persist_fallback(module)      # a host-side counter: no synchronisation
                     if log_norms:      # read back on the logged steps only (synchronises): Lightning 1.x's track_grad_norm=2 key names
                         gn = module.engine.grad_norms(per_tensor=self.track_grad_norm == 2.0)
                         module.logged["grad_2.0_norm_total"] = gn["total"]

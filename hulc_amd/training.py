@@ -102,10 +102,10 @@ def resolve_log_dir(log_dir: str, resume: bool, rank: int = 0, world: int = 1, f
 def trainer_kwargs(cfg, callbacks=None) -> dict:
     """The keywords hulc_amd.trainer.Trainer gets from a composed config.  The reference hands the whole `trainer` group to Lightning
     (hulc/training.py:57-71: Trainer(**cfg.trainer, ...)); here the run length, the log directory and — when the group sets them — Lightning's
-    gradient_clip_val / gradient_clip_algorithm / track_grad_norm are forwarded."""
+    gradient_clip_val / gradient_clip_algorithm / track_grad_norm / deterministic are forwarded."""
     tc = cfg.trainer
     kw = dict(max_epochs=tc.max_epochs, max_steps=tc.get("max_steps", -1), log_dir=cfg.log_dir, callbacks=callbacks)
-    for k in ("gradient_clip_val", "gradient_clip_algorithm", "track_grad_norm"):
+    for k in ("gradient_clip_val", "gradient_clip_algorithm", "track_grad_norm", "deterministic"):
         if k in tc:
             kw[k] = tc[k]
     return kw

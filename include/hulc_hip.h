@@ -487,7 +487,11 @@ int hulc_set_dropout(hulc_ctx* ctx, float p);
  * and direction in the 16-bit engines (csrc/rnn_persist.h) — it needs every CU of the GPU; 0 = one launch per time step (choose this when
  * several processes share one GPU).  "fused_transformer" (default 1): one launch per plan-recognition encoder layer in the forward of the
  * 16-bit engines (csrc/tr_fused.h; plan_recognition_net.py:98-117; windows of up to 64 rows), 0 = the unfused kernels.  "timer_event_fence"
- * (default 0): 1 = the class timers below use default (system-fenced) HIP events instead of timing-only ones.  Returns non-zero for an unknown name. */
+ * (default 0): 1 = the class timers below use default (system-fenced) HIP events instead of timing-only ones.  "reproducible" (default 0): 1 = every
+ * launch of the training step, of hulc_validate and of the optimizer step sums in a fixed order (no float atomics, no dynamically claimed work under an
+ * accumulator): the same inputs, weights, seed and step index give the same bits.  Latched by the next hulc_zero_grads without a pending forward,
+ * hulc_forward_loss / _pair or hulc_validate; allocates nothing.  One exception: a persistent recurrence that falls back ("persistent_rnn_fallbacks")
+ * changes kernel form and bits.  Returns non-zero for an unknown name. */
 int hulc_set_option(hulc_ctx* ctx, const char* name, int64_t value);
 /* Reads an option back.  Besides the settable names: "persistent_rnn" reports the EFFECTIVE state (0 once a persistent launch failed its census or
  * timed out — the context then runs one launch per time step; a failed launch never reaches the weights: its optimizer step skips itself on the
@@ -495,7 +499,8 @@ int hulc_set_option(hulc_ctx* ctx, const char* name, int64_t value);
  * "persist_under_comm" (default 0: recurrences that follow an issued bucket of hulc_backward_allreduce run one launch per step, because RCCL's
  * kernels hold CUs), "comm_timing" (hulc_comm_timeline), "debug_poison_partials" (tests).  Read-only: "encoder_frames" = the number of frames the
  * perceptual encoders ran on in the last hulc_forward_loss / _pair or hulc_validate: B * S (the pair: both batches' sum), or N' with
- * hulc_batch::window_len_host. */
+ * hulc_batch::window_len_host; "nondeterministic_sites" = cumulative bitmask since hulc_ctx_create, one bit per audited launch site whose summation
+ * order depends on scheduling (csrc/repro_sites.h), set whenever such a form is issued — 0 for a context that ran reproducible steps only. */
 int hulc_get_option(hulc_ctx* ctx, const char* name, int64_t* value);
 
 /* HIP-event timers around the launches of each kernel class, recorded on the context's stream (bench.py's roofline leg).
