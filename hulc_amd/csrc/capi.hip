@@ -517,25 +517,12 @@ int hulc_k_attention(int32_t variant, const float* qkv, float* P, float* ao, con
     hipStream_t st = (hipStream_t)stream;
     const int D = 128, NH = 8;
     if (S < 1 || S > 64 || (variant == 1 && S > 32)) { hulc_set_error("hulc_k_attention: S=%d not covered by variant %d", S, variant); return 1; }
-    if (variant == 2) {                         // four waves per (b, head): the S <= 64 kernels the 16-bit engines run for S > 32
-        if (!dao) hipLaunchKernelGGL((attention_fwd64_kernel<float>), dim3(B * NH), dim3(256), 0, st, qkv, B, S, D, NH, P, ao, drop_p, (unsigned long long)seed);
-        else {
-            hipFuncSetAttribute((const void*)attention_bwd64_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_BWD64_LDS);
-            hipLaunchKernelGGL((attention_bwd64_kernel<float>), dim3(B * NH), dim3(256), ATT_BWD64_LDS, st, qkv, P, dao, B, S, D, NH, dqkv, drop_p, (unsigned long long)seed);
-        }
-        if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_attention: launch failed"); return 1; }
-        return 0;
-    }
-    const dim3 grid(B * NH), block(64);
-    if (!dao) {
-        if (variant == 1) hipLaunchKernelGGL((attention_fwd32_kernel<float>), grid, block, 0, st, qkv, B, S, D, NH, P, ao, drop_p, (unsigned long long)seed);
-        else if (S <= 32) hipLaunchKernelGGL((attention_fwd_kernel<float, 32>), grid, block, 0, st, qkv, B, S, D, NH, P, ao, drop_p, (unsigned long long)seed);
-        else hipLaunchKernelGGL((attention_fwd_kernel<float, 64>), grid, block, 0, st, qkv, B, S, D, NH, P, ao, drop_p, (unsigned long long)seed);
-    } else {
-        if (variant == 1) hipLaunchKernelGGL((attention_bwd32_kernel<float>), grid, block, 0, st, qkv, P, dao, B, S, D, NH, dqkv, drop_p, (unsigned long long)seed);
-        else if (S <= 32) hipLaunchKernelGGL((attention_bwd_kernel<float, 32>), grid, block, 0, st, qkv, P, dao, B, S, D, NH, dqkv, drop_p, (unsigned long long)seed);
-        else hipLaunchKernelGGL((attention_bwd_kernel<float, 64>), grid, block, 0, st, qkv, P, dao, B, S, D, NH, dqkv, drop_p, (unsigned long long)seed);
-    }
+    // 1: two lanes per query row (the 16-bit engines' S <= 32 form); 2: four waves per (b, head) (their S > 32 form, here at any S <= 64); else: the fp32 engine's serial kernels
+    const bool wide = variant == 1 || variant == 2, s64 = variant == 2 || (!wide && attention_s64(S));
+    if (wide && !dao) launch_attention_fwd<float, true>(st, s64, qkv, B, S, D, NH, P, ao, drop_p, (unsigned long long)seed);
+    else if (wide) launch_attention_bwd<float, true>(st, s64, qkv, P, dao, B, S, D, NH, dqkv, drop_p, (unsigned long long)seed);
+    else if (!dao) launch_attention_fwd<float, false>(st, s64, qkv, B, S, D, NH, P, ao, drop_p, (unsigned long long)seed);
+    else launch_attention_bwd<float, false>(st, s64, qkv, P, dao, B, S, D, NH, dqkv, drop_p, (unsigned long long)seed);
     if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_attention: launch failed"); return 1; }
     return 0;
 }

@@ -33,7 +33,7 @@ struct Engine : IEngine {
     hulc_config cfg;
     // ---- model dims
     static constexpr int EMB = 128, VF = 64, GOAL = 32, LANG = 384, HID = 2048, NCAT = 32, NCLS = 32, NH = 8, FF = 2048,
-                         FCH = 4096, NMIX = 10;
+                         FCH = 4096, NMIX = LL_NMIX;
     // per model kind: PLAN = width of the two fc_state outputs (32x32 logits; mcil: mean|var of a 256-d Normal), NDIM = mixture
     // dimensions (6 + discrete gripper head; mcil: 7, no gripper head), NHEAD = packed head columns (16-aligned), DE = decoder's slice
     // of the perceptual embedding (perceptual_emb_slice [64,128]; mcil: all 128)
@@ -474,9 +474,6 @@ struct Engine : IEngine {
         }
     }
     int frag_linked = 0;                    // weights whose fragment-ordered copies ride on their transpose descriptor (2 frag jobs each)
-    // unfused attention: two lanes per query row in the 16-bit engines; the fp32 (parity) engine keeps the one-lane kernel's summation order: the hulc_visonly
-    // fixture has an FFN pre-activation within fp32 epsilon of zero, and an epsilon-level change upstream flips its ReLU (1e-3 gradient gate)
-    static constexpr bool att_wide = !std::is_same<T, float>::value;
     static constexpr int TRT = std::is_same<T, float>::value ? 32 : 64;     // transpose tile (bf16: 64x64, 16-byte accesses)
     void add_tr(const float* w32, const T* w, T* wt, int R, int C) {
         TrDesc d; d.src = std::is_same<T, float>::value ? (const void*)w32 : (const void*)w; d.dst = wt; d.lds = C; d.ldt = R; d.R = R; d.C = C;
@@ -821,7 +818,7 @@ struct Engine : IEngine {
     void lin_dgrad(const T* dY, int M, const LinW& L, EpiP ep, const DenseOut& om) {
         gemm(dense<T>(dY, M, L.N), dense<T>(L.Wt, L.K, L.N), om, ep, M, L.K, L.N);
     }
-    // the LayerNorm launches and their decisions live in plan_ln_launch.h (shared with the test entries of k_entries.h)
+    // the LayerNorm launches and their decisions live in plan_ln_launch.h (shared with the test entries of k_entries.h), like every other kernels.h launch helper
     void ln_fwd(const float* x, long long ldx, int rows, int n, const float* g, const float* b, T* out, long long ldo, float* outf, long long ldf,
                 float* stats) {
         launch_ln_fwd<T>(st, x, ldx, rows, n, g, b, out, ldo, outf, ldf, stats);

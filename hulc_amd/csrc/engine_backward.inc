@@ -351,7 +351,7 @@
         if (!hold_buckets && bucket_ready(0)) return 1;       // action_decoder.*, proj_vis_lang.*, logit_scale are final: their all-reduce starts under the rest of the backward
         // ---- straight-through + KL -> logits grads; plan proposal backward
         if (hulc) {
-            hipLaunchKernelGGL((st_softmax_bwd_kernel<T>), dim3(B * NCAT), dim3(64), 0, st, probs, dplan, dpr_kl, NCLS, dprl, dprl_t, dpp_kl, dppl_t);
+            launch_st_softmax_bwd<T>(st, probs, dplan, dpr_kl, dpp_kl, B * NCAT, NCLS, dprl, dprl_t, dppl_t);
             DenseOut om = dense_out(EMB + GOAL);
             mlp_bwd(dppl_t, ppx, EMB + GOAL, B, pp, 5, ppa, dt_a, dt_a + (long long)B * HID, dppx, &om, 0);
             hipLaunchKernelGGL(pp_input_bwd_kernel, dim3(cdiv(B * (EMB + GOAL), 256)), dim3(256), 0, st, dppx, B, EMB, GOAL, demb, (long long)S * EMB, dgoal);
@@ -367,7 +367,7 @@
         // ---- mcil: reparametrised sample + KL -> fc_state grads; plan proposal and BiRNN backward
         if (mcil) {
             const int n = PLAN / 2;
-            hipLaunchKernelGGL((normal_rsample_bwd_kernel<T>), dim3(cdiv(B * n, 256)), dim3(256), 0, st, dplan, plan_eps, pr_logits, dpr_kl, B, n, dprl_t);
+            launch_normal_rsample_bwd<T>(st, dplan, plan_eps, pr_logits, dpr_kl, B, n, dprl_t);
             hipLaunchKernelGGL((cast_kernel<float, T>), dim3(cdiv(B * PLAN, 256)), dim3(256), 0, st, dpp_kl, dppl_t, (long long)B * PLAN);
             DenseOut om = dense_out(EMB + GOAL);
             mlp_bwd(dppl_t, ppx, EMB + GOAL, B, pp, 5, ppa, dt_a, dt_a + (long long)B * HID, dppx, &om, 0);
@@ -443,17 +443,7 @@
                 if (defer_w) tr_wgrad_add(b_d, ao[l], tr_out[l]);
                 else lin_wgrad(b_d, ao[l], EMB, N, EMB, EMB, tr_out[l].dW, EMB, tr_out[l].db);
                 { EpiP ep = epi(dt_a, false); lin_dgrad(b_d, N, tr_out[l], ep, dense_out(EMB)); }
-                if constexpr (att_wide) {
-                    if (S <= 32) hipLaunchKernelGGL((attention_bwd32_kernel<T>), dim3(B * NH), dim3(64), 0, st, qkv[l], Pat[l], dt_a, B, S, EMB, NH, b_b, dp, site_seed(1 + 4 * l));
-                    else {
-                        static bool attr = false;
-                        if (!attr) { hipFuncSetAttribute((const void*)attention_bwd64_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_BWD64_LDS); attr = true; }
-                        hipLaunchKernelGGL((attention_bwd64_kernel<T>), dim3(B * NH), dim3(256), ATT_BWD64_LDS, st, qkv[l], Pat[l], dt_a, B, S, EMB, NH, b_b, dp, site_seed(1 + 4 * l));
-                    }
-                } else {
-                    if (S <= 32) hipLaunchKernelGGL((attention_bwd_kernel<T, 32>), dim3(B * NH), dim3(64), 0, st, qkv[l], Pat[l], dt_a, B, S, EMB, NH, b_b, dp, site_seed(1 + 4 * l));
-                    else hipLaunchKernelGGL((attention_bwd_kernel<T, 64>), dim3(B * NH), dim3(64), 0, st, qkv[l], Pat[l], dt_a, B, S, EMB, NH, b_b, dp, site_seed(1 + 4 * l));
-                }
+                launch_attention_bwd<T>(st, attention_s64(S), qkv[l], Pat[l], dt_a, B, S, EMB, NH, b_b, dp, site_seed(1 + 4 * l));
                 if (defer_w) tr_wgrad_add(b_b, xt[l], tr_in[l]);
                 else lin_wgrad(b_b, xt[l], EMB, N, 3 * EMB, EMB, tr_in[l].dW, EMB, tr_in[l].db);
                 { EpiP ep = epi(dx, true); ep.res = dy_f; ep.res_f32 = 1; ep.res_ld = EMB; lin_dgrad(b_b, N, tr_in[l], ep, dense_out(EMB)); }

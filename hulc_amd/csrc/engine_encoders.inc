@@ -202,7 +202,7 @@
         const EncW& e = encw(k); EncA& a = enca(k);
         const T* fin;
         if (!e.gripper) {
-            if constexpr (std::is_same<T, h16_t>::value) hipLaunchKernelGGL(spatial_softmax_fwd64_kernel, dim3(Nf), dim3(256), 0, st, a.a3, e.H3, e.H3, a.ss, a.ssstats);
+            if constexpr (std::is_same<T, h16_t>::value) launch_spatial_softmax64_fwd(st, a.a3, Nf, e.H3, e.H3, a.ss, a.ssstats);
             else hipLaunchKernelGGL((spatial_softmax_fwd_kernel<T>), dim3(Nf), dim3(256), 0, st, a.a3, e.H3, e.H3, 64, a.ss, (float*)nullptr, a.ssstats);
             fin = a.ss;
         } else {
@@ -594,7 +594,7 @@
                 { EpiP ep = epi(a.d_ss, true); lin_dgrad(a.d_f1, Nf, e.fc1, ep, dense_out(128)); }
                 lin_wgrad(a.d_f1, a.ss, 128, Nf, 512, 128, e.fc1.dW, 128, e.fc1.db);
             }
-            if constexpr (std::is_same<T, h16_t>::value) hipLaunchKernelGGL(spatial_softmax_bwd64_kernel, dim3(Nf), dim3(256), 0, st, a.a3, a.ssstats, a.d_ss, e.H3, e.H3, a.dact3);
+            if constexpr (std::is_same<T, h16_t>::value) launch_spatial_softmax64_bwd(st, a.a3, a.ssstats, a.d_ss, Nf, e.H3, e.H3, a.dact3);
             else hipLaunchKernelGGL((spatial_softmax_bwd_kernel<T>), dim3(Nf), dim3(256), 0, st, a.a3, a.ssstats, a.d_ss, e.H3, e.H3, 64, a.dact3);
         } else {
             if (!tail_done) {

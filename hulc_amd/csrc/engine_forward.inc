@@ -147,18 +147,12 @@
                     launch_tr_layer_fwd(st, q);
                 }
                 // the last norm2 and the mean over the window in one launch (the normalised rows are kept for tests only)
-                hipLaunchKernelGGL((layernorm_mean_kernel<T>), dim3(B), dim3(1024), 0, st, y2[1], S, EMB, tr_n2g[1], tr_n2b[1], st2[1], xm, xf[2]);
+                launch_ln_mean<T>(st, y2[1], B, S, EMB, tr_n2g[1], tr_n2b[1], st2[1], xm, xf[2]);
             }
         }
         for (int l = 0; l < 2 && !fused; ++l) {
             { EpiP ep = epi(qkv[l], false); lin_fwd(xt[l], EMB, N, tr_in[l], ep, 3 * EMB); }
-            if constexpr (att_wide) {
-                if (S <= 32) hipLaunchKernelGGL((attention_fwd32_kernel<T>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
-                else hipLaunchKernelGGL((attention_fwd64_kernel<T>), dim3(B * NH), dim3(256), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
-            } else {
-                if (S <= 32) hipLaunchKernelGGL((attention_fwd_kernel<T, 32>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
-                else hipLaunchKernelGGL((attention_fwd_kernel<T, 64>), dim3(B * NH), dim3(64), 0, st, qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
-            }
+            launch_attention_fwd<T>(st, attention_s64(S), qkv[l], B, S, EMB, NH, Pat[l], ao[l], dp, site_seed(1 + 4 * l));
             { EpiP ep = epi(y1[l], true); ep.res = xf[l]; ep.res_f32 = 1; ep.res_ld = EMB; ep.res_late = 1; ep.drop_p = dp; ep.drop_seed = site_seed(2 + 4 * l);
               lin_fwd(ao[l], EMB, N, tr_out[l], ep, EMB); }
             ln_fwd(y1[l], EMB, N, EMB, tr_n1g[l], tr_n1b[l], x1t[l], EMB, x1f[l], EMB, st1[l]);
@@ -187,8 +181,7 @@
                 EpiP ep = epi(Cplan, true); ep.bias = bih0; ep.bias2 = bhh0;
                 gemm(dense<T>(plan_t, B, dec_plan), dense<T>(wih0, HID, KIN), dense_out(HID), ep, B, HID, dec_plan);
             } else      // the one-hot plan gather and the time-major embedding copy are independent: one launch
-            hipLaunchKernelGGL((plan_gather_t_kernel<T>), dim3(cdiv(B * HID, 256) + cdiv(SB * DE, 256)), dim3(256), 0, st, wih0T, plan_idx, B, hulc ? NCAT : 0, NCLS, HID, bih0,
-                               bhh0, Cplan, emb, embg, S, DE, goal_t, GOAL, dec_plan + DE, cb_fused ? Cb : (T*)nullptr);
+            launch_plan_gather<T>(st, wih0T, plan_idx, B, hulc ? NCAT : 0, NCLS, HID, bih0, bhh0, Cplan, emb, embg, S, DE, goal_t, GOAL, dec_plan + DE, cb_fused ? Cb : (T*)nullptr);
             if (!cb_fused) { EpiP ep = epi(Cb, false); ep.res = Cplan; ep.res_f32 = 1; ep.res_ld = HID;
               gemm(dense<T>(goal_t, B, GOAL), dense<T>(wih0 + dec_plan + DE, HID, KIN), dense_out(HID), ep, B, HID, GOAL); }
             if (mlp) {      // feed-forward body (rnn.py mlp_decoder): a0 = relu(W0 x + b0) with the time-invariant term as the broadcast residual, a1 = relu(W1 a0 + b1), y = W2 a1 + b2
@@ -232,10 +225,8 @@
         if (!bound) { hulc_set_error("hulc_forward_loss_pair before hulc_bind_params"); return 1; }
         if (vb->is_lang || !lb->is_lang || !lb->lang) { hulc_set_error("hulc_forward_loss_pair: first batch must be the vis modality, second the lang modality with embeddings"); return 1; }
         if (vb->B != lb->B || vb->S != lb->S) { hulc_set_error("hulc_forward_loss_pair: both modalities need the same B and S (got %dx%d and %dx%d)", vb->B, vb->S, lb->B, lb->S); return 1; }
-        for (const hulc_batch* b : {vb, lb}) {
-            if (store_args_bad(b)) return 1;
-            if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
-        }
+        for (const hulc_batch* b : {vb, lb})
+            if (ingest_args_bad(b)) return 1;
         if ((vb->window_len_host != nullptr) != (lb->window_len_host != nullptr)) {
             hulc_set_error("hulc_forward_loss_pair: window_len_host (ragged encoder pass) must be given for both modalities or for neither"); return 1; }
         if (vb->frames_u8 != lb->frames_u8 || vb->actions_absolute != lb->actions_absolute || vb->max_rel_pos != lb->max_rel_pos || vb->max_rel_orn != lb->max_rel_orn) {
@@ -285,18 +276,33 @@
             if (h[i] < 0 || h[i] >= NCLS) { hulc_set_error("%s: injected plan index %d (window %d, category %d) is outside [0, %d)", who, h[i], i / NCAT, i % NCAT, NCLS); return 1; }
         return 0;
     }
+    // the frame-store and RandomShiftsAug arguments of one batch
+    static bool ingest_args_bad(const hulc_batch* b) {
+        if (store_args_bad(b)) return true;
+        if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return true; }
+        return false;
+    }
+    // what a training forward and a validation forward ask of their batch's shape and modality (its ingest arguments: ingest_args_bad, which validation checks later)
+    bool batch_args_bad(const hulc_batch* b) {
+        if (b->B < 1 || b->S < 1 || b->B > maxB || b->S > maxS || b->S > cfg.max_window || b->S > 64) { hulc_set_error("batch (B=%d,S=%d) exceeds workspace (max_batch=%d,max_seq=%d,max_window=%d)", b->B, b->S, maxB, maxS, cfg.max_window); return true; }
+        if (b->is_lang && !b->lang) { hulc_set_error("lang modality batch without language embeddings (hulc.py:440 KeyError 'lang')"); return true; }
+        if (b->actions_absolute && !(b->max_rel_pos > 0.f && b->max_rel_orn > 0.f)) { hulc_set_error("actions_absolute needs max_rel_pos > 0 and max_rel_orn > 0 (RelativeActions, transforms.py:35-37)"); return true; }
+        return false;
+    }
+    // gather the flagged rows of seqf_t and goal_t, then the two CLIP projections (hulc.py:650-695): img, txt [n][GOAL] fp32.  auxrows holds the n row indices
+    void clip_proj_fwd(int n) {
+        hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * FCH, 256)), dim3(256), 0, st, seqf_t, (long long)FCH, auxrows, n, FCH, sf_m);
+        hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * GOAL, 256)), dim3(256), 0, st, goal_t, (long long)GOAL, auxrows, n, GOAL, g_m);
+        { EpiP ep = epi(im1, false); ep.relu = 1; lin_fwd(sf_m, FCH, n, cl_im0, ep, 128); }
+        { EpiP ep = epi(img, true); lin_fwd(im1, 128, n, cl_im2, ep, GOAL); }
+        { EpiP ep = epi(la1, false); ep.relu = 1; lin_fwd(g_m, GOAL, n, cl_la0, ep, 128); }
+        { EpiP ep = epi(txt, true); lin_fwd(la1, 128, n, cl_la2, ep, GOAL); }
+    }
     int forward_impl(const hulc_batch* b, float lw, float cw, float* out, int on_host) {
         if (!bound) { hulc_set_error("hulc_forward_loss before hulc_bind_params"); return 1; }
         persist_check("hulc_forward_loss", false);
         repro_latch();
-        if (b->B < 1 || b->S < 1 || b->B > maxB || b->S > maxS || b->S > cfg.max_window || b->S > 64) {
-            hulc_set_error("batch (B=%d,S=%d) exceeds workspace (max_batch=%d,max_seq=%d,max_window=%d)", b->B, b->S, maxB, maxS, cfg.max_window);
-            return 1;
-        }
-        if (b->is_lang && !b->lang) { hulc_set_error("lang modality batch without language embeddings (hulc.py:440 KeyError 'lang')"); return 1; }
-        if (b->actions_absolute && !(b->max_rel_pos > 0.f && b->max_rel_orn > 0.f)) { hulc_set_error("actions_absolute needs max_rel_pos > 0 and max_rel_orn > 0 (RelativeActions, transforms.py:35-37)"); return 1; }
-        if (store_args_bad(b)) return 1;
-        if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
+        if (batch_args_bad(b) || ingest_args_bad(b)) return 1;
         if (cfg.kind == HULC_KIND_HULC && b->plan_idx && plan_idx_bad(b->plan_idx, b->B * NCAT, "hulc_forward_loss")) return 1;
         cur = *b; cur_lw = lw; cur_cw = cw; have_fwd = false; val_clip_n = 0;
         if (window_tables(*b, pair ? pairBv : b->B, pair ? &cur2 : nullptr)) return 1;
@@ -313,45 +319,35 @@
         }
         trunk_fwd(b, dp);
         if (pend_zero[0]) { hulc_set_error("forward: the loss accumulators were not cleared (no conv1 launch took them)"); return 1; }
+        // ---- sample + KL (hulc.py:289-296, 539-561); mcil: the reparametrised Normal sample
+        const float wpp = lw * cfg.kl_beta * cfg.kl_balancing_mix / Bm, wpr = lw * cfg.kl_beta * (1.f - cfg.kl_balancing_mix) / Bm;
         if (mcil) {
             if (gru) bigru_fwd(B, S); else birnn_fwd(B, S);
             const int n = PLAN / 2;
             const float* eps = nullptr;
             if (b->plan_eps) { HIP_CHECK(hipMemcpyAsync(plan_eps_in, b->plan_eps, sizeof(float) * B * n, hipMemcpyDefault, st)); eps = plan_eps_in; }
-            const float wpp = lw * cfg.kl_beta * cfg.kl_balancing_mix / Bm, wpr = lw * cfg.kl_beta * (1.f - cfg.kl_balancing_mix) / Bm;
-            hipLaunchKernelGGL((normal_kl_sample_kernel<T>), dim3(cdiv(B * n, 256)), dim3(256), 0, st, pr_logits, pp_logits, B, n, eps, plan_eps, plan_f, plan_t, klel,
-                               dpp_kl, dpr_kl, wpp, wpr, site_seed(20), lscale());
-            if (pair) {
-                hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, klel, Bm * n, cfg.kl_beta / Bm, losses + 1);
-                hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, klel + (long long)Bm * n, Bm * n, cfg.kl_beta / Bm, losses2 + 1);
-            } else { kl_src = klel; kl_n = Bm * n; }      // summed by finish_losses_kernel at the end of the forward
+            launch_normal_kl_sample<T>(st, pr_logits, pp_logits, B, n, eps, plan_eps, plan_f, plan_t, klel, dpp_kl, dpr_kl, wpp, wpr, site_seed(20), lscale());
+            kl_src = klel; kl_n = Bm * n;
         } else pr_fwd(B, S, dp);
-        // ---- sample + KL (hulc.py:289-296, 539-561)
         if (hulc) {
             const int* idx_in = nullptr;
             if (b->plan_idx) { HIP_CHECK(hipMemcpyAsync(pidx_in, b->plan_idx, sizeof(int) * B * NCAT, hipMemcpyDefault, st)); idx_in = pidx_in; }
-            const float wpp = lw * cfg.kl_beta * cfg.kl_balancing_mix / Bm, wpr = lw * cfg.kl_beta * (1.f - cfg.kl_balancing_mix) / Bm;
-            hipLaunchKernelGGL(plan_kl_sample_kernel, dim3(B * NCAT), dim3(64), 0, st, pr_logits, pp_logits, B, NCAT, NCLS, idx_in, pidx, probs, klcat, dpp_kl,
-                               dpr_kl, wpp, wpr, site_seed(20), lscale());
-            if (pair) {
-                hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, klcat, Bm * NCAT, cfg.kl_beta / Bm, losses + 1);
-                hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, klcat + Bm * NCAT, Bm * NCAT, cfg.kl_beta / Bm, losses2 + 1);
-            } else { kl_src = klcat; kl_n = Bm * NCAT; }
+            launch_plan_kl_sample(st, pr_logits, pp_logits, B, NCAT, NCLS, idx_in, pidx, probs, klcat, dpp_kl, dpr_kl, wpp, wpr, site_seed(20), lscale());
+            kl_src = klcat; kl_n = Bm * NCAT;
+        }
+        if (pair && kl_src) {      // per-modality KL sums; one modality: summed by finish_losses_kernel at the end of the forward
+            launch_sum_reduce(st, kl_src, kl_n, cfg.kl_beta / Bm, losses + 1);
+            launch_sum_reduce(st, kl_src + kl_n, kl_n, cfg.kl_beta / Bm, losses2 + 1);
         }
         // ---- action decoder (logistic_decoder_rnn.py:260-287): plan/goal terms hoisted out of the time loop
         {
             dec_fwd(pidx, B, S, nullptr, nullptr);
             // mcil_default.yaml: gripper_control false (no tcp-frame transform), discrete_gripper false (7th mixture dimension instead of the CE head)
-            constexpr int ll_block = 64;     // one wave per workgroup: 256 CUs x 1 wave instead of 64 CUs x 4 (the kernel is one long serial chain per thread)
-            // 16-bit engines: one lane per mixture component (kernels.h logistic_loss_wide_kernel: 17.9 -> ~6 us); the fp32 parity engine keeps the serial kernel's summation order
             if (det)      // tanh head + Huber / MSE against the world-frame actions (deterministic_decoder.py:82-94) + the pre-activation gradient, one launch
                 launch_det_head_loss<T>(st, H1, det_w, det_b32, actions_of(*b), b->robot_obs, B, S, det_crit, 0, lw / (float)(S * Bm), lscale(), rowloss, 8, nullptr, dpre);
-            else if (!std::is_same<T, float>::value && NMIX <= 16 && NDIM <= 7)
-                hipLaunchKernelGGL((logistic_loss_wide_kernel<T>), dim3(SB), dim3(128), 0, st, heads, NHEAD, actions_of(*b), b->robot_obs, B, S, NMIX, NDIM,
-                                   cfg.num_classes, cfg.log_scale_min, cfg.gripper_alpha, mcil ? 0 : 1, lw / (float)(S * Bm), rowloss, a_tcp, dheads, mcil ? 0 : 1, lscale());
-            else
-            hipLaunchKernelGGL((logistic_loss_kernel<T, NMIX>), dim3(cdiv(SB * 8, ll_block)), dim3(ll_block), 0, st, heads, NHEAD, actions_of(*b), b->robot_obs, B, S, NMIX, NDIM,
-                               cfg.num_classes, cfg.log_scale_min, cfg.gripper_alpha, mcil ? 0 : 1, lw / (float)(S * Bm), rowloss, a_tcp, dheads, mcil ? 0 : 1, lscale());
+            else      // the wide kernel on the 16-bit engines, the serial one on the fp32 parity engine (plan_ln_launch.h)
+                launch_logistic_loss<T>(st, logistic_loss_wide<T>(NMIX, NDIM), heads, NHEAD, actions_of(*b), b->robot_obs, B, S, NMIX, NDIM, cfg.num_classes, cfg.log_scale_min,
+                                        cfg.gripper_alpha, mcil ? 0 : 1, mcil ? 0 : 1, lw / (float)(S * Bm), lscale(), rowloss, a_tcp, dheads);
             if (pair) hipLaunchKernelGGL(sum_rows_pair_kernel, dim3(1), dim3(256), 0, st, rowloss, SB, B, pairBv, 1.f / (S * Bm), losses + 0, losses2 + 0);
             // one modality: the action-loss sum, the KL sum, the packing and the copy to a device `out` are ONE launch at the end (finish_losses_kernel)
         }
@@ -362,12 +358,7 @@
             if (n > B) { hulc_set_error("clip aux rows n=%d unsupported (<= B=%d)", n, B); return 1; }
             clip_n = n;
             HIP_CHECK(hipMemcpyAsync(auxrows, b->aux_rows, sizeof(int) * n, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * FCH, 256)), dim3(256), 0, st, seqf_t, (long long)FCH, auxrows, n, FCH, sf_m);
-            hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * GOAL, 256)), dim3(256), 0, st, goal_t, (long long)GOAL, auxrows, n, GOAL, g_m);
-            { EpiP ep = epi(im1, false); ep.relu = 1; lin_fwd(sf_m, FCH, n, cl_im0, ep, 128); }
-            { EpiP ep = epi(img, true); lin_fwd(im1, 128, n, cl_im2, ep, GOAL); }
-            { EpiP ep = epi(la1, false); ep.relu = 1; lin_fwd(g_m, GOAL, n, cl_la0, ep, 128); }
-            { EpiP ep = epi(txt, true); lin_fwd(la1, 128, n, cl_la2, ep, GOAL); }
+            clip_proj_fwd(n);
             static_assert(GOAL == CLIP_D, "the CLIP loss kernels are built for 32-wide projections");
             // n <= 64: one workgroup (the 1024-thread form on the 16-bit engines, the serial one on the fp32 parity engine); above: the tiled launches of aux_rows.h
             if (!launch_clip_loss(st, !std::is_same<T, float>::value, img, txt, n, logit_scale, cw, (pair ? losses2 : losses) + 2, dimg, dtxt, dlogit_scale, lscale(), clip_rows_ws)) {

@@ -14,8 +14,7 @@
     // KL(state || kl_with) lands in klel (no gradient weights)
     void sample_cont(const float* state, const float* kl_with, const float* inject, int B, uint64_t seed) {
         const int n = PLAN / 2;
-        hipLaunchKernelGGL((normal_kl_sample_kernel<T>), dim3(cdiv(B * n, 256)), dim3(256), 0, st, state, kl_with, B, n, (const float*)nullptr, plan_eps, plan_f, plan_t, klel,
-                           dpp_kl, dpr_kl, 0.f, 0.f, seed);
+        launch_normal_kl_sample<T>(st, state, kl_with, B, n, nullptr, plan_eps, plan_f, plan_t, klel, dpp_kl, dpr_kl, 0.f, 0.f, seed, nullptr);
         if (inject) {
             hipMemcpyAsync(plan_f, inject, sizeof(float) * B * n, hipMemcpyDefault, st);
             hipLaunchKernelGGL((cast_kernel<float, T>), dim3(cdiv(B * n, 256)), dim3(256), 0, st, plan_f, plan_t, (long long)B * n);
@@ -32,18 +31,12 @@
     int validate_impl(const hulc_batch* b, const hulc_val_noise* nz, float* out17, int32_t* plan_pp_out, int32_t* plan_pr_out, float* pred_pp_out,
                       float* pred_pr_out) {
         if (!bound) { hulc_set_error("hulc_validate before hulc_bind_params"); return 1; }
+        if (batch_args_bad(b)) return 1;
         const bool hulc = cfg.kind == HULC_KIND_HULC;     // GCBC (gcbc.py:214-246): one decoder pass without a plan, reported in the "pp" slots
-        if (b->B < 1 || b->S < 1 || b->B > maxB || b->S > maxS || b->S > cfg.max_window || b->S > 64) {
-            hulc_set_error("batch (B=%d,S=%d) exceeds workspace (max_batch=%d,max_seq=%d,max_window=%d)", b->B, b->S, maxB, maxS, cfg.max_window);
-            return 1;
-        }
-        if (b->is_lang && !b->lang) { hulc_set_error("lang modality batch without language embeddings (hulc.py:440 KeyError 'lang')"); return 1; }
-        if (b->actions_absolute && !(b->max_rel_pos > 0.f && b->max_rel_orn > 0.f)) { hulc_set_error("actions_absolute needs max_rel_pos > 0 and max_rel_orn > 0 (RelativeActions, transforms.py:35-37)"); return 1; }
         val_alloc();
         if (alloc_failed) { hulc_set_error("hulc_validate: workspace allocation failed"); return 1; }
         repro_latch();
-        if (store_args_bad(b)) return 1;
-        if (b->frames_u8 && (b->shift_static || b->shift_gripper) && (b->pad_static < 0 || b->pad_static > CONV1_RAW_MARGIN || b->pad_gripper < 0 || b->pad_gripper > CONV1_RAW_MARGIN)) { hulc_set_error("RandomShiftsAug pads must lie in [0, %d] (the staged rows' replicate margin); got pad_static=%d, pad_gripper=%d", CONV1_RAW_MARGIN, b->pad_static, b->pad_gripper); return 1; }
+        if (ingest_args_bad(b)) return 1;
         static const hulc_val_noise none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         if (!nz) nz = &none;
         if (hulc && ((nz->plan_idx_pr && plan_idx_bad(nz->plan_idx_pr, b->B * NCAT, "hulc_validate (plan_idx_pr)")) ||
@@ -58,56 +51,47 @@
         const int* in_pr = nullptr;
         if (hulc) {
         if (nz->plan_idx_pr) { HIP_CHECK(hipMemcpyAsync(pidx_in, nz->plan_idx_pr, sizeof(int) * B * NCAT, hipMemcpyDefault, st)); in_pr = pidx_in; }
-        hipLaunchKernelGGL(plan_kl_sample_kernel, dim3(B * NCAT), dim3(64), 0, st, pr_logits, pp_logits, B, NCAT, NCLS, in_pr, pidx, probs, klcat, dpp_kl, dpr_kl, 0.f,
-                           0.f, site_seed(40));
-        hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, klcat, B * NCAT, cfg.kl_beta / B, valm + 2);
+        launch_plan_kl_sample(st, pr_logits, pp_logits, B, NCAT, NCLS, in_pr, pidx, probs, klcat, dpp_kl, dpr_kl, 0.f, 0.f, site_seed(40), nullptr);
+        launch_sum_reduce(st, klcat, B * NCAT, cfg.kl_beta / B, valm + 2);
         const int* in_pp = nullptr;
         if (nz->plan_idx_pp) { HIP_CHECK(hipMemcpyAsync(pidx_in, nz->plan_idx_pp, sizeof(int) * B * NCAT, hipMemcpyDefault, st)); in_pp = pidx_in; }
-        hipLaunchKernelGGL(plan_kl_sample_kernel, dim3(B * NCAT), dim3(64), 0, st, pp_logits, (const float*)nullptr, B, NCAT, NCLS, in_pp, pidx_pp, probs, klcat,
-                           dpp_kl, dpr_kl, 0.f, 0.f, site_seed(41));
+        launch_plan_kl_sample(st, pp_logits, nullptr, B, NCAT, NCLS, in_pp, pidx_pp, probs, klcat, dpp_kl, dpr_kl, 0.f, 0.f, site_seed(41), nullptr);
         }
         const float* acts = actions_of(*b);
         for (int pass = 0; pass < ((hulc || mcil) ? 2 : 1); ++pass) {          // 0: plan proposal, 1: plan recognition (loss_and_act, logistic_decoder_rnn.py:85-100)
             if (mcil) {      // continuous plan: Independent(Normal).sample() (distributions.py:37-38) or the injected draw (B,256) fp32
                 sample_cont(pass == 0 ? pp_logits : pr_logits, pass == 0 ? nullptr : pp_logits, reinterpret_cast<const float*>(pass == 0 ? nz->plan_idx_pp : nz->plan_idx_pr),
                             B, site_seed(41 - pass));
-                if (pass == 1) hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, klel, B * (PLAN / 2), cfg.kl_beta / B, valm + 2);
+                if (pass == 1) launch_sum_reduce(st, klel, B * (PLAN / 2), cfg.kl_beta / B, valm + 2);
                 int32_t* po = pass == 0 ? plan_pp_out : plan_pr_out;
                 if (po) HIP_CHECK(hipMemcpyAsync(po, plan_f, sizeof(float) * B * (PLAN / 2), hipMemcpyDefault, st));
             }
             dec_fwd(pass == 0 ? pidx_pp : pidx, B, S, nullptr, nullptr);
-            if (det) {      // loss_and_act (deterministic_decoder.py:63-80): the criterion in the tcp frame, the prediction in the world frame; no noise (u_mix / u_act ignored)
-                launch_det_head_loss<T>(st, H1, det_w, det_b32, acts, b->robot_obs, B, S, det_crit, 1, 0.f, nullptr, rowloss, 8, nullptr, dpre);
-                hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, rowloss, SB * 8, 1.f / SB, valm + pass);
-                // metrics: one atomic per row and component; reproducible mode sums the stored predictions in a fixed order instead (val_metrics_kernel)
-                if (!repro && SB > 1) nd(ND_VAL_METRICS);
-                launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, b->robot_obs, acts, B, S, pass == 0 ? pred_pp : pred_pr, repro ? (float*)nullptr : valm + 8 + 8 * pass);
-                if (repro) hipLaunchKernelGGL(val_metrics_kernel, dim3(1), dim3(256), 0, st, (const float*)(pass == 0 ? pred_pp : pred_pr), acts, SB, valm + 8 + 8 * pass);
-                continue;
-            }
-            hipLaunchKernelGGL((logistic_loss_kernel<T, NMIX>), dim3(cdiv(SB * 8, 256)), dim3(256), 0, st, heads, NHEAD, acts, b->robot_obs, B, S, NMIX, NDIM,
-                               cfg.num_classes, cfg.log_scale_min, cfg.gripper_alpha, mcil ? 0 : 1, 0.f, rowloss, a_tcp, dheads, mcil ? 0 : 1);
-            hipLaunchKernelGGL(sum_reduce_kernel, dim3(1), dim3(256), 0, st, rowloss, SB * 8, 1.f / SB, valm + pass);
-            const float* um = pass == 0 ? nz->u_mix_pp : nz->u_mix_pr;
-            const float* ua = pass == 0 ? nz->u_act_pp : nz->u_act_pr;
-            if (um) { HIP_CHECK(hipMemcpyAsync(nz_mix, um, sizeof(float) * SB * NDIM * NMIX, hipMemcpyDefault, st)); um = nz_mix; }
-            if (ua) { HIP_CHECK(hipMemcpyAsync(nz_act, ua, sizeof(float) * SB * NDIM, hipMemcpyDefault, st)); ua = nz_act; }
-            hipLaunchKernelGGL(logistic_sample_kernel, dim3(cdiv(SB, 64)), dim3(64), 0, st, heads, NHEAD, b->robot_obs, acts, um, ua, B, S, NMIX, NDIM,
-                               cfg.log_scale_min, mcil ? 0 : 1, site_seed(42 + pass), pass == 0 ? pred_pp : pred_pr, repro ? (float*)nullptr : valm + 8 + 8 * pass, mcil ? 0 : 1);
+            // metrics: one atomic per row and component; reproducible mode sums the stored predictions in a fixed order instead (val_metrics_kernel)
+            float *const pred = pass == 0 ? pred_pp : pred_pr, *const metrics = valm + 8 + 8 * pass;
             if (!repro && SB > 1) nd(ND_VAL_METRICS);
-            if (repro) hipLaunchKernelGGL(val_metrics_kernel, dim3(1), dim3(256), 0, st, (const float*)(pass == 0 ? pred_pp : pred_pr), acts, SB, valm + 8 + 8 * pass);
+            // loss_and_act; det (deterministic_decoder.py:63-80): criterion in the tcp frame, prediction in the world frame, no noise; mixture head: the serial loss kernel on every engine
+            if (det) launch_det_head_loss<T>(st, H1, det_w, det_b32, acts, b->robot_obs, B, S, det_crit, 1, 0.f, nullptr, rowloss, 8, nullptr, dpre);
+            else launch_logistic_loss<T>(st, false, heads, NHEAD, acts, b->robot_obs, B, S, NMIX, NDIM, cfg.num_classes, cfg.log_scale_min, cfg.gripper_alpha, mcil ? 0 : 1, mcil ? 0 : 1,
+                                         0.f, nullptr, rowloss, a_tcp, dheads);
+            launch_sum_reduce(st, rowloss, SB * 8, 1.f / SB, valm + pass);
+            if (det) launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, b->robot_obs, acts, B, S, pred, repro ? nullptr : metrics);
+            else {
+                const float* um = pass == 0 ? nz->u_mix_pp : nz->u_mix_pr;
+                const float* ua = pass == 0 ? nz->u_act_pp : nz->u_act_pr;
+                if (um) { HIP_CHECK(hipMemcpyAsync(nz_mix, um, sizeof(float) * SB * NDIM * NMIX, hipMemcpyDefault, st)); um = nz_mix; }
+                if (ua) { HIP_CHECK(hipMemcpyAsync(nz_act, ua, sizeof(float) * SB * NDIM, hipMemcpyDefault, st)); ua = nz_act; }
+                launch_logistic_sample(st, heads, NHEAD, b->robot_obs, acts, um, ua, B, S, NMIX, NDIM, cfg.log_scale_min, mcil ? 0 : 1, mcil ? 0 : 1, site_seed(42 + pass), pred,
+                                       repro ? nullptr : metrics);
+            }
+            if (repro) hipLaunchKernelGGL(val_metrics_kernel, dim3(1), dim3(256), 0, st, (const float*)pred, acts, SB, metrics);
         }
         // val/val_pred_clip_loss (hulc.py:804-808): the CLIP auxiliary loss of the lang modality on the masked rows, forward only
         if (b->is_lang && cfg.use_clip && b->n_aux > 0) {
             const int n = b->n_aux;
             if (n > B) { hulc_set_error("clip aux rows n=%d unsupported (<= B=%d)", n, B); return 1; }
             HIP_CHECK(hipMemcpyAsync(auxrows, b->aux_rows, sizeof(int) * n, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * FCH, 256)), dim3(256), 0, st, seqf_t, (long long)FCH, auxrows, n, FCH, sf_m);
-            hipLaunchKernelGGL((gather_rows_kernel<T, T>), dim3(cdiv(n * GOAL, 256)), dim3(256), 0, st, goal_t, (long long)GOAL, auxrows, n, GOAL, g_m);
-            { EpiP ep = epi(im1, false); ep.relu = 1; lin_fwd(sf_m, FCH, n, cl_im0, ep, 128); }
-            { EpiP ep = epi(img, true); lin_fwd(im1, 128, n, cl_im2, ep, GOAL); }
-            { EpiP ep = epi(la1, false); ep.relu = 1; lin_fwd(g_m, GOAL, n, cl_la0, ep, 128); }
-            { EpiP ep = epi(txt, true); lin_fwd(la1, 128, n, cl_la2, ep, GOAL); }
+            clip_proj_fwd(n);
             const bool one_wg = n <= AUX_ROWS_SINGLE;          // the single-workgroup kernel also writes gradients (times 0, into scratch); above 64 rows: loss only
             if (!launch_clip_loss(st, false, img, txt, n, logit_scale, 0.f, valm + 3, one_wg ? dimg : nullptr, one_wg ? dtxt : nullptr, one_wg ? valm + 31 : nullptr, nullptr, clip_rows_ws)) {
                 hulc_set_error("clip loss: n=%d rows not covered by this context's workspace (max_batch=%d)", n, maxB); return 1; }
@@ -240,8 +224,7 @@
             if (plan_out) HIP_CHECK(hipMemcpyAsync(plan_out, plan_f, sizeof(float) * (PLAN / 2), hipMemcpyDefault, st));
         } else if (!gcbc) {
         if (plan_inject) { HIP_CHECK(hipMemcpyAsync(pidx_in, plan_inject, sizeof(int) * NCAT, hipMemcpyDefault, st)); inj = pidx_in; }
-        hipLaunchKernelGGL(plan_kl_sample_kernel, dim3(NCAT), dim3(64), 0, st, pp_logits, (const float*)nullptr, 1, NCAT, NCLS, inj, roll_plan, probs, klcat, dpp_kl,
-                           dpr_kl, 0.f, 0.f, site_seed(50));
+        launch_plan_kl_sample(st, pp_logits, nullptr, 1, NCAT, NCLS, inj, roll_plan, probs, klcat, dpp_kl, dpr_kl, 0.f, 0.f, site_seed(50), nullptr);
         }
         HIP_CHECK(hipMemcpyAsync(roll_goal, goal_t, sizeof(T) * GOAL, hipMemcpyDeviceToDevice, st));
         if (!gcbc) roll_has_h = false;                 // action_decoder.clear_hidden_state() (hulc.py:925 / :946); GCBC.step never clears it (gcbc.py:286-320)
@@ -300,8 +283,7 @@
         if (det) { u_mix = u_act = nullptr; launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, roll_ro, nullptr, 1, 1, roll_pred, nullptr); }      // deterministic head: the noise is ignored
         if (u_mix) { HIP_CHECK(hipMemcpyAsync(nz_mix, u_mix, sizeof(float) * NDIM * NMIX, hipMemcpyDefault, st)); u_mix = nz_mix; }
         if (u_act) { HIP_CHECK(hipMemcpyAsync(nz_act, u_act, sizeof(float) * NDIM, hipMemcpyDefault, st)); u_act = nz_act; }
-        if (!det) hipLaunchKernelGGL(logistic_sample_kernel, dim3(1), dim3(64), 0, st, heads, NHEAD, roll_ro, (const float*)nullptr, u_mix, u_act, 1, 1, NMIX, NDIM,
-                           cfg.log_scale_min, mcil ? 0 : 1, site_seed(51), roll_pred, (float*)nullptr, mcil ? 0 : 1);
+        if (!det) launch_logistic_sample(st, heads, NHEAD, roll_ro, nullptr, u_mix, u_act, 1, 1, NMIX, NDIM, cfg.log_scale_min, mcil ? 0 : 1, mcil ? 0 : 1, site_seed(51), roll_pred, nullptr);
         HIP_CHECK(hipMemcpyAsync(action_out, roll_pred, sizeof(float) * 7, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         if (hipGetLastError() != hipSuccess) { hulc_set_error("kernel launch failed in rollout_act"); return 1; }

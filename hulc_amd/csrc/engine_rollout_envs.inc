@@ -117,8 +117,7 @@
         else if (!gcbc) {
             const int* inj = nullptr;
             if (plan_inject) { HIP_CHECK(hipMemcpyAsync(pidx_in, plan_inject, sizeof(int) * n * NCAT, hipMemcpyDefault, st)); inj = pidx_in; }
-            hipLaunchKernelGGL(plan_kl_sample_kernel, dim3(n * NCAT), dim3(64), 0, st, pp_logits, (const float*)nullptr, n, NCAT, NCLS, inj, env_pidx, probs, klcat, dpp_kl,
-                               dpr_kl, 0.f, 0.f, site_seed(52));
+            launch_plan_kl_sample(st, pp_logits, nullptr, n, NCAT, NCLS, inj, env_pidx, probs, klcat, dpp_kl, dpr_kl, 0.f, 0.f, site_seed(52), nullptr);
         }
         env_store(n, env_pidx, mcil ? plan_f : nullptr, !gcbc && !mlp);       // action_decoder.clear_hidden_state() per planned slot (hulc.py:925 / :946); GCBC.step never clears it
         if (plan_out && mcil) HIP_CHECK(hipMemcpyAsync(plan_out, plan_f, sizeof(float) * n * (PLAN / 2), hipMemcpyDefault, st));
@@ -163,6 +162,14 @@
         for (int r = 0; r < n; ++r) env_has_plan[env_desc[r] & 0xffff] = 1;
         return 0;
     }
+    // 16-bit engines: heads GEMM + sampler over the new layer-1 state of every row's slot (byrow: over rows 0..n-1 of the feed-forward body's row buffer; never mcil)
+    void env_heads_sample(int n, const T* h1, bool byrow, const float* u_mix, const float* u_act) {
+        EnvHeadsP hp{};
+        hp.rowdesc = env_rows; hp.n = n; hp.max_envs = env_cap; hp.h1 = h1; hp.W = wheads; hp.bias = bheads; hp.robot_obs = env_ro; hp.u_mix = u_mix; hp.u_act = u_act;
+        hp.NMIX = NMIX; hp.NDIM = NDIM; hp.log_scale_min = cfg.log_scale_min; hp.gripper_control = mcil ? 0 : 1; hp.discrete_gripper = mcil ? 0 : 1;
+        hp.seed = site_seed(53); hp.pred = env_pred;
+        launch_env_heads_sample(st, hp, NHEAD, byrow);
+    }
     int rollout_envs_act(const hulc_rollout_envs_obs* obs, const float* u_mix, const float* u_act, float* actions_out) override {
         const char* fn = "hulc_rollout_envs_act";
         if (env_check(fn, obs->n, obs->slots, false, true)) return 1;
@@ -191,12 +198,7 @@
             hipLaunchKernelGGL((env_rnn_layer_kernel<false, true>), dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l);
             l.x = H1; l.Wx = mlp2.W; l.h = Zx1; l.b1 = mlp2.b32; l.w16 = a16(l.Wx);
             hipLaunchKernelGGL((env_rnn_layer_kernel<false, false>), dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l);
-            EnvHeadsP hp{};
-            hp.rowdesc = env_rows; hp.n = n; hp.max_envs = env_cap; hp.h1 = Zx1; hp.W = wheads; hp.bias = bheads; hp.robot_obs = env_ro; hp.u_mix = u_mix; hp.u_act = u_act;
-            hp.NMIX = NMIX; hp.NDIM = NDIM; hp.log_scale_min = cfg.log_scale_min; hp.gripper_control = 1; hp.discrete_gripper = 1;
-            hp.seed = site_seed(53); hp.pred = env_pred;
-            if (NHEAD == 192) hipLaunchKernelGGL((env_heads_sample_kernel<12, true>), dim3(cdiv(n, 16)), dim3(ENV_WAVES * 64), 0, st, hp);
-            else hipLaunchKernelGGL((env_heads_sample_kernel<14, true>), dim3(cdiv(n, 16)), dim3(ENV_WAVES * 64), 0, st, hp);
+            env_heads_sample(n, Zx1, true, u_mix, u_act);
             }
         } else if (mlp) {
             // feed-forward body, fp32 engine: slot plan / goal -> rows, dec_fwd at B = n, S = 1, the validation sampler; no state goes back to the slots
@@ -204,8 +206,7 @@
             g.s_plan_i = env_plan_i; g.s_plan_f = env_plan_f; g.s_goal = env_goal; g.pidx = env_ncat() ? env_pidx : nullptr; g.goal_t = goal_t;
             hipLaunchKernelGGL((env_gather_kernel<T>), dim3(n), dim3(256), 0, st, g);
             dec_fwd(env_pidx, n, 1, nullptr, nullptr);
-            hipLaunchKernelGGL(logistic_sample_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, heads, NHEAD, env_ro, (const float*)nullptr, u_mix, u_act, n, 1, NMIX, NDIM,
-                               cfg.log_scale_min, 1, site_seed(53), env_pred, (float*)nullptr, 1);
+            launch_logistic_sample(st, heads, NHEAD, env_ro, nullptr, u_mix, u_act, n, 1, NMIX, NDIM, cfg.log_scale_min, 1, 1, site_seed(53), env_pred, nullptr);
         } else if constexpr (std::is_same<T, h16_t>::value) {
             // embedding -> actions: three launches, no copy (rollout_step.h)
             auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
@@ -220,14 +221,7 @@
             l1.w16 = a16(l1.Wx) && a16(l1.Whh);
             hipLaunchKernelGGL((env_rnn_layer_kernel<true, true>), dim3(HID / ENV_COLS), dim3(ENV_WAVES * 64), 0, st, l1);
             if (det) launch_det_head_act<T>(st, env_h1, env_rows, env_cap, det_w, det_b32, env_ro, nullptr, n, 1, env_pred, nullptr);      // the new layer-1 state of every row's slot
-            else {
-            EnvHeadsP hp{};
-            hp.rowdesc = env_rows; hp.n = n; hp.max_envs = env_cap; hp.h1 = env_h1; hp.W = wheads; hp.bias = bheads; hp.robot_obs = env_ro; hp.u_mix = u_mix; hp.u_act = u_act;
-            hp.NMIX = NMIX; hp.NDIM = NDIM; hp.log_scale_min = cfg.log_scale_min; hp.gripper_control = mcil ? 0 : 1; hp.discrete_gripper = mcil ? 0 : 1;
-            hp.seed = site_seed(53); hp.pred = env_pred;
-            if (NHEAD == 192) hipLaunchKernelGGL((env_heads_sample_kernel<12>), dim3(cdiv(n, 16)), dim3(ENV_WAVES * 64), 0, st, hp);
-            else hipLaunchKernelGGL((env_heads_sample_kernel<14>), dim3(cdiv(n, 16)), dim3(ENV_WAVES * 64), 0, st, hp);
-            }
+            else env_heads_sample(n, env_h1, false, u_mix, u_act);
         } else {
             // the fp32 parity engine composes the generic path: slot state -> rows, dec_fwd at B = n, S = 1, rows -> slots, the validation sampler
             EnvGatherP g{}; g.rowdesc = env_rows; g.n = n; g.max_envs = env_cap; g.NCAT = env_ncat(); g.PC = env_pc();
@@ -237,8 +231,7 @@
             dec_fwd(env_pidx, n, 1, env_ha, env_hb);
             hipLaunchKernelGGL((env_scatter_hidden_kernel<T>), dim3(n), dim3(256), 0, st, env_rows, env_cap, H0, H1, env_h0, env_h1);
             if (det) launch_det_head_act<T>(st, H1, nullptr, 0, det_w, det_b32, env_ro, nullptr, n, 1, env_pred, nullptr);
-            else hipLaunchKernelGGL(logistic_sample_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, heads, NHEAD, env_ro, (const float*)nullptr, u_mix, u_act, n, 1, NMIX, NDIM,
-                               cfg.log_scale_min, mcil ? 0 : 1, site_seed(53), env_pred, (float*)nullptr, mcil ? 0 : 1);
+            else launch_logistic_sample(st, heads, NHEAD, env_ro, nullptr, u_mix, u_act, n, 1, NMIX, NDIM, cfg.log_scale_min, mcil ? 0 : 1, mcil ? 0 : 1, site_seed(53), env_pred, nullptr);
         }
         HIP_CHECK(hipMemcpyAsync(actions_out, env_pred, sizeof(float) * 7 * n, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));

@@ -1,12 +1,12 @@
 // hulc_amd/csrc/k_entries.h — per-kernel test entries of the 16-bit encoder head and of the action loss (include/hulc_hip.h: hulc_k_spatial_softmax64,
 // hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss), of the latent-plan kernels (hulc_k_plan_*, hulc_k_st_softmax_bwd, hulc_k_normal_*), of
-// the LayerNorm family (hulc_k_layernorm_*; launched through plan_ln_launch.h, which the engine calls too) and of the fused transformer layer kernels
+// the LayerNorm family (hulc_k_layernorm_*) and of the fused transformer layer kernels
 // (hulc_k_tr_layer_fwd, hulc_k_tr_ffn_bwd, hulc_k_tr_attn_bwd; launched through tr_fused.h's helpers), and of the GEMM core with its runtime epilogue
 // (hulc_k_gemm_epi, hulc_k_gemm_multi, hulc_k_gemm_pick, hulc_k_gemm_wgrad_nsplit; launched through gemm.h's launchers and routing), and of the encoder's convolution family
 // (hulc_k_conv_tile, hulc_k_conv_pair, hulc_k_conv_wgrad, hulc_k_conv1_wgrad_u8 and their per-type forms; launched through the launchers of conv_tile.h, conv_reg.h and
 // conv_wgrad.h).  Included by engine.h inside each translation unit, so every entry exists once per
-// 16-bit type (hulc_bf16 / hulc_f16; iengine.h declares them).  Nothing here restates a kernel: each entry checks its arguments, then launches through the
-// helper the engine calls (enc_tail.h) or with the grid and block of the engine's launch site (engine_encoders.inc, engine_forward.inc).
+// 16-bit type (hulc_bf16 / hulc_f16; iengine.h declares them).  Nothing here restates a kernel or a launch: every entry checks its arguments, then launches
+// through the helper the engine calls (plan_ln_launch.h for the kernels.h families, enc_tail.h, det_head.h, tr_fused.h, gemm.h, the conv launchers).
 #pragma once
 #include "iengine.h"
 #include "kernels.h"
@@ -32,8 +32,8 @@ int k_spatial_softmax64(const void* f, int H, int W, int Nf, void* out, float* s
     if (Nf < 1 || H < 2 || W < 2 || (long long)H * W > (1 << 20)) { hulc_set_error("hulc_k_spatial_softmax64: Nf=%d H=%d W=%d (need Nf >= 1, H, W >= 2)", Nf, H, W); return 1; }
     if (!f || !stats || (dout ? !df : !out)) { hulc_set_error("hulc_k_spatial_softmax64: null argument"); return 1; }
     if (k_misaligned16(f) || k_misaligned16(stats) || k_misaligned16(dout) || k_misaligned16(df)) { hulc_set_error("hulc_k_spatial_softmax64: f, stats, dout, df must be 16-byte aligned"); return 1; }
-    if (!dout) hipLaunchKernelGGL(spatial_softmax_fwd64_kernel, dim3(Nf), dim3(256), 0, st, (const h16_t*)f, H, W, (h16_t*)out, stats);
-    else hipLaunchKernelGGL(spatial_softmax_bwd64_kernel, dim3(Nf), dim3(256), 0, st, (const h16_t*)f, (const float*)stats, dout, H, W, (h16_t*)df);
+    if (!dout) launch_spatial_softmax64_fwd(st, (const h16_t*)f, Nf, H, W, (h16_t*)out, stats);
+    else launch_spatial_softmax64_bwd(st, (const h16_t*)f, stats, dout, Nf, H, W, (h16_t*)df);
     return k_launched("hulc_k_spatial_softmax64");
 }
 
@@ -84,47 +84,28 @@ int k_enc_tail_bwd(int Nf, int ldemb, const hulc_enc_tail_bwd_job* a, const hulc
     return k_launched("hulc_k_enc_tail_bwd");
 }
 
-// T of dheads: 0 = float, 1 = this translation unit's 16-bit type
+// t16 of the typed entries: 0 = float, 1 = this translation unit's 16-bit type (the fp32 instances live in the bf16 unit).  HULC_K_T runs the launch, an
+// expression over the element type TT, for the selected type
+#ifdef HULC_HALF_F16
+#define HULC_K_T(who, ...) do { if (t16) { using TT = h16_t; __VA_ARGS__; } else { hulc_set_error(who ": the fp32 instances live in the bf16 translation unit"); return 1; } } while (0)
+#else
+#define HULC_K_T(who, ...) do { if (t16) { using TT = h16_t; __VA_ARGS__; } else { using TT = float; __VA_ARGS__; } } while (0)
+#endif
 int k_logistic_loss(int t16, int wide, const float* heads, int ldh, const float* actions, const float* robot_obs, int B, int S, int nmix, int ndim, int num_classes,
                     float log_scale_min, float gripper_alpha, int gripper_control, int discrete_gripper, float grad_scale, const float* lscale, float* row_loss, float* a_tcp_out,
                     void* dheads, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    constexpr int NMIX = 10;                       // Engine::NMIX, the serial kernel's compile-time mixture count
-    if (B < 1 || S < 1 || (long long)B * S > (1 << 24) || nmix != NMIX || ndim < 1 || ndim > (discrete_gripper ? 6 : 7) || num_classes < 2) {
-        hulc_set_error("hulc_k_logistic_loss: B=%d S=%d nmix=%d (must be %d) ndim=%d (1..%d) num_classes=%d", B, S, nmix, NMIX, ndim, discrete_gripper ? 6 : 7, num_classes); return 1;
+    if (B < 1 || S < 1 || (long long)B * S > (1 << 24) || nmix != LL_NMIX || ndim < 1 || ndim > (discrete_gripper ? 6 : 7) || num_classes < 2) {
+        hulc_set_error("hulc_k_logistic_loss: B=%d S=%d nmix=%d (must be %d) ndim=%d (1..%d) num_classes=%d", B, S, nmix, LL_NMIX, ndim, discrete_gripper ? 6 : 7, num_classes); return 1;
     }
     if (ldh < 3 * nmix * ndim + (discrete_gripper ? 2 : 0)) { hulc_set_error("hulc_k_logistic_loss: ldh=%d narrower than the heads", ldh); return 1; }
     if (!heads || !actions || !row_loss || !dheads || (gripper_control && !robot_obs)) { hulc_set_error("hulc_k_logistic_loss: null argument"); return 1; }
-    const int SB = S * B;
-    constexpr int ll_block = 64;                   // engine_forward.inc: one wave per workgroup
-#define HULC_K_LL(TT)                                                                                                                                              \
-    do {                                                                                                                                                           \
-        if (wide) hipLaunchKernelGGL((logistic_loss_wide_kernel<TT>), dim3(SB), dim3(128), 0, st, heads, ldh, actions, robot_obs, B, S, nmix, ndim, num_classes,     \
-                                     log_scale_min, gripper_alpha, gripper_control, grad_scale, row_loss, a_tcp_out, (TT*)dheads, discrete_gripper, lscale);         \
-        else hipLaunchKernelGGL((logistic_loss_kernel<TT, NMIX>), dim3(cdiv(SB * 8, ll_block)), dim3(ll_block), 0, st, heads, ldh, actions, robot_obs, B, S, nmix,  \
-                                ndim, num_classes, log_scale_min, gripper_alpha, gripper_control, grad_scale, row_loss, a_tcp_out, (TT*)dheads, discrete_gripper,    \
-                                lscale);                                                                                                                           \
-    } while (0)
-    if (t16) HULC_K_LL(h16_t);
-    else {
-#ifdef HULC_HALF_F16
-        hulc_set_error("hulc_k_logistic_loss: the fp32 instances live in the bf16 translation unit"); return 1;
-#else
-        HULC_K_LL(float);
-#endif
-    }
-#undef HULC_K_LL
+    HULC_K_T("hulc_k_logistic_loss", launch_logistic_loss<TT>(st, wide != 0, heads, ldh, actions, robot_obs, B, S, nmix, ndim, num_classes, log_scale_min, gripper_alpha, gripper_control,
+                                                               discrete_gripper, grad_scale, lscale, row_loss, a_tcp_out, (TT*)dheads));
     return k_launched("hulc_k_logistic_loss");
 }
 
 // ---------------------------------------------------------------------------------------------------- latent plan + LayerNorm
-// t16 of the entries below: 0 = float, 1 = this translation unit's 16-bit type (the fp32 instances live in the bf16 unit, as for hulc_k_logistic_loss)
-#ifdef HULC_HALF_F16
-#define HULC_K_T(who, LAUNCH)                                                                                            \
-    do { if (t16) { LAUNCH(h16_t); } else { hulc_set_error(who ": the fp32 instances live in the bf16 translation unit"); return 1; } } while (0)
-#else
-#define HULC_K_T(who, LAUNCH) do { if (t16) { LAUNCH(h16_t); } else { LAUNCH(float); } } while (0)
-#endif
 static inline bool k_misaligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) != 0; }
 // plan indices address LDS rows and weight rows unchecked inside the kernels: the entry reads them back (a synchronous copy) and refuses any outside [0, NCLS)
 static int k_idx_out_of_range(const char* who, const int* idx, long long count, int NCLS, hipStream_t st) {
@@ -150,9 +131,7 @@ int k_det_head_loss(int t16, const void* H1, const void* W, const float* bias, c
     if (!H1 || !W || !bias || !actions || !robot_obs || !row_loss || !pred || !dpre) { hulc_set_error("hulc_k_det_head_loss: null argument"); return 1; }
     if (k_misaligned(H1, 16) || k_misaligned(W, 16) || k_misaligned(dpre, 16) || k_misaligned(bias, 4) || k_misaligned(actions, 4) || k_misaligned(robot_obs, 4) ||
         k_misaligned(lscale, 4) || k_misaligned(row_loss, 4) || k_misaligned(pred, 4)) { hulc_set_error("hulc_k_det_head_loss: misaligned pointer (H1, W, dpre: 16 bytes; the rest: 4)"); return 1; }
-#define HULC_K_L(TT) launch_det_head_loss<TT>(st, (const TT*)H1, (const TT*)W, bias, actions, robot_obs, B, S, criterion, frame, grad_scale, lscale, row_loss, 1, pred, dpre)
-    HULC_K_T("hulc_k_det_head_loss", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_det_head_loss", launch_det_head_loss<TT>(st, (const TT*)H1, (const TT*)W, bias, actions, robot_obs, B, S, criterion, frame, grad_scale, lscale, row_loss, 1, pred, dpre));
     return k_launched("hulc_k_det_head_loss");
 }
 int k_det_head_bwd(int t16, const float* dpre, const void* W, const void* H1, int B, int S, void* dH1, void* dZ1, float* dW, float* db, void* stream) {
@@ -186,9 +165,7 @@ int k_det_head_act(int t16, const void* h1, const void* W, const float* bias, co
     if (!h1 || !W || !bias || !robot_obs || !out) { hulc_set_error("hulc_k_det_head_act: null argument"); return 1; }
     if (k_misaligned(h1, 16) || k_misaligned(W, 16) || k_misaligned(bias, 4) || k_misaligned(robot_obs, 4) || k_misaligned(out, 4)) {
         hulc_set_error("hulc_k_det_head_act: misaligned pointer (h1, W: 16 bytes; the rest: 4)"); return 1; }
-#define HULC_K_L(TT) launch_det_head_act<TT>(st, (const TT*)h1, nullptr, 0, (const TT*)W, bias, robot_obs, nullptr, n, 1, out, nullptr)
-    HULC_K_T("hulc_k_det_head_act", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_det_head_act", launch_det_head_act<TT>(st, (const TT*)h1, nullptr, 0, (const TT*)W, bias, robot_obs, nullptr, n, 1, out, nullptr));
     return k_launched("hulc_k_det_head_act");
 }
 
@@ -200,7 +177,7 @@ int k_plan_kl_sample(const float* pr_logits, const float* pp_logits, int B, int 
     if (k_misaligned(pr_logits, 4) || k_misaligned(pp_logits, 4) || k_misaligned(idx_in, 4) || k_misaligned(idx_out, 4) || k_misaligned(probs, 4) || k_misaligned(kl_cat, 4) ||
         k_misaligned(dpp, 4) || k_misaligned(dpr, 4) || k_misaligned(lscale, 4)) { hulc_set_error("hulc_k_plan_kl_sample: every pointer must be 4-byte aligned"); return 1; }
     if (idx_in && k_idx_out_of_range("hulc_k_plan_kl_sample", idx_in, (long long)B * NCAT, NCLS, st)) return 1;
-    hipLaunchKernelGGL(plan_kl_sample_kernel, dim3(B * NCAT), dim3(64), 0, st, pr_logits, pp_logits, B, NCAT, NCLS, idx_in, idx_out, probs, kl_cat, dpp, dpr, w_pp, w_pr, seed, lscale);
+    launch_plan_kl_sample(st, pr_logits, pp_logits, B, NCAT, NCLS, idx_in, idx_out, probs, kl_cat, dpp, dpr, w_pp, w_pr, seed, lscale);
     return k_launched("hulc_k_plan_kl_sample");
 }
 
@@ -213,14 +190,12 @@ int k_st_softmax_bwd(int t16, const float* probs, const float* dplan, const floa
     if (k_misaligned(probs, 4) || k_misaligned(dplan, 4) || k_misaligned(dpr_kl, 4) || k_misaligned(dpp_kl, 4) || k_misaligned(out, 4) || k_misaligned(out_t, ta) || k_misaligned(dpp_t, ta)) {
         hulc_set_error("hulc_k_st_softmax_bwd: a pointer is not aligned to its element type"); return 1;
     }
-#define HULC_K_L(TT) hipLaunchKernelGGL((st_softmax_bwd_kernel<TT>), dim3(rows), dim3(64), 0, st, probs, dplan, dpr_kl, NCLS, out, (TT*)out_t, dpp_kl, (TT*)dpp_t)
-    HULC_K_T("hulc_k_st_softmax_bwd", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_st_softmax_bwd", launch_st_softmax_bwd<TT>(st, probs, dplan, dpr_kl, dpp_kl, rows, NCLS, out, (TT*)out_t, (TT*)dpp_t));
     return k_launched("hulc_k_st_softmax_bwd");
 }
 
-// embg == null: no trailing blocks (the engine's grid always carries them; without the copy they have nothing to do).  The rows grow0 .. grow0 + G - 1 of w_t
-// and its plan rows 0 .. NCAT * NCLS - 1 are the caller's to provide.
+// embg == null: S = W = 0, no trailing blocks (the engine's grid always carries them; without the copy they have nothing to do).  The rows grow0 .. grow0 + G - 1 of
+// w_t and its plan rows 0 .. NCAT * NCLS - 1 are the caller's to provide.
 int k_plan_gather(int t16, const void* w_t, const int* idx, int B, int NCAT, int NCLS, int H, const float* b1, const float* b2, float* out, const void* emb, void* embg, int S,
                   int W, const void* goal, int G, int grow0, void* cb, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -234,13 +209,8 @@ int k_plan_gather(int t16, const void* w_t, const int* idx, int B, int NCAT, int
     if (k_misaligned(w_t, ta) || k_misaligned(idx, 4) || k_misaligned(b1, 4) || k_misaligned(b2, 4) || k_misaligned(out, 4) || k_misaligned(emb, ta) || k_misaligned(embg, ta) ||
         k_misaligned(goal, ta) || k_misaligned(cb, ta)) { hulc_set_error("hulc_k_plan_gather: a pointer is not aligned to its element type"); return 1; }
     if (NCAT > 0 && k_idx_out_of_range("hulc_k_plan_gather", idx, (long long)B * NCAT, NCLS, st)) return 1;
-    const int SBW = embg ? S * B * W : 0;
     if (!embg) { S = 0; W = 0; }
-#define HULC_K_L(TT)                                                                                                                                             \
-    hipLaunchKernelGGL((plan_gather_t_kernel<TT>), dim3(cdiv((long long)B * H, 256) + cdiv(SBW, 256)), dim3(256), 0, st, (const TT*)w_t, idx, B, NCAT, NCLS, H, b1, b2, out, \
-                       (const TT*)emb, (TT*)embg, S, W, (const TT*)goal, G, grow0, (TT*)cb)
-    HULC_K_T("hulc_k_plan_gather", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_plan_gather", launch_plan_gather<TT>(st, (const TT*)w_t, idx, B, NCAT, NCLS, H, b1, b2, out, (const TT*)emb, (TT*)embg, S, W, (const TT*)goal, G, grow0, (TT*)cb));
     return k_launched("hulc_k_plan_gather");
 }
 
@@ -257,9 +227,7 @@ int k_plan_scatter_grad(int t16, int form, const void* dC, const int* idx, int B
     if (k_misaligned(dC, t16 ? 2 : 4) || k_misaligned(idx, 4) || k_misaligned(dw, 4)) { hulc_set_error("hulc_k_plan_scatter_grad: a pointer is not aligned to its element type"); return 1; }
     if (form == 1 && !(t16 ? plan_scatter_w4<h16_t>(NCLS) : plan_scatter_w4<float>(NCLS))) { hulc_set_error("hulc_k_plan_scatter_grad: form 1 (w4) serves the 16-bit types only"); return 1; }
     if (k_idx_out_of_range("hulc_k_plan_scatter_grad", idx, (long long)B * NCAT, NCLS, st)) return 1;
-#define HULC_K_L(TT) launch_plan_scatter_grad<TT>(st, form == 1, (const TT*)dC, idx, B, NCAT, NCLS, H, KIN, dw, store)
-    HULC_K_T("hulc_k_plan_scatter_grad", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_plan_scatter_grad", launch_plan_scatter_grad<TT>(st, form == 1, (const TT*)dC, idx, B, NCAT, NCLS, H, KIN, dw, store));
     return k_launched("hulc_k_plan_scatter_grad");
 }
 
@@ -270,11 +238,7 @@ int k_normal_kl_sample(int t16, const float* pr_state, const float* pp_state, in
     if (!pr_state || !eps_out || !plan_f || !plan_t || (pp_state && (!kl_elem || !dpp || !dpr))) { hulc_set_error("hulc_k_normal_kl_sample: null argument"); return 1; }
     if (k_misaligned(pr_state, 4) || k_misaligned(pp_state, 4) || k_misaligned(eps_in, 4) || k_misaligned(eps_out, 4) || k_misaligned(plan_f, 4) || k_misaligned(plan_t, t16 ? 2 : 4) ||
         k_misaligned(kl_elem, 4) || k_misaligned(dpp, 4) || k_misaligned(dpr, 4) || k_misaligned(lscale, 4)) { hulc_set_error("hulc_k_normal_kl_sample: a pointer is not aligned to its element type"); return 1; }
-#define HULC_K_L(TT)                                                                                                                                               \
-    hipLaunchKernelGGL((normal_kl_sample_kernel<TT>), dim3(cdiv((long long)B * n, 256)), dim3(256), 0, st, pr_state, pp_state, B, n, eps_in, eps_out, plan_f, (TT*)plan_t, kl_elem, \
-                       dpp, dpr, w_pp, w_pr, seed, lscale)
-    HULC_K_T("hulc_k_normal_kl_sample", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_normal_kl_sample", launch_normal_kl_sample<TT>(st, pr_state, pp_state, B, n, eps_in, eps_out, plan_f, (TT*)plan_t, kl_elem, dpp, dpr, w_pp, w_pr, seed, lscale));
     return k_launched("hulc_k_normal_kl_sample");
 }
 
@@ -285,9 +249,7 @@ int k_normal_rsample_bwd(int t16, const float* dplan, const float* eps, const fl
     if (k_misaligned(dplan, 4) || k_misaligned(eps, 4) || k_misaligned(pr_state, 4) || k_misaligned(dpr_kl, 4) || k_misaligned(out, t16 ? 2 : 4)) {
         hulc_set_error("hulc_k_normal_rsample_bwd: a pointer is not aligned to its element type"); return 1;
     }
-#define HULC_K_L(TT) hipLaunchKernelGGL((normal_rsample_bwd_kernel<TT>), dim3(cdiv((long long)B * n, 256)), dim3(256), 0, st, dplan, eps, pr_state, dpr_kl, B, n, (TT*)out)
-    HULC_K_T("hulc_k_normal_rsample_bwd", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_normal_rsample_bwd", launch_normal_rsample_bwd<TT>(st, dplan, eps, pr_state, dpr_kl, B, n, (TT*)out));
     return k_launched("hulc_k_normal_rsample_bwd");
 }
 
@@ -300,9 +262,7 @@ int k_layernorm_fwd(int t16, const float* x, long long ldx, int rows, int n, con
     if (k_misaligned(x, 4) || k_misaligned(g, 4) || k_misaligned(b, 4) || k_misaligned(out, t16 ? 2 : 4) || k_misaligned(out_f32, 4) || k_misaligned(stats, 4)) {
         hulc_set_error("hulc_k_layernorm_fwd: a pointer is not aligned to its element type"); return 1;
     }
-#define HULC_K_L(TT) launch_ln_fwd<TT>((hipStream_t)stream, x, ldx, rows, n, g, b, (TT*)out, ldo, out_f32, ldf, stats)
-    HULC_K_T("hulc_k_layernorm_fwd", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_layernorm_fwd", launch_ln_fwd<TT>((hipStream_t)stream, x, ldx, rows, n, g, b, (TT*)out, ldo, out_f32, ldf, stats));
     return k_launched("hulc_k_layernorm_fwd");
 }
 
@@ -325,11 +285,8 @@ int k_layernorm_bwd(int t16, const float* dy, long long lddy, const float* x, lo
     if (!t16 && (drop_p > 0.f || seed != 0) && dx_t && dx_f32 && (ldd != n || ldt != n)) { hulc_set_error("hulc_k_layernorm_bwd: fp32 with a dropout mask and both outputs needs ldd == ldt == n"); return 1; }
     if (k_misaligned(dy, 4) || k_misaligned(x, 4) || k_misaligned(stats, 4) || k_misaligned(g, 4) || k_misaligned(dx_f32, 4) || k_misaligned(dx_t, t16 ? 2 : 4) || k_misaligned(dg, 4) ||
         k_misaligned(db, 4) || k_misaligned(scratch, 4)) { hulc_set_error("hulc_k_layernorm_bwd: a pointer is not aligned to its element type"); return 1; }
-#define HULC_K_L(TT)                                                                                                                                                  \
-    launch_ln_bwd<TT>((hipStream_t)stream, scratch, dy, lddy, x, ldx, stats, g, rows, n, dx_f32, ldd, accumulate, (TT*)dx_t, ldt, dg, db, drop_p, seed, bcast_rows, bcast_div, \
-                      dy_parts, dy_part_stride)
-    HULC_K_T("hulc_k_layernorm_bwd", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_layernorm_bwd", launch_ln_bwd<TT>((hipStream_t)stream, scratch, dy, lddy, x, ldx, stats, g, rows, n, dx_f32, ldd, accumulate, (TT*)dx_t, ldt, dg, db, drop_p, seed,
+              bcast_rows, bcast_div, dy_parts, dy_part_stride));
     return k_launched("hulc_k_layernorm_bwd");
 }
 
@@ -340,9 +297,7 @@ int k_layernorm_mean(int t16, const float* x, int B, int S, int n, const float* 
     if (k_misaligned(x, 4) || k_misaligned(g, 4) || k_misaligned(b, 4) || k_misaligned(stats, 4) || k_misaligned(out, t16 ? 2 : 4) || k_misaligned(yout, 4)) {
         hulc_set_error("hulc_k_layernorm_mean: a pointer is not aligned to its element type"); return 1;
     }
-#define HULC_K_L(TT) hipLaunchKernelGGL((layernorm_mean_kernel<TT>), dim3(B), dim3(1024), 0, st, x, S, n, g, b, stats, (TT*)out, yout)      /* engine_forward.inc */
-    HULC_K_T("hulc_k_layernorm_mean", HULC_K_L);
-#undef HULC_K_L
+    HULC_K_T("hulc_k_layernorm_mean", launch_ln_mean<TT>(st, x, B, S, n, g, b, stats, (TT*)out, yout));
     return k_launched("hulc_k_layernorm_mean");
 }
 #undef HULC_K_T

@@ -253,6 +253,14 @@ __global__ void __launch_bounds__(ENV_WAVES * 64) env_heads_sample_kernel(EnvHea
 #pragma unroll
     for (int i = 0; i < 7; ++i) p.pred[(long long)(r0 + tid) * 7 + i] = w[i];
 }
+// one workgroup per 16-row tile; NT = NHEAD / 16 accumulator tiles (192 packed head columns: hulc / gcbc, 224: mcil); byrow: the feed-forward body's row buffer
+inline void launch_env_heads_sample(hipStream_t st, const EnvHeadsP& p, int NHEAD, bool byrow) {
+    const dim3 grid((p.n + 15) / 16), block(ENV_WAVES * 64);
+    if (NHEAD == 192 && byrow) hipLaunchKernelGGL((env_heads_sample_kernel<12, true>), grid, block, 0, st, p);
+    else if (NHEAD == 192) hipLaunchKernelGGL((env_heads_sample_kernel<12>), grid, block, 0, st, p);
+    else if (byrow) hipLaunchKernelGGL((env_heads_sample_kernel<14, true>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((env_heads_sample_kernel<14>), grid, block, 0, st, p);
+}
 
 // ---- slot state: store at plan time / install, gather for reads and for the fp32 engine's composed step ----------------------------------------------
 struct EnvStoreP {

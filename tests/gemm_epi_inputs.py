@@ -70,18 +70,18 @@ EPI = {
     "out2_window": dict(out2=(0.3, 0.7), out2_relu=1),
     "out2_mask": dict(out2=(0.5, 1.0), out2_mask=1),
     # ---- pairs
-    "res_late_drop": dict(out_f32=1, bias=1, res="f32", res_late=1, drop_p=0.1),          # engine_forward.inc:161 / :165, x + dropout(linear(x))
-    "relu_drop": dict(bias=1, relu=1, drop_p=0.1),                                        # engine_forward.inc:164
+    "res_late_drop": dict(out_f32=1, bias=1, res="f32", res_late=1, drop_p=0.1),          # engine_forward.inc:157 / :161, x + dropout(linear(x))
+    "relu_drop": dict(bias=1, relu=1, drop_p=0.1),                                        # engine_forward.inc:159
     "alpha_bias": dict(out_f32=1, alpha=0.75, bias=1),
     "mask_alpha": dict(mask=1, alpha=1.0 / (1.0 - 0.1)),                                  # engine_backward.inc:394
     "rnn_fwd": dict(res="t", relu=1),                                                     # engine_recurrent.inc:107 / :145
     "rnn_fwd_tanh": dict(res="t", relu=2),                                                # engine_recurrent.inc:145 with act = 2, :220
     "rnn_bwd": dict(mask=1, res="t"),                                                     # engine_recurrent.inc:126 / :177
     "rnn_bwd_tanh": dict(mask=1, mask_tanh=1, res="t"),
-    "zx0": dict(res="t", res_rowmod=6, out2="first", out2_relu=1),                        # engine_forward.inc:194
-    "zx1": dict(bias=1, bias2=1, out2="first", out2_relu=1),                              # engine_forward.inc:198
+    "zx0": dict(res="t", res_rowmod=6, out2="first", out2_relu=1),                        # engine_forward.inc:199
+    "zx1": dict(bias=1, bias2=1, out2="first", out2_relu=1),                              # engine_forward.inc:203
     "dh_last": dict(out2="last", out2_mask=1),                                            # engine_backward.inc:210 / :276
-    "cplan": dict(out_f32=1, bias=1, bias2=1),                                            # engine_forward.inc:186
+    "cplan": dict(out_f32=1, bias=1, bias2=1),                                            # engine_forward.inc:182
     "dnext": dict(out_f32=1, res="f32"),                                                  # engine_backward.inc:396 / :432
 }
 for _k, _v in EPI.items():
@@ -110,17 +110,17 @@ def dims(kind):
 
 
 SITES = [
-    ("tr_in", "engine_forward.inc:153", "bias12_16", lambda B, S, d: (B * S, 3 * d["EMB"], d["EMB"])),
-    ("tr_out", "engine_forward.inc:161", "res_late_drop", lambda B, S, d: (B * S, d["EMB"], d["EMB"])),
-    ("tr_l1", "engine_forward.inc:164", "relu_drop", lambda B, S, d: (B * S, d["FF"], d["EMB"])),
-    ("tr_l2", "engine_forward.inc:165", "res_late_drop", lambda B, S, d: (B * S, d["EMB"], d["FF"])),
-    ("pr_fc", "engine_forward.inc:171", "out2_copy", lambda B, S, d: (B, d["FCH"], d["EMB"])),
-    ("pr_fs", "engine_forward.inc:173", "bias", lambda B, S, d: (B, d["PLAN"], d["FCH"])),
-    ("cplan", "engine_forward.inc:186", "cplan", lambda B, S, d: (B, d["HID"], max(d["dec_plan"], 32))),
-    ("cb", "engine_forward.inc:191", "res16_vs_32", lambda B, S, d: (B, d["HID"], d["GOAL"])),
-    ("zx0", "engine_forward.inc:194", "zx0", lambda B, S, d: (B * S, d["HID"], d["DE"])),
-    ("zx1", "engine_forward.inc:198", "zx1", lambda B, S, d: (B * S, d["HID"], d["HID"])),
-    ("heads", "engine_forward.inc:202", "bias", lambda B, S, d: (B * S, d["NHEAD"], d["HID"])),
+    ("tr_in", "engine_forward.inc:154", "bias12_16", lambda B, S, d: (B * S, 3 * d["EMB"], d["EMB"])),
+    ("tr_out", "engine_forward.inc:157", "res_late_drop", lambda B, S, d: (B * S, d["EMB"], d["EMB"])),
+    ("tr_l1", "engine_forward.inc:159", "relu_drop", lambda B, S, d: (B * S, d["FF"], d["EMB"])),
+    ("tr_l2", "engine_forward.inc:161", "res_late_drop", lambda B, S, d: (B * S, d["EMB"], d["FF"])),
+    ("pr_fc", "engine_forward.inc:167", "out2_copy", lambda B, S, d: (B, d["FCH"], d["EMB"])),
+    ("pr_fs", "engine_forward.inc:168", "bias", lambda B, S, d: (B, d["PLAN"], d["FCH"])),
+    ("cplan", "engine_forward.inc:182", "cplan", lambda B, S, d: (B, d["HID"], max(d["dec_plan"], 32))),
+    ("cb", "engine_forward.inc:186", "res16_vs_32", lambda B, S, d: (B, d["HID"], d["GOAL"])),
+    ("zx0", "engine_forward.inc:199", "zx0", lambda B, S, d: (B * S, d["HID"], d["DE"])),
+    ("zx1", "engine_forward.inc:203", "zx1", lambda B, S, d: (B * S, d["HID"], d["HID"])),
+    ("heads", "engine_forward.inc:207", "bias", lambda B, S, d: (B * S, d["NHEAD"], d["HID"])),
     ("mlp_fwd", "engine_forward.inc:8", "relu", lambda B, S, d: (B, d["HID"], d["HID"])),
     ("mlp_bwd", "engine_forward.inc:40", "mask", lambda B, S, d: (B, d["HID"], d["HID"])),
     ("rnn_step", "engine_recurrent.inc:107", "rnn_fwd", lambda B, S, d: (B, d["HID"], d["HID"])),

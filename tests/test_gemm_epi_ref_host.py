@@ -31,7 +31,7 @@ def operands(M, N, K, tag="h"):
 
 
 def test_residual_plus_dropout_of_linear_under_an_explicit_mask():
-    """engine_forward.inc:161 / :165: y = x + dropout(ao Wo^T + bo), the residual late, the mask from the hash of the element offset"""
+    """engine_forward.inc:157 / :161: y = x + dropout(ao Wo^T + bo), the residual late, the mask from the hash of the element offset"""
     M, N, K, p = 21, 12, 40, 0.3
     A, B = operands(M, N, K)
     bias, x = GI.vector("h1", N), GI.matrix("hx", M, N, "fp32")
@@ -67,7 +67,7 @@ def test_relu_mask_treats_both_zeros_as_not_positive():
 
 
 def test_broadcast_residual_over_time_and_the_second_store():
-    """engine_forward.inc:194: Zx0[t * B + b] = embg W^T + Cb[b], H[0] = relu(Zx0[0]) stored a second time; engine_backward.inc:210: dZ[S-1] = dH[S-1] * (H[S-1] > 0)"""
+    """engine_forward.inc:199: Zx0[t * B + b] = embg W^T + Cb[b], H[0] = relu(Zx0[0]) stored a second time; engine_backward.inc:210: dZ[S-1] = dH[S-1] * (H[S-1] > 0)"""
     Bw, S, N, K = 5, 4, 8, 16
     M = Bw * S
     A, B = operands(M, N, K, "z")
