@@ -304,6 +304,20 @@ int hulc_grad_norm_get(hulc_ctx* ctx, float* total, float* coef, float* per_tens
     if (!ctx) { hulc_set_error("hulc_grad_norm_get: null context"); return 1; }
     return ctx->e->grad_norm_get(total, coef, per_tensor_host, cap);
 }
+int hulc_trainable_set(hulc_ctx* ctx, int32_t n_tensors, const uint8_t* trainable) {
+    if (!trainable) { hulc_set_error("hulc_trainable_set: null mask"); return 1; }      // the arguments first: each refusal is reachable without a device
+    if (!ctx) { hulc_set_error("hulc_trainable_set: null context"); return 1; }
+    return ctx->e->trainable_set(n_tensors, trainable);
+}
+int hulc_trainable_get(hulc_ctx* ctx, int64_t cap, uint8_t* trainable_out, int64_t* frozen_steps_out) {
+    if (!ctx) { hulc_set_error("hulc_trainable_get: null context"); return 1; }
+    return ctx->e->trainable_get(cap, trainable_out, frozen_steps_out);
+}
+int hulc_trainable_steps_set(hulc_ctx* ctx, int32_t n_tensors, const int64_t* frozen_steps, int64_t steps_taken) {
+    if (!frozen_steps) { hulc_set_error("hulc_trainable_steps_set: null counts"); return 1; }
+    if (!ctx) { hulc_set_error("hulc_trainable_steps_set: null context"); return 1; }
+    return ctx->e->trainable_steps_set(n_tensors, frozen_steps, steps_taken);
+}
 int hulc_set_kl_beta(hulc_ctx* ctx, float b) { ctx->e->set_kl_beta(b); return 0; }
 int hulc_set_dropout(hulc_ctx* ctx, float p) {
     if (!(p >= 0.f && p < 1.f)) { hulc_set_error("hulc_set_dropout: p must be in [0,1)"); return 1; }      // NaN is refused too

@@ -10,6 +10,7 @@
 
 #include "iengine.h"
 #include "repro_sites.h"
+#include "trainable_plan.h"
 #include "gemm.h"
 #include "kernels.h"
 #include "plan_ln_launch.h"
@@ -128,7 +129,7 @@ struct Engine : IEngine {
     void adam_tables_build() {
         tr_table_free(tr_adam); tr_table_free(tr_rest); rest_by_pack = false; frag_by_adam = false;
         if (adam_chunk_start) { hipFree(adam_chunk_start); adam_chunk_start = nullptr; } if (adam_chunk_n) { hipFree(adam_chunk_n); adam_chunk_n = nullptr; }
-        adam_chunks = 0;
+        adam_chunks = 0; tr_fused_host.clear(); tr_rest_host.clear();
         if (std::is_same<T, float>::value || !wshadow || (numel & 3)) return;
         std::vector<TrDesc> fused, rest;
         std::vector<std::pair<long long, long long>> rng;
@@ -147,6 +148,7 @@ struct Engine : IEngine {
         for (auto& r : rng) { cover(pos, r.first); pos = r.second; }
         cover(pos, numel);
         if (!tr_table_build(tr_adam, fused) || !tr_table_build(tr_rest, rest)) { tr_table_free(tr_adam); tr_table_free(tr_rest); return; }
+        tr_fused_host = fused; tr_rest_host = rest;      // hulc_trainable_set filters them (engine_trainable.inc)
         // every transpose the optimizer does not write comes from a matrix weight_pack_kernel packs (the permuted fc7, the decoder heads): it writes their transposed copies as well
         { int lf = 0; for (const TrDesc& d : fused) if (d.fr && d.frT) ++lf; frag_by_adam = fragbatch.n > 0 && 2 * lf == fragbatch.n && lf == frag_linked; }
         rest_by_pack = true;
@@ -157,7 +159,7 @@ struct Engine : IEngine {
         }
         adam_chunks = (int)cs.size();
         if (adam_chunks) {
-            if (hipMalloc((void**)&adam_chunk_start, sizeof(long long) * cs.size()) != hipSuccess || hipMalloc((void**)&adam_chunk_n, sizeof(int) * cn.size()) != hipSuccess) { tr_table_free(tr_adam); tr_table_free(tr_rest); adam_chunks = 0; return; }
+            if (hipMalloc((void**)&adam_chunk_start, sizeof(long long) * cs.size()) != hipSuccess || hipMalloc((void**)&adam_chunk_n, sizeof(int) * cn.size()) != hipSuccess) { tr_table_free(tr_adam); tr_table_free(tr_rest); adam_chunks = 0; tr_fused_host.clear(); tr_rest_host.clear(); return; }
             hipMemcpy(adam_chunk_start, cs.data(), sizeof(long long) * cs.size(), hipMemcpyHostToDevice);
             hipMemcpy(adam_chunk_n, cn.data(), sizeof(int) * cn.size(), hipMemcpyHostToDevice);
         }
@@ -234,7 +236,7 @@ struct Engine : IEngine {
         KIN = dec_plan + DE + GOAL;
         maxB = cfg.max_batch; maxS = cfg.max_seq; maxN = maxB * maxS;
     }
-    ~Engine() override { for (void* p : allocs) hipFree(p); if (rp_err_host) hipHostFree((void*)rp_err_host); if (blk2desc_dev) hipFree(blk2desc_dev); if (trdesc_dev) hipFree(trdesc_dev); tr_table_free(tr_adam); tr_table_free(tr_rest); if (adam_chunk_start) hipFree(adam_chunk_start); if (adam_chunk_n) hipFree(adam_chunk_n); gn_free(); if (clip_state) hipFree(clip_state); if (env_rows_host) hipHostFree(env_rows_host); }
+    ~Engine() override { for (void* p : allocs) hipFree(p); if (rp_err_host) hipHostFree((void*)rp_err_host); if (blk2desc_dev) hipFree(blk2desc_dev); if (trdesc_dev) hipFree(trdesc_dev); tr_table_free(tr_adam); tr_table_free(tr_rest); if (adam_chunk_start) hipFree(adam_chunk_start); if (adam_chunk_n) hipFree(adam_chunk_n); gn_free(); tm_free(); if (clip_state) hipFree(clip_state); if (env_rows_host) hipHostFree(env_rows_host); }
     int64_t workspace_bytes() const override { return ws_bytes; }
     void set_kl_beta(float b) override { cfg.kl_beta = b; }
     void set_dropout(float p) override { cfg.dropout_p = p; }
@@ -517,6 +519,8 @@ struct Engine : IEngine {
         for (int i = 0; i < n; ++i) tab[names[i]] = Ref{offs[i], numels[i]};
         gn_tens.clear(); gn_built = false; gn_have = false;      // the gradient-norm tables follow the tensor table (rebuilt at the end of this bind if clipping by norm / tracking is configured)
         for (int i = 0; i < n; ++i) gn_tens.push_back(Ref{offs[i], numels[i]});
+        tm_reset(); tm_names.clear();      // a new tensor table: every tensor trainable until hulc_trainable_set says otherwise
+        for (int i = 0; i < n; ++i) tm_names.push_back(names[i]);
         tab_order.assign(tab.begin(), tab.end());
         std::sort(tab_order.begin(), tab_order.end(), [](const std::pair<std::string, Ref>& a, const std::pair<std::string, Ref>& b) { return a.second.off < b.second.off; });
         // data parallelism: the "this step's gradients are garbage" vote rides in an alignment-padding element of the LAST bucket (see skip_vote_put)
@@ -837,6 +841,9 @@ struct Engine : IEngine {
     // NHWC-permuted gripper fc and the packed decoder heads
     int prepare_weights(bool shadow_fresh = false) override {
         if (!bound) { hulc_set_error("hulc_prepare_weights before hulc_bind_params"); return 1; }
+        // under a trainable mask the refresh behind an optimizer step leaves every copy of a frozen tensor alone (an explicit hulc_prepare_weights refreshes all)
+        const bool masked = shadow_fresh && tm_active;
+        if (masked && tm_ntrain == 0) return 0;
         c1_bias_fold_valid = false;
         if constexpr (!std::is_same<T, float>::value) {
             if (!shadow_fresh) hipLaunchKernelGGL((cast_kernel<float, T>), dim3(2048), dim3(256), 0, st, P, wshadow, (long long)numel);
@@ -846,22 +853,29 @@ struct Engine : IEngine {
             int k = 0, blk = 0;
             for (EncW* e : {&encS, &encG})
                 for (ConvW* c : {&e->c1, &e->c2, &e->c3}) {
-                    d.w[k] = c->W32; d.wf[k] = c->Wf; d.wd[k] = c->nhwc ? c->Wd : nullptr; d.O[k] = c->O; d.I[k] = c->I; d.K[k] = c->KH; d.S[k] = c->S; d.nhwc[k] = c->nhwc;
+                    d.w[k] = c->W32; d.wf[k] = c->Wf; d.wd[k] = c->nhwc ? c->Wd : nullptr; d.O[k] = (masked && !tm_trainable_w(c->W32)) ? 0 : c->O; d.I[k] = c->I; d.K[k] = c->KH; d.S[k] = c->S; d.nhwc[k] = c->nhwc;
                     d.blk0[k] = blk; blk += cdiv(c->O * c->I * c->KH * c->KW, 256); ++k;
                 }
             d.blk0[6] = blk;
             const int blkA = blk, blkB = blkA + cdiv(128 * 3136, 256);
             // packed heads [192][2048]: prob | mean | log_scale | gripper | zero pad
-            const HeadPack hp = head_pack();
+            HeadPack hp = head_pack();
             const int rows = head_rows[0] + head_rows[1] + head_rows[2] + head_rows[3];
+            const int r7 = (masked && !tm_trainable_w(encG.fc7.W32)) ? 0 : 128;      // zero rows: the blocks of a frozen job return without a store
+            if (masked && !heads_trainable()) for (int i = 0; i < 4; ++i) hp.rows[i] = 0;
             // 16-bit engines: the transposed copies of the two packed matrices are written by this launch too (rest_by_pack: then no transpose launch is left behind Adam)
             T* const f7t = rest_by_pack ? encG.fc7.Wt : (T*)nullptr;
             T* const wht = rest_by_pack ? wheadsT : (T*)nullptr;
-            hipLaunchKernelGGL((weight_pack_kernel<T>), dim3(blkB + cdiv((long long)rows * HID, 256)), dim3(256), 0, st, d, blkA, encG.fc7.W32, encG.fc7.W, 128, 64, 49, blkB, hp,
+            hipLaunchKernelGGL((weight_pack_kernel<T>), dim3(blkB + cdiv((long long)rows * HID, 256)), dim3(256), 0, st, d, blkA, encG.fc7.W32, encG.fc7.W, r7, 64, 49, blkB, hp,
                                wheads, bheads, HID, f7t, wht, NHEAD);
         }
         // ... then every transposed copy — the Linear weights, the permuted fc7 and the packed heads — in ONE batched launch
-        if (std::is_same<T, float>::value) hipLaunchKernelGGL((batched_transpose_kernel<float, T>), dim3(tr_blocks), dim3(256), 0, st, trdesc_dev, (int)trdesc.size());
+        if (masked) {
+            if (std::is_same<T, float>::value) { if (tm_tr_all.blocks) hipLaunchKernelGGL((batched_transpose_kernel<float, T>), dim3(tm_tr_all.blocks), dim3(256), 0, st, (const TrDesc*)tm_tr_all.desc, tm_tr_all.n); }
+            else if (tr_fresh) { if (tm_tr_rest.blocks && !rest_by_pack) hipLaunchKernelGGL(batched_transpose64_kernel, dim3(tm_tr_rest.blocks), dim3(256), 0, st, (const TrDesc*)tm_tr_rest.desc, tm_tr_rest.n, (const unsigned short*)tm_tr_rest.b2d); }
+            else if (tm_tr_all.blocks) hipLaunchKernelGGL(batched_transpose64_kernel, dim3(tm_tr_all.blocks), dim3(256), 0, st, (const TrDesc*)tm_tr_all.desc, tm_tr_all.n, (const unsigned short*)tm_tr_all.b2d);
+        }
+        else if (std::is_same<T, float>::value) hipLaunchKernelGGL((batched_transpose_kernel<float, T>), dim3(tr_blocks), dim3(256), 0, st, trdesc_dev, (int)trdesc.size());
         else if (tr_fresh && tr_adam.n) {      // the optimizer wrote the shadow-sourced transposed copies (adam_tiled_kernel): only the packed sources are left
             if (tr_rest.blocks && !rest_by_pack) hipLaunchKernelGGL(batched_transpose64_kernel, dim3(tr_rest.blocks), dim3(256), 0, st, tr_rest.desc, tr_rest.n, (const unsigned short*)tr_rest.b2d);
         }
@@ -870,7 +884,8 @@ struct Engine : IEngine {
         tr_fresh = false;
         if constexpr (std::is_same<T, h16_t>::value) {
             // (the optimizer's tile pass wrote them when every frag job is linked to a tiled descriptor: frag_by_adam)
-            if (fragbatch.n && !(was_fresh && frag_by_adam)) hipLaunchKernelGGL(frag_pack_kernel, dim3(frag_blocks), dim3(256), 0, st, fragbatch);
+            if (masked) { if (tm_frag.n && !(was_fresh && frag_by_adam)) hipLaunchKernelGGL(frag_pack_kernel, dim3(tm_frag_blocks), dim3(256), 0, st, tm_frag); }
+            else if (fragbatch.n && !(was_fresh && frag_by_adam)) hipLaunchKernelGGL(frag_pack_kernel, dim3(frag_blocks), dim3(256), 0, st, fragbatch);
         }
         if (hipGetLastError() != hipSuccess) { hulc_set_error("kernel launch failed in prepare_weights"); return 1; }
         return 0;
@@ -987,6 +1002,7 @@ struct Engine : IEngine {
 #include "engine_inference.inc"      // validation forward (a20), the CLIP ground-truth metric, the stateful rollout
 #include "engine_rollout_envs.inc"      // the batched multi-environment rollout: max_envs policy slots per context (rollout_step.h)
 #include "engine_recurrent.inc"      // the 2048-wide recurrences: persistent launches (rnn_persist.h) with their probe / fallback protocol, the mcil BiRNN and BiGRU plan encoders (a12, a19)
+#include "engine_trainable.inc"      // the per-tensor trainable mask: hulc_trainable_set / _get / _steps_set and the optimizer / refresh tables without the frozen tensors
 #include "engine_backward.inc"      // gradient all-reduce buckets + the job-wide skip vote (comm.h), hulc_backward / hulc_backward_part / hulc_backward_allreduce (a16-a17)
     // ---------------------------------------------------------------- dynamic loss scaling (kernels.h: ScalerState)
     ScalerState* scaler = nullptr;          // device; null = off (fp32 / bf16 default)
@@ -1042,13 +1058,16 @@ struct Engine : IEngine {
     int gn_build() {
         gn_free();
         std::vector<long long> cs; std::vector<int> cn, tf;
-        for (const Ref& r : gn_tens) {
+        for (size_t t = 0; t < gn_tens.size(); ++t) {
+            const Ref& r = gn_tens[t];
             if (r.off < 0 || r.n < 0 || (r.off & 3) || r.off + r.n > numel) { hulc_set_error("gradient norm: tensor at offset %lld (%lld elements) is misaligned or outside the bound buffer", (long long)r.off, (long long)r.n); return 1; }
             tf.push_back((int)cs.size());
+            if (tm_active && !tm_mask[t]) continue;      // a frozen tensor has no chunk: it is not read, adds nothing to the total and reports 0
             for (int64_t x = 0; x < r.n; x += GN_CHUNK) { cs.push_back(r.off + x); cn.push_back((int)std::min<int64_t>(GN_CHUNK, r.n - x)); }
         }
         tf.push_back((int)cs.size());
-        if (cs.empty()) { hulc_set_error("gradient norm: no bound tensors"); return 1; }
+        if (cs.empty() && !tm_active) { hulc_set_error("gradient norm: no bound tensors"); return 1; }
+        if (cs.empty()) { cs.push_back(0); cn.push_back(0); }      // every tensor frozen: one empty chunk behind the table (the step launches nothing)
         const size_t nc = cs.size(), nt = gn_tens.size();
         if (hipMalloc((void**)&gn_chunk_start, sizeof(long long) * nc) != hipSuccess || hipMalloc((void**)&gn_chunk_n, sizeof(int) * nc) != hipSuccess ||
             hipMalloc((void**)&gn_tfirst, sizeof(int) * (nt + 1)) != hipSuccess || hipMalloc((void**)&gn_partial, sizeof(float) * nc) != hipSuccess ||
@@ -1058,7 +1077,7 @@ struct Engine : IEngine {
         HIP_CHECK(hipMemcpy(gn_chunk_start, cs.data(), sizeof(long long) * nc, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(gn_chunk_n, cn.data(), sizeof(int) * nc, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(gn_tfirst, tf.data(), sizeof(int) * (nt + 1), hipMemcpyHostToDevice));
-        gn_chunks = (int)nc; gn_built = true;
+        gn_chunks = tf.back(); gn_built = true;
         return 0;
     }
     int clip_state_write(float total, float coef) {
@@ -1093,6 +1112,16 @@ struct Engine : IEngine {
         if (!bound) { hulc_set_error("hulc_optimizer_step before hulc_bind_params"); return 1; }
         const bool want_norm = clip_algo == HULC_CLIP_NORM || clip_track;
         if (want_norm && !gn_built) { hulc_set_error("hulc_optimizer_step: the gradient-norm tables are missing (hulc_bind_params / hulc_grad_clip_set build them)"); return 1; }      // before the step tag advances
+        // trainable mask: per-group numbers of this step (kernels.h OptGroups) — a tensor that sat out k steps is at its own step o.step - k
+        OptGroups og{};
+        if (tm_active && o.step >= 1) {
+            for (int g = 0; g < tm_ngroups; ++g) {
+                const int64_t own = o.step - tm_goff[g];
+                if (!scaler && own < 1) { hulc_set_error("hulc_optimizer_step: step %lld, but a trainable tensor sat out %lld steps (hulc_trainable_steps_set)", (long long)o.step, (long long)tm_goff[g]); return 1; }
+                og.bc1[g] = (float)(1.0 - pow((double)o.beta1, (double)own)); og.bc2_sqrt[g] = (float)sqrt(1.0 - pow((double)o.beta2, (double)own));
+                og.off[g] = (int)tm_goff[g]; og.first[g] = own == 1;
+            }
+        }
         persist_check("hulc_optimizer_step", false);
         lazy_sweep(0, numel, st);            // an optimizer step without a backward behind hulc_zero_grads: the lazily zeroed tensors become zeros now
         bwd_since_opt = false;
@@ -1105,6 +1134,32 @@ struct Engine : IEngine {
         h16_t* const shadow = std::is_same<T, float>::value ? (h16_t*)nullptr : (h16_t*)wshadow;
         // after the all-reduce, whoever performed it: every rank sees the same flag and derives the same clipping coefficient from the same reduced buffer
         const ClipState* const cs = clip_algo != HULC_CLIP_OFF ? clip_state : nullptr;
+        tm_last_step = step;      // what hulc_trainable_set converts a tensor's sat-out count and its own step count with
+        if (tm_active) {
+            if (tm_ntrain == 0) return 0;      // every tensor frozen: nothing is read, written or launched
+            if (want_norm) {
+                hipLaunchKernelGGL(grad_sumsq_kernel, dim3(gn_chunks), dim3(256), 0, st, (const float*)G, (const long long*)gn_chunk_start, (const int*)gn_chunk_n, gn_partial, scaler);
+                hipLaunchKernelGGL(grad_norm_combine_kernel, dim3(1), dim3(1024), 0, st, (const float*)gn_partial, (const int*)gn_tfirst, (int)gn_tens.size(), gscale, (const ScalerState*)scaler,
+                                   clip_state, gn_tsq, gn_tnorm);
+                gn_have = true;
+            } else if (scaler)      // the non-finite check reads the gradients the step will read, no others: the norm pass's chunk walk over the trainable tensors (its sums are not used)
+                hipLaunchKernelGGL(grad_sumsq_kernel, dim3(gn_chunks), dim3(256), 0, st, (const float*)G, (const long long*)gn_chunk_start, (const int*)gn_chunk_n, gn_partial, scaler);
+            if (o.kind == HULC_OPT_SGD)
+                hipLaunchKernelGGL(sgd_grouped_kernel, dim3(tm_flat.chunks), dim3(256), 0, st, P, (const float*)G, AM, (const long long*)tm_flat.start, (const int*)tm_flat.n, (const unsigned char*)tm_flat.gid, og,
+                                   lr, o.momentum, o.dampening, o.weight_decay, (int)(o.nesterov != 0), gscale, shadow, (const ScalerState*)scaler, (const unsigned*)rp_skip, tag, cs);
+            else {
+                const bool tiles = adam_fuse_tr && tm_tile_ok && tm_tiles.n && shadow;
+                const ChunkTable& ct = tiles ? tm_comp : tm_flat;
+                AdamArgs a{P, G, AM, AV, lr, b1, b2, eps, 1.f, 1.f, gscale, o.weight_decay, (int)(o.kind == HULC_OPT_ADAMW), shadow, (const ScalerState*)scaler, (const unsigned*)rp_skip, tag, cs};
+                hipLaunchKernelGGL(adam_grouped_kernel, dim3((tiles ? tm_tiles.blocks : 0) + ct.chunks), dim3(256), 0, st, a, (const TrDesc*)(tiles ? tm_tiles.desc : nullptr),
+                                   (const unsigned short*)(tiles ? tm_tiles.b2d : nullptr), (const unsigned char*)(tiles ? tm_tile_gid : nullptr), tiles ? tm_tiles.blocks : 0,
+                                   (const long long*)ct.start, (const int*)ct.n, (const unsigned char*)ct.gid, og);
+                if (tiles) tr_fresh = true;
+            }
+            if (scaler) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(1), 0, st, scaler, (const unsigned*)rp_skip, tag);
+            if (hipGetLastError() != hipSuccess) { hulc_set_error("optimizer launch failed"); return 1; }
+            return prepare_weights(true);
+        }
         if (want_norm) {        // one read of G: the norm pass raises found_inf itself (fp16), the separate check is skipped
             hipLaunchKernelGGL(grad_sumsq_kernel, dim3(gn_chunks), dim3(256), 0, st, (const float*)G, (const long long*)gn_chunk_start, (const int*)gn_chunk_n, gn_partial, scaler);
             hipLaunchKernelGGL(grad_norm_combine_kernel, dim3(1), dim3(1024), 0, st, (const float*)gn_partial, (const int*)gn_tfirst, (int)gn_tens.size(), gscale, (const ScalerState*)scaler,

@@ -63,7 +63,7 @@
         if (hi <= lo) return 0;
         GradComm& c = *comm;
         const bool vote = vote_pad() >= 0 ? (skip_pad >= lo && skip_pad < hi) : lo == 0;      // the range that carries the job-wide skip vote: the bucket issued LAST (perceptual encoders, offset 0) / the whole buffer
-        if (vote) skip_vote_put(st);
+        if (vote) { skip_vote_put(st); ar_voted = true; }
         c.gate_from(st);
         const size_t n = (size_t)(hi - lo);
         if (span >= 0) c.span_begin(span, (dtype == HULC_DTYPE_F32 ? 4.0 : 2.0) * n);
@@ -97,11 +97,29 @@
         if (rc != 0) { hulc_set_error("ncclAllReduce failed: %s", GradComm::err(rc)); return 1; }
         return 0;
     }
+    // trainable mask: a bucket whose tensors are all frozen is not reduced (a partly frozen one is reduced whole).  When the range that would have carried the
+    // job-wide skip vote is among them, the vote travels alone: one 4-byte all-reduce of the engine's own word behind the last bucket
+    bool ar_voted = false;      // a range of this backward / all-reduce has carried the vote
+    int vote_only() {
+        if (!rp_skip) rp_skip = alloc<unsigned>(64);
+        if (!vote_word) vote_word = alloc<float>(64);
+        if (!rp_skip || !vote_word) { hulc_set_error("skip vote: allocation failed"); return 1; }
+        GradComm& c = *comm;
+        hipLaunchKernelGGL(dp_skip_put_kernel, dim3(1), dim3(1), 0, st, (const unsigned*)rp_skip, opt_seq + 1, vote_word);
+        c.gate_from(st);
+        const int rc = GradComm::api().allreduce(vote_word, vote_word, 1, GradComm::F32, GradComm::SUM, c.comm, c.cs);
+        c.n_collectives++; c.bytes_reduced += 4.0;
+        hipLaunchKernelGGL(dp_skip_get_kernel, dim3(1), dim3(1), 0, c.cs, vote_word, rp_skip, opt_seq + 1);
+        ar_voted = true;
+        if (rc != 0) { hulc_set_error("ncclAllReduce failed: %s", GradComm::err(rc)); return 1; }
+        return 0;
+    }
     // called by backward() after the stage that finalises bucket i has been enqueued
     int bucket_ready(int i) {
         if (ar_dtype < 0 || (ar_sent >> i) & 1u) return 0;
         const std::vector<Bucket> v = bucket_plan();
         ar_sent |= 1u << i;
+        if (range_all_frozen(v[i].lo, v[i].hi)) return (i == 4 && !ar_voted) ? vote_only() : 0;      // bucket 4 is the last one issued
         lazy_sweep(v[i].lo, v[i].hi, st);    // the bucket is final: a lazily zeroed tensor in it that no writer touched becomes zeros before it goes on the wire
         return reduce_range(v[i].lo, v[i].hi, ar_dtype, comm_timing ? i : -1);
     }
@@ -123,7 +141,20 @@
         if (!bound) { hulc_set_error("hulc_allreduce_grads before hulc_bind_params"); return 1; }
         if (bwd_stage != 0) { hulc_set_error("hulc_allreduce_grads: encoder part of the backward still pending"); return 1; }
         lazy_sweep(0, numel, st);
-        if (reduce_range(0, numel, dtype)) return 1;
+        if (tm_active && bucket_plan_ok()) {      // the buckets in buffer order, runs of neighbours that are still trained as one collective each
+            std::vector<Bucket> v = bucket_plan();
+            v.erase(std::remove_if(v.begin(), v.end(), [](const Bucket& b) { return b.hi <= b.lo; }), v.end());
+            std::sort(v.begin(), v.end(), [](const Bucket& a, const Bucket& b) { return a.lo < b.lo; });
+            ar_voted = false;
+            for (size_t i = 0; i < v.size();) {
+                if (range_all_frozen(v[i].lo, v[i].hi)) { ++i; continue; }
+                size_t j = i;
+                while (j + 1 < v.size() && !range_all_frozen(v[j + 1].lo, v[j + 1].hi)) ++j;
+                if (reduce_range(v[i].lo, v[j].hi, dtype)) return 1;
+                i = j + 1;
+            }
+            if (!ar_voted && vote_only()) return 1;
+        } else if (reduce_range(0, numel, dtype)) return 1;
         comm->gate_to(st);
         return 0;
     }
@@ -139,7 +170,7 @@
     int backward_allreduce(int dtype) override {
         if (check_ar_dtype(dtype, "hulc_backward_allreduce")) return 1;
         if (!bucket_plan_ok()) { hulc_set_error("hulc_backward_allreduce: the module-group buckets do not partition the gradient buffer (layout changed?)"); return 1; }
-        ar_dtype = dtype; ar_sent = 0;
+        ar_dtype = dtype; ar_sent = 0; ar_voted = false;
         if (comm_timing) comm->bwd_mark(true, st);
         int rc = backward(-1);
         if (!rc) for (int i = 0; i < 5 && !rc; ++i) rc = bucket_ready(i);     // whatever no stage hook covered (model kinds without that stage)
@@ -163,7 +194,10 @@
         const float dp = cfg.dropout_p;
         const long long BH = (long long)B * HID;
         const bool cs16 = std::is_same<T, h16_t>::value && !repro;      // the bias gradients ride on the dZ transposes (atomics); else the two-stage column sums of the fp32 engine
-        if (part == 1) goto encoders;
+        if (part == 1) { if (bwd_skip_enc) goto finish; goto encoders; }
+        // every perceptual_encoder.* tensor frozen (hulc_trainable_set): the backward stops behind part 0, and the launches of part 0 whose only product is the
+        // embedding gradient are left out.  Latched here: part 1 follows the decision its part 0 ran with
+        bwd_skip_enc = tm_enc_frozen;
         if (!arena_clean) HIP_CHECK(hipMemsetAsync(zero_arena, 0, sizeof(float) * zero_n, st));   // demb, dgoal, dseqf, heads / fc7 gradient temporaries, work counters
         arena_clean = false;
         work_ctr_next = 0;
@@ -319,7 +353,7 @@
             }
             }
             // d emb (gripper half), scattered back to (B,S,128)[..., 64:128]
-            { EpiP ep = epi(demb + (EMB - DE), true); ep.accumulate = 1;
+            if (!bwd_skip_enc) { EpiP ep = epi(demb + (EMB - DE), true); ep.accumulate = 1;
               gemm(dense<T>(dZ0, SB, HID), dense<T>(wih0T + (long long)dec_plan * HID, DE, HID), dense_out_map(B, EMB, (long long)S * EMB), ep, SB, DE, HID); }
             hipLaunchKernelGGL((sum_over_t_kernel<T>), dim3(cdiv(BH, 256)), dim3(256), 0, st, dZ0, S, BH, dC);
             if constexpr (!std::is_same<T, h16_t>::value) colsum(dC, HID, B, HID, dbih0, dbhh0);
@@ -464,7 +498,7 @@
             T* al[2] = {gl1 + (long long)Bv * HID, gl2 + (long long)Bv * HID};
             ln_bwd(dgoal, GOAL, gl3, GOAL, goal_st, ln_vg_g, Bv, GOAL, nullptr, 0, 0, dgl3_t, GOAL, d_ln_vg_g, d_ln_vg_b);
             DenseOut om = dense_out((long long)S * EMB);
-            mlp_bwd(dgl3_t, emb + (long long)(S - 1) * EMB, (long long)S * EMB, Bv, vg, 3, av, dt_a, dt_a + (long long)B * HID, demb + (long long)(S - 1) * EMB, &om, 1);
+            mlp_bwd(dgl3_t, emb + (long long)(S - 1) * EMB, (long long)S * EMB, Bv, vg, 3, av, dt_a, dt_a + (long long)B * HID, bwd_skip_enc ? nullptr : demb + (long long)(S - 1) * EMB, bwd_skip_enc ? nullptr : &om, bwd_skip_enc ? 0 : 1);
             ln_bwd(dgoal + Bv * GOAL, GOAL, gl3 + Bv * GOAL, GOAL, goal_st + 2 * Bv, ln_lg_g, Bl, GOAL, nullptr, 0, 0, dgl3_t + Bv * GOAL, GOAL, d_ln_lg_g, d_ln_lg_b);
             mlp_bwd(dgl3_t + Bv * GOAL, lang_t, LANG, Bl, lg, 3, al, dt_a, dt_a + (long long)B * HID, nullptr, nullptr, 0);
         } else {
@@ -476,7 +510,7 @@
                 ln_bwd(dgoal, GOAL, gl3, GOAL, goal_st, ln_vg_g, B, GOAL, nullptr, 0, 0, dgl3_t, GOAL, d_ln_vg_g, d_ln_vg_b);
                 DenseOut om = dense_out((long long)S * EMB);
                 mlp_bwd(dgl3_t, emb + (long long)(S - 1) * EMB, (long long)S * EMB, B, vg, 3, acts, dt_a, dt_a + (long long)B * HID,
-                        demb + (long long)(S - 1) * EMB, &om, 1);
+                        bwd_skip_enc ? nullptr : demb + (long long)(S - 1) * EMB, bwd_skip_enc ? nullptr : &om, bwd_skip_enc ? 0 : 1);
             }
         }
         }
@@ -487,6 +521,7 @@
             bwd_stage = 1;
             return 0;
         }
+        if (bwd_skip_enc) goto finish;
     encoders:
         // ---- encoders backward
         {
@@ -499,6 +534,7 @@
             enc_bwd_both(src, pair ? src2 : nullptr, Nenc, tail_fused);
             flush_unpacks();
         }
+    finish:
         if (bucket_ready(4)) return 1;       // perceptual_encoder.* final
         lazy_sweep(0, numel, st);
         if (hipGetLastError() != hipSuccess) { hulc_set_error("kernel launch failed in backward"); return 1; }

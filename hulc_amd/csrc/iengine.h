@@ -57,6 +57,10 @@ struct IEngine {
     // ---- gradient clipping / gradient norms inside the optimizer step (engine.h: optim)
     virtual int grad_clip_set(int32_t algo, float limit, int32_t track) = 0;
     virtual int grad_norm_get(float* total, float* coef, float* per_tensor, int64_t cap) = 0;
+    // ---- per-tensor trainable mask (engine_trainable.inc)
+    virtual int trainable_set(int32_t n, const uint8_t* trainable) = 0;
+    virtual int trainable_get(int64_t cap, uint8_t* trainable_out, int64_t* frozen_steps_out) = 0;
+    virtual int trainable_steps_set(int32_t n, const int64_t* frozen_steps, int64_t steps_taken) = 0;
     // ---- data-parallel gradient all-reduce (comm.h): whole buffer after a finished backward, or bucketed inside the backward
     virtual int allreduce_grads(int bucket_dtype) = 0;
     virtual int backward_allreduce(int bucket_dtype) = 0;

@@ -2625,6 +2625,45 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 // into an LDS tile whose read-out is the transpose's (transpose_tile64_store).  Everything else — biases, LayerNorm and conv weights, matrices without a transposed
 // copy — is covered by 4096-element CHUNK blocks behind the tile blocks (chunk table built at bind time: the complement of the tiled matrices in the flat buffer).
 constexpr int ADAM_CHUNK = 4096;
+// adam_tiled_kernel's tile body as a function of the block's descriptor, for adam_grouped_kernel below (adam_tiled_kernel keeps its own copy: its code is
+// the step without a mask and does not change with this one)
+DEVI void adam_tile_block(const AdamArgs& a, float bc1, float bc2_sqrt, float gscale, float vclip, const TrDesc& D, int blk, unsigned short (*tile)[66]) {
+    const int tid = threadIdx.x;
+    const int b = blk - D.blk0;
+    const int c0 = (b % D.tiles_x) * 64, r0 = (b / D.tiles_x) * 64;
+    const long long off = reinterpret_cast<const h16_t*>(D.src) - a.shadow;       // the matrix's offset in the flat parameter buffer
+    // all four passes' 16 loads are requested before the first update (64 registers): the tile's 64 KB of p / g / m / v are in flight together
+    const int cc = (tid & 15) * 4, c = c0 + cc;
+    AdamQuad q[4];
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+        const int r = r0 + ps * 16 + (tid >> 4);
+        if (r < D.R && c < D.C) adam_load4(a, off + (long long)r * D.C + c, q[ps]);       // C % 4 == 0 (checked at bind)
+    }
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+        const int row = ps * 16 + (tid >> 4), r = r0 + row;
+        unsigned lo = 0u, hi = 0u;
+        if (r < D.R && c < D.C) adam_finish4(a, bc1, bc2_sqrt, gscale, off + (long long)r * D.C + c, q[ps], lo, hi, vclip);
+        *reinterpret_cast<unsigned*>(&tile[row][cc]) = lo;
+        *reinterpret_cast<unsigned*>(&tile[row][cc + 2]) = hi;
+    }
+    __syncthreads();
+    if (D.fr) {      // fragment-ordered copy of W: chunk (row, 8 k) -> row tile row / 16, k-step k / 32, lane (k % 32) / 8 * 16 + row % 16 (two chunks per thread)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int q = tid + u * 256, row = q >> 3, c8 = q & 7;
+            const int r = r0 + row, k = c0 + c8 * 8;
+            if (r < D.R && k + 7 < D.C) {
+                uint4 v;
+                v.x = *reinterpret_cast<const unsigned*>(&tile[row][c8 * 8]); v.y = *reinterpret_cast<const unsigned*>(&tile[row][c8 * 8 + 2]);
+                v.z = *reinterpret_cast<const unsigned*>(&tile[row][c8 * 8 + 4]); v.w = *reinterpret_cast<const unsigned*>(&tile[row][c8 * 8 + 6]);
+                *reinterpret_cast<uint4*>(reinterpret_cast<h16_t*>(D.fr) + ((((long long)(r >> 4) * (D.C >> 5) + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (r & 15)) << 3)) = v;
+            }
+        }
+    }
+    transpose_tile64_store(D, b, tile);
+}
 __global__ void __launch_bounds__(256) adam_tiled_kernel(AdamArgs a, const TrDesc* __restrict__ desc, const unsigned short* __restrict__ blk2desc, int ntile,
                                                          const long long* __restrict__ chunk_start, const int* __restrict__ chunk_n) {
     __shared__ __attribute__((aligned(16))) unsigned short tile[64][66];
@@ -2684,7 +2723,73 @@ __global__ void __launch_bounds__(256) adam_tiled_kernel(AdamArgs a, const TrDes
     }
 }
 
+// =========================================================================================================
+// Trainable mask (hulc_trainable_set): the optimizer over the TRAINABLE tensors only.  A frozen tensor's parameter, moments, 16-bit shadow and derived
+// copies are in no table of these launches, so nothing of it is read or written.  torch.optim keeps `step` per parameter: a tensor that sat out k
+// optimizer steps takes its bias corrections (SGD: its first-step rule buf = grad) from step - k.  Tensors are grouped by k (at most OPT_GROUPS values
+// alive at once): one group id per chunk / tiled matrix on the device, the per-group numbers in the kernel arguments.  bc1 / bc2_sqrt come from the
+// host, computed as the ungrouped kernels' are; under the loss scaler (fp16) the kernel derives them from the device-side count of taken steps minus off[g].
+// =========================================================================================================
+constexpr int OPT_GROUPS = 8;
+struct OptGroups { float bc1[OPT_GROUPS], bc2_sqrt[OPT_GROUPS]; int off[OPT_GROUPS]; int first[OPT_GROUPS]; };
+// blocks [0, ntile): 64 x 64 tiles of the trainable tiled matrices (16-bit engines, adam_tiled_kernel's tile pass); behind them one block per chunk of every
+// other trainable tensor (chunk_n a multiple of 4: a tensor's last quad may end in its own alignment padding, as in the flat kernels).  ntile == 0 is the
+// chunk-table form of adam_kernel (fp32 engine, "adam_fused_transposes" 0)
+__global__ void __launch_bounds__(256) adam_grouped_kernel(AdamArgs a, const TrDesc* __restrict__ desc, const unsigned short* __restrict__ blk2desc,
+                                                           const unsigned char* __restrict__ desc_gid, int ntile, const long long* __restrict__ chunk_start,
+                                                           const int* __restrict__ chunk_n, const unsigned char* __restrict__ chunk_gid, OptGroups og) {
+    __shared__ __attribute__((aligned(16))) unsigned short tile[64][66];
+    if (a.skip && *a.skip == a.tag) return;
+    const bool tiled = (int)blockIdx.x < ntile;
+    const int di = tiled ? (int)blk2desc[blockIdx.x] : 0;
+    const int g = (tiled ? desc_gid[di] : chunk_gid[blockIdx.x - ntile]) & (OPT_GROUPS - 1);
+    float gscale = a.gscale, bc1 = og.bc1[g], bc2_sqrt = og.bc2_sqrt[g];
+    if (a.ss) {
+        if (a.ss->found_inf) return;
+        gscale /= a.ss->scale;
+        const float t = (float)(a.ss->steps + 1 - og.off[g]);
+        bc1 = 1.f - powf(a.b1, t);
+        bc2_sqrt = sqrtf(1.f - powf(a.b2, t));
+    }
+    float vclip;
+    clip_read(a.cs, gscale, vclip);
+    if (tiled) {
+        const TrDesc D = desc[di];
+        adam_tile_block(a, bc1, bc2_sqrt, gscale, vclip, D, blockIdx.x, tile);
+    } else {
+        const int j = blockIdx.x - ntile;
+        const long long start = chunk_start[j];
+        const int n = chunk_n[j];
+        for (int i = threadIdx.x * 4; i + 3 < n; i += 1024) { unsigned lo, hi; adam_update4(a, bc1, bc2_sqrt, gscale, start + i, lo, hi, vclip); }
+    }
+}
+
 // torch.optim.SGD (conf/model/optimizer/sgd.yaml: momentum 0.9) over the flat buffer; buf = the bound first-moment buffer
+DEVI void sgd_update4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long i, float lr, float momentum, float dampening, float wd,
+                      int nesterov, int first, float gscale, float vclip, h16_t* __restrict__ shadow) {
+    float4 pp = *reinterpret_cast<float4*>(p + i), gg = *reinterpret_cast<const float4*>(g + i), bb = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (momentum != 0.f && !first) bb = *reinterpret_cast<const float4*>(buf + i);
+    float* P = &pp.x; float* G = &gg.x; float* Bf = &bb.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float gr = G[e] * gscale;
+        if (vclip > 0.f) gr = gr > vclip ? vclip : (gr < -vclip ? -vclip : gr);
+        if (wd != 0.f) gr += wd * P[e];
+        if (momentum != 0.f) {
+            Bf[e] = first ? gr : momentum * Bf[e] + (1.f - dampening) * gr;
+            gr = nesterov ? gr + momentum * Bf[e] : Bf[e];
+        }
+        P[e] -= lr * gr;
+    }
+    *reinterpret_cast<float4*>(p + i) = pp;
+    if (momentum != 0.f) *reinterpret_cast<float4*>(buf + i) = bb;
+    if (shadow) {
+        uint2 o;
+        o.x = pack2h(pp.x, pp.y);
+        o.y = pack2h(pp.z, pp.w);
+        *reinterpret_cast<uint2*>(shadow + i) = o;
+    }
+}
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long n, float lr, float momentum,
                            float dampening, float wd, int nesterov, int first, float gscale, h16_t* __restrict__ shadow,
                            const ScalerState* __restrict__ ss = nullptr, const unsigned* __restrict__ skip = nullptr, unsigned tag = 0,
@@ -2723,6 +2828,26 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
             *reinterpret_cast<uint2*>(shadow + i) = o;
         }
     }
+}
+// chunk-table form under a trainable mask (see adam_grouped_kernel): one block per chunk of a trainable tensor, the first-step rule per group
+// (og.first[g]; under the loss scaler: the device-side count of taken steps equals the group's offset)
+__global__ void __launch_bounds__(256) sgd_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, const long long* __restrict__ chunk_start,
+                                                          const int* __restrict__ chunk_n, const unsigned char* __restrict__ chunk_gid, OptGroups og, float lr, float momentum,
+                                                          float dampening, float wd, int nesterov, float gscale, h16_t* __restrict__ shadow, const ScalerState* __restrict__ ss,
+                                                          const unsigned* __restrict__ skip, unsigned tag, const ClipState* __restrict__ cs) {
+    if (skip && *skip == tag) return;
+    const int gi = chunk_gid[blockIdx.x] & (OPT_GROUPS - 1);
+    int first = og.first[gi];
+    if (ss) {
+        if (ss->found_inf) return;
+        gscale /= ss->scale;
+        first = ss->steps == og.off[gi];
+    }
+    float vclip;
+    clip_read(cs, gscale, vclip);
+    const long long start = chunk_start[blockIdx.x];
+    const int n = chunk_n[blockIdx.x];
+    for (int i = threadIdx.x * 4; i + 3 < n; i += 1024) sgd_update4(p, g, buf, start + i, lr, momentum, dampening, wd, nesterov, first, gscale, vclip, shadow);
 }
 
 // embg[(t*B+b)*W + c] = emb[(b*S+t)*128 + (128-W) + c]   (time-major copy of the last W columns: W = 64 is the gripper half,

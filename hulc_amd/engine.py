@@ -691,6 +691,47 @@ class StepEngine:
             out["per_tensor"] = {name: float(per[i]) for i, name in enumerate(self.layout.keys())}
         return out
 
+    # ---- frozen parameters: the per-tensor trainable mask (include/hulc_hip.h: hulc_trainable_*) ---------------------------------------------
+    def set_trainable(self, mask) -> None:
+        """hulc_trainable_set: `mask` = {name: bool} (missing names keep their state) or a sequence of len(layout) flags in layout order.  A frozen
+        tensor is left alone by the optimizer step (parameter, moments, 16-bit copies, no weight decay), its gradient is never read, and with every
+        perceptual_encoder.* tensor frozen the encoder backward is not run.  Rebuilds the optimizer's tables: call it between steps, not in them."""
+        names = list(self.layout.keys())
+        if isinstance(mask, dict):
+            unknown = [n for n in mask if n not in self.layout]
+            if unknown:
+                raise KeyError(f"set_trainable: unknown tensors {unknown[:5]}")
+            cur = self.trainable()
+            flags = [bool(mask.get(n, cur[n])) for n in names]
+        else:
+            flags = [bool(x) for x in mask]
+        arr = np.ascontiguousarray(flags, np.uint8)
+        L.check(self.lib.hulc_trainable_set(self.ctx, len(arr), arr.ctypes.data))
+
+    def _trainable_get(self):
+        n = len(self.layout)
+        m, k = np.empty(n, np.uint8), np.empty(n, np.int64)
+        L.check(self.lib.hulc_trainable_get(self.ctx, n, m.ctypes.data, k.ctypes.data))
+        return m, k
+
+    def trainable(self) -> Dict[str, bool]:
+        """{name: trainable} as the engine holds it (all True before any set_trainable)."""
+        m, _ = self._trainable_get()
+        return {name: bool(m[i]) for i, name in enumerate(self.layout.keys())}
+
+    def frozen_steps(self) -> Dict[str, int]:
+        """{name: optimizer steps the tensor has sat out}: what torch.optim's per-parameter `step` is short of the global count."""
+        _, k = self._trainable_get()
+        return {name: int(k[i]) for i, name in enumerate(self.layout.keys())}
+
+    def set_frozen_steps(self, steps, steps_taken: int = -1) -> None:
+        """hulc_trainable_steps_set (checkpoint restore, after set_trainable): {name: count} (missing = 0) or a sequence in layout order, as of
+        `steps_taken` optimizer steps (-1: the count the context holds)."""
+        names = list(self.layout.keys())
+        vals = [int(steps.get(n, 0)) for n in names] if isinstance(steps, dict) else [int(x) for x in steps]
+        arr = np.ascontiguousarray(vals, np.int64)
+        L.check(self.lib.hulc_trainable_steps_set(self.ctx, len(arr), arr.ctypes.data, int(steps_taken)))
+
     def get_tensor(self, name: str, n: int) -> np.ndarray:
         out = np.zeros(n, np.float32)
         got = C.c_int64()

@@ -55,8 +55,15 @@ class FusedAdam:
     def zero_grad(self, set_to_none: bool = False):
         self.module.engine.zero_grads()
 
+    def _sync_trainable(self, force: bool = False):
+        """Hulc._sync_trainable of the owning module; an owner without parameters to flag (a bare engine holder) has nothing to compare."""
+        sync = getattr(self.module, "_sync_trainable", None)
+        if sync is not None:
+            sync(force=force)
+
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        self._sync_trainable()              # requires_grad flags changed since the last step reach the engine before it steps
         g = self.param_groups[0]
         world = parallel.world_size()
         if not self.module._grads_reduced:               # training_step already overlapped the all-reduce with the backward
@@ -87,6 +94,11 @@ class FusedAdam:
             # (device-side) count, so it is what a checkpoint must carry — `calls` keeps the number of optimizer.step() calls made
             sd["step"] = int(st["taken_steps"])
             sd["grad_scaler"] = dict(scale=st["scale"], _growth_tracker=st["growth_tracker"], skipped_steps=int(st["skipped_steps"]), calls=int(e.adam_t))
+        # frozen parameters: the mask and, per tensor, the optimizer steps it sat out (torch keeps `step` per parameter; here it is sd["step"] minus this count)
+        self._sync_trainable()
+        if hasattr(e, "trainable"):
+            sd["trainable"] = {n: bool(v) for n, v in e.trainable().items()}
+            sd["frozen_steps"] = e.frozen_steps()
         return sd
 
     def load_state_dict(self, sd):
@@ -102,6 +114,20 @@ class FusedAdam:
             else:                   # a checkpoint without scaler state (e.g. saved by an fp32 / bf16 run): keep the current scale, restore the count
                 st = e.scaler_state()
                 e.scaler_load(float(st["scale"]), int(st["growth_tracker"]), int(sd["step"]))
+        # a checkpoint from before the mask existed: every tensor trainable, nothing sat out
+        tr = sd.get("trainable")
+        flagged = getattr(self.module, "_params", None)      # Hulc / GCBC: the requires_grad flags of these parameters are what the engine follows
+        if tr is None and (flagged is None or not self.module._mask_pushed):
+            return                          # the engine never saw a mask: it stays on the path without one
+        names = list(e.layout.keys())
+        tr = {n: True for n in names} if tr is None else {n: bool(tr.get(n, True)) for n in names}
+        if flagged is None:
+            e.set_trainable(tr)
+        else:
+            for n, p in flagged.items():
+                p.requires_grad_(tr[n])
+            self._sync_trainable(force=True)
+        e.set_frozen_steps(sd.get("frozen_steps") or {}, steps_taken=int(sd["step"]))
 
 
 class LambdaSchedule:
@@ -210,6 +236,7 @@ class Hulc(torch.nn.Module):
         max_seq_len: Optional[int] = None,
         device: str = "cuda:0",
         seed: int = 42,
+        freeze_modules=None,
     ):
         super().__init__()
         # ---- options outside the hot path are rejected loudly instead of silently ignored (SURVEY §2.1 OUT OF SCOPE rows)
@@ -361,7 +388,11 @@ class Hulc(torch.nn.Module):
         self._params = {n: torch.nn.Parameter(v, requires_grad=True) for n, v in self.engine.views(self.engine.flat_params).items()}
         for n, g in self.engine.views(self.engine.flat_grads).items():
             self._params[n].grad = g
+        self._grad_views = {n: p.grad for n, p in self._params.items()}
+        self._mask_pushed: Optional[Dict[str, bool]] = None      # the mask the engine holds (None: it never got one and runs the path without a mask)
         self.reset_parameters(seed)
+        if freeze_modules:
+            self.freeze_modules(freeze_modules)
         self.logged: Dict[str, float] = {}
         self._epoch_acc: Dict[str, list] = {}
         self._grads_reduced = False
@@ -385,6 +416,49 @@ class Hulc(torch.nn.Module):
     def parameters(self, recurse: bool = True):  # type: ignore[override]
         for _, p in self.named_parameters():
             yield p
+
+    # ---- frozen parameters: requires_grad flags on the entries of named_parameters() are the interface, the engine's mask follows them
+    def _sync_trainable(self, force: bool = False) -> None:
+        """Compare the parameters' requires_grad flags with the mask the engine holds and hand it the new one when they differ (StepEngine.set_trainable
+        rebuilds the optimizer's tables, so this happens between steps: training_step and FusedAdam.step call it first).  A frozen parameter's .grad reads
+        None, as an untouched torch parameter's does; its region of the flat gradient buffer is unspecified."""
+        want = {n: bool(p.requires_grad) for n, p in self._params.items()}
+        if self._mask_pushed is None and all(want.values()) and not force:
+            return
+        if not force and want == self._mask_pushed:
+            return
+        self.engine.set_trainable(want)
+        self._mask_pushed = want
+        for n, p in self._params.items():
+            p.grad = self._grad_views[n] if want[n] else None
+
+    def freeze_modules(self, prefixes) -> None:
+        """requires_grad_(False) on every parameter under the given module paths (one string or a sequence, e.g. "perceptual_encoder"); a path
+        that names nothing is a KeyError."""
+        for p, hit in zip(self._params.values(), spec.prefix_mask(self._params.keys(), prefixes)):
+            if hit:
+                p.requires_grad_(False)
+        self._sync_trainable()
+
+    def unfreeze_modules(self, prefixes) -> None:
+        for p, hit in zip(self._params.values(), spec.prefix_mask(self._params.keys(), prefixes)):
+            if hit:
+                p.requires_grad_(True)
+        self._sync_trainable()
+
+    def freeze(self) -> None:
+        """LightningModule.freeze: no parameter is trained, and the module goes into eval mode."""
+        for p in self._params.values():
+            p.requires_grad_(False)
+        self._sync_trainable()
+        self.eval()
+
+    def unfreeze(self) -> None:
+        """LightningModule.unfreeze: every parameter is trained again, and the module goes into train mode."""
+        for p in self._params.values():
+            p.requires_grad_(True)
+        self._sync_trainable()
+        self.train()
 
     def _buffers_dict(self) -> Dict[str, torch.Tensor]:
         lin = torch.linspace(-1.0, 1.0, 21)
@@ -652,6 +726,7 @@ class Hulc(torch.nn.Module):
             self._comm_tried = True
             parallel.configure_shared_gpu(eng)                      # several ranks on one device: no persistent recurrences
             parallel.setup_comm(eng, os.environ.get("HULC_BUCKET_DTYPE", "fp32"))
+        self._sync_trainable()
         eng.zero_grads()
         nmod = len(batch)
         aux_heads = self.use_bc_z_auxiliary_loss or self.use_mia_auxiliary_loss

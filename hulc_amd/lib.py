@@ -120,7 +120,7 @@ EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_s
            "hulc_k_window_compact", "hulc_k_rows_expand", "hulc_k_rows_reduce", "hulc_k_gemm_epi", "hulc_k_gemm_multi", "hulc_k_gemm_pick", "hulc_k_gemm_wgrad_nsplit",
            "hulc_k_det_head_loss", "hulc_k_det_head_bwd", "hulc_k_det_head_act",
            "hulc_k_conv_wgrad_t", "hulc_k_conv1_wgrad_u8_t", "hulc_k_conv_tile_t", "hulc_k_conv_pair_t", "hulc_k_conv_plan",
-           "hulc_decoder_body_select"]
+           "hulc_decoder_body_select", "hulc_trainable_set", "hulc_trainable_get", "hulc_trainable_steps_set"]
 
 _lib = None
 
@@ -280,6 +280,10 @@ def load():
         lib.hulc_k_det_head_act.argtypes = [I, P, P, P, P, I, P, P]
     if hasattr(lib, "hulc_decoder_body_select") or not os.environ.get("HULC_LIB_PATH"):
         lib.hulc_decoder_body_select.argtypes = [C.c_void_p, C.c_int32]
+    if hasattr(lib, "hulc_trainable_set") or not os.environ.get("HULC_LIB_PATH"):
+        lib.hulc_trainable_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        lib.hulc_trainable_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.hulc_trainable_steps_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
     if hasattr(lib, "hulc_k_conv_plan") or not os.environ.get("HULC_LIB_PATH"):
         P, I, PI = C.c_void_p, C.c_int32, C.POINTER(C.c_int32)
         lib.hulc_k_conv_wgrad_t.argtypes = [I, I, P, P, P, P, I, I, PI, P]

@@ -210,6 +210,26 @@ def layout(d: ModelDims, pad: int = 64):
     return out, off
 
 
+def prefix_mask(names, prefixes) -> List[bool]:
+    """One flag per tensor name: True where a prefix selects it.  A prefix selects the tensor of that exact name and every tensor under it as a module
+    path ("visual_goal" selects visual_goal.mlp.0.weight, not visual_goal_x.*); a trailing dot is accepted.  `prefixes` is one string or a sequence;
+    a prefix that selects nothing is a KeyError (a typo must not silently train what was meant to be frozen)."""
+    if prefixes is None:
+        prefixes = []
+    if isinstance(prefixes, str):
+        prefixes = [prefixes]
+    names = list(names)
+    out = [False] * len(names)
+    for p in prefixes:
+        q = str(p).rstrip(".")
+        hit = [i for i, n in enumerate(names) if q and (n == q or n.startswith(q + "."))]
+        if not hit:
+            raise KeyError(f"no parameter is named or lies under {p!r}")
+        for i in hit:
+            out[i] = True
+    return out
+
+
 def n_params(d: ModelDims) -> int:
     return sum(int(np.prod(s)) if len(s) else 1 for _, s, _ in param_table(d))
 

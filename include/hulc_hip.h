@@ -260,6 +260,32 @@ int hulc_grad_clip_set(hulc_ctx* ctx, int32_t algo, float limit, int32_t track);
  * Each pointer is optional.  Synchronises the stream.  An error if the last step computed no norm. */
 int hulc_grad_norm_get(hulc_ctx* ctx, float* total, float* coef, float* per_tensor_host, int64_t cap);
 
+/* ---- Frozen parameters: a per-tensor trainable mask (torch's p.requires_grad_(False), Lightning's freeze() / BaseFinetuning).
+ * trainable[i] != 0: tensor i of the hulc_bind_params table (bind order) is trained; 0: it is FROZEN.  Valid only after hulc_bind_params (a new bind makes
+ * every tensor trainable again); may be called again between steps, to freeze or to unfreeze.  Errors, none of which launches anything: a null context or
+ * mask, a call before the bind, n_tensors different from the bound count, more than 8 distinct frozen-step counts among the trainable tensors (below).
+ * All-frozen is legal: the optimizer step is then a no-op.  A context that never calls these entries allocates, launches and computes what it always did.
+ *   optimizer  a frozen tensor's parameter, both moment buffers (the SGD momentum buffer included), its 16-bit shadow and its transposed, fragment-ordered
+ *              and packed copies are not written by hulc_adam_step / hulc_optimizer_step, and it gets no weight decay.  torch.optim keeps `step` per
+ *              parameter: a tensor that sat out k optimizer steps takes its Adam bias corrections from step - k, and SGD's first-step rule (buf = grad)
+ *              applies at its own first step.  Tensors are grouped by k; at most 8 distinct values may be alive among the trainable tensors at once.
+ *   gradients  the library never READS a frozen tensor's gradient region — not in the norm (it is excluded from the total and reports 0 per tensor), the
+ *              clip, the fp16 non-finite check (an inf there neither skips the step nor backs off the loss scale), the optimizer or the all-reduce.
+ *              After a backward the contents of that region are unspecified.
+ *   backward   when every perceptual_encoder.* tensor is frozen, hulc_backward runs part 0 only (minus the launches whose only product is the embedding
+ *              gradient) and hulc_backward_part(ctx, 1) succeeds without launching anything.  Other frozen tensors' gradients may still be computed.
+ *   all-reduce a bucket (hulc_comm_buckets) whose tensors are all frozen is not reduced by hulc_allreduce_grads / hulc_backward_allreduce; a partly frozen
+ *              bucket is reduced whole.
+ * The tables behind all this are rebuilt inside these calls (they synchronise the stream), never on the step path. */
+int hulc_trainable_set(hulc_ctx* ctx, int32_t n_tensors, const uint8_t* trainable);
+/* The mask and, per tensor, the number of optimizer steps it has sat out so far (what a checkpoint must carry); either pointer may be NULL, cap >= the bound
+ * count.  Before any hulc_trainable_set: all 1 / all 0.  Synchronises the stream under the fp16 loss scaler (steps it skipped are nobody's steps). */
+int hulc_trainable_get(hulc_ctx* ctx, int64_t cap, uint8_t* trainable_out, int64_t* frozen_steps_out);
+/* Checkpoint restore: the per-tensor sat-out counts as of steps_taken optimizer steps (0 <= frozen_steps[i] <= steps_taken).  steps_taken = the `step` the
+ * next hulc_optimizer_step will pass minus 1; < 0 = take the count the context holds (the last step's hulc_optim::step, or — under the loss scaler — the
+ * device-side count, so call hulc_scaler_set first).  Call it after the hulc_trainable_set that restores the mask. */
+int hulc_trainable_steps_set(hulc_ctx* ctx, int32_t n_tensors, const int64_t* frozen_steps, int64_t steps_taken);
+
 /* ---- Validation forward: one modality of Hulc.validation_step (hulc/models/hulc.py:770-797) = lmp_val
  * (:301-388): plan proposal and plan recognition each sample a plan (distributions.py:37-41), the decoder is run with both
  * (LogisticDecoderRNN.loss_and_act, logistic_decoder_rnn.py:85-100): NLL loss, a sampled action (_sample :234-258) mapped back to
