@@ -318,6 +318,29 @@ int hulc_trainable_steps_set(hulc_ctx* ctx, int32_t n_tensors, const int64_t* fr
     if (!ctx) { hulc_set_error("hulc_trainable_steps_set: null context"); return 1; }
     return ctx->e->trainable_steps_set(n_tensors, frozen_steps, steps_taken);
 }
+int hulc_ema_enable(hulc_ctx* ctx, float* ema, float decay, int64_t start_step, int32_t warmup) {
+    // the arguments first: the refusal is reachable without a device
+    if (ema && (!(decay > 0.f && decay < 1.f) || start_step < 0)) { hulc_set_error("hulc_ema_enable: need 0 < decay < 1 and start_step >= 0 (got %g, %lld)", (double)decay, (long long)start_step); return 1; }
+    if (!ctx) { hulc_set_error("hulc_ema_enable: null context"); return 1; }
+    return ctx->e->ema_enable(ema, decay, start_step, warmup);
+}
+int hulc_ema_state_get(hulc_ctx* ctx, int64_t* updates, float* last_decay) {
+    if (!ctx) { hulc_set_error("hulc_ema_state_get: null context"); return 1; }
+    return ctx->e->ema_state_get(updates, last_decay);
+}
+int hulc_ema_state_set(hulc_ctx* ctx, int64_t updates) {
+    if (updates < 0) { hulc_set_error("hulc_ema_state_set: updates %lld is negative", (long long)updates); return 1; }
+    if (!ctx) { hulc_set_error("hulc_ema_state_set: null context"); return 1; }
+    return ctx->e->ema_state_set(updates);
+}
+int hulc_ema_swap(hulc_ctx* ctx) {
+    if (!ctx) { hulc_set_error("hulc_ema_swap: null context"); return 1; }
+    return ctx->e->ema_swap();
+}
+int hulc_ema_swapped(hulc_ctx* ctx, int32_t* out) {
+    if (!ctx || !out) { hulc_set_error("hulc_ema_swapped: null argument"); return 1; }
+    return ctx->e->ema_is_swapped(out);
+}
 int hulc_set_kl_beta(hulc_ctx* ctx, float b) { ctx->e->set_kl_beta(b); return 0; }
 int hulc_set_dropout(hulc_ctx* ctx, float p) {
     if (!(p >= 0.f && p < 1.f)) { hulc_set_error("hulc_set_dropout: p must be in [0,1)"); return 1; }      // NaN is refused too
@@ -459,6 +482,14 @@ int hulc_k_cast(int32_t dtype, const float* src, void* dst, int64_t n, void* str
     if (dtype == HULC_DTYPE_F32) hipLaunchKernelGGL((cast_kernel<float, float>), dim3(1024), dim3(256), 0, st, src, (float*)dst, (long long)n);
     else hipLaunchKernelGGL((cast_kernel<float, h16_t>), dim3(1024), dim3(256), 0, st, src, (h16_t*)dst, (long long)n);
     if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_cast: launch failed"); return 1; }
+    return 0;
+}
+// the averaged weights' update pass alone, through the optimizer step's launch (kernels.h launch_ema_update): chunks == 0 is the flat form over ema[0, n)
+int hulc_k_ema_update(float* ema, const float* p, int64_t n, float w, const int64_t* chunk_start, const int32_t* chunk_n, int32_t chunks, void* stream) {
+    if (!ema || !p || n < 1 || chunks < 0 || (chunks && (!chunk_start || !chunk_n)) || ((uintptr_t)ema | (uintptr_t)p) % 16) {
+        hulc_set_error("hulc_k_ema_update: null or misaligned argument, or n=%lld, chunks=%d out of range", (long long)n, (int)chunks); return 1; }
+    launch_ema_update((hipStream_t)stream, ema, p, (long long)n, nullptr, w, reinterpret_cast<const long long*>(chunk_start), chunk_n, chunks, nullptr, nullptr, 0);
+    if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_ema_update: launch failed"); return 1; }
     return 0;
 }
 // the row kernels of the ragged encoder pass (conv_wgrad.h), through the engine's launchers.  lens / off are device arrays the caller built (ragged_plan)

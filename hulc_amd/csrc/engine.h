@@ -520,6 +520,7 @@ struct Engine : IEngine {
         gn_tens.clear(); gn_built = false; gn_have = false;      // the gradient-norm tables follow the tensor table (rebuilt at the end of this bind if clipping by norm / tracking is configured)
         for (int i = 0; i < n; ++i) gn_tens.push_back(Ref{offs[i], numels[i]});
         tm_reset(); tm_names.clear();      // a new tensor table: every tensor trainable until hulc_trainable_set says otherwise
+        ema = nullptr; ema_swapped = false;      // ... and no average: its buffer was borrowed for the old table (hulc_ema_enable again)
         for (int i = 0; i < n; ++i) tm_names.push_back(names[i]);
         tab_order.assign(tab.begin(), tab.end());
         std::sort(tab_order.begin(), tab_order.end(), [](const std::pair<std::string, Ref>& a, const std::pair<std::string, Ref>& b) { return a.second.off < b.second.off; });
@@ -1003,6 +1004,7 @@ struct Engine : IEngine {
 #include "engine_rollout_envs.inc"      // the batched multi-environment rollout: max_envs policy slots per context (rollout_step.h)
 #include "engine_recurrent.inc"      // the 2048-wide recurrences: persistent launches (rnn_persist.h) with their probe / fallback protocol, the mcil BiRNN and BiGRU plan encoders (a12, a19)
 #include "engine_trainable.inc"      // the per-tensor trainable mask: hulc_trainable_set / _get / _steps_set and the optimizer / refresh tables without the frozen tensors
+#include "engine_ema.inc"      // the averaged weights: hulc_ema_enable / _state_get / _state_set / _swap, the update pass behind the optimizer kernel
 #include "engine_backward.inc"      // gradient all-reduce buckets + the job-wide skip vote (comm.h), hulc_backward / hulc_backward_part / hulc_backward_allreduce (a16-a17)
     // ---------------------------------------------------------------- dynamic loss scaling (kernels.h: ScalerState)
     ScalerState* scaler = nullptr;          // device; null = off (fp32 / bf16 default)
@@ -1110,6 +1112,7 @@ struct Engine : IEngine {
 
     int optim(const hulc_optim& o) override {
         if (!bound) { hulc_set_error("hulc_optimizer_step before hulc_bind_params"); return 1; }
+        if (ema_refuse("hulc_optimizer_step")) return 1;
         const bool want_norm = clip_algo == HULC_CLIP_NORM || clip_track;
         if (want_norm && !gn_built) { hulc_set_error("hulc_optimizer_step: the gradient-norm tables are missing (hulc_bind_params / hulc_grad_clip_set build them)"); return 1; }      // before the step tag advances
         // trainable mask: per-group numbers of this step (kernels.h OptGroups) — a tensor that sat out k steps is at its own step o.step - k
@@ -1156,6 +1159,7 @@ struct Engine : IEngine {
                                    (const long long*)ct.start, (const int*)ct.n, (const unsigned char*)ct.gid, og);
                 if (tiles) tr_fresh = true;
             }
+            if (ema) ema_step(tag);
             if (scaler) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(1), 0, st, scaler, (const unsigned*)rp_skip, tag);
             if (hipGetLastError() != hipSuccess) { hulc_set_error("optimizer launch failed"); return 1; }
             return prepare_weights(true);
@@ -1177,6 +1181,7 @@ struct Engine : IEngine {
         } else
             hipLaunchKernelGGL(adam_kernel, dim3(2048), dim3(256), 0, st, P, G, AM, AV, (long long)numel, lr, b1, b2, eps, (float)bc1d, (float)sqrt(bc2d), gscale,
                                shadow, (const ScalerState*)scaler, o.weight_decay, (int)(o.kind == HULC_OPT_ADAMW), (const unsigned*)rp_skip, tag, cs);
+        if (ema) ema_step(tag);      // the averaged weights follow the step under the step's own skip conditions (engine_ema.inc)
         if (scaler) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(1), 0, st, scaler, (const unsigned*)rp_skip, tag);
         if (hipGetLastError() != hipSuccess) { hulc_set_error("adam launch failed"); return 1; }
         return prepare_weights(true);

@@ -168,6 +168,7 @@
         return true;
     }
     int backward_allreduce(int dtype) override {
+        if (ema_refuse("hulc_backward_allreduce")) return 1;
         if (check_ar_dtype(dtype, "hulc_backward_allreduce")) return 1;
         if (!bucket_plan_ok()) { hulc_set_error("hulc_backward_allreduce: the module-group buckets do not partition the gradient buffer (layout changed?)"); return 1; }
         ar_dtype = dtype; ar_sent = 0; ar_voted = false;
@@ -183,6 +184,7 @@
 
     int bwd_stage = 0;    // 0: nothing pending; 1: part 0 done, encoders pending
     int backward(int part = -1) override {
+        if (ema_refuse("hulc_backward")) return 1;
         if (!have_fwd) { hulc_set_error("hulc_backward without a preceding hulc_forward_loss"); return 1; }
         persist_check("hulc_backward", false);
         bwd_since_opt = true;

@@ -161,6 +161,7 @@
 
     int trainable_set(int32_t n, const uint8_t* trainable) override {
         char msg[256];
+        if (ema_refuse("hulc_trainable_set")) return 1;
         if (hulc_trainable::check_call("hulc_trainable_set", bound, (long long)gn_tens.size(), n, msg, sizeof(msg))) { hulc_set_error("%s", msg); return 1; }
         int64_t taken = 0;
         if (steps_now(&taken)) return 1;

@@ -61,6 +61,12 @@ struct IEngine {
     virtual int trainable_set(int32_t n, const uint8_t* trainable) = 0;
     virtual int trainable_get(int64_t cap, uint8_t* trainable_out, int64_t* frozen_steps_out) = 0;
     virtual int trainable_steps_set(int32_t n, const int64_t* frozen_steps, int64_t steps_taken) = 0;
+    // ---- averaged weights (engine_ema.inc)
+    virtual int ema_enable(float* buf, float decay, int64_t start_step, int32_t warmup) = 0;
+    virtual int ema_state_get(int64_t* updates, float* last_decay) = 0;
+    virtual int ema_state_set(int64_t updates) = 0;
+    virtual int ema_swap() = 0;
+    virtual int ema_is_swapped(int32_t* out) = 0;
     // ---- data-parallel gradient all-reduce (comm.h): whole buffer after a finished backward, or bucketed inside the backward
     virtual int allreduce_grads(int bucket_dtype) = 0;
     virtual int backward_allreduce(int bucket_dtype) = 0;

@@ -2850,6 +2850,102 @@ __global__ void __launch_bounds__(256) sgd_grouped_kernel(float* __restrict__ p,
     for (int i = threadIdx.x * 4; i + 3 < n; i += 1024) sgd_update4(p, g, buf, start + i, lr, momentum, dampening, wd, nesterov, first, gscale, vclip, shadow);
 }
 
+// =========================================================================================================
+// Averaged weights (hulc_ema_enable): an exponential moving average e of the parameters p, e += (1 - d) (p - e), kept by ONE streaming pass behind the
+// optimizer kernel on its stream.  The pass is launched before scaler_update_kernel, so it sees the found_inf and the skip / tag pair the optimizer kernel
+// saw: a step the optimizer dropped leaves e and the update count alone.  The optimizer kernels themselves are not touched (their bits are pinned by the
+// reproducible-mode tests); the price is 12 bytes per averaged parameter and step (p read, e read and written).
+// The schedule lives on the device (one code path with and without the loss scaler): update number n = updates + 1 takes d = min(decay, (1 + n) / (10 + n))
+// under warm-up, else d = decay; while n < start_step the pass copies e = p (e + 1 (p - e) would not be bit-exact).
+// =========================================================================================================
+struct EmaState {
+    long long updates;      // passes that ran so far = optimizer steps taken since hulc_ema_enable / hulc_ema_state_set
+    float decay;
+    long long start_step;
+    int warmup;
+};
+// decay of update number n (n >= 1); the quotient in fp64 so that host and device round it alike
+static inline __host__ __device__ float ema_decay_of(long long n, float decay, int warmup) {
+    if (!warmup) return decay;
+    const float r = (float)((double)(1 + n) / (double)(10 + n));
+    return r < decay ? r : decay;
+}
+// one element quad.  Contraction is OFF (as in adam_finish4): w (p - e) is rounded before it is added, so p == e leaves e alone and the flat and the chunk
+// form give the same bits.  e is touched once per step: non-temporal load and store, like the optimizer's moments; p is read with a plain load (the
+// optimizer just wrote it, the weight repacks read it next)
+DEVI void ema_update4(float* __restrict__ e, const float* __restrict__ p, long long i, float w, bool copy) {
+#pragma clang fp contract(off)
+    typedef float f32x4nt __attribute__((ext_vector_type(4)));
+    const float4 pp = *reinterpret_cast<const float4*>(p + i);
+    f32x4nt ee;
+    if (copy) ee = f32x4nt{pp.x, pp.y, pp.z, pp.w};
+    else {
+        ee = __builtin_nontemporal_load(reinterpret_cast<const f32x4nt*>(e + i));
+        const float* P = &pp.x;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float r = ee[k] + w * (P[k] - ee[k]);
+            ee[k] = P[k] == ee[k] ? ee[k] : r;      // (-0) + 0 would be +0: an element that equals its parameter keeps its bits
+        }
+    }
+    __builtin_nontemporal_store(ee, reinterpret_cast<f32x4nt*>(e + i));
+}
+// chunks == 0: the whole buffer e[0, n), grid-stride (n % 4 elements at the end are updated one by one); chunks > 0: one block per chunk of the table
+// (chunk_n a multiple of 4, starts 16-byte aligned: the trainable mask's tm_flat) — what no chunk lists is neither read nor written.
+// es == null: the weight w as given (the kernel-level test entry); else w and the copy phase come from the device-side state.
+__global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, long long n, const EmaState* __restrict__ es, float w,
+                                                         const long long* __restrict__ chunk_start, const int* __restrict__ chunk_n, int chunks,
+                                                         const ScalerState* __restrict__ ss, const unsigned* __restrict__ skip, unsigned tag) {
+#pragma clang fp contract(off)
+    if (skip && *skip == tag) return;
+    if (ss && ss->found_inf) return;
+    bool copy = false;
+    if (es) {
+        const long long k = es->updates + 1;
+        copy = k < es->start_step;
+        w = 1.f - ema_decay_of(k, es->decay, es->warmup);
+    }
+    if (chunks) {
+        const long long start = chunk_start[blockIdx.x];
+        const int cn = chunk_n[blockIdx.x];
+        for (int i = threadIdx.x * 4; i + 3 < cn; i += 1024) ema_update4(e, p, start + i, w, copy);
+        return;
+    }
+    long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const long long stride = (long long)gridDim.x * blockDim.x * 4;
+    for (; i + 3 < n; i += stride) ema_update4(e, p, i, w, copy);
+    if (i < n)
+        for (long long j = i; j < n && j < i + 4; ++j) {
+            const float r = e[j] + w * (p[j] - e[j]);
+            e[j] = (copy || p[j] == e[j]) ? (copy ? p[j] : e[j]) : r;
+        }
+}
+// behind the pass, one thread: the update count advances under the pass's own conditions (scaler_update_kernel, launched after this, clears found_inf)
+__global__ void ema_count_kernel(EmaState* __restrict__ es, const ScalerState* __restrict__ ss, const unsigned* __restrict__ skip, unsigned tag) {
+    if (skip && *skip == tag) return;
+    if (ss && ss->found_inf) return;
+    es->updates++;
+}
+// p <-> e over the whole buffer (hulc_ema_swap); nothing else is written — the host refreshes the weight copies with the full hulc_prepare_weights
+__global__ void __launch_bounds__(256) ema_swap_kernel(float* __restrict__ p, float* __restrict__ e, long long n) {
+    long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const long long stride = (long long)gridDim.x * blockDim.x * 4;
+    for (; i + 3 < n; i += stride) {
+        const float4 a = *reinterpret_cast<const float4*>(p + i), b = *reinterpret_cast<const float4*>(e + i);
+        *reinterpret_cast<float4*>(p + i) = b;
+        *reinterpret_cast<float4*>(e + i) = a;
+    }
+    if (i < n)
+        for (long long j = i; j < n && j < i + 4; ++j) { const float a = p[j]; p[j] = e[j]; e[j] = a; }
+}
+// the launch both the optimizer step and the test entry (hulc_k_ema_update) go through
+static inline void launch_ema_update(hipStream_t st, float* e, const float* p, long long n, const EmaState* es, float w, const long long* chunk_start, const int* chunk_n,
+                                     int chunks, const ScalerState* ss, const unsigned* skip, unsigned tag) {
+    const long long quads = (n + 3) / 4;
+    const int grid = chunks ? chunks : (int)std::min<long long>(2048, std::max<long long>(1, (quads + 255) / 256));
+    hipLaunchKernelGGL(ema_update_kernel, dim3(grid), dim3(256), 0, st, e, p, n, es, w, chunk_start, chunk_n, chunks, ss, skip, tag);
+}
+
 // embg[(t*B+b)*W + c] = emb[(b*S+t)*128 + (128-W) + c]   (time-major copy of the last W columns: W = 64 is the gripper half,
 // perceptual_emb_slice [64,128]; W = 128 the whole embedding, mcil)
 template <typename T>

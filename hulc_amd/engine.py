@@ -67,6 +67,7 @@ class StepEngine:
         L.check(self.lib.hulc_bind_params(self.ctx, self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.adam_m.data_ptr(),
                                           self.adam_v.data_ptr(), self.numel, len(self.layout), self._names, self._offs, self._nums))
         self._bound = True
+        self.flat_ema = None      # a new bind switches the averaged weights off (hulc_ema_enable)
 
     def load_numpy(self, params: Dict[str, np.ndarray]):
         v = self.views(self.flat_params)
@@ -573,14 +574,20 @@ class StepEngine:
 
     def adam_step(self, lr=2e-4, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0):
         self.adam_t += 1
-        L.check(self.lib.hulc_adam_step(self.ctx, lr, b1, b2, eps, self.adam_t, grad_scale))
+        self._check_step(self.lib.hulc_adam_step(self.ctx, lr, b1, b2, eps, self.adam_t, grad_scale))
+
+    def _check_step(self, rc: int) -> None:
+        """L.check for the optimizer entries: a call refused because the averaged weights are swapped in was no step, `adam_t` does not count it."""
+        if rc and self.flat_ema is not None and self.ema_swapped:
+            self.adam_t -= 1
+        L.check(rc)
 
     def optimizer_step(self, kind="adam", lr=2e-4, b1=0.9, b2=0.999, eps=1e-8, weight_decay=0.0, momentum=0.0, dampening=0.0, nesterov=False, grad_scale=1.0):
         """hulc_optimizer_step: torch.optim.Adam / AdamW / SGD (conf/model/optimizer/*.yaml) over the flat buffers; `adam_t` counts the calls."""
         self.adam_t += 1
         o = L.HulcOptim(kind=L.OPTIM[kind], lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=weight_decay, momentum=momentum, dampening=dampening,
                         nesterov=int(bool(nesterov)), step=self.adam_t, grad_scale=grad_scale)
-        L.check(self.lib.hulc_optimizer_step(self.ctx, C.byref(o)))
+        self._check_step(self.lib.hulc_optimizer_step(self.ctx, C.byref(o)))
 
     # ---- data-parallel gradient all-reduce owned by the library (RCCL over xGMI, include/hulc_hip.h: hulc_comm_*) ---------------
     @staticmethod
@@ -731,6 +738,53 @@ class StepEngine:
         vals = [int(steps.get(n, 0)) for n in names] if isinstance(steps, dict) else [int(x) for x in steps]
         arr = np.ascontiguousarray(vals, np.int64)
         L.check(self.lib.hulc_trainable_steps_set(self.ctx, len(arr), arr.ctypes.data, int(steps_taken)))
+
+    # ---- averaged weights: an EMA of the parameters kept behind the optimizer step (include/hulc_hip.h: hulc_ema_*) ------------------------------
+    def ema_enable(self, decay: Optional[float], start_step: int = 0, warmup: bool = True) -> None:
+        """hulc_ema_enable: allocate `flat_ema` (numel fp32, +4 bytes per parameter), fill it with the current parameters and average from the next
+        optimizer step on: e += (1 - d)(p - e), d = spec.ema_decay_at(update number, decay, warmup); a copy e = p while the update number is below
+        start_step.  decay None switches the average off."""
+        if decay is None:
+            L.check(self.lib.hulc_ema_enable(self.ctx, None, 0.0, 0, 0))
+            self.flat_ema = None
+            return
+        spec.ema_check(decay, start_step)
+        buf = torch.empty(self.numel, dtype=torch.float32, device=self.device)
+        L.check(self.lib.hulc_ema_enable(self.ctx, buf.data_ptr(), float(decay), int(start_step), int(bool(warmup))))
+        self.flat_ema = buf
+        self._ema_cfg = dict(decay=float(decay), start_step=int(start_step), warmup=bool(warmup))
+
+    flat_ema: Optional[torch.Tensor] = None
+
+    def ema_state(self) -> Dict:
+        """{"updates", "last_decay", "decay", "start_step", "warmup"} — synchronises the stream."""
+        n, d = C.c_int64(), C.c_float()
+        L.check(self.lib.hulc_ema_state_get(self.ctx, C.byref(n), C.byref(d)))
+        return dict(updates=int(n.value), last_decay=float(d.value), **self._ema_cfg)
+
+    def ema_load(self, named_tensors: Dict, updates: int) -> None:
+        """Checkpoint restore: {name: tensor} for every tensor of the layout into `flat_ema`, and the update count (hulc_ema_state_set)."""
+        if self.flat_ema is None:
+            raise RuntimeError("ema_load: the average is off (ema_enable first)")
+        if self.ema_swapped:
+            raise RuntimeError("ema_load: the averaged weights are swapped in (ema_swap back first)")
+        missing = [n for n in self.layout if n not in named_tensors]
+        if missing:
+            raise KeyError(f"ema_load: missing tensors {missing[:5]}")
+        for n, t in self.views(self.flat_ema).items():
+            t.copy_(torch.as_tensor(named_tensors[n]).to(self.device, torch.float32).reshape(t.shape))
+        L.check(self.lib.hulc_ema_state_set(self.ctx, int(updates)))
+
+    def ema_swap(self) -> None:
+        """hulc_ema_swap: exchange `flat_params` and `flat_ema` bit for bit and rebuild every weight copy; a second call swaps back.  While swapped,
+        validate / forward_loss / the rollouts run on the averaged weights and optimizer_step / backward / set_trainable / ema_enable raise."""
+        L.check(self.lib.hulc_ema_swap(self.ctx))
+
+    @property
+    def ema_swapped(self) -> bool:
+        out = C.c_int32()
+        L.check(self.lib.hulc_ema_swapped(self.ctx, C.byref(out)))
+        return bool(out.value)
 
     def get_tensor(self, name: str, n: int) -> np.ndarray:
         out = np.zeros(n, np.float32)

@@ -15,6 +15,7 @@ There is no torch/CPU fallback: constructing the module without the HIP library 
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import math
 import os
@@ -237,8 +238,13 @@ class Hulc(torch.nn.Module):
         device: str = "cuda:0",
         seed: int = 42,
         freeze_modules=None,
+        ema_decay: Optional[float] = None,
+        ema_start_step: int = 0,
+        ema_warmup: bool = True,
     ):
         super().__init__()
+        if ema_decay is not None:      # before an engine is built: the argument rules of hulc_ema_enable
+            spec.ema_check(ema_decay, ema_start_step)
         # ---- options outside the hot path are rejected loudly instead of silently ignored (SURVEY §2.1 OUT OF SCOPE rows)
         if state_recons:
             raise NotImplementedError("state_recons needs the proprio encoder, which changes the width of the perceptual latent (disabled in every BASELINE config): not built")
@@ -393,6 +399,11 @@ class Hulc(torch.nn.Module):
         self.reset_parameters(seed)
         if freeze_modules:
             self.freeze_modules(freeze_modules)
+        # averaged weights: the engine keeps an EMA of the parameters behind every optimizer step; ema_scope() swaps it in
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_start_step, self.ema_warmup = int(ema_start_step), bool(ema_warmup)
+        if self.ema_decay is not None:
+            self.ema_restart()
         self.logged: Dict[str, float] = {}
         self._epoch_acc: Dict[str, list] = {}
         self._grads_reduced = False
@@ -460,6 +471,41 @@ class Hulc(torch.nn.Module):
         self._sync_trainable()
         self.train()
 
+    # ---- averaged weights ------------------------------------------------------------------
+    @property
+    def ema_enabled(self) -> bool:
+        return self.ema_decay is not None
+
+    def ema_restart(self) -> None:
+        """Start the average again from the current parameters, update count 0 (construction; a resume from a checkpoint without `ema_state`)."""
+        self.engine.ema_enable(self.ema_decay, self.ema_start_step, self.ema_warmup)
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """Swap the averaged weights in on entry and the raw ones back on exit, also on an exception.  Inside, state_dict(), validation_step, reset / step
+        and BatchedPolicy see the averaged weights (the parameter views alias the flat buffer); training_step and the optimizer raise.  Nested scopes and
+        a module without ema_decay pass through."""
+        if not self.ema_enabled or self.engine.ema_swapped:
+            yield self
+            return
+        self.engine.ema_swap()
+        try:
+            yield self
+        finally:
+            self.engine.ema_swap()
+
+    def ema_state_dict(self) -> Dict[str, Any]:
+        """What a checkpoint carries under "ema_state": the averaged tensors by parameter name, the update count and the schedule."""
+        e = self.engine
+        if e.ema_swapped:
+            raise RuntimeError("ema_state_dict inside ema_scope(): the averaged weights are swapped in")
+        st = e.ema_state()
+        return dict(params={n: v.detach().clone() for n, v in e.views(e.flat_ema).items()}, updates=st["updates"], decay=st["decay"],
+                    start_step=st["start_step"], warmup=st["warmup"])
+
+    def load_ema_state_dict(self, sd: Dict[str, Any]) -> None:
+        self.engine.ema_load(sd["params"], int(sd["updates"]))
+
     def _buffers_dict(self) -> Dict[str, torch.Tensor]:
         lin = torch.linspace(-1.0, 1.0, 21)
         ad = "action_decoder."
@@ -499,6 +545,8 @@ class Hulc(torch.nn.Module):
                         src = src[: p.shape[0]]          # hulc/utils/utils.py:9-11 trims position-embedding rows
                     p.copy_(src.to(p.device, torch.float32).reshape(p.shape))
         self.engine.prepare_weights()
+        if self.ema_enabled and not self.engine.ema_swapped:
+            self.ema_restart()      # the average starts from the weights it was handed (a resume restores it afterwards: load_ema_state_dict)
         return missing, unexpected
 
     # ---- Lightning-style hooks -------------------------------------------------------------------------------

@@ -120,7 +120,8 @@ EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_s
            "hulc_k_window_compact", "hulc_k_rows_expand", "hulc_k_rows_reduce", "hulc_k_gemm_epi", "hulc_k_gemm_multi", "hulc_k_gemm_pick", "hulc_k_gemm_wgrad_nsplit",
            "hulc_k_det_head_loss", "hulc_k_det_head_bwd", "hulc_k_det_head_act",
            "hulc_k_conv_wgrad_t", "hulc_k_conv1_wgrad_u8_t", "hulc_k_conv_tile_t", "hulc_k_conv_pair_t", "hulc_k_conv_plan",
-           "hulc_decoder_body_select", "hulc_trainable_set", "hulc_trainable_get", "hulc_trainable_steps_set"]
+           "hulc_decoder_body_select", "hulc_trainable_set", "hulc_trainable_get", "hulc_trainable_steps_set",
+           "hulc_ema_enable", "hulc_ema_state_get", "hulc_ema_state_set", "hulc_ema_swap", "hulc_ema_swapped", "hulc_k_ema_update"]
 
 _lib = None
 
@@ -284,6 +285,13 @@ def load():
         lib.hulc_trainable_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         lib.hulc_trainable_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.hulc_trainable_steps_set.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    if hasattr(lib, "hulc_ema_enable") or not os.environ.get("HULC_LIB_PATH"):
+        lib.hulc_ema_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int32]
+        lib.hulc_ema_state_get.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        lib.hulc_ema_state_set.argtypes = [C.c_void_p, C.c_int64]
+        lib.hulc_ema_swap.argtypes = [C.c_void_p]
+        lib.hulc_ema_swapped.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        lib.hulc_k_ema_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     if hasattr(lib, "hulc_k_conv_plan") or not os.environ.get("HULC_LIB_PATH"):
         P, I, PI = C.c_void_p, C.c_int32, C.POINTER(C.c_int32)
         lib.hulc_k_conv_wgrad_t.argtypes = [I, I, P, P, P, P, I, I, PI, P]

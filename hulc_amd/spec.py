@@ -230,6 +230,23 @@ def prefix_mask(names, prefixes) -> List[bool]:
     return out
 
 
+def ema_decay_at(n: int, decay: float, warmup: bool = True) -> float:
+    """Decay of update number n (counted from 1) of the averaged weights (hulc_ema_enable): min(decay, (1 + n) / (10 + n)) under warm-up — 2/11 at the
+    first update, rising monotonically until it reaches `decay` — else `decay` throughout.  The engine evaluates the same expression on the device."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"ema_decay_at: updates count from 1 (got {n})")
+    return min(float(decay), (1.0 + n) / (10.0 + n)) if warmup else float(decay)
+
+
+def ema_check(decay, start_step: int = 0) -> None:
+    """The argument rules of hulc_ema_enable, for callers that must refuse before an engine exists."""
+    if not (isinstance(decay, (int, float)) and 0.0 < float(decay) < 1.0):
+        raise ValueError(f"ema_decay {decay!r}: the decay of the averaged weights must lie in (0, 1)")
+    if int(start_step) < 0:
+        raise ValueError(f"ema_start_step {start_step!r} must not be negative")
+
+
 def n_params(d: ModelDims) -> int:
     return sum(int(np.prod(s)) if len(s) else 1 for _, s, _ in param_table(d))
 

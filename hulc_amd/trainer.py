@@ -6,6 +6,7 @@ One process per GPU; gradients are combined by hulc_amd.parallel (RCCL).
 """
 from __future__ import annotations
 
+import contextlib
 import glob
 import math
 import os
@@ -116,11 +117,15 @@ class ModelCheckpoint:
 
 def save_checkpoint(path, module, optimizer, epoch, global_step, lr_scheduler=None):
     """Lightning-style checkpoint dict; `state_dict` keys are the reference's."""
-    torch.save({"epoch": epoch, "global_step": global_step, "state_dict": {k: v.cpu() for k, v in module.state_dict().items()},
-                "optimizer_states": [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in optimizer.state_dict().items()}],
-                "lr_schedulers": [lr_scheduler.state_dict()] if lr_scheduler is not None and hasattr(lr_scheduler, "state_dict") else [],
-                "hyper_parameters": {"kind": module.kind, "use_clip_auxiliary_loss": module.use_clip_auxiliary_loss, "precision": module.precision,
-                                     "rnn_type": module.dims.rnn_type, "max_window": module.dims.max_window, "decoder_body": module.dims.decoder_body}}, path)
+    ck = {"epoch": epoch, "global_step": global_step, "state_dict": {k: v.cpu() for k, v in module.state_dict().items()},
+          "optimizer_states": [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in optimizer.state_dict().items()}],
+          "lr_schedulers": [lr_scheduler.state_dict()] if lr_scheduler is not None and hasattr(lr_scheduler, "state_dict") else [],
+          "hyper_parameters": {"kind": module.kind, "use_clip_auxiliary_loss": module.use_clip_auxiliary_loss, "precision": module.precision,
+                               "rnn_type": module.dims.rnn_type, "max_window": module.dims.max_window, "decoder_body": module.dims.decoder_body}}
+    if getattr(module, "ema_enabled", False):      # the averaged weights next to the raw ones (`state_dict` stays raw: a resume continues the same trajectory)
+        es = module.ema_state_dict()
+        ck["ema_state"] = dict(es, params={k: v.cpu() for k, v in es["params"].items()})
+    torch.save(ck, path)
 
 
 def get_last_checkpoint(log_dir: str) -> Optional[str]:
@@ -259,6 +264,14 @@ class Trainer:
         """Lightning's validation loop for this module: eval mode, validation_step over the val batches, mean of every `val*` metric."""
         if not hasattr(datamodule, "val_dataloader"):
             return {}
+        # a module with averaged weights (ema_decay) is validated on them: swapped in before on_validation_epoch_start (the CLIP ground-truth projections are
+        # encoded with the weights the batches run on), swapped out behind on_validation_epoch_end
+        with (module.ema_scope() if getattr(module, "ema_enabled", False) else contextlib.nullcontext()):
+            out = self._validation_loop(module, datamodule)
+        self.val_history.append(out)
+        return out
+
+    def _validation_loop(self, module, datamodule) -> Dict[str, float]:
         module.eval()
         if hasattr(module, "on_validation_epoch_start"):
             module.on_validation_epoch_start()
@@ -279,9 +292,7 @@ class Trainer:
         module.train()
         if hasattr(module, "on_validation_epoch_end"):
             module.on_validation_epoch_end()
-        out = parallel.mean_metrics(sums, counts, device=module.device)
-        self.val_history.append(out)
-        return out
+        return parallel.mean_metrics(sums, counts, device=module.device)
 
     def fit(self, module, datamodule, ckpt_path: Optional[str] = None):
         self.rank, self.world, self.local = parallel.init_from_env()
@@ -310,6 +321,13 @@ class Trainer:
             self.optimizer.load_state_dict({k: (v.to(module.device) if torch.is_tensor(v) else v) for k, v in ck["optimizer_states"][0].items()})
             if ck.get("lr_schedulers") and hasattr(sched, "load_state_dict"):
                 sched.load_state_dict(ck["lr_schedulers"][0])
+            if getattr(module, "ema_enabled", False):
+                if ck.get("ema_state"):
+                    module.load_ema_state_dict(ck["ema_state"])
+                else:      # a checkpoint written without the average: it starts from the loaded weights
+                    module.ema_restart()
+                    if self.rank == 0:
+                        print(f"[hulc_amd] {ckpt_path} holds no ema_state: the averaged weights start from the loaded weights", flush=True)
             self.current_epoch, self.global_step = ck["epoch"] + 1, ck["global_step"]
             module.global_step = self.global_step
         module.on_fit_start()

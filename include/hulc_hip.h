@@ -286,6 +286,33 @@ int hulc_trainable_get(hulc_ctx* ctx, int64_t cap, uint8_t* trainable_out, int64
  * device-side count, so call hulc_scaler_set first).  Call it after the hulc_trainable_set that restores the mask. */
 int hulc_trainable_steps_set(hulc_ctx* ctx, int32_t n_tensors, const int64_t* frozen_steps, int64_t steps_taken);
 
+/* ---- Averaged weights: an exponential moving average (EMA) of the bound parameters, kept behind the optimizer step and swapped in for validation and rollout.
+ * hulc_ema_enable: `ema` = numel fp32 on the device in the layout of hulc_bind_params, BORROWED like the four buffers of that call (16-byte aligned; it must
+ * outlive the context or a later hulc_ema_enable(NULL)); NULL switches the average off.  Enabling copies the current parameters into it and sets the update
+ * count to 0.  Errors, none of which launches anything: a call before hulc_bind_params, decay outside (0, 1), start_step < 0, a call while swapped.  A new
+ * hulc_bind_params switches the average off.  A context that never enables it allocates, launches and computes what it always did.
+ *   update   every hulc_adam_step / hulc_optimizer_step that the optimizer kernel performs is followed, on the same stream, by e += (1 - d) (p - e) in fp32
+ *            over the bound buffer (12 bytes per parameter: p read, e read and written).  Update number n (counted from 1) uses d = decay, or with
+ *            warmup != 0 d = min(decay, (1 + n) / (10 + n)); while n < start_step the pass copies e = p instead.  The schedule is evaluated on the device.
+ *   skips    a step the optimizer drops — non-finite gradients under the fp16 loss scaler, a failed persistent recurrence — leaves e untouched and does
+ *            not count as an update.
+ *   frozen   under a trainable mask (hulc_trainable_set) the pass walks the mask's chunk table: the average of a frozen tensor is neither read nor written.
+ *   ranks    data parallel: every rank holds the same parameters after the step and applies the same update; no collective is involved.
+ * Not built: the average fused into the optimizer kernels, uniform (SWA) averaging, an average of anything but the bound parameters. */
+int hulc_ema_enable(hulc_ctx* ctx, float* ema, float decay, int64_t start_step, int32_t warmup);
+/* The update count and the decay the last update used (0 before the first one and during the copy phase); either pointer may be NULL.  Synchronises the stream. */
+int hulc_ema_state_get(hulc_ctx* ctx, int64_t* updates, float* last_decay);
+/* Checkpoint restore: the update count.  The contents of the buffer are the caller's to restore. */
+int hulc_ema_state_set(hulc_ctx* ctx, int64_t updates);
+/* Exchange the parameter buffer with the average, element for element, and rebuild every weight copy from it (the full hulc_prepare_weights: frozen tensors
+ * included).  A second call swaps back; both buffers get their bits back exactly.  While swapped the forward-only entries (hulc_validate, hulc_forward_loss,
+ * hulc_rollout_*, hulc_clip_gt_encode ...) run on the averaged weights, and hulc_optimizer_step, hulc_adam_step, hulc_backward, hulc_backward_part,
+ * hulc_backward_allreduce, hulc_ema_enable and hulc_trainable_set return an error that says so before any launch.  Every swap drops what was computed from
+ * the other weights: the activations of the last forward (a backward needs a new forward), the B = 1 rollout state and every rollout slot, as
+ * hulc_rollout_reset and hulc_rollout_envs_reset(all) would; the projections of hulc_clip_gt_encode are the caller's to encode again. */
+int hulc_ema_swap(hulc_ctx* ctx);
+int hulc_ema_swapped(hulc_ctx* ctx, int32_t* out);
+
 /* ---- Validation forward: one modality of Hulc.validation_step (hulc/models/hulc.py:770-797) = lmp_val
  * (:301-388): plan proposal and plan recognition each sample a plan (distributions.py:37-41), the decoder is run with both
  * (LogisticDecoderRNN.loss_and_act, logistic_decoder_rnn.py:85-100): NLL loss, a sampled action (_sample :234-258) mapped back to
@@ -755,6 +782,10 @@ int hulc_k_rows_expand(int32_t elem_bytes, const void* src, const int32_t* lens,
 /* hulc_k_rows_reduce: rows_reduce_kernel.  src [B*S][n] fp32 -> dst [N'][n] fp32: dst[off[b] + t] = src[b, t] for t < lens[b] - 1, dst[off[b] + lens[b] - 1] =
  *   ((src[b, lens[b]-1] + src[b, lens[b]]) + ...) + src[b, S-1] in fp32, ascending t, no atomics.  n a multiple of 4, both pointers 16-byte aligned. */
 int hulc_k_rows_reduce(const float* src, const int32_t* lens, const int32_t* off, int32_t B, int32_t S, int32_t n, float* dst, void* hip_stream);
+/* hulc_k_ema_update: ema_update_kernel (the averaged weights' pass, hulc_ema_enable) with the weight given: ema[i] += w (p[i] - ema[i]) in fp32, the product
+ *   rounded before the sum; an element equal to its parameter keeps its bits.  chunks == 0: the flat form over [0, n); chunks > 0: one block per entry of the
+ *   DEVICE tables chunk_start / chunk_n (starts and lengths multiples of 4) — elements no chunk lists are neither read nor written.  Both pointers 16-byte aligned. */
+int hulc_k_ema_update(float* ema, const float* p, int64_t n, float w, const int64_t* chunk_start, const int32_t* chunk_n, int32_t chunks, void* hip_stream);
 
 /* ---- the fused plan-recognition transformer layer kernels (csrc/tr_fused.h), launched as the engine launches them.  dtype = HULC_DTYPE_BF16 or HULC_DTYPE_F16
  * (the kernels exist in the 16-bit units only; HULC_DTYPE_F32 is refused).  d_model 128, 8 heads of 16, 2048 hidden units; N = B * S rows, window b = rows
