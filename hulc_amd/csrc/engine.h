@@ -808,7 +808,7 @@ struct Engine : IEngine {
     void lin_wgrad(const T* dY, const T* X, long long ldx, int M, int N, int K, float* dW, long long lddw, float* db, float* db2 = nullptr) {
         if constexpr (std::is_same<T, h16_t>::value) {
             if (M <= 64) {          // one fused launch: tr-read wgrad + bias grad, no transposed copies
-                hipLaunchKernelGGL(lin_bwd_smallm_kernel, dim3(cdiv(N, 64), cdiv(K, 128)), dim3(256), 0, st, dY, (long long)N, X, ldx, M, N, K, dW, lddw, db, db2, 64, grad_first(dW) ? 1 : 0);
+                hipLaunchKernelGGL(lin_bwd_smallm_kernel, dim3(cdiv(N, 64), cdiv(K, 128)), dim3(256), 0, st, dY, (long long)N, X, ldx, M, N, K, dW, lddw, db, db2, grad_first(dW) ? 1 : 0);
                 return;
             }
             grad_ensure_zero(dW);      // the paths below accumulate
@@ -894,38 +894,65 @@ struct Engine : IEngine {
     // grads_fresh: the gradient buffer is all zeros (hulc_zero_grads was the last thing that touched it).  The first backward after it may STORE
     // the weight gradients that have a single whole-tensor contribution instead of reading the zeros back and adding (200 MB of reads per step):
     // 0 + x == x exactly, so the result is bit-identical.  A second backward before the next zero_grads (one pass per modality) accumulates.
-    // deferred weight gradients of the plan-recognition transformer (16-bit fused path): jobs collected by tr_wgrad_add, one launch in tr_wgrads_flush
+    // ---- deferred Linear weight / bias gradients (16-bit engines).  Nothing in a backward reads a weight gradient before its all-reduce bucket, the end of the
+    // backward or the optimizer, so part 0 only QUEUES them (wq_add: the decoder heads, every M = B MLP layer, fc_state / fc of the plan recognition, the eight
+    // transformer Linears) and wq_flush runs the queue as two launches at the end of part 0 — the M <= 64 jobs in lin_bwd_smallm_batched_kernel (one row step,
+    // write-bound), the many-row jobs in lin_bwd_stream_kernel — instead of seven dependent launches behind their data-gradient GEMMs plus two slab sums.  dY and X
+    // of a queued job must stay untouched until the flush: forward activations and gradient buffers of their own (trb_*, mlp_dy sets, dheads, dprl_t, dseq_t, ...).
+    // With a collective armed (ar_dtype >= 0) bucket_ready flushes before it puts a bucket on the wire.  The lazy-zero state of a target (grad_first) is read at
+    // flush time, when the launch that stores or adds is actually enqueued.
     T *trb_c[2] = {nullptr, nullptr}, *trb_a[2] = {nullptr, nullptr}, *trb_d[2] = {nullptr, nullptr}, *trb_b[2] = {nullptr, nullptr};
-    LinBwdBatch tr_wjobs{};
-    int tr_wblocks = 0;
-    void tr_wgrad_add(const T* dY, const T* X, const LinW& L) {
-        if constexpr (std::is_same<T, h16_t>::value) {
-            LinBwdJob& J = tr_wjobs.j[tr_wjobs.n++];
-            J.dY = dY; J.X = X; J.dW = L.dW; J.db = L.db; J.ldx = L.K; J.lddw = L.K; J.N = L.N; J.K = L.K; J.nx = cdiv(L.N, 64); J.blk0 = tr_wblocks; J.part = nullptr;
-            tr_wblocks += J.nx * cdiv(L.K, 128);
-        }
+    struct WqJob { const T* dY; const T* X; long long ldx, lddw; int M, N, K; float* dW; float* db; bool heads; };
+    std::vector<WqJob> wq;
+    // row ranges of a many-row job: one (no slab, the workgroup writes dW itself) when the launch has at least a workgroup for every second CU anyway, else two
+    static int lin_stream_nsplit(int tiles, int M) { return (M > 256 && tiles < 128) ? 2 : 1; }
+    // the M = B layers outside the MLP helper join the queue in the row range their one-launch form (lin_wgrad) covers; more rows keep lin_wgrad's transposed GEMM
+    bool wq_small(int M) const { return std::is_same<T, h16_t>::value && M <= 64; }
+    void wq_add(const T* dY, const T* X, long long ldx, int M, int N, int K, float* dW, long long lddw, float* db, bool heads = false) {
+        wq.push_back(WqJob{dY, X, ldx, lddw, M, N, K, dW, db, heads});
     }
-    void tr_wgrads_flush(int M) {
+    void wq_add(const T* dY, const T* X, int M, const LinW& L) {
         if constexpr (std::is_same<T, h16_t>::value) {
-            if (tr_wjobs.n == 0) return;
-            const int chunk = 256, nz = cdiv(M, chunk);
-            tr_wjobs.M = M; tr_wjobs.store = 0; tr_wjobs.mchunk = chunk;
-            // slabs [nz][N][K] per job out of the convolution slab arena (free here: the encoders' backward has not started), summed by an unpack launch
-            UnpackBatch ub{};
-            int64_t cur = 0; int ublocks = 0;
-            for (int i = 0; i < tr_wjobs.n; ++i) {
-                LinBwdJob& J = tr_wjobs.j[i];
-                const int64_t need = (int64_t)nz * J.N * J.K;
-                if (part_cur + cur + need > this->partcap) { J.part = nullptr; continue; }      // no room: this job adds with atomics
-                J.part = this->part + part_cur + cur; cur += need;
-                UnpackJob& U = ub.j[ub.n++];
-                U.part = J.part; U.grad = J.dW; U.slab = (long long)J.N * J.K; U.nsplit = nz; U.O = J.N; U.I = J.K; U.KH = U.KW = 1; U.nhwc = 0; U.blk0 = ublocks; U.ysplit = 1;
-                ublocks += cdiv(J.N * J.K, 1024);
+            if (M <= 64 || lin_stream_ok(dY, X, L.K, L.N)) { wq_add(dY, X, L.K, M, L.N, L.K, L.dW, L.K, L.db); return; }
+        }
+        lin_wgrad(dY, X, L.K, M, L.N, L.K, L.dW, L.K, L.db);      // rows the streaming body's DMA cannot fetch: the transposed GEMM, at once
+    }
+    void wq_flush() {
+        if constexpr (std::is_same<T, h16_t>::value) {
+            if (wq.empty()) return;
+            int tiles = 0;
+            for (const WqJob& q : wq) if (q.M > 64) tiles += cdiv(q.N, 64) * cdiv(q.K, 128);
+            LinBwdBatch ob{}; int oblk = 0;
+            LinStreamBatch sb{}; int sblk = 0;
+            auto run_one = [&]() { if (ob.n) hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(oblk), dim3(256), 0, st, ob); ob.n = 0; oblk = 0; };
+            auto run_str = [&]() { launch_lin_stream(st, sb, sblk); sb.n = 0; sblk = 0; };
+            const WqJob* hj = nullptr; int hsplit = 1; bool hcolsum = false;
+            for (const WqJob& q : wq) {
+                if (q.M <= 64) {
+                    if (ob.n == LBS_MAX_JOBS) run_one();
+                    LinBwdJob& J = ob.j[ob.n++];
+                    J.dY = q.dY; J.X = q.X; J.dW = q.dW; J.db = q.db; J.ldx = q.ldx; J.lddw = q.lddw; J.M = q.M; J.N = q.N; J.K = q.K; J.nx = cdiv(q.N, 64); J.blk0 = oblk;
+                    J.store = grad_first(q.dW) ? 1 : 0;
+                    oblk += J.nx * cdiv(q.K, 128);
+                    continue;
+                }
+                if (sb.n == LBT_MAX_JOBS) run_str();
+                if (q.heads) {      // the packed heads: slab(s) at the start of the (idle) convolution slab arena, re-packed into the four tensors by unpack_heads_grad_kernel below
+                    hj = &q; hsplit = lin_stream_nsplit(tiles, q.M);
+                    if (part_cur + (int64_t)hsplit * q.N * q.K > this->partcap) hsplit = 1;      // (room for one slab was checked when the job was queued)
+                    hcolsum = repro && hsplit > 1;      // reproducible mode: the two ranges' bias sums would land with atomics -> two-stage column sum instead
+                    if (hsplit > 1 && !repro) nd(ND_LIN_BWD_ROWS);
+                    lin_stream_add(sb, sblk, (const h16_t*)q.dY, (const h16_t*)q.X, q.ldx, q.M, q.N, q.K, nullptr, q.lddw, hcolsum ? nullptr : q.db, this->part + part_cur, hsplit, 1);
+                } else lin_stream_add(sb, sblk, (const h16_t*)q.dY, (const h16_t*)q.X, q.ldx, q.M, q.N, q.K, q.dW, q.lddw, q.db, nullptr, 1, grad_first(q.dW) ? 1 : 0);
             }
-            if (nz > 1) nd(ND_LIN_BWD_ROWS);      // the jobs' bias gradients (and the weight gradients of a job without slabs) land with atomics
-            hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(tr_wblocks, nz), dim3(256), 0, st, tr_wjobs);
-            if (ub.n > 0) hipLaunchKernelGGL(unpack_conv_wgrad_batched_kernel, dim3(ublocks, 1), dim3(256), 0, st, ub);
-            tr_wjobs.n = 0; tr_wblocks = 0;
+            run_one(); run_str();
+            if (hj) {
+                if (hcolsum) colsum(hj->dY, hj->N, hj->M, hj->N, hj->db);
+                const HeadPack hp = head_pack();
+                const int rows = head_rows[0] + head_rows[1] + head_rows[2] + head_rows[3];
+                hipLaunchKernelGGL(unpack_heads_grad_kernel, dim3(cdiv((long long)rows * HID, 256)), dim3(256), 0, st, hp, (const float*)(this->part + part_cur), (const float*)hj->db, HID, hsplit, (long long)hj->N * hj->K);
+            }
+            wq.clear();
         }
     }
     float* dparts = nullptr;                // fused FFN backward: the four hidden-quarter partials of the gradient entering norm1

@@ -117,6 +117,7 @@
     // called by backward() after the stage that finalises bucket i has been enqueued
     int bucket_ready(int i) {
         if (ar_dtype < 0 || (ar_sent >> i) & 1u) return 0;
+        wq_flush();                          // the bucket must carry final gradients: the queued weight gradients (whichever bucket they lie in) are enqueued in front of it
         const std::vector<Bucket> v = bucket_plan();
         ar_sent |= 1u << i;
         if (range_all_frozen(v[i].lo, v[i].hi)) return (i == 4 && !ar_voted) ? vote_only() : 0;      // bucket 4 is the last one issued
@@ -203,6 +204,7 @@
         if (!arena_clean) HIP_CHECK(hipMemsetAsync(zero_arena, 0, sizeof(float) * zero_n, st));   // demb, dgoal, dseqf, heads / fc7 gradient temporaries, work counters
         arena_clean = false;
         work_ctr_next = 0;
+        wq.clear(); mlp_dy_next = 0;         // (a backward that failed half way leaves nothing behind in the weight-gradient queue)
         // tests (hulc_set_option debug_poison_partials): the weight-gradient slab arena is never zeroed — every slab element must be WRITTEN before the
         // unpack launches sum it.  NaN-filling it makes a slab cell that is read-modify-written (ADVICE r3: the ragged last k-tile of fc7) visible
         if (poison_partials) HIP_CHECK(hipMemsetAsync(this->part, 0xFF, sizeof(float) * (size_t)this->partcap, st));
@@ -258,18 +260,9 @@
                 const T* const hx = mlp ? Zx1 : H1;      // what the heads read: y of the feed-forward body, else the layer-1 state
                 bool slabs = false;
                 if constexpr (std::is_same<T, h16_t>::value) {
-                    // row-split weight gradient (see tr_wgrads_flush): one slab per 256 rows in the (idle) convolution slab arena, summed by the unpack launch
-                    const int nz = cdiv(SB, 256);
-                    if (SB > 64 && part_cur + (int64_t)nz * NHEAD * HID <= this->partcap) {
-                        LinBwdBatch bt{}; bt.M = SB; bt.store = 0; bt.mchunk = 256; bt.n = 1;
-                        LinBwdJob& J = bt.j[0];
-                        // the row chunks' bias sums land with atomics (nz > 1); reproducible mode takes the bias gradient from the two-stage column sum below
-                        if (nz > 1 && !repro) nd(ND_LIN_BWD_ROWS);
-                        J.dY = dheads; J.X = hx; J.dW = nullptr; J.db = (repro && nz > 1) ? nullptr : dbheads_tmp; J.ldx = HID; J.lddw = HID; J.N = NHEAD; J.K = HID; J.nx = cdiv(NHEAD, 64); J.blk0 = 0;
-                        J.part = this->part + part_cur;
-                        hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(J.nx * cdiv(HID, 128), nz), dim3(256), 0, st, bt);
-                        if (!J.db) colsum(dheads, NHEAD, SB, NHEAD, dbheads_tmp);
-                        hipLaunchKernelGGL(unpack_heads_grad_kernel, dim3(cdiv((long long)rows * HID, 256)), dim3(256), 0, st, hp, J.part, dbheads_tmp, HID, nz, (long long)NHEAD * HID);
+                    // many rows: queued for the flush at the end of part 0 (wq_flush: slab(s) in the idle convolution slab arena, re-packed by unpack_heads_grad_kernel there)
+                    if (SB > 64 && lin_stream_ok(dheads, hx, HID, NHEAD) && part_cur + (int64_t)NHEAD * HID <= this->partcap) {
+                        wq_add(dheads, hx, HID, SB, NHEAD, HID, nullptr, HID, dbheads_tmp, true);
                         slabs = true;
                     }
                 }
@@ -393,7 +386,8 @@
             hipLaunchKernelGGL(pp_input_bwd_kernel, dim3(cdiv(B * (EMB + GOAL), 256)), dim3(256), 0, st, dppx, B, EMB, GOAL, demb, (long long)S * EMB, dgoal);
             if (bucket_ready(1)) return 1;   // plan_proposal.* final
             // fc_state of plan recognition
-            lin_wgrad(dprl_t, seqf_t, FCH, B, PLAN, FCH, pr_fs.dW, FCH, pr_fs.db);
+            if (wq_small(B)) wq_add(dprl_t, seqf_t, B, pr_fs);
+            else lin_wgrad(dprl_t, seqf_t, FCH, B, PLAN, FCH, pr_fs.dW, FCH, pr_fs.db);
             { EpiP ep = epi(dseqf, true);
               if (have_dseq) ep.accumulate = 1;       // the CLIP branch already wrote its share
               else { ep.out2 = dseq_t; ep.out2_lo = 0; ep.out2_hi = (long long)B * FCH; dseq_cast_done = true; }     // sole contribution: plain store + the 16-bit copy in the same epilogue
@@ -415,7 +409,8 @@
         // ---- plan recognition backward
         if (have_dseq) {
             if (!dseq_cast_done) hipLaunchKernelGGL((cast_kernel<float, T>), dim3(cdiv(B * FCH, 256)), dim3(256), 0, st, dseqf, dseq_t, (long long)B * FCH);
-            lin_wgrad(dseq_t, xm, EMB, B, FCH, EMB, pr_fc.dW, EMB, pr_fc.db);
+            if (wq_small(B)) wq_add(dseq_t, xm, B, pr_fc);
+            else lin_wgrad(dseq_t, xm, EMB, B, FCH, EMB, pr_fc.dW, EMB, pr_fc.db);
             { EpiP ep = epi(dxm, true); lin_dgrad(dseq_t, B, pr_fc, ep, dense_out(EMB)); }
             float* dx = dxa; float* dnext = dxb;
             if (!ln_bwd_can_bcast) hipLaunchKernelGGL(bcast_over_s_kernel, dim3(cdiv((long long)N * EMB, 256)), dim3(256), 0, st, dxm, B, S, EMB, dx);
@@ -425,7 +420,7 @@
                 bool ffn_fused = false;
                 if constexpr (std::is_same<T, h16_t>::value) ffn_fused = trf_on() && S <= 64;       // row-wise: half windows for S > 32
                 // 16-bit fused path: every incoming gradient of the layer's four Linear layers stays in its own buffer, and the eight weight / bias
-                // gradients of both layers run as ONE row-split launch after the loop (tr_wgrads_flush) instead of 16 transposes + GEMMs
+                // gradients of both layers are queued for the flush at the end of part 0 (wq_add / wq_flush) instead of 16 transposes + GEMMs
                 T *b_c = dt_c, *b_a = dt_a, *b_d = dt_c, *b_b = dt_b;
                 bool defer_w = false;
                 if constexpr (std::is_same<T, h16_t>::value) {
@@ -447,7 +442,7 @@
                             if (B > 1) nd(ND_TR_LN_BWD);      // norm2's parameter gradients: one atomic per column and window
                             launch_tr_ffn_bwd(st, q);
                         }
-                        tr_wgrad_add(b_c, hff[l], tr_l2[l]); tr_wgrad_add(b_a, x1t[l], tr_l1[l]);
+                        wq_add(b_c, hff[l], N, tr_l2[l]); wq_add(b_a, x1t[l], N, tr_l1[l]);
                     }
                 }
                 if (!ffn_fused) {
@@ -468,23 +463,22 @@
                         q.Wot = tr_out[l].Wtfr; q.Wint = tr_in[l].Wtfr; q.qkv = qkv[l]; q.Pat = Pat[l]; q.b_d = b_d; q.b_b = b_b; q.dy_f = dy_f; q.dx = dx;
                         q.B = B; q.S = S; q.dp = dp; q.seed_o = site_seed(2 + 4 * l); q.seed_att = site_seed(1 + 4 * l);
                         launch_tr_attn_bwd(st, q);
-                        tr_wgrad_add(b_d, ao[l], tr_out[l]);
-                        tr_wgrad_add(b_b, xt[l], tr_in[l]);
+                        wq_add(b_d, ao[l], N, tr_out[l]);
+                        wq_add(b_b, xt[l], N, tr_in[l]);
                         continue;
                     }
                 }
                 // LN1 (after the fused FFN backward its incoming gradient is the sum of the four hidden-quarter partials)
                 ln_bwd(ffn_fused ? dparts : dnext, EMB, y1[l], EMB, st1[l], tr_n1g[l], N, EMB, dy_f, EMB, 0, b_d, EMB, d_tr_n1g[l], d_tr_n1b[l], dp, site_seed(2 + 4 * l), 0, 1.f,
                        ffn_fused ? 4 : 1, (long long)N * EMB);
-                if (defer_w) tr_wgrad_add(b_d, ao[l], tr_out[l]);
+                if (defer_w) wq_add(b_d, ao[l], N, tr_out[l]);
                 else lin_wgrad(b_d, ao[l], EMB, N, EMB, EMB, tr_out[l].dW, EMB, tr_out[l].db);
                 { EpiP ep = epi(dt_a, false); lin_dgrad(b_d, N, tr_out[l], ep, dense_out(EMB)); }
                 launch_attention_bwd<T>(st, attention_s64(S), qkv[l], Pat[l], dt_a, B, S, EMB, NH, b_b, dp, site_seed(1 + 4 * l));
-                if (defer_w) tr_wgrad_add(b_b, xt[l], tr_in[l]);
+                if (defer_w) wq_add(b_b, xt[l], N, tr_in[l]);
                 else lin_wgrad(b_b, xt[l], EMB, N, 3 * EMB, EMB, tr_in[l].dW, EMB, tr_in[l].db);
                 { EpiP ep = epi(dx, true); ep.res = dy_f; ep.res_f32 = 1; ep.res_ld = EMB; lin_dgrad(b_b, N, tr_in[l], ep, dense_out(EMB)); }
             }
-            tr_wgrads_flush(N);
             // x0 = dropout(emb + pos): d(emb) += mask*dx ; dpos += sum_b
             {
                 const int bchunk = (std::is_same<T, float>::value || repro) ? B : 8;       // fp32 (parity) engine, reproducible mode: one pass over the windows in order
@@ -516,6 +510,7 @@
             }
         }
         }
+        wq_flush();                          // every queued weight / bias gradient of part 0: two launches (with a collective armed the buckets above flushed what was queued by then)
         if (bucket_ready(3)) return 1;       // visual_goal.*, language_goal.* final
         if (part == 0) {
             lazy_sweep(0, numel, st);        // every lazy tensor is final here (none belongs to the encoders): what no writer touched is zeroed now

@@ -310,25 +310,22 @@
             const bool slab_pg = repro && nblk > 1;      // reproducible mode: LayerNorm parameter partials stored per workgroup (cspart), summed in block order
             if (slab_pg) for (int k = 0; k < 2; ++k) q.cam[k].pg_slab = cspart + (long long)k * 2 * nblk * 64;
             if (!repro && Nf > 16) nd(ND_ENC_TAIL_LN);
-            if (!repro && Nf > 256) nd(ND_LIN_BWD_ROWS);      // the five jobs' bias gradients below: one atomic per column and row chunk
             launch_enc_tail_bwd(st, q);
             if (slab_pg)
                 for (int k = 0; k < 2; ++k) {
                     hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, st, (const float*)q.cam[k].pg_slab, nblk, 64, encw(k).dlng, (float*)nullptr, 1.f);
                     hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, st, (const float*)q.cam[k].pg_slab + (long long)nblk * 64, nblk, 64, encw(k).dlnb, (float*)nullptr, 1.f);
                 }
-            // weight / bias gradients of the four Linear layers: one launch, frames split over blockIdx.y, operands read as they lie.  Every row chunk writes its own
-            // slab; the slabs are summed into the gradient by the encoders' one unpack launch (no per-element atomics here: 1.5 M of them made this launch 39 us).
-            // A job without room for its slabs (part == nullptr) adds with fp32 atomics
-            constexpr int chunk = 256;
-            LinBwdBatch bt{}; bt.M = Nf; bt.store = 0; bt.mchunk = chunk;
+            // weight / bias gradients of the four Linear layers (+ fc7): one launch of the streaming body (lin_bwd_stream_kernel), operands read as they lie, the frames
+            // walked in one or two ranges (74 tiles at the model's shape: two).  Every range writes its own slab; the slabs are summed into the gradient by the encoders'
+            // one unpack launch (no per-element atomics here: 1.5 M of them made this launch 39 us).  A job without room for its slabs (null) adds to the gradient itself, with fp32 atomics when there are two ranges
+            const int nz = enc_tail_nsplit(Nf);
+            if (!repro && nz > 1) nd(ND_LIN_BWD_ROWS);      // the five jobs' bias gradients: one atomic per column and row range
+            LinStreamBatch bt{};
             int blk = 0;
-            const int nz = cdiv(Nf, chunk);
-            const bool cs_bias = repro && nz > 1;      // reproducible mode: the bias gradients are two-stage column sums behind the launch, not the row chunks' atomics
+            const bool cs_bias = repro && nz > 1;      // reproducible mode: the bias gradients are two-stage column sums behind the launch, not the row ranges' atomics
             auto add = [&](const T* dY, const T* X, const LinW& L, float* dW, float* slabs) {
-                LinBwdJob& J = bt.j[bt.n++];
-                J.dY = dY; J.X = X; J.dW = dW; J.db = cs_bias ? nullptr : L.db; J.ldx = L.K; J.lddw = L.K; J.N = L.N; J.K = L.K; J.nx = cdiv(L.N, 64); J.blk0 = blk; J.part = slabs;
-                blk += J.nx * cdiv(L.K, 128);
+                lin_stream_add(bt, blk, (const h16_t*)dY, (const h16_t*)X, L.K, Nf, L.N, L.K, dW, L.K, cs_bias ? nullptr : L.db, slabs, nz, 0);
             };
             for (int k = 0; k < 2; ++k) {
                 const EncW& e = encw(k); EncA& a = enca(k);
@@ -341,7 +338,7 @@
             float* const slabs7 = L.N == 128 && L.K == 3136 ? queue_unpack(L.dW, 128, 64, 7, 7, 1, nz, 1) : nullptr;
             tail_fc7_done = slabs7 != nullptr;      // else head_bwd runs fc7's weight gradient
             if (slabs7) add(aG.d_g0, aG.a3, L, nullptr, slabs7);
-            hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(blk, nz), dim3(256), 0, st, bt);
+            launch_lin_stream(st, bt, blk);
             if (cs_bias) {
                 for (int k = 0; k < 2; ++k) {
                     const EncW& e = encw(k); EncA& a = enca(k);
@@ -352,9 +349,11 @@
             }
         }
     }
+    // row ranges of the tails' weight-gradient launch (74 tiles: two ranges from 257 frames up)
+    static int enc_tail_nsplit(int Nf) { return lin_stream_nsplit(2 * (1 * 4 + 8 * 1) + 2 * 25, Nf); }
     // reproducible mode runs the fused tail backward only when every job of its weight-gradient launch gets slabs (a job without slabs adds with atomics)
     bool enc_tail_bwd_room(int Nf) const {
-        const int64_t nz = cdiv(Nf, 256);
+        const int64_t nz = enc_tail_nsplit(Nf);
         return unpack_room(5, nz * (2 * (64ll * 512 + 512ll * 128) + 128ll * 3136));
     }
     h16_t* zero_page = nullptr;

@@ -13,29 +13,25 @@
         }
     }
     // dy: T [M][N_last]; x: first-layer input (ldx). dxf: optional fp32 output (accumulating) with map
-    T* mlp_dy[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // 16-bit engines, M <= 64: the weight / bias gradients are queued (wq_add) and read every layer's incoming gradient at the flush, so each mlp_bwd call of a backward
+    // keeps its chain in a buffer set of its own (mlp_dy_next counts the calls; reset when a backward starts).  A set = 7 x 64 x 2048 values of T
+    static constexpr int MLP_DY_SETS = 4;
+    T* mlp_dy[MLP_DY_SETS][8] = {};
+    int mlp_dy_next = 0;
     void mlp_bwd(const T* dy, const T* x, long long ldx, int M, LinW* L, int n, T** acts, T* s0, T* s1, float* dxf, const DenseOut* om, int dx_acc) {
         const T* d = dy;
         if constexpr (std::is_same<T, h16_t>::value) {
-            // M <= 64 (every M = B MLP): the data-gradient chain first, every layer's incoming gradient kept in its own buffer, then the weight /
-            // bias gradients of ALL layers in one launch (lin_bwd_smallm_batched_kernel) instead of one ~9 us launch per layer
-            if (M <= 64 && n <= 8) {
-                // one store flag for the whole batch: every layer's weight gradient is in the same state (fresh zeros / stale = first write of the step, or
-                // already written = a second backward before the optimizer); a mixed batch (never seen) zeroes its stale tensors and accumulates
-                bool all_first = true;
-                for (int i = 0; i < n; ++i) { const int z = lazy_find(L[i].dW); all_first = all_first && (z >= 0 ? lazy[z].stale : grads_fresh); }
-                for (int i = 0; i < n; ++i) { if (all_first) grad_first(L[i].dW); else grad_ensure_zero(L[i].dW); }
-                LinBwdBatch bt{}; bt.M = M; bt.store = all_first ? 1 : 0;
-                int blk = 0;
+            // M <= 64 (every M = B MLP): the data-gradient chain runs here, every layer's incoming gradient kept in its own buffer; the weight / bias gradients of
+            // all layers join the backward's one batched launch (wq_flush) instead of one ~9 us launch per layer.  Store or add is decided per tensor at the flush
+            if (M <= 64 && n <= 8 && mlp_dy_next < MLP_DY_SETS) {
+                T** const set = mlp_dy[mlp_dy_next++];
                 for (int i = n - 1; i >= 0; --i) {
                     const T* in = i > 0 ? acts[i - 1] : x;
                     const long long ld = i > 0 ? L[i - 1].N : ldx;
-                    LinBwdJob& J = bt.j[bt.n++];
-                    J.dY = d; J.X = in; J.dW = L[i].dW; J.db = L[i].db; J.ldx = ld; J.lddw = L[i].K; J.N = L[i].N; J.K = L[i].K; J.nx = cdiv(L[i].N, 64); J.blk0 = blk;
-                    blk += J.nx * cdiv(L[i].K, 128);
+                    wq_add(d, in, ld, M, L[i].N, L[i].K, L[i].dW, L[i].K, L[i].db);
                     if (i > 0) {
-                        if (!mlp_dy[i]) mlp_dy[i] = alloc<T>((int64_t)64 * 2048);
-                        T* o = L[i].K <= 2048 ? mlp_dy[i] : (T*)nullptr;
+                        if (!set[i]) set[i] = alloc<T>((int64_t)64 * 2048);
+                        T* o = L[i].K <= 2048 ? set[i] : (T*)nullptr;
                         if (!o) { hulc_set_error("mlp_bwd: hidden width %d exceeds the per-layer gradient buffers", L[i].K); return; }
                         EpiP ep = epi(o, false); ep.mask = acts[i - 1];
                         lin_dgrad(d, M, L[i], ep, dense_out(L[i].K));
@@ -45,7 +41,6 @@
                         lin_dgrad(d, M, L[i], ep, *om);
                     }
                 }
-                hipLaunchKernelGGL(lin_bwd_smallm_batched_kernel, dim3(blk), dim3(256), 0, st, bt);
                 return;
             }
         }

@@ -239,6 +239,8 @@ struct IEngine {
     int k_gemm_multi(int form, const hulc_gemm_epi_job* jobs, int n, int sh, int* ran, void* stream);                                           \
     int k_gemm_pick(int t16, int M, int N, int K, long long lda, long long ldb, int* pick, int* bk);                                            \
     int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big);                                                               \
+    int k_lin_bwd_stream(const void* dY, const void* X, long long ldx, int M, int N, int K, int nsplit, int store, float* dW, long long lddw,    \
+                         float* db, float* slabs, void* stream);                                                                                \
     int k_conv_wgrad(const char* who, int typed, int which, const void* X, const void* dY, float* out, float* db_out, int Nf, int IH, int* slabs, \
                      void* stream);                                                                                                             \
     int k_conv1_wgrad_u8(const char* who, int typed, const void* X, const int* shifts, int pad, const void* dY, float* dw_out, float* db_out,   \

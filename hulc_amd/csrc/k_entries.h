@@ -616,6 +616,30 @@ int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big) {
     return 0;
 }
 
+// hulc_k_lin_bwd_stream: lin_bwd_stream_kernel (conv_wgrad.h) on one job, rows split into nsplit ranges; the four forms the engine launches.  slabs == null, nsplit = 1: the
+// tile is stored to (store != 0) or added to dW by the kernel itself; slabs == null, nsplit > 1: the ranges add to dW with fp32 atomics (store != 0: dW is cleared first).
+// slabs given (any nsplit, 1 included: the decoder heads' form): every range stores its slab ([nsplit][N][K], never read before it is written) and slab_sum_kernel
+// adds them to dW in index order (store != 0: dW is cleared first).  nsplit > 1: the bias sums of the ranges land in db with atomics.  db (may be null) is always added to.
+int k_lin_bwd_stream(const void* dY, const void* X, long long ldx, int M, int N, int K, int nsplit, int store, float* dW, long long lddw, float* db, float* slabs, void* stream) {
+    static const char* who = "hulc_k_lin_bwd_stream";
+    hipStream_t st = (hipStream_t)stream;
+    if (!dY || !X || !dW || M < 1 || N < 1 || K < 1 || ldx < K || lddw < K || nsplit < 1 || nsplit > 64) { hulc_set_error("%s: null argument or bad shape (M=%d N=%d K=%d nsplit=%d)", who, M, N, K, nsplit); return 1; }
+    if ((long long)M * std::max<long long>(N, ldx) >= (1ll << 31) || (long long)N * lddw >= (1ll << 31)) { hulc_set_error("%s: operand too large", who); return 1; }
+    if (!lin_stream_ok(dY, X, ldx, N)) { hulc_set_error("%s: rows must start 8-byte aligned (N, ldx multiples of 4; dY, X 8-byte aligned)", who); return 1; }
+    if (k_misaligned16(slabs)) { hulc_set_error("%s: the slab buffer [nsplit][N][K] must be 16-byte aligned", who); return 1; }
+    LinStreamBatch bt{};
+    int blocks = 0;
+    lin_stream_add(bt, blocks, (const h16_t*)dY, (const h16_t*)X, ldx, M, N, K, dW, lddw, db, slabs, nsplit, store ? 1 : 0);
+    const bool clear = store && (slabs || nsplit > 1);      // the slab sum and the atomics add
+    if (clear && hipMemset2DAsync(dW, sizeof(float) * lddw, 0, sizeof(float) * K, N, st) != hipSuccess) { hulc_set_error("%s: clearing dW failed", who); return 1; }
+    launch_lin_stream(st, bt, blocks);
+    if (slabs) {
+        const int vec = (K & 3) == 0 && (lddw & 3) == 0 && !k_misaligned16(dW);
+        hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv((long long)N * K, vec ? 1024 : 256)), dim3(256), 0, st, (const float*)slabs, nsplit, (long long)N * K, N, K, dW, lddw, vec);
+    }
+    return k_launched(who);
+}
+
 // ---------------------------------------------------------------------------------------------------- the encoder's convolution family (conv_tile.h, conv_reg.h, conv_wgrad.h)
 // hulc_k_conv_wgrad, hulc_k_conv1_wgrad_u8, hulc_k_conv_tile, hulc_k_conv_pair (the bf16 wrappers: typed == 0) and their per-type forms hulc_k_*_t (typed == 1), launched
 // through the launchers engine_encoders.inc calls.  who = the C entry's name (error messages).  typed: the bench-only forms no launch site of engine_encoders.inc names

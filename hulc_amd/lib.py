@@ -121,7 +121,8 @@ EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_s
            "hulc_k_det_head_loss", "hulc_k_det_head_bwd", "hulc_k_det_head_act",
            "hulc_k_conv_wgrad_t", "hulc_k_conv1_wgrad_u8_t", "hulc_k_conv_tile_t", "hulc_k_conv_pair_t", "hulc_k_conv_plan",
            "hulc_decoder_body_select", "hulc_trainable_set", "hulc_trainable_get", "hulc_trainable_steps_set",
-           "hulc_ema_enable", "hulc_ema_state_get", "hulc_ema_state_set", "hulc_ema_swap", "hulc_ema_swapped", "hulc_k_ema_update"]
+           "hulc_ema_enable", "hulc_ema_state_get", "hulc_ema_state_set", "hulc_ema_swap", "hulc_ema_swapped", "hulc_k_ema_update",
+           "hulc_k_lin_bwd_stream"]
 
 _lib = None
 
@@ -273,6 +274,9 @@ def load():
         lib.hulc_k_gemm_multi.argtypes = [I, I, C.POINTER(HulcGemmEpiJob), I, I, PI, C.c_void_p]
         lib.hulc_k_gemm_pick.argtypes = [I, I, I, I, Q, Q, PI, PI]
         lib.hulc_k_gemm_wgrad_nsplit.argtypes = [I, I, I, I, PI, PI]
+    if hasattr(lib, "hulc_k_lin_bwd_stream") or not os.environ.get("HULC_LIB_PATH"):
+        P, I, Q = C.c_void_p, C.c_int32, C.c_int64
+        lib.hulc_k_lin_bwd_stream.argtypes = [I, P, P, Q, I, I, I, I, I, P, Q, P, P, P]
     if hasattr(lib, "hulc_decoder_select") or not os.environ.get("HULC_LIB_PATH"):
         P, I, F = C.c_void_p, C.c_int32, C.c_float
         lib.hulc_decoder_select.argtypes = [P, I, I]

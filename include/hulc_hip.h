@@ -870,6 +870,13 @@ int hulc_k_gemm_multi(int32_t dtype, int32_t form, const hulc_gemm_epi_job* jobs
  * the skinny and LDS-DMA kernels).  hulc_k_gemm_wgrad_nsplit: Engine::gemm_wgrad's split-K factor (1 = none), *big = 1: the 128x128 tile. */
 int hulc_k_gemm_pick(int32_t dtype, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int32_t* pick, int32_t* bk);
 int hulc_k_gemm_wgrad_nsplit(int32_t dtype, int32_t M, int32_t N, int32_t K, int32_t* nsplit, int32_t* big);
+/* The streaming weight / bias gradient of a Linear layer (conv_wgrad.h lin_bwd_stream_kernel; 16-bit types): dW[N][K] (pitch lddw) = or += dY[M][N]^T X[M][K] (pitch ldx)
+ * and db[N] += column sums of dY (db may be NULL).  The M rows are walked in nsplit ranges.  slabs == NULL: nsplit = 1, the kernel stores (store != 0: what dW held is
+ * not read) or adds; nsplit > 1, the ranges add with fp32 atomics (store != 0: to a cleared dW).  slabs given ([nsplit][N][K], 16-byte aligned, never read before it is
+ * written; nsplit = 1 allowed): every range stores its own fp32 slab and the slabs are summed into dW in index order (store != 0: into a cleared dW).  With nsplit > 1 the
+ * ranges' bias sums land with atomics.  N and ldx multiples of 4, dY and X 8-byte aligned. */
+int hulc_k_lin_bwd_stream(int32_t dtype, const void* dY, const void* X, int64_t ldx, int32_t M, int32_t N, int32_t K, int32_t nsplit, int32_t store, float* dW, int64_t lddw,
+                          float* db, float* slabs, void* hip_stream);
 
 #ifdef __cplusplus
 }
