@@ -395,8 +395,8 @@ int hulc_k_tr_ffn_bwd(int32_t dtype, const hulc_tr_ffn_bwd_job* job, int32_t B, 
 int hulc_k_tr_attn_bwd(int32_t dtype, const hulc_tr_attn_bwd_job* job, int32_t B, int32_t S, int32_t nparts, int64_t part_stride, float dp, void* stream) {
     HULC_K_16BIT("hulc_k_tr_attn_bwd", k_tr_attn_bwd(job, B, S, nparts, (long long)part_stride, dp, stream));
 }
-int hulc_k_gemm_multi(int32_t dtype, int32_t form, const hulc_gemm_epi_job* jobs, int32_t n, int32_t sh, int32_t* ran, void* stream) {
-    HULC_K_16BIT("hulc_k_gemm_multi", k_gemm_multi(form, jobs, n, sh, ran, stream));
+int hulc_k_gemm_dual(int32_t dtype, const hulc_gemm_epi_job* jobs, int32_t* ran, void* stream) {
+    HULC_K_16BIT("hulc_k_gemm_dual", k_gemm_dual(jobs, ran, stream));
 }
 int hulc_k_lin_bwd_stream(int32_t dtype, const void* dY, const void* X, int64_t ldx, int32_t M, int32_t N, int32_t K, int32_t nsplit, int32_t store, float* dW, int64_t lddw,
                           float* db, float* slabs, void* stream) {

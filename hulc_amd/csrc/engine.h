@@ -194,7 +194,7 @@ struct Engine : IEngine {
     T *dprl_t, *dppl_t, *dseq_t, *dt_a, *dt_b, *dt_c, *dgl3_t;
     T *tA, *tB; int64_t tcap;
     bool h0t_valid = false;                 // tB2 holds H0^T of the current backward (16-bit engines)
-    T* tB2 = nullptr;                       // second transposed-operand buffer (the paired layer-1 weight-gradient GEMM reads H1^T and H0^T at once)
+    T* tB2 = nullptr;                       // second transposed-operand buffer (H0^T, transposed once next to dZ1^T and H1^T: read by dW_ih1 and again by dW_hh0)
     float *part; int64_t partcap; float* cspart;
     // clip
     int* auxrows; T *sf_m, *im1, *g_m, *la1, *img_t, *txt_t; float *img, *txt, *dimg, *dtxt, *dsf_m, *dg_m; T *dimg_t, *dtxt_t, *dim1, *dla1;
@@ -728,36 +728,9 @@ struct Engine : IEngine {
         }
     }
     // dense NT GEMM with tile selection
-    // ---- grouped launches (gemm.h gemm_glds_group_kernel): between gemm_group_begin() and gemm_group_end() up to three INDEPENDENT 128 x 128-tile products are
-    // collected and issued as one grid; anything else that arrives in between flushes the queue first, so program order is kept.  The caller vouches for the
-    // independence of what it brackets (no queued product reads another's output).
-    GemmGroupP gq{}; bool gq_open = false; double gq_fl = 0, gq_by = 0;
-    void gemm_group_begin() { gq_open = gemm_group_mode; gq.n = 0; gq_fl = gq_by = 0; }
-    void gemm_group_flush() {
-        if constexpr (std::is_same<T, h16_t>::value) {
-            if (gq.n == 1) { TimerScope ts(this, "gemm_128x128", "mfma", gq_fl, gq_by); launch_gemm_glds(st, gq.a[0], gq.b[0], gq.om[0], gq.ep[0], gq.M[0], gq.N[0], gq.K[0]); }
-            else if (gq.n > 1) { TimerScope ts(this, "gemm_128x128", "mfma", gq_fl, gq_by, 1); launch_gemm_glds_group(st, gq); }
-        }
-        gq.n = 0; gq_fl = gq_by = 0;
-    }
-    void gemm_group_end() { gemm_group_flush(); gq_open = false; }
     void gemm(const DenseLoader<T>& a, const DenseLoader<T>& b, const DenseOut& om, const EpiP& ep, int M, int N, int K) {
-        if constexpr (std::is_same<T, h16_t>::value) {
-            if (gq_open) {
-                const long long w128g = (long long)cdiv(M, 128) * cdiv(N, 128);
-                const bool skinny = a.R1 == 0x7fffffff && b.R1 == 0x7fffffff && ep.z_stride == 0 && skinny_ok(M, N, K, a.s1, b.s1, a.p, b.p);
-                if (!skinny && M >= 512 && N >= 128 && w128g >= 128 && gemm_use_glds && gemm_glds_ok(a, b, ep, M, N, K)) {
-                    if (gq.n == 3) gemm_group_flush();
-                    const int i = gq.n++;
-                    gq.a[i] = a; gq.b[i] = b; gq.om[i] = om; gq.ep[i] = ep; gq.M[i] = M; gq.N[i] = N; gq.K[i] = K;
-                    gq_fl += 2.0 * M * N * K; gq_by += ((double)M * K + (double)N * K + (double)M * N) * sizeof(T);
-                    return;
-                }
-                gemm_group_flush();
-            }
-        }
         const double fl = 2.0 * M * N * K, by = ((double)M * K + (double)N * K + (double)M * N) * sizeof(T);
-        const GemmPick pick = gemm_pick<T>(a, b, ep, M, N, K, gemm_use_glds);      // gemm.h: the tile and kernel decision
+        const GemmPick pick = gemm_pick<T>(a, b, ep, M, N, K);      // gemm.h: the tile and kernel decision
         if (pick == GEMM_PICK_SKINNY) {
             // two roles share the skinny kernels: M <= 64 layers stream a whole weight matrix per launch (weight-bound), many-row GEMMs
             // (small-N heads / weight gradients with K = 2048) stream activations

@@ -259,16 +259,14 @@
             fused_prev = false;
             if (!i) break;
             if constexpr (std::is_same<T, h16_t>::value) {      // carry GEMM + the gate backward of step i-1 in one launch (gemm.h: GruBwdP)
-                if (skinny_use_lds) {
-                    const long long tp = at(i - 1);
-                    GruBwdP gbp{};
-                    gbp.dH = dH_last_only ? nullptr : dH + tp * BH;
-                    gbp.R = g.R + tp * BH; gbp.Z = g.Z + tp * BH; gbp.Nn = g.N + tp * BH; gbp.GN = g.GN + tp * BH;
-                    gbp.Hprev = i - 1 ? g.H + at(i - 2) * BH : nullptr;
-                    gbp.dzx = g.dZx + tp * 3 * BH; gbp.dg = g.dG + tp * 3 * BH; gbp.direct = gcarB; gbp.direct_in = gcarB;     // each thread reads its 4 direct[t] values before it writes direct[t-1] over them
-                    EpiP ep = epi(gcarA, false);
-                    if (launch_skinny_lds_kchunk(st, g.dG + t * 3 * BH, 3 * HID, whh.Wtfr ? whh.Wtfr : whh.Wt, whh.Wtfr ? 0 : 3 * HID, B, HID, 3 * HID, dense_out(HID), ep, gbp)) { fused_prev = true; continue; }
-                }
+                const long long tp = at(i - 1);
+                GruBwdP gbp{};
+                gbp.dH = dH_last_only ? nullptr : dH + tp * BH;
+                gbp.R = g.R + tp * BH; gbp.Z = g.Z + tp * BH; gbp.Nn = g.N + tp * BH; gbp.GN = g.GN + tp * BH;
+                gbp.Hprev = i - 1 ? g.H + at(i - 2) * BH : nullptr;
+                gbp.dzx = g.dZx + tp * 3 * BH; gbp.dg = g.dG + tp * 3 * BH; gbp.direct = gcarB; gbp.direct_in = gcarB;     // each thread reads its 4 direct[t] values before it writes direct[t-1] over them
+                EpiP ep = epi(gcarA, false);
+                if (launch_skinny_lds_kchunk(st, g.dG + t * 3 * BH, 3 * HID, whh.Wtfr ? whh.Wtfr : whh.Wt, whh.Wtfr ? 0 : 3 * HID, B, HID, 3 * HID, dense_out(HID), ep, gbp)) { fused_prev = true; continue; }
             }
             { EpiP ep = epi(gcarA, false); ep.res = gcarB; ep.res_ld = HID;
               gemm(dense<T>(g.dG + t * 3 * BH, B, 3 * HID), dense<T>(whh.Wt, HID, 3 * HID), dense_out(HID), ep, B, HID, 3 * HID); }
@@ -278,7 +276,7 @@
     void gru_recur_fwd2(GruBuf* const g[2], const LinW* const whh[2], const float* const bhh[2], int B, int S) {
         const long long BH = (long long)B * HID;
         bool dual = false;
-        if constexpr (std::is_same<T, h16_t>::value) dual = S > 1 && skinny_use_lds;
+        if constexpr (std::is_same<T, h16_t>::value) dual = S > 1;
         if (dual) {
             auto at = [&](int d, int i) { return (long long)(d ? S - 1 - i : i); };
             for (int i = 0; i < S; ++i) {
@@ -309,7 +307,7 @@
     void gru_recur_bwd2(GruBuf* const g[2], T* const dH[2], const LinW* const whh[2], int B, int S) {
         const long long BH = (long long)B * HID;
         bool dual = false;
-        if constexpr (std::is_same<T, h16_t>::value) dual = S > 1 && skinny_use_lds && B <= 64 && (3 * HID) % 2048 == 0 && 3 * HID > 2048;   // = what launch_skinny_lds_kchunk covers
+        if constexpr (std::is_same<T, h16_t>::value) dual = S > 1 && B <= 64 && (3 * HID) % 2048 == 0 && 3 * HID > 2048;   // = what launch_skinny_lds_kchunk covers
         if constexpr (std::is_same<T, h16_t>::value) {
             if (dual) {
                 if (!gcarB2) gcarB2 = alloc<T>((int64_t)maxB * HID);

@@ -774,151 +774,6 @@ __global__ void __launch_bounds__(NW * 64) gemm_glds_kernel(DenseLoader<h16_t> a
                                                            int tiles_m, int tiles_n) {
     gemm_glds_body<NST, NW>(al, bl, om, ep, M, N, K, tiles_m, tiles_n, (int)blockIdx.x);
 }
-// ---------------------------------------------------------------------------------------------------------
-// Up to three INDEPENDENT gemm_glds problems as one launch (round 6): the decoder backward issues dW_hh1, dW_ih1 and dH0 = dZ1 W_ih1 back to
-// back — three 2048^3 products of 256 tiles each, none reading another's output.  As three launches every one of them pays the stream's kernel boundary (all 256
-// workgroups of launch i drain their epilogue stores before the first DMA of launch i + 1 is issued) and its own pipeline fill; as ONE grid of 768 workgroups a CU
-// starts its next tile the moment its previous workgroup retires.  A workgroup finds its problem from blockIdx.x (uniform: the descriptors stay in scalar
-// registers); problem p's tile order is the single launch's (first tile a multiple of 8 -> block b still runs on XCD b % 8).
-// ---------------------------------------------------------------------------------------------------------
-struct GemmGroupP { DenseLoader<h16_t> a[3], b[3]; DenseOut om[3]; EpiP ep[3]; int M[3], N[3], K[3], tm[3], tn[3], t0[3]; int n; };
-template <int NST, int NW>
-__global__ void __launch_bounds__(NW * 64) gemm_glds_group_kernel(GemmGroupP g) {
-    const int b = (int)blockIdx.x;
-    const int p = (g.n > 2 && b >= g.t0[2]) ? 2 : ((g.n > 1 && b >= g.t0[1]) ? 1 : 0);      // uniform
-    const int bid = b - g.t0[p];
-    if (bid >= g.tm[p] * g.tn[p]) return;                 // a problem's block range is padded to a multiple of 8 (XCD alignment of the next problem)
-    gemm_glds_body<NST, NW>(g.a[p], g.b[p], g.om[p], g.ep[p], g.M[p], g.N[p], g.K[p], g.tm[p], g.tn[p], bid);
-}
-// ---------------------------------------------------------------------------------------------------------
-// TWO NT GEMMs that share their A operand up to a shift along K, as one launch (round 5):
-//     C1[m][n] = sum_{k = sh}^{K-1} A[m][k] B1[n][k - sh]          C2[m][n] = sum_{k = 0}^{K-1} A[m][k] B2[n][k]
-// — the two weight gradients of the decoder's layer 1, dW_hh1 = dZ1[1:]^T H1[:-1] and dW_ih1 = dZ1^T H0 (A = dZ1^T, k = (t, b) token, sh = B tokens = one
-// time step).  gemm_glds_kernel is bound by the bytes a CU pulls through its load path (1 MB per 128 x 128 tile at K = 2048 -> ~28 us); here a workgroup owns
-// the 128 x 128 tile of BOTH outputs and streams A once: 1.5 MB for what took 2 MB.  Same ring, swizzle and counted waits as above with three operands per
-// stage (48 KB x 3 stages = 144 KB of LDS); sh and K are multiples of the 64-wide k-step, so B1's stage kt is simply B1's own step kt - sh / 64 (the first
-// sh / 64 steps fetch a valid dummy stage and skip B1's MFMAs).
-// ---------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(512) gemm_glds_pair_kernel(DenseLoader<h16_t> al, DenseLoader<h16_t> bl1, DenseLoader<h16_t> bl2, DenseOut om, EpiP ep1, EpiP ep2,
-                                                           int M, int N, int K, int shs, int tiles_m, int tiles_n) {
-    constexpr int NST = 3, NW = 8, STAGE = 48 * 1024, PW = 2, TM = 2, WROWS = 32;
-    extern __shared__ __attribute__((aligned(16))) char gg_smem[];
-    typedef __attribute__((address_space(3))) char lchar;
-    lchar* lds = (lchar*)gg_smem;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4, li = lane & 15;
-    int tm, tn;
-    {
-        const int nt = tiles_m * tiles_n, per = nt / 8, rem = nt % 8;
-        const int x = blockIdx.x % 8, q = blockIdx.x / 8;
-        const int tile = x * per + min(x, rem) + q;
-        constexpr int GM = 4;
-        const int gsz = GM * tiles_n, grp = tile / gsz, first_m = grp * GM, gm = min(GM, tiles_m - first_m);
-        tm = first_m + (tile % gsz) % gm;
-        tn = (tile % gsz) / gm;
-    }
-    const int m0 = tm * 128, n0 = tn * 128;
-    const int r = lane >> 3, cs = (lane & 7) ^ (r & 6);
-    const h16_t* asrc[PW];
-    const h16_t* b1src[PW];
-    const h16_t* b2src[PW];
-#pragma unroll
-    for (int j = 0; j < PW; ++j) {
-        asrc[j] = al.row(min(m0 + (wave * PW + j) * 8 + r, M - 1), 0).base + cs * 8;
-        b1src[j] = bl1.row(min(n0 + (wave * PW + j) * 8 + r, N - 1), 0).base + cs * 8;
-        b2src[j] = bl2.row(min(n0 + (wave * PW + j) * 8 + r, N - 1), 0).base + cs * 8;
-    }
-    const int nk = K >> 6;
-    auto issue = [&](int kt, int buf) {
-        lchar* st = lds + buf * STAGE + wave * PW * 1024;
-        const long long ko = (long long)kt * 64, ko1 = (long long)max(kt - shs, 0) * 64;
-#pragma unroll
-        for (int j = 0; j < PW; ++j) {
-            lds_dma16(asrc[j] + ko, (unsigned)(size_t)(st + j * 1024));
-            lds_dma16(b1src[j] + ko1, (unsigned)(size_t)(st + 16384 + j * 1024));
-            lds_dma16(b2src[j] + ko, (unsigned)(size_t)(st + 32768 + j * 1024));
-        }
-    };
-    f32x4 acc1[TM][4], acc2[TM][4];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    const int wm = wave >> 1, wn = wave & 1;
-    const int foff = (li >> 3) * 1024 + (li & 7) * 128;
-#pragma unroll
-    for (int j = 0; j < NST - 1; ++j)
-        if (j < nk) issue(j, j);
-    int buf = 0;
-#pragma unroll 1
-    for (int kt = 0; kt < nk; ++kt) {
-        const int ahead = min(NST - 2, nk - 1 - kt);             // stages in flight behind stage kt: 3 * PW = 6 DMA instructions per wave each
-        if (ahead >= 1) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        if (kt + NST - 1 < nk) issue(kt + NST - 1, buf == 0 ? NST - 1 : buf - 1);
-        lchar* sa = lds + buf * STAGE + wm * (WROWS / 8) * 1024 + foff;
-        lchar* sb1 = lds + buf * STAGE + 16384 + wn * 8192 + foff;
-        lchar* sb2 = lds + buf * STAGE + 32768 + wn * 8192 + foff;
-        const bool with1 = kt >= shs;
-#pragma unroll 1
-        for (int kk = 0; kk < 2; ++kk) {
-            const int chunk = (((kk << 2) + g) ^ (li & 6)) << 4;
-            // all ten fragments are requested before the first MFMA (a second read phase behind B2's MFMAs exposed the LDS latency once more per k-half)
-            h16x8_t a[TM], b[4], c[4];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = *(__attribute__((address_space(3))) h16x8_t*)(sa + i * 2048 + chunk);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = *(__attribute__((address_space(3))) h16x8_t*)(sb2 + j * 2048 + chunk);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) c[j] = *(__attribute__((address_space(3))) h16x8_t*)(sb1 + j * 2048 + chunk);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc2[i][j] = MFMA_16x16x32_H(b[j], a[i], acc2[i][j], 0, 0, 0);
-            if (with1) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc1[i][j] = MFMA_16x16x32_H(c[j], a[i], acc1[i][j], 0, 0, 0);
-            }
-        }
-        buf = buf == NST - 1 ? 0 : buf + 1;
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int row = m0 + wm * WROWS + i * 16 + li;
-        if (row < M) {
-            const long long obase = om.offset(row, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int col = n0 + wn * 64 + j * 16 + g * 4;
-                if (col < N) {
-                    if (((om.s1 | om.s0) & 3) == 0 && col + 3 < N) { epi_plain4(ep1, acc1[i][j], obase + col); epi_plain4(ep2, acc2[i][j], obase + col); continue; }      // plain by gemm_glds_pair_ok
-                    const float v1[4] = {acc1[i][j][0], acc1[i][j][1], acc1[i][j][2], acc1[i][j][3]};
-                    epi_store4<h16_t>(ep1, v1, row, col, N, obase + col);
-                    const float v2[4] = {acc2[i][j][0], acc2[i][j][1], acc2[i][j][2], acc2[i][j][3]};
-                    epi_store4<h16_t>(ep2, v2, row, col, N, obase + col);
-                }
-            }
-        }
-    }
-}
-// both outputs [M][N] through the same DenseOut; plain epilogues only (fp32 store / accumulate: the weight-gradient form)
-static inline bool gemm_glds_pair_ok(const DenseLoader<h16_t>& a, const DenseLoader<h16_t>& b1, const DenseLoader<h16_t>& b2, const EpiP& ep1, const EpiP& ep2, int M, int N, int K, int sh) {
-    auto row_ok = [](const DenseLoader<h16_t>& l) { return (l.s0 % 8) == 0 && (l.s1 % 8) == 0 && ((uintptr_t)l.p % 16) == 0 && l.R1 == 0x7fffffff; };
-    // epi_plain4 is a 16-byte f32x4 load / store of the bare product: same conditions as the single-GEMM plain path (alpha 1, 16-byte aligned output)
-    auto plain = [](const EpiP& e) {
-        return !e.generic_only && e.out_f32 && !e.atomic && e.z_stride == 0 && !e.bias && !e.bias2 && !e.res && !e.mask && !e.relu && e.drop_p == 0.f && !e.out2 && e.alpha == 1.f && ((uintptr_t)e.out & 15) == 0;
-    };
-    return K >= 192 && (K % 64) == 0 && sh > 0 && (sh % 64) == 0 && sh < K && (M % 128) == 0 && (N % 128) == 0 && row_ok(a) && row_ok(b1) && row_ok(b2) && plain(ep1) && plain(ep2);
-}
-static inline void launch_gemm_glds_pair(hipStream_t st, const DenseLoader<h16_t>& a, const DenseLoader<h16_t>& b1, const DenseLoader<h16_t>& b2, const DenseOut& om, const EpiP& ep1,
-                                         const EpiP& ep2, int M, int N, int K, int sh) {
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute((const void*)gemm_glds_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024); attr_set = true; }
-    const int tiles_m = M / 128, tiles_n = N / 128;
-    hipLaunchKernelGGL(gemm_glds_pair_kernel, dim3(tiles_m * tiles_n), dim3(512), 144 * 1024, st, a, b1, b2, om, ep1, ep2, M, N, K, sh / 64, tiles_m, tiles_n);
-}
 static inline bool gemm_glds_ok(const DenseLoader<h16_t>& a, const DenseLoader<h16_t>& b, const EpiP& ep, int M, int N, int K) {
     auto row_ok = [](const DenseLoader<h16_t>& l) { return (l.s0 % 8) == 0 && (l.s1 % 8) == 0 && ((uintptr_t)l.p % 16) == 0; };
     return K >= 64 && (K % 32) == 0 && ep.z_stride == 0 && row_ok(a) && row_ok(b);
@@ -929,14 +784,6 @@ static inline void launch_gemm_glds(hipStream_t st, const DenseLoader<h16_t>& a,
     const int tiles_m = (M + 127) / 128, tiles_n = (N + 127) / 128;
     // a three-stage ring, eight waves (a four-stage ring measured no faster: the operand stream of a tile is not latency-bound)
     hipLaunchKernelGGL((gemm_glds_kernel<3, 8>), dim3(tiles_m * tiles_n), dim3(512), 96 * 1024, st, a, b, om, ep, M, N, K, tiles_m, tiles_n);
-}
-
-static inline void launch_gemm_glds_group(hipStream_t st, GemmGroupP& g) {
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute((const void*)gemm_glds_group_kernel<3, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr_set = true; }
-    int tot = 0;
-    for (int i = 0; i < g.n; ++i) { g.tm[i] = (g.M[i] + 127) / 128; g.tn[i] = (g.N[i] + 127) / 128; g.t0[i] = tot; tot += (g.tm[i] * g.tn[i] + 7) / 8 * 8; }
-    hipLaunchKernelGGL((gemm_glds_group_kernel<3, 8>), dim3(tot), dim3(512), 96 * 1024, st, g);
 }
 // ---------------------------------------------------------------------------------------------------------
 // skinny GEMM (bf16): M <= 64 rows (the per-timestep recurrent GEMMs and every M = B MLP layer).
@@ -1063,8 +910,6 @@ DEVI const h16_t* skinny_wfrag_ptr(const h16_t* W, long long ldw, int n0, int Nc
     *wstep = 32;
     return W + (long long)min(n0 + (lane & 15), Nclamp) * ldw + kb + (lane >> 4) * 8;
 }
-static bool skinny_use_lds = true;
-static bool gemm_use_glds = true;   // tests / tools can force the register-fragment kernel
 // skinny GEMM, A through LDS (K % 512 == 0, MT*16 rows x K bf16 <= 128 KB): the A rows — 2/3 of the bytes a workgroup pulls, and
 // re-read by every column workgroup — arrive as full 128-byte lines by LDS-DMA (global_load_lds_dwordx4: one wave instruction =
 // 8 rows x 128 B, XOR-swizzled on the SOURCE address so the later ds_read_b128 fragments are conflict-free) instead of
@@ -1476,7 +1321,7 @@ static inline bool skinny_lds_dual_ok(const h16_t* A0, const h16_t* W0, const h1
 }
 static inline bool launch_skinny_lds_dual(hipStream_t st, const h16_t* A0, const h16_t* W0, const EpiP& ep0, const h16_t* A1, const h16_t* W1, const EpiP& ep1, long long lda,
                                           long long ldw, int M, int N, int K, const DenseOut& om) {
-    if (!skinny_use_lds || !skinny_lds_dual_ok(A0, W0, A1, W1, lda, ldw, M, N, K)) return false;
+    if (!skinny_lds_dual_ok(A0, W0, A1, W1, lda, ldw, M, N, K)) return false;
     static bool attr16 = false;
     if (!attr16) { hipFuncSetAttribute((const void*)skinny_lds_kernel<2, 4, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr16 = true; }
     Skinny2 p2; p2.A = A1; p2.W = W1; p2.ep = ep1;
@@ -1485,7 +1330,7 @@ static inline bool launch_skinny_lds_dual(hipStream_t st, const h16_t* A0, const
 }
 template <int NW>
 static inline void launch_skinny_nw(hipStream_t st, const h16_t* A, long long lda, const h16_t* W, long long ldw, int M, int N, int K,
-                                    const DenseOut& om, const EpiP& ep) {
+                                    const DenseOut& om, const EpiP& ep, bool use_lds = true) {
     // The kernel is bound by the per-CU load path (~10 B/clk/CU): every workgroup streams its A rows (M x K) and a 16-row W slice.
     // With only N/16 workgroups (128 at N = 2048) half the CUs idle, so split the rows in two 32-row blocks when that fills the chip.
     int MT = M >= 64 ? 4 : (M + 15) / 16;
@@ -1494,7 +1339,7 @@ static inline void launch_skinny_nw(hipStream_t st, const h16_t* A, long long ld
     // LDS-DMA kernel eligible (64 rows x 2048 would not fit LDS) and double the workgroup count of the small-M cases
     if (M > 32 && K == 2048 && NW == 8) MT = 2;
     if (M > 16 && M <= 32 && K == 2048 && NW == 8 && (N / 16) * 2 <= 320) MT = 1;     // 16-row blocks: twice the workgroups, 128 KB instead of 192 KB each
-    if (NW == 8 && skinny_use_lds && launch_skinny_lds(st, A, lda, W, ldw, M, N, K, MT, om, ep)) return;
+    if (NW == 8 && use_lds && launch_skinny_lds(st, A, lda, W, ldw, M, N, K, MT, om, ep)) return;
     dim3 grid(N / 16, (M + MT * 16 - 1) / (MT * 16)), block(NW * 64);
     switch (MT) {
         case 1: hipLaunchKernelGGL((skinny_gemm_kernel<NW, 1>), grid, block, 0, st, A, lda, W, ldw, M, N, K, om, ep); break;
@@ -1504,10 +1349,10 @@ static inline void launch_skinny_nw(hipStream_t st, const h16_t* A, long long ld
     }
 }
 static inline void launch_skinny(hipStream_t st, const h16_t* A, long long lda, const h16_t* W, long long ldw, int M, int N, int K,
-                                 const DenseOut& om, const EpiP& ep) {
-    if (skinny_use_lds && M > 16 && launch_skinny_lds_kchunk(st, A, lda, W, ldw, M, N, K, om, ep)) return;     // K = n x 2048, M <= 64 (GRU BPTT step)
-    if (K % 512 == 0) launch_skinny_nw<8>(st, A, lda, W, ldw, M, N, K, om, ep);     // 8 waves x >=2 k-steps
-    else launch_skinny_nw<4>(st, A, lda, W, ldw, M, N, K, om, ep);
+                                 const DenseOut& om, const EpiP& ep, bool use_lds = true) {
+    if (use_lds && M > 16 && launch_skinny_lds_kchunk(st, A, lda, W, ldw, M, N, K, om, ep)) return;     // K = n x 2048, M <= 64 (GRU BPTT step)
+    if (K % 512 == 0) launch_skinny_nw<8>(st, A, lda, W, ldw, M, N, K, om, ep, use_lds);     // 8 waves x >=2 k-steps
+    else launch_skinny_nw<4>(st, A, lda, W, ldw, M, N, K, om, ep, use_lds);
 }
 static inline bool skinny_ok(int M, int N, int K, long long lda, long long ldw, const void* A, const void* W) {
     // many-row use: every 64-row block of A is re-read by each of the N/16 column workgroups -> only when M*N is small
@@ -1533,7 +1378,7 @@ static inline int gemm_pick_tile(GemmPick p) {
     }
 }
 template <typename T>
-static inline GemmPick gemm_pick(const DenseLoader<T>& a, const DenseLoader<T>& b, const EpiP& ep, int M, int N, int K, bool use_glds) {
+static inline GemmPick gemm_pick(const DenseLoader<T>& a, const DenseLoader<T>& b, const EpiP& ep, int M, int N, int K) {
     constexpr bool H16 = sizeof(T) == 2;
     if constexpr (H16) {
         if (a.R1 == 0x7fffffff && b.R1 == 0x7fffffff && ep.z_stride == 0 && skinny_ok(M, N, K, a.s1, b.s1, a.p, b.p)) return GEMM_PICK_SKINNY;
@@ -1541,7 +1386,7 @@ static inline GemmPick gemm_pick(const DenseLoader<T>& a, const DenseLoader<T>& 
     const long long w128 = (long long)((M + 127) / 128) * ((N + 127) / 128), w64 = (long long)((M + 63) / 64) * ((N + 63) / 64);
     if (M >= 512 && N >= 128 && w128 >= 128) {
         if constexpr (H16) {
-            if (use_glds && gemm_glds_ok(a, b, ep, M, N, K)) return GEMM_PICK_GLDS;
+            if (gemm_glds_ok(a, b, ep, M, N, K)) return GEMM_PICK_GLDS;
             if (K >= 128) return GEMM_PICK_128_BK64;
         }
         return GEMM_PICK_128_BK32;

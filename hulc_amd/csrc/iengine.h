@@ -107,7 +107,7 @@ struct IEngine {
     // "lazy_zero_grads": 1 (default; 16-bit engines) = hulc_zero_grads only marks the large store-first weight gradients stale instead of zeroing them
     // (engine.h: LazyG); 0 = the plain memset of the whole buffer.
     int repro_opt = 0;      // "reproducible" as last set; Engine::repro is the latched value the launches read
-    int persist_mode = 1, tr_fused_mode = 1, persist_under_comm = 0, comm_timing = 0, poison_partials = 0, persist_fault = 0, lazy_zero_mode = 1, u8_fold_mode = 1, force_vote_word = 0, gemm_group_mode = 0, hold_buckets_mode = 1;
+    int persist_mode = 1, tr_fused_mode = 1, persist_under_comm = 0, comm_timing = 0, poison_partials = 0, persist_fault = 0, lazy_zero_mode = 1, u8_fold_mode = 1, force_vote_word = 0, hold_buckets_mode = 1;
     virtual int get_option(const char* name, long long* value) = 0;
     virtual void dp_skip_vote(int phase) = 0;
     virtual void set_adam_fuse(bool on) = 0;
@@ -126,11 +126,6 @@ struct IEngine {
         if (name && !strcmp(name, "comm_timing")) { comm_timing = value != 0; return 0; }
         if (name && !strcmp(name, "debug_poison_partials")) { poison_partials = value != 0; return 0; }
         if (name && !strcmp(name, "lazy_zero_grads")) { lazy_zero_mode = value != 0; return 0; }
-        // "gemm_pair" (default 0; 16-bit engines): the decoder's two layer-1 weight gradients, which share dZ1^T up to a shift of one time step, run as ONE launch that
-        // streams the shared operand once (gemm.h gemm_glds_pair_kernel; needs the batch to be a multiple of 64 windows); 0 = two launches
-        if (name && !strcmp(name, "gemm_pair")) { gemm_pair_mode = value != 0; return 0; }
-        // "gemm_group" (default 0: measured equal to the three launches, profiles/r06_ab_gemm_group.txt; 16-bit engines): the decoder backward's three independent 2048^3 products (dW_hh1, dW_ih1, dH0) as ONE grouped launch (gemm.h gemm_glds_group_kernel)
-        if (name && !strcmp(name, "gemm_group")) { gemm_group_mode = value != 0; return 0; }
         if (name && !strcmp(name, "epilogue_fast")) { epilogue_fast = value != 0; return 0; }
         // "adam_fused_transposes" (default 1; 16-bit engines): the Adam / AdamW step writes the transposed 16-bit weight copies itself (kernels.h adam_tiled_kernel); 0 = flat pass + batched transpose
         if (name && !strcmp(name, "adam_fused_transposes")) { set_adam_fuse(value != 0); return 0; }
@@ -151,7 +146,6 @@ struct IEngine {
     struct KTimer { std::string name, bound; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; double flops = 0, bytes = 0; long long launches = 0; };
     std::map<std::string, KTimer> timers;
     bool epilogue_fast = true;              // hulc_set_option "epilogue_fast" 0: every GEMM epilogue through the generic path (A/B)
-    bool gemm_pair_mode = false;            // measured SLOWER in the step (3.048 against 3.032 ms, class gemm_128x128 0.225 against 0.217 ms): off
     bool timing = false;
     std::string timing_filter;      // empty = every class; else ",a,b,": only the listed classes (keeps event overhead out of the timed region)
     int timer_depth = 0;            // a group scope (e.g. the S recurrent steps) suppresses the per-launch scopes inside it
@@ -236,7 +230,7 @@ struct IEngine {
     int k_tr_ffn_bwd(const hulc_tr_ffn_bwd_job* j, int B, int S, int bcast, float bdiv, float dp, void* stream);                                \
     int k_tr_attn_bwd(const hulc_tr_attn_bwd_job* j, int B, int S, int nparts, long long part_stride, float dp, void* stream);                  \
     int k_gemm_epi(int t16, const hulc_gemm_epi_job* j, int kernel, int* ran, void* stream);                                                    \
-    int k_gemm_multi(int form, const hulc_gemm_epi_job* jobs, int n, int sh, int* ran, void* stream);                                           \
+    int k_gemm_dual(const hulc_gemm_epi_job* jobs, int* ran, void* stream);                                                                     \
     int k_gemm_pick(int t16, int M, int N, int K, long long lda, long long ldb, int* pick, int* bk);                                            \
     int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big);                                                               \
     int k_lin_bwd_stream(const void* dY, const void* X, long long ldx, int M, int N, int K, int nsplit, int store, float* dW, long long lddw,    \

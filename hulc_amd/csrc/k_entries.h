@@ -2,7 +2,7 @@
 // hulc_k_enc_tail_fwd, hulc_k_enc_tail_bwd, hulc_k_logistic_loss), of the latent-plan kernels (hulc_k_plan_*, hulc_k_st_softmax_bwd, hulc_k_normal_*), of
 // the LayerNorm family (hulc_k_layernorm_*) and of the fused transformer layer kernels
 // (hulc_k_tr_layer_fwd, hulc_k_tr_ffn_bwd, hulc_k_tr_attn_bwd; launched through tr_fused.h's helpers), and of the GEMM core with its runtime epilogue
-// (hulc_k_gemm_epi, hulc_k_gemm_multi, hulc_k_gemm_pick, hulc_k_gemm_wgrad_nsplit; launched through gemm.h's launchers and routing), and of the encoder's convolution family
+// (hulc_k_gemm_epi, hulc_k_gemm_dual, hulc_k_gemm_pick, hulc_k_gemm_wgrad_nsplit; launched through gemm.h's launchers and routing), and of the encoder's convolution family
 // (hulc_k_conv_tile, hulc_k_conv_pair, hulc_k_conv_wgrad, hulc_k_conv1_wgrad_u8 and their per-type forms; launched through the launchers of conv_tile.h, conv_reg.h and
 // conv_wgrad.h).  Included by engine.h inside each translation unit, so every entry exists once per
 // 16-bit type (hulc_bf16 / hulc_f16; iengine.h declares them).  Nothing here restates a kernel or a launch: every entry checks its arguments, then launches
@@ -417,8 +417,8 @@ int k_tr_attn_bwd(const hulc_tr_attn_bwd_job* j, int B, int S, int nparts, long 
 }
 
 // ---------------------------------------------------------------------------------------------------- the GEMM core with its runtime epilogue (gemm.h)
-// hulc_k_gemm_epi / hulc_k_gemm_multi: a job mirrors EpiP field for field.  Everything is checked first — with the predicates the engine's routing uses (gemm_pick,
-// gemm_glds_ok, gemm_glds_pair_ok, skinny_ok, skinny_lds_kchunk_ok, skinny_lds_dual_ok) — and only then launched, through the launchers the engine calls.
+// hulc_k_gemm_epi / hulc_k_gemm_dual: a job mirrors EpiP field for field.  Everything is checked first — with the predicates the engine's routing uses (gemm_pick,
+// gemm_glds_ok, skinny_ok, skinny_lds_kchunk_ok, skinny_lds_dual_ok) — and only then launched, through the launchers the engine calls.
 // esz = bytes of the storage type T
 static int k_gemm_job_bad(const char* who, int idx, const hulc_gemm_epi_job* jp, int esz) {
     if (!jp) { hulc_set_error("%s: null job", who); return 1; }
@@ -486,7 +486,7 @@ static int k_gemm_epi_t(const hulc_gemm_epi_job& j, int kernel, int* ran, hipStr
     if ((kernel < 1 || kernel > 3) && kernel != 8 && (j.nsplit != 1 || j.z_stride != 0)) { hulc_set_error("%s: kernel %d takes nsplit = 1 and z_stride = 0", who, kernel); return 1; }
     if (kernel >= 1 && kernel <= 3 && (j.nsplit > 1) != (j.z_stride > 0)) { hulc_set_error("%s: kernels 1 .. 3: nsplit > 1 goes with z_stride > 0 (partial slabs) and the reverse", who); return 1; }
     if (kernel == 0) {
-        const GemmPick pick = gemm_pick<T>(a, b, ep, M, N, K, gemm_use_glds);
+        const GemmPick pick = gemm_pick<T>(a, b, ep, M, N, K);
         if (!gemm_launch_picked<T>(st, pick, a, b, om, ep, M, N, K)) { hulc_set_error("%s: gemm_pick chose a kernel this type does not have", who); return 1; }
         *ran = pick == GEMM_PICK_SKINNY ? HULC_GEMM_RAN_SKINNY_ROUTER : pick == GEMM_PICK_GLDS ? HULC_GEMM_RAN_GLDS : gemm_pick_tile(pick) == 128 ? HULC_GEMM_RAN_128 :
                gemm_pick_tile(pick) == 64 ? HULC_GEMM_RAN_64 : HULC_GEMM_RAN_32;
@@ -517,10 +517,7 @@ static int k_gemm_epi_t(const hulc_gemm_epi_job& j, int kernel, int* ran, hipStr
             hulc_set_error("%s: kernel %d: skinny_ok refuses (M <= 64 or few rows of tiles, K %% 32 == 0, K >= 128, N %% 16 == 0, rows 16-byte aligned)", who, kernel); return 1;
         }
         if (kernel == 5 || kernel == 6) {
-            const bool saved = skinny_use_lds;
-            if (kernel == 6) skinny_use_lds = false;
-            launch_skinny(st, A, j.lda, W, j.ldb, M, N, K, om, ep);
-            skinny_use_lds = saved;
+            launch_skinny(st, A, j.lda, W, j.ldb, M, N, K, om, ep, kernel == 5);
             *ran = kernel;
             return k_launched(who);
         }
@@ -550,49 +547,29 @@ int k_gemm_epi(int t16, const hulc_gemm_epi_job* j, int kernel, int* ran, void* 
     return k_gemm_epi_t<float>(*j, kernel, ran, (hipStream_t)stream);
 #endif
 }
-int k_gemm_multi(int form, const hulc_gemm_epi_job* jobs, int n, int sh, int* ran, void* stream) {
-    static const char* who = "hulc_k_gemm_multi";
+// two independent recurrent steps of one shape as ONE launch (launch_skinny_lds_dual): jobs[0] and jobs[1]
+int k_gemm_dual(const hulc_gemm_epi_job* jobs, int* ran, void* stream) {
+    static const char* who = "hulc_k_gemm_dual";
     hipStream_t st = (hipStream_t)stream;
     int dummy = 0;
     if (!ran) ran = &dummy;
     *ran = HULC_GEMM_RAN_NONE;
     if (!jobs) { hulc_set_error("%s: null jobs", who); return 1; }
-    if (form < 0 || form > 2 || n < 2 || n > (form == 0 ? 3 : 2)) { hulc_set_error("%s: form=%d n=%d (form 0: n = 2 or 3; forms 1, 2: n = 2)", who, form, n); return 1; }
-    DenseLoader<h16_t> a[3], b[3]; DenseOut om[3]; EpiP ep[3];
-    for (int i = 0; i < n; ++i) {
+    DenseLoader<h16_t> a[2], b[2]; DenseOut om[2]; EpiP ep[2];
+    for (int i = 0; i < 2; ++i) {
         const hulc_gemm_epi_job& j = jobs[i];
         if (k_gemm_job_bad(who, i, &j, 2)) return 1;
         if (j.nsplit != 1 || j.z_stride != 0 || j.atomic || j.wfrag) { hulc_set_error("%s: job %d: nsplit = 1, z_stride = 0, no atomic, no wfrag", who, i); return 1; }
         a[i] = dense<h16_t>((const h16_t*)j.A, j.M, j.lda); b[i] = dense<h16_t>((const h16_t*)j.B, j.N, j.ldb); om[i] = k_gemm_job_om(j); ep[i] = k_gemm_job_epi(j);
     }
     const hulc_gemm_epi_job &j0 = jobs[0], &j1 = jobs[1];
-    if (form == 0) {
-        GemmGroupP g{};
-        g.n = n;
-        for (int i = 0; i < n; ++i) {
-            if (!gemm_glds_ok(a[i], b[i], ep[i], jobs[i].M, jobs[i].N, jobs[i].K)) { hulc_set_error("%s: job %d: gemm_glds_ok refuses (K >= 64, K %% 32 == 0, rows 16-byte aligned)", who, i); return 1; }
-            g.a[i] = a[i]; g.b[i] = b[i]; g.om[i] = om[i]; g.ep[i] = ep[i]; g.M[i] = jobs[i].M; g.N[i] = jobs[i].N; g.K[i] = jobs[i].K;
-        }
-        launch_gemm_glds_group(st, g);
-        *ran = HULC_GEMM_RAN_GROUP;
-        return k_launched(who);
-    }
     if (j0.M != j1.M || j0.N != j1.N || j0.K != j1.K || j0.lda != j1.lda || j0.ldb != j1.ldb || j0.ldc != j1.ldc || j0.out_R1 != j1.out_R1 || j0.out_s0 != j1.out_s0) {
-        hulc_set_error("%s: forms 1 and 2: the two jobs share M, N, K, the leading dimensions and the output map", who); return 1;
+        hulc_set_error("%s: the two jobs share M, N, K, the leading dimensions and the output map", who); return 1;
     }
-    if (form == 1) {
-        if (j0.A != j1.A) { hulc_set_error("%s: form 1: the two jobs share A", who); return 1; }
-        if (!gemm_glds_pair_ok(a[0], b[0], b[1], ep[0], ep[1], j0.M, j0.N, j0.K, sh)) {
-            hulc_set_error("%s: form 1: gemm_glds_pair_ok refuses (K >= 192, K, sh multiples of 64, 0 < sh < K, M, N multiples of 128, plain fp32 epilogues, 16-byte aligned)", who); return 1;
-        }
-        launch_gemm_glds_pair(st, a[0], b[0], b[1], om[0], ep[0], ep[1], j0.M, j0.N, j0.K, sh);
-        *ran = HULC_GEMM_RAN_PAIR;
-        return k_launched(who);
+    if (!skinny_lds_dual_ok(a[0].p, b[0].p, a[1].p, b[1].p, j0.lda, j0.ldb, j0.M, j0.N, j0.K)) {
+        hulc_set_error("%s: shape not covered by the dual launch (32 < M <= 64, K = 2048, N %% 16 == 0, lda %% 64 == 0, A 128-byte aligned, W 16-byte aligned)", who); return 1;
     }
-    if (!skinny_use_lds || !skinny_lds_dual_ok(a[0].p, b[0].p, a[1].p, b[1].p, j0.lda, j0.ldb, j0.M, j0.N, j0.K)) {
-        hulc_set_error("%s: form 2: shape not covered by the dual launch (32 < M <= 64, K = 2048, N %% 16 == 0, lda %% 64 == 0, A 128-byte aligned, W 16-byte aligned)", who); return 1;
-    }
-    if (!launch_skinny_lds_dual(st, a[0].p, b[0].p, ep[0], a[1].p, b[1].p, ep[1], j0.lda, j0.ldb, j0.M, j0.N, j0.K, om[0])) { hulc_set_error("%s: form 2: the launcher refused", who); return 1; }
+    if (!launch_skinny_lds_dual(st, a[0].p, b[0].p, ep[0], a[1].p, b[1].p, ep[1], j0.lda, j0.ldb, j0.M, j0.N, j0.K, om[0])) { hulc_set_error("%s: the launcher refused", who); return 1; }
     *ran = HULC_GEMM_RAN_DUAL;
     return k_launched(who);
 }
@@ -602,8 +579,8 @@ int k_gemm_pick(int t16, int M, int N, int K, long long lda, long long ldb, int*
     EpiP ep;
     GemmPick p;
     const void* al = (const void*)(uintptr_t)0x10000;       // never dereferenced: stands for an aligned operand
-    if (t16) p = gemm_pick<h16_t>(dense<h16_t>((const h16_t*)al, M, lda), dense<h16_t>((const h16_t*)al, N, ldb), ep, M, N, K, gemm_use_glds);
-    else p = gemm_pick<float>(dense<float>((const float*)al, M, lda), dense<float>((const float*)al, N, ldb), ep, M, N, K, gemm_use_glds);
+    if (t16) p = gemm_pick<h16_t>(dense<h16_t>((const h16_t*)al, M, lda), dense<h16_t>((const h16_t*)al, N, ldb), ep, M, N, K);
+    else p = gemm_pick<float>(dense<float>((const float*)al, M, lda), dense<float>((const float*)al, N, ldb), ep, M, N, K);
     *pick = p == GEMM_PICK_SKINNY ? HULC_GEMM_RAN_SKINNY_ROUTER : p == GEMM_PICK_GLDS ? HULC_GEMM_RAN_GLDS : gemm_pick_tile(p) == 128 ? HULC_GEMM_RAN_128 : gemm_pick_tile(p) == 64 ? HULC_GEMM_RAN_64 : HULC_GEMM_RAN_32;
     *bk = (p == GEMM_PICK_SKINNY || p == GEMM_PICK_GLDS) ? 0 : (p == GEMM_PICK_64_BK128 || p == GEMM_PICK_32_BK128) ? 128 : p == GEMM_PICK_128_BK64 ? 64 : 32;
     return 0;

@@ -190,30 +190,6 @@ __global__ void __launch_bounds__(256) pair_transpose_kernel(TrPair pr) {
 //   dgrad pack Wd[zc][ci][(a,b,co)] = W[co][ci][ph+S*a][pw+S*b],  zc = ph*S+pw
 // the six conv layers of the two encoders in ONE launch (after every optimizer step): block b belongs to the conv whose block range holds it
 struct ConvPackBatch { const float* w[6]; void* wf[6]; void* wd[6]; int O[6], I[6], K[6], S[6], nhwc[6], blk0[7]; };
-template <typename T>
-__global__ void pack_conv_w_batched_kernel(ConvPackBatch d) {
-    int c = 0;
-    while (c < 5 && (int)blockIdx.x >= d.blk0[c + 1]) ++c;
-    const int idx = (blockIdx.x - d.blk0[c]) * blockDim.x + threadIdx.x;
-    const int O = d.O[c], I = d.I[c], KH = d.K[c], KW = d.K[c], S = d.S[c];
-    if (idx >= O * I * KH * KW) return;
-    int kw = idx % KW, t = idx / KW;
-    int kh = t % KH; t /= KH;
-    int ci = t % I, o = t / I;
-    const float v = d.w[c][idx];
-    T* wf = reinterpret_cast<T*>(d.wf[c]);
-    T* wd = reinterpret_cast<T*>(d.wd[c]);
-    if (wf) {
-        if (d.nhwc[c]) wf[(long long)o * (KH * KW * I) + (kh * KW + kw) * I + ci] = from_f<T>(v);
-        else wf[idx] = from_f<T>(v);
-    }
-    if (wd) {
-        const int ph = kh % S, a = kh / S, pw = kw % S, b = kw / S;
-        const int TA = KH / S, TB = KW / S;
-        const int zc = ph * S + pw;
-        wd[((long long)zc * I + ci) * (TA * TB * O) + (a * TB + b) * O + o] = from_f<T>(v);
-    }
-}
 
 // conv wgrad partial slabs [nsplit][O][Kc] (packed K order) -> summed, un-permuted, accumulated into torch-layout grad.
 // grid.y splits the slab range; each part lands with one fp32 atomicAdd (<= gridDim.y adds per element).
@@ -718,21 +694,10 @@ __global__ void __launch_bounds__(256) spatial_softmax_bwd64_kernel(const h16_t*
 // the four decoder heads (prob | mean | log_scale | gripper) as one packed [NHEAD][HID] GEMM operand: ONE launch packs weights
 // + biases, ONE launch adds the packed gradient back into the four parameter gradients (was 8 + 8 copy2d launches per step)
 struct HeadPack { const float* w[4]; const float* b[4]; float* dw[4]; float* db[4]; int rows[4]; };
-template <typename T>
-__global__ void pack_heads_kernel(HeadPack hp, T* __restrict__ wheads, float* __restrict__ bheads, int HID) {
-    const int total_rows = hp.rows[0] + hp.rows[1] + hp.rows[2] + hp.rows[3];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)total_rows * HID) return;
-    int r = (int)(idx / HID);
-    const int k = (int)(idx % HID);
-    int i = 0;
-    while (i < 3 && r >= hp.rows[i]) { r -= hp.rows[i]; ++i; }
-    wheads[idx] = from_f<T>(hp.w[i][(long long)r * HID + k]);
-    if (k == 0) bheads[idx / HID] = hp.b[i][r];
-}
 // the three independent repacks that follow an optimizer step in ONE launch (they were three): blocks [0, blkA) the six conv weight packs
-// (pack_conv_w_batched_kernel's body), [blkA, blkB) the gripper fc7's NHWC column permutation (permute_cols_kernel, R x (CH * P) fp32 -> T),
-// [blkB, ..) the packed decoder heads (pack_heads_kernel).  Their transposed copies ride on the batched transpose launch that follows.
+// (one thread per weight: block b belongs to the conv whose range blk0 holds it; the forward and the dgrad layouts described at ConvPackBatch),
+// [blkA, blkB) the gripper fc7's NHWC column permutation (R x (CH * P) fp32 -> T, column (ch, p) -> (p, ch)),
+// [blkB, ..) the packed decoder heads (one thread per element of the [NHEAD][HID] operand cast to T; the thread of column 0 also copies the row's bias).
 template <typename T>
 __global__ void __launch_bounds__(256) weight_pack_kernel(ConvPackBatch d, int blkA, const float* __restrict__ fc7_src, T* __restrict__ fc7_dst, int R7, int CH7,
                                                           int P7, int blkB, HeadPack hp, T* __restrict__ wheads, float* __restrict__ bheads, int HID,
@@ -1412,7 +1377,7 @@ __global__ void bcast_over_s_kernel(const float* __restrict__ dxm, int B, int S,
 }
 // backward of x0 = dropout(emb + pos) in ONE launch (was dropout_apply + copy2d + pos_grad): g = mask * dx / (1 - p);
 // demb[b][t][d] += g ; dpos[t][d] += sum_b g.  One thread per (t, d) and window chunk (grid.y chunks of `bchunk` windows, eight in flight);
-// grid.y == 1 (fp32 parity engine) adds b ascending like pos_grad_kernel, grid.y > 1 lands each chunk's partial sum with one fp32 atomic.
+// grid.y == 1 (fp32 parity engine) adds the windows in ascending b, grid.y > 1 lands each chunk's partial sum with one fp32 atomic.
 __global__ void __launch_bounds__(256) pr_input_bwd_kernel(const float* __restrict__ dx, int B, int S, int D, float drop_p, unsigned long long seed,
                                                            float* __restrict__ demb, float* __restrict__ dpos, int bchunk) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1436,14 +1401,6 @@ __global__ void __launch_bounds__(256) pr_input_bwd_kernel(const float* __restri
     }
     if (gridDim.y > 1) unsafeAtomicAdd(dpos + idx, s);
     else dpos[idx] += s;
-}
-// dpos[t][d] += sum_b dx[b][t][d]
-__global__ void pos_grad_kernel(const float* __restrict__ dx, int B, int S, int D, float* __restrict__ dpos) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= S * D) return;
-    float s = 0.f;
-    for (int b = 0; b < B; ++b) s += dx[(long long)b * S * D + idx];
-    dpos[idx] += s;
 }
 
 // =========================================================================================================

@@ -109,15 +109,15 @@ class HulcGemmEpiJob(C.Structure):      # hulc_gemm_epi_job: EpiP field for fiel
                 ("out2_relu", C.c_int32), ("generic_only", C.c_int32)]
 
 
-GEMM_RAN = {"none": 0, "32": 1, "64": 2, "128": 3, "glds": 4, "skinny_router": 5, "skinny_reg": 6, "kchunk": 7, "splitk_64": 8, "splitk_128": 9, "group": 10, "pair": 11,
-            "dual": 12}      # HULC_GEMM_RAN_*
+GEMM_RAN = {"none": 0, "32": 1, "64": 2, "128": 3, "glds": 4, "skinny_router": 5, "skinny_reg": 6, "kchunk": 7, "splitk_64": 8, "splitk_128": 9,
+            "dual": 12}      # HULC_GEMM_RAN_* (10 and 11: retired launch forms)
 
 EXPORTS = ["hulc_last_error", "hulc_ctx_create", "hulc_ctx_destroy", "hulc_set_stream", "hulc_workspace_bytes",
            "hulc_bind_params", "hulc_prepare_weights", "hulc_zero_grads", "hulc_flush_grads", "hulc_forward_loss", "hulc_forward_loss_pair", "hulc_backward", "hulc_backward_part",
            "hulc_adam_step", "hulc_optimizer_step", "hulc_comm_unique_id", "hulc_comm_prepare", "hulc_comm_init", "hulc_comm_destroy", "hulc_comm_buckets", "hulc_comm_stats", "hulc_comm_size", "hulc_comm_timeline", "hulc_allreduce_grads", "hulc_backward_allreduce", "hulc_scaler_enable", "hulc_scaler_get", "hulc_scaler_set", "hulc_grad_clip_set", "hulc_grad_norm_get", "hulc_validate", "hulc_store_gather", "hulc_store_stage", "hulc_store_stage_join", "hulc_store_stage_stats", "hulc_clip_gt_encode", "hulc_clip_gt_scores", "hulc_aux_heads_enable", "hulc_decoder_select", "hulc_aux_weights_set", "hulc_aux_losses_get", "hulc_rollout_reset", "hulc_rollout_plan", "hulc_rollout_act", "hulc_rollout_get_goal", "hulc_rollout_set_state", "hulc_rollout_envs_init", "hulc_rollout_envs_reset", "hulc_rollout_envs_plan", "hulc_rollout_envs_act", "hulc_rollout_envs_get_state", "hulc_rollout_envs_set_state", "hulc_sbert_create", "hulc_sbert_destroy", "hulc_sbert_set_stream", "hulc_sbert_bind", "hulc_sbert_encode", "hulc_set_kl_beta", "hulc_set_dropout", "hulc_set_option", "hulc_get_option", "hulc_timers_enable", "hulc_timers_read", "hulc_get_tensor", "hulc_get_plan_idx", "hulc_k_gemm_nt", "hulc_k_cast", "hulc_k_trread_probe", "hulc_k_conv_wgrad", "hulc_k_conv1_wgrad_u8", "hulc_k_conv1_interior_groups", "hulc_k_conv_tile", "hulc_k_camera_split", "hulc_k_conv_pair", "hulc_k_skinny", "hulc_k_attention", "hulc_k_rnn_persist", "hulc_k_rnn_persist_flag_words", "hulc_k_clip_loss", "hulc_k_clip_loss_fp32", "hulc_k_mia_head", "hulc_k_cosine_dist", "hulc_k_spatial_softmax64", "hulc_k_enc_tail_fwd", "hulc_k_enc_tail_bwd", "hulc_k_logistic_loss",
            "hulc_k_plan_kl_sample", "hulc_k_st_softmax_bwd", "hulc_k_plan_gather", "hulc_k_plan_scatter_grad", "hulc_k_normal_kl_sample", "hulc_k_normal_rsample_bwd",
            "hulc_k_layernorm_fwd", "hulc_k_layernorm_bwd", "hulc_k_layernorm_mean", "hulc_k_tr_layer_fwd", "hulc_k_tr_ffn_bwd", "hulc_k_tr_attn_bwd",
-           "hulc_k_window_compact", "hulc_k_rows_expand", "hulc_k_rows_reduce", "hulc_k_gemm_epi", "hulc_k_gemm_multi", "hulc_k_gemm_pick", "hulc_k_gemm_wgrad_nsplit",
+           "hulc_k_window_compact", "hulc_k_rows_expand", "hulc_k_rows_reduce", "hulc_k_gemm_epi", "hulc_k_gemm_dual", "hulc_k_gemm_pick", "hulc_k_gemm_wgrad_nsplit",
            "hulc_k_det_head_loss", "hulc_k_det_head_bwd", "hulc_k_det_head_act",
            "hulc_k_conv_wgrad_t", "hulc_k_conv1_wgrad_u8_t", "hulc_k_conv_tile_t", "hulc_k_conv_pair_t", "hulc_k_conv_plan",
            "hulc_decoder_body_select", "hulc_trainable_set", "hulc_trainable_get", "hulc_trainable_steps_set",
@@ -271,9 +271,10 @@ def load():
     if hasattr(lib, "hulc_k_gemm_epi") or not os.environ.get("HULC_LIB_PATH"):
         I, Q, PI = C.c_int32, C.c_int64, C.POINTER(C.c_int32)
         lib.hulc_k_gemm_epi.argtypes = [I, C.POINTER(HulcGemmEpiJob), I, PI, C.c_void_p]
-        lib.hulc_k_gemm_multi.argtypes = [I, I, C.POINTER(HulcGemmEpiJob), I, I, PI, C.c_void_p]
         lib.hulc_k_gemm_pick.argtypes = [I, I, I, I, Q, Q, PI, PI]
         lib.hulc_k_gemm_wgrad_nsplit.argtypes = [I, I, I, I, PI, PI]
+    if hasattr(lib, "hulc_k_gemm_dual") or not os.environ.get("HULC_LIB_PATH"):
+        lib.hulc_k_gemm_dual.argtypes = [C.c_int32, C.POINTER(HulcGemmEpiJob), C.POINTER(C.c_int32), C.c_void_p]
     if hasattr(lib, "hulc_k_lin_bwd_stream") or not os.environ.get("HULC_LIB_PATH"):
         P, I, Q = C.c_void_p, C.c_int32, C.c_int64
         lib.hulc_k_lin_bwd_stream.argtypes = [I, P, P, Q, I, I, I, I, I, P, Q, P, P, P]

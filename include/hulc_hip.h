@@ -844,7 +844,7 @@ int hulc_k_tr_attn_bwd(int32_t dtype, const hulc_tr_attn_bwd_job* job, int32_t B
  * Refused before any launch: null job / A / B / out, M, N, K < 1, leading dimensions shorter than a row, drop_p outside [0, 1), out2_lo / out2_hi not multiples of
  * 4 or out of order, accumulate or atomic together with out2, relu not 0 / 1 / 2, pointers not aligned to their element type, bias / bias2 not 16-byte aligned, res / mask /
  * out / out2 / out2_mask not aligned to four of their elements (the vector paths read and write them that way; every buffer the engine passes is), and every
- * shape or alignment the chosen kernel's own predicate (skinny_ok, gemm_glds_ok, gemm_glds_pair_ok, the launch_skinny_lds* launchers) does not accept. */
+ * shape or alignment the chosen kernel's own predicate (skinny_ok, gemm_glds_ok, the launch_skinny_lds* launchers) does not accept. */
 typedef struct hulc_gemm_epi_job {
     const void* A; const void* B; int32_t M, N, K; int64_t lda, ldb;
     int64_t ldc; int32_t out_R1; int64_t out_s0;
@@ -860,11 +860,11 @@ typedef struct hulc_gemm_epi_job {
  * register-fragment skinny_gemm_kernel (the LDS forms switched off for the call); 7 = skinny_lds_kchunk_kernel; 8 = atomic split K (atomic = 1, out_f32 = 1,
  * nsplit >= 2) through gemm_kernel at the tile Engine::gemm_wgrad takes.  *ran (may be NULL) receives what was launched: HULC_GEMM_RAN_*. */
 enum { HULC_GEMM_RAN_NONE = 0, HULC_GEMM_RAN_32 = 1, HULC_GEMM_RAN_64 = 2, HULC_GEMM_RAN_128 = 3, HULC_GEMM_RAN_GLDS = 4, HULC_GEMM_RAN_SKINNY_ROUTER = 5, HULC_GEMM_RAN_SKINNY_REG = 6,
-       HULC_GEMM_RAN_KCHUNK = 7, HULC_GEMM_RAN_SPLITK_64 = 8, HULC_GEMM_RAN_SPLITK_128 = 9, HULC_GEMM_RAN_GROUP = 10, HULC_GEMM_RAN_PAIR = 11, HULC_GEMM_RAN_DUAL = 12 };
+       HULC_GEMM_RAN_KCHUNK = 7, HULC_GEMM_RAN_SPLITK_64 = 8, HULC_GEMM_RAN_SPLITK_128 = 9, /* 10 and 11: retired launch forms, not reused */ HULC_GEMM_RAN_DUAL = 12 };
 int hulc_k_gemm_epi(int32_t dtype, const hulc_gemm_epi_job* job, int32_t kernel, int32_t* ran, void* hip_stream);
-/* form 0: launch_gemm_glds_group over n = 2 or 3 independent jobs; form 1: launch_gemm_glds_pair, two jobs that share A (and M, N, K, the output map): job 0 is
- * C1 = sum_{k >= sh} A[m][k] B1[n][k - sh], job 1 is C2 = A B2^T; form 2: launch_skinny_lds_dual, two jobs of one shape (32 < M <= 64, K = 2048).  16-bit types only. */
-int hulc_k_gemm_multi(int32_t dtype, int32_t form, const hulc_gemm_epi_job* jobs, int32_t n, int32_t sh, int32_t* ran, void* hip_stream);
+/* launch_skinny_lds_dual: jobs[0] and jobs[1], exactly two jobs of one shape (32 < M <= 64, K = 2048; the same M, N, K, leading dimensions and output map), each with
+ * its own operands and epilogue, as one launch.  16-bit types only. */
+int hulc_k_gemm_dual(int32_t dtype, const hulc_gemm_epi_job* jobs, int32_t* ran, void* hip_stream);
 /* host arithmetic only (no device is touched): the engine's routing.  hulc_k_gemm_pick: *pick = the HULC_GEMM_RAN_* kernel family (32 / 64 / 128 / GLDS /
  * SKINNY_ROUTER) gemm_pick chooses for a dense product with 256-byte aligned operands, leading dimensions lda, ldb and z_stride = 0, *bk = its k-step (0 for
  * the skinny and LDS-DMA kernels).  hulc_k_gemm_wgrad_nsplit: Engine::gemm_wgrad's split-K factor (1 = none), *big = 1: the 128x128 tile. */

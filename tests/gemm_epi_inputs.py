@@ -16,7 +16,8 @@ SEED = 0x5EED1234ABCD
 OLD = 7.0          # what every output buffer holds before a launch (plan_ln_gpu_util.sevens): the accumulate cases add to it, gaps and guards must keep it
 
 # HULC_GEMM_RAN_* (hulc_amd/lib.py GEMM_RAN)
-RAN_32, RAN_64, RAN_128, RAN_GLDS, RAN_ROUTER, RAN_REG, RAN_KCHUNK, RAN_SPLIT64, RAN_SPLIT128, RAN_GROUP, RAN_PAIR, RAN_DUAL = range(1, 13)
+RAN_32, RAN_64, RAN_128, RAN_GLDS, RAN_ROUTER, RAN_REG, RAN_KCHUNK, RAN_SPLIT64, RAN_SPLIT128 = range(1, 10)
+RAN_DUAL = 12      # 10 and 11: retired launch forms, not reused
 
 
 @functools.lru_cache(maxsize=None)

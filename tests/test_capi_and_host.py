@@ -284,7 +284,7 @@ def test_fused_transformer_entries_refuse_bad_arguments_before_touching_the_devi
 
 
 def test_gemm_epilogue_entries_refuse_bad_arguments_before_touching_the_device():
-    """hulc_k_gemm_epi / hulc_k_gemm_multi check every argument, and the preconditions of the kernel asked for with the predicates the engine's routing uses, before
+    """hulc_k_gemm_epi / hulc_k_gemm_dual check every argument, and the preconditions of the kernel asked for with the predicates the engine's routing uses, before
     anything is launched: the pointers here are made-up addresses that are never dereferenced (without a GPU a launch would report a HIP failure instead of
     naming the argument; with one, an LDS-DMA kernel outside its preconditions would read out of bounds)."""
     import ctypes as C
@@ -360,27 +360,17 @@ def test_gemm_epilogue_entries_refuse_bad_arguments_before_touching_the_device()
     refused(ep(kernel=7, K=4096, lda=4096, ldb=4104, wfrag=1), e, "wfrag repacks a dense B")
     assert ran.value == 0, "nothing ran"
 
-    e = "hulc_k_gemm_multi"
-    def multi(form, jobs, n=None, sh=0, dt=BF):
-        arr = (L.HulcGemmEpiJob * len(jobs))(*jobs)
-        return lib.hulc_k_gemm_multi(dt, form, arr, len(jobs) if n is None else n, sh, C.byref(ran), None)
-    pj = lambda **over: mk(**{**dict(M=128, N=128, K=192, lda=192, ldb=192, ldc=128, out_f32=1), **over})
-    refused(lib.hulc_k_gemm_multi(BF, 0, None, 2, 0, None, None), e, "null jobs")
-    refused(multi(0, [mk(), mk()], dt=F32), e, "not a 16-bit type")
-    for form, n in ((3, 2), (-1, 2), (0, 1), (0, 4), (1, 3), (2, 3)):
-        refused(multi(form, [mk(), mk(), mk(), mk()], n=n), e, "form=")
-    refused(multi(0, [mk(), mk(drop_p=1.0)]), e, "job 1: drop_p")
-    refused(multi(0, [mk(nsplit=2, z_stride=64), mk()]), e, "job 0: nsplit = 1")
-    refused(multi(0, [mk(), mk(), mk(K=40, lda=40, ldb=40)]), e, "job 2: gemm_glds_ok")
-    refused(multi(1, [pj(), pj(M=256)], sh=64), e, "share M, N, K")
-    refused(multi(1, [pj(), pj(A=A + 0x400000)], sh=64), e, "share A")
-    for sh, kw in ((0, {}), (32, {}), (192, {}), (64, dict(K=128, lda=128, ldb=128)), (64, dict(M=130)), (64, dict(N=120, ldc=120)), (64, dict(out_f32=0)), (64, dict(bias=A)),
-                   (64, dict(alpha=2.0)), (64, dict(relu=1)), (64, dict(generic_only=1)), (64, dict(lda=196))):
-        refused(multi(1, [pj(**kw), pj(**kw)], sh=sh), e, "gemm_glds_pair_ok")
+    e = "hulc_k_gemm_dual"
+    def dual(j0, j1, dt=BF):
+        return lib.hulc_k_gemm_dual(dt, (L.HulcGemmEpiJob * 2)(j0, j1), C.byref(ran), None)
+    refused(lib.hulc_k_gemm_dual(BF, None, None, None), e, "null jobs")
+    refused(dual(mk(), mk(), dt=F32), e, "not a 16-bit type")
+    refused(dual(mk(), mk(drop_p=1.0)), e, "job 1: drop_p")
+    refused(dual(mk(nsplit=2, z_stride=64), mk()), e, "job 0: nsplit = 1")
     dj = lambda **over: mk(**{**dict(M=64, N=48, ldc=48), **over})
     for kw in (dict(M=32), dict(M=65), dict(K=1024, lda=1024, ldb=1024), dict(N=40, ldc=40), dict(lda=2048 + 8), dict(A=A + 64), dict(B=A + 8), dict(ldb=2052)):
-        refused(multi(2, [dj(**kw), dj(**kw)]), e, "dual launch")
-    refused(multi(2, [dj(), dj(ldc=64)]), e, "share M, N, K")
+        refused(dual(dj(**kw), dj(**kw)), e, "dual launch")
+    refused(dual(dj(), dj(ldc=64)), e, "share M, N, K")
     assert ran.value == 0, "nothing ran"
 
 

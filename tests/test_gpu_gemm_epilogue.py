@@ -1,4 +1,4 @@
-"""GPU (-m gpu): every GEMM kernel of csrc/gemm.h with the whole runtime epilogue (EpiP), through the C-ABI entries hulc_k_gemm_epi / hulc_k_gemm_multi, which launch
+"""GPU (-m gpu): every GEMM kernel of csrc/gemm.h with the whole runtime epilogue (EpiP), through the C-ABI entries hulc_k_gemm_epi / hulc_k_gemm_dual, which launch
 through the launchers the engine calls and report which kernel ran (asserted in every case: nothing falls through to another kernel).
 
 Two comparisons per case, per element, no element excused.  PRODUCT: a launch with a plain fp32 store against gemm_epi_ref.product of the device's own rounded
@@ -13,13 +13,13 @@ plus one rounding per slab over 7 + product.
 Bit identity (drop_p = 0, alpha = 1): generic_only = 1 equals generic_only = 0 wherever epi_fast16 / epi_plain4 can run (kernels 4 and 5), and a rerun with an
 odd ldc (scalar epi_store, (o & 3) != 0) equals the vector path after de-striding (kernels 2, 4, 5).
 
-Cases: 425 tests, 2256 kernel launches, 3.5 s on one MI355X (bf16, fp16 and fp32; the LDS-DMA and skinny kernels for the 16-bit types).  Every one of the 34
+Cases: 401 tests, 2224 kernel launches, 3.5 s on one MI355X (bf16, fp16 and fp32; the LDS-DMA and skinny kernels for the 16-bit types).  Every one of the 34
 epilogue cases of tests/gemm_epi_inputs.py EPI (each EpiP field alone, the pairs, every row of the launch-site table) runs on each of the kernels 1 .. 7; the
 shape tests rotate a few of them over the shapes; no full cross product.
 
-Worst err / gate measured (all types): product — gemm_kernel 32 / 64 / 128: 0.086 / 0.16 / 0.091, glds 0.025, group 0.025, pair 0.028, skinny (router and
+Worst err / gate measured (all types): product — gemm_kernel 32 / 64 / 128: 0.086 / 0.16 / 0.091, glds 0.025, skinny (router and
 register form) 0.0074, kchunk 0.0001, dual 0.0003, atomic split K 0.0022; epilogue `out` — gemm_kernel 0.64 / 0.64 / 0.65, glds 0.62, skinny register form
-0.58, router 0.53, kchunk, group, dual 0.50; `out2` — 0.47 .. 0.53.  (0.5 is the half ulp of round-to-nearest under a gate of one ulp; the values above it are
+0.58, router 0.53, kchunk, dual 0.50; `out2` — 0.47 .. 0.53.  (0.5 is the half ulp of round-to-nearest under a gate of one ulp; the values above it are
 fp32 stores of a single fp32 operation, where one rounding sits under a bound of (1 + 1) 2^-24.)  Device tanhf against float64 tanh: measured 1.39e-7 relative
 (2.3 x 2^-24, the rounding of the argument's sum included); the gate allows twice that (TANH_REL below).
 
@@ -29,13 +29,12 @@ bias + bias2 first, the scalar path one after the other: measured, about one ele
 497 of 4760 elements differ in the last bit.  Neither is a defect — both lie within the derived bound, where the tests gate them — and the arithmetic stays as
 it is (the fp32 engine must reproduce the parent's bits); the claim is corrected instead: gemm.h now records the two differences at epi_prefetch4.
 
-Mutations of gemm.h shown to fail these tests (each applied once to a scratch copy, bf16 + fp32 unit, one run; failing tests of 425): dropout index col + r
+Mutations of gemm.h shown to fail these tests (each applied once to a scratch copy, bf16 + fp32 unit, one run; failing tests of the 425 the file had then, the retired grouped and shared-operand launch forms included): dropout index col + r
 for o + r in epi_apply4 — 46 (every dropout case on every kernel with a vector path, the padded-ldc / row-map test); res_late ignored in epi_apply4 — 45
 (res_late, res_late_drop, and the odd-ldc identity); the residual row (row + 1) % res_rowmod — 30 (rowmod, zx0; run in this in-bounds form: the literal
-"without % res_rowmod" reads past the residual buffer, so it moves a load); bias2 skipped in epi_fast16_pre — 16 (bias12_16, zx1 on glds / skinny LDS / group,
+"without % res_rowmod" reads past the residual buffer, so it moves a load); bias2 skipped in epi_fast16_pre — 16 (bias12_16, zx1 on glds / skinny LDS,
 and generic_only identity); mask test >= 0 — 59 (+0.0 and -0.0 of every ReLU mask and out2_mask); 1 - m for 1 - m * m — 30; out2_relu ignored — 76;
-accumulate ignored by epi_plain4 — 17 (glds acc32, every-tile-once, group, pair, both identities); group selection b > t0[p] — all 4 group cases (the first
-tile of problems 1, 2 keeps its 7.0); pair's B1 stage at kt — all 8 pair cases of the unit; alpha applied after the bias (vector paths) — 9 (alpha_bias).
+accumulate ignored by epi_plain4 (glds acc32, every-tile-once, both identities); alpha applied after the bias (vector paths) — 9 (alpha_bias).
 None uncaught."""
 import ctypes as C
 
@@ -94,10 +93,10 @@ def host(t):
 class Prob:
     """one product out = epilogue(A B^T): operands on the device, the output's element offsets, and per launch the buffers of an epilogue case"""
 
-    def __init__(self, dtype, M, N, K, ldc=None, R1=0, s0=0, tag="", A=None):
+    def __init__(self, dtype, M, N, K, ldc=None, R1=0, s0=0, tag=""):
         self.dtype, self.M, self.N, self.K = dtype, M, N, K
         self.ldc, self.R1, self.s0 = ldc or N, R1, s0
-        self.A = A if A is not None else GI.matrix("A" + tag, M, K, dtype)
+        self.A = GI.matrix("A" + tag, M, K, dtype)
         self.B = GI.matrix("B" + tag, N, K, dtype)
         self.dA, self.dB = buf(self.A, dtype), buf(self.B, dtype)
         self.off = G.offsets(M, N, self.ldc, R1, s0)
@@ -454,52 +453,19 @@ def test_odd_leading_dimension_equals_the_vector_path_bit_for_bit(kernel, shape,
     assert not bad, "\n".join(bad)
 
 
-# ==================================================================================================== group, pair, dual
-def multi(L, lib, dtype, form, probs, epis, sh, want, what, acc=None):
-    """one hulc_k_gemm_multi launch over `probs` with the epilogue cases `epis` -> the contexts"""
-    jobs, ctxs = (L.HulcGemmEpiJob * len(probs))(), []
+# ==================================================================================================== dual
+def dual(L, lib, dtype, probs, epis, what):
+    """one hulc_k_gemm_dual launch over the two `probs` with the epilogue cases `epis` -> the contexts"""
+    jobs, ctxs = (L.HulcGemmEpiJob * 2)(), []
     for i, (p, name) in enumerate(zip(probs, epis)):
         jobs[i], ctx = p.job(L, GI.EPI[name])
         ctxs.append(ctx)
     ran = C.c_int32(-1)
-    L.check(lib.hulc_k_gemm_multi(L.DTYPE[dtype], form, jobs, len(probs), sh, C.byref(ran), None))
+    L.check(lib.hulc_k_gemm_dual(L.DTYPE[dtype], jobs, C.byref(ran), None))
     torch.cuda.synchronize()
     COUNT[0] += 1
-    assert ran.value == want, (what, ran.value)
+    assert ran.value == GI.RAN_DUAL, (what, ran.value)
     return ctxs
-
-
-GROUP_SHAPES = {6: (300, 256), 2: (100, 250), 9: (384, 384), 8: (512, 256)}          # tiles of 128 x 128 -> (M, N)
-
-
-@pytest.mark.parametrize("dtype", GI.DTYPES16)
-@pytest.mark.parametrize("tiles", [(6, 2, 9), (6, 2), (8, 2), (2, 8, 6)])
-def test_group_launch(tiles, dtype):
-    """gemm_glds_group_kernel: block ranges padded to 8, problems of different K and epilogue, one of them accumulating"""
-    L, lib = load()
-    Ks, epis = (64, 96, 192), ("bias12_16", "acc32", "rnn_fwd")
-    probs = [Prob(dtype, *GROUP_SHAPES[t], Ks[i], tag=f"g{i}") for i, t in enumerate(tiles)]
-    what = f"group [{dtype}] tiles {tiles}"
-    accs = [p.read(c, what) for p, c in zip(probs, multi(L, lib, dtype, 0, probs, ["bare32"] * len(probs), 0, GI.RAN_GROUP, what))]
-    ctxs = multi(L, lib, dtype, 0, probs, epis[:len(probs)], 0, GI.RAN_GROUP, what)
-    for i, (p, c, a) in enumerate(zip(probs, ctxs, accs)):
-        check_product(p, a, "group", f"{what} problem {i}")
-        check_epilogue(p, c, a, "group", f"{what} problem {i} {epis[i]}")
-
-
-@pytest.mark.parametrize("dtype", GI.DTYPES16)
-@pytest.mark.parametrize("M,N,K,sh,ldc", [(128, 128, 192, 64, 128), (128, 128, 192, 128, 128), (256, 384, 320, 64, 384), (128, 128, 256, 64, 130)])
-@pytest.mark.parametrize("acc", [(0, 1), (1, 0)])
-def test_pair_launch(M, N, K, sh, ldc, acc, dtype):
-    """gemm_glds_pair_kernel: C1 = sum_{k >= sh} A[m][k] B1[n][k - sh], C2 = A B2^T; accumulate set independently; ldc = 130: the scalar fall-back of its epilogue"""
-    L, lib = load()
-    p1 = Prob(dtype, M, N, K, ldc=ldc, tag="p1")
-    p2 = Prob(dtype, M, N, K, ldc=ldc, tag="p2", A=p1.A)
-    p2.dA = p1.dA
-    what = f"pair [{dtype}] {M}x{N}x{K} sh={sh} ldc={ldc} acc={acc}"
-    ctxs = multi(L, lib, dtype, 1, (p1, p2), ["acc32" if a else "bare32" for a in acc], sh, GI.RAN_PAIR, what)
-    check_product(p1, p1.read(ctxs[0], what), "pair", what + " C1", old=GI.OLD * acc[0], ops=(p1.A[:, sh:], p1.B[:, :K - sh]))
-    check_product(p2, p2.read(ctxs[1], what), "pair", what + " C2", old=GI.OLD * acc[1])
 
 
 @pytest.mark.parametrize("dtype", GI.DTYPES16)
@@ -510,8 +476,8 @@ def test_dual_launch_with_two_different_epilogues(M, N, epis, dtype):
     L, lib = load()
     probs = [Prob(dtype, M, N, 2048, tag=f"d{i}") for i in range(2)]
     what = f"dual [{dtype}] {M}x{N}x2048 {epis}"
-    accs = [p.read(c, what) for p, c in zip(probs, multi(L, lib, dtype, 2, probs, ["bare32"] * 2, 0, GI.RAN_DUAL, what))]
-    ctxs = multi(L, lib, dtype, 2, probs, epis, 0, GI.RAN_DUAL, what)
+    accs = [p.read(c, what) for p, c in zip(probs, dual(L, lib, dtype, probs, ["bare32"] * 2, what))]
+    ctxs = dual(L, lib, dtype, probs, epis, what)
     for i, (p, c, a) in enumerate(zip(probs, ctxs, accs)):
         check_product(p, a, "dual", f"{what} problem {i}")
         check_epilogue(p, c, a, "dual", f"{what} problem {i} {epis[i]}")

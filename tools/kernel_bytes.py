@@ -32,17 +32,30 @@ def kernels(obj):
         elif len(f) == 8 and f[3] == "OBJECT" and f[7].endswith(".kd"):
             kd.add(f[7][:-3])                                       # a kernel = a function with a kernel descriptor
     assert text, "no .text section in the gfx950 code object of " + obj
-    return {n: hashlib.sha1(data[a - text[1] + text[2]: a - text[1] + text[2] + sz]).hexdigest() for n, (a, sz, ndx) in syms.items() if ndx == text[0] and n in kd}
+    return {n: data[a - text[1] + text[2]: a - text[1] + text[2] + sz] for n, (a, sz, ndx) in syms.items() if ndx == text[0] and n in kd}
+
+
+def how(x, y):
+    """what differs between two byte strings of one kernel: the 32-bit words, and whether all of them moved by one constant (the literal of a pc-relative address
+    of a device variable moves by what was removed between the kernel and the variable; the instructions are the same)"""
+    if len(x) != len(y):
+        return f"{len(x)} against {len(y)} bytes"
+    w = [i for i in range(0, len(x), 4) if x[i:i + 4] != y[i:i + 4]]
+    deltas = {(int.from_bytes(x[i:i + 4], "little") - int.from_bytes(y[i:i + 4], "little")) & 0xffffffff for i in w}
+    return f"{len(w)} of {len(x) // 4} words" + (f", every one shifted by {deltas.pop():#x}" if len(deltas) == 1 else "")
 
 
 def main():
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    sha = lambda d: hashlib.sha1(d).hexdigest()
     removed, added = sorted(set(a) - set(b)), sorted(set(b) - set(a))
-    differ = sorted(n for n in set(a) & set(b) if a[n] != b[n])
+    differ = sorted(n for n in set(a) & set(b) if sha(a[n]) != sha(b[n]))
     print(f"{sys.argv[1]}: {len(a)} kernels; {sys.argv[2]}: {len(b)} kernels; removed {len(removed)}, added {len(added)}, surviving with different bytes {len(differ)}")
-    for title, names in (("removed", removed), ("added", added), ("different", differ)):
+    for title, names in (("removed", removed), ("added", added)):
         for n in names:
             print(f"  {title}: {n}")
+    for n in differ:
+        print(f"  different: {n} ({how(a[n], b[n])})")
     return 1 if added or differ else 0
 
 
