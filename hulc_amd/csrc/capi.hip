@@ -496,7 +496,7 @@ int hulc_k_ema_update(float* ema, const float* p, int64_t n, float w, const int6
     if (hipGetLastError() != hipSuccess) { hulc_set_error("hulc_k_ema_update: launch failed"); return 1; }
     return 0;
 }
-// the row kernels of the ragged encoder pass (conv_wgrad.h), through the engine's launchers.  lens / off are device arrays the caller built (ragged_plan)
+// the row kernels of the ragged encoder pass (window_rows.h), through the engine's launchers.  lens / off are device arrays the caller built (ragged_plan)
 int hulc_k_window_compact(const int64_t* window_start, const int32_t* lens, const int32_t* off, int32_t off_base, int32_t B, int32_t S, int64_t store_frames,
                           const int32_t* shift_static, const int32_t* shift_gripper, int64_t* frame_out, int32_t* shift_static_out, int32_t* shift_gripper_out, void* stream) {
     if (!window_start || !lens || !off || !frame_out || B < 1 || S < 1 || store_frames < 1 || (shift_static && !shift_static_out) || (shift_gripper && !shift_gripper_out)) {
@@ -591,7 +591,7 @@ int hulc_k_conv_wgrad_t(int32_t dtype, int32_t which, const void* X, const void*
     HULC_K_CONV_T("hulc_k_conv_wgrad_t", k_conv_wgrad("hulc_k_conv_wgrad_t", 1, which, X, dY, out, db_out, Nf, IH, slabs, stream));
 }
 
-// host arithmetic only (no device needed): the interior group range the uint8 conv1 kernels convert without clamps (conv_wgrad.h::conv1_interior_groups)
+// host arithmetic only (no device needed): the interior group range the uint8 conv1 kernels convert without clamps (conv1_stage.h::conv1_interior_groups)
 int hulc_k_conv1_interior_groups(int32_t IW, int32_t pad, int32_t cap, int32_t* first, int32_t* count) {
     int cl = 0, wi = 0;
     conv1_interior_groups(IW, pad, cap, cl, wi);
@@ -622,7 +622,7 @@ int hulc_k_conv_plan(int32_t form, int32_t frames, int32_t in_side, int32_t out_
     return hulc_bf16::k_conv_plan(form, frames, in_side, out_side, wgs, nbands, rows_per_band, frames_per_band, items);
 }
 
-// host arithmetic only (no device needed): the division of a launch's persistent workgroups between the two cameras' jobs (conv_wgrad.h::camera_split)
+// host arithmetic only (no device needed): the division of a launch's persistent workgroups between the two cameras' jobs (common.h::camera_split)
 int hulc_k_camera_split(int32_t grid, double work_static, double work_gripper, int32_t* wg_static, int32_t* wg_gripper) {
     int a = 0, b = 0;
     camera_split(grid, work_static, work_gripper, a, b);

@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 
 void hulc_set_error(const char* fmt, ...);
 
@@ -148,6 +149,26 @@ DEVI uint32_t hash_u32(uint64_t seed, uint64_t idx) {
 }
 DEVI float hash_uniform(uint64_t seed, uint64_t idx) {
     return ((hash_u32(seed, idx) >> 8) + 0.5f) * (1.0f / 16777216.0f);
+}
+
+// ---- host-side launch helpers shared by the kernel families
+// The opt-in to more than 64 KB of dynamic LDS, once per kernel instance K (a function-local flag per instantiation): called immediately in front of every launch of
+// K that may ask for it, as max_dyn_lds_once<&kernel<3>>(bytes).
+template <auto K> static inline void max_dyn_lds_once(int bytes) {
+    static bool done = false;
+    if (!done) { hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); done = true; }
+}
+// host side: how a launch's persistent workgroups are divided between two independent jobs (the two cameras' copies of one stage): job B gets
+// round(grid * wB / (wA + wB)) of them, both jobs at least one; wA / wB = the jobs' multiply work in the units of the launchers' cost models
+// (items x rounds per item).  wB <= 0 (one job): the whole grid is job A's.  hulc_k_camera_split exposes it to the host tests.
+static inline void camera_split(int grid, double wA, double wB, int& nA, int& nB) {
+    if (grid < 1) grid = 1;
+    if (!(wB > 0.0)) { nA = grid; nB = 0; return; }
+    if (!(wA > 0.0)) { nA = 0; nB = grid; return; }
+    if (grid < 2) { nA = nB = 1; return; }      // (callers never ask: two jobs need two workgroups)
+    int b = (int)(grid * (wB / (wA + wB)) + 0.5);
+    b = std::min(std::max(b, 1), grid - 1);
+    nA = grid - b; nB = b;
 }
 
 }  // namespace HULC_NS

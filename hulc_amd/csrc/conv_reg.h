@@ -597,11 +597,7 @@ static inline bool launch_conv_reg_jobs(hipStream_t st, const ConvTileP* jobs, i
     }
     size_t ldsmax = 0;
     for (int k = 0; k < n; ++k) { bt.blk0[k + 1] = bt.blk0[k] + nw[k]; ldsmax = std::max(ldsmax, lds[k]); }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, PKR, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / (NWV == 8 ? 1 : 2) - 64);
-        attr_set = true;
-    }
+    max_dyn_lds_once<&conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, PKR, EPI>>(160 * 1024 / (NWV == 8 ? 1 : 2) - 64);
     hipLaunchKernelGGL((conv_reg_kernel<CK, TA, TB, SI, REV, OS, NWV, PKR, EPI>), dim3(bt.blk0[n]), dim3(NWV * 64), ldsmax, st, bt);
     return true;
 }

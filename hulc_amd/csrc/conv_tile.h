@@ -13,7 +13,7 @@
 // ends up with 4 consecutive output channels of one pixel -> 8-byte stores, 4-channel bias / mask loads.
 #pragma once
 #include "common.h"
-#include "conv_wgrad.h"   // lds_char, u32x4_t
+#include "conv1_stage.h"   // Conv1Src, conv1_stage_band; lds_types.h
 
 namespace HULC_NS {
 
@@ -446,11 +446,7 @@ static inline bool launch_conv_tile_nw(hipStream_t st, ConvTileP p) {
         if (bestf > 1) { p.FPB = bestf; p.VPI = vpi; p.VPO = vpo; }
     }
     const size_t lds = C::lds_bytes(p.LR, p.LP, p.maskbits != nullptr);      // without a bitmask the 8 KB mask region is not allocated: conv3's forward then holds a WHOLE frame per band
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)conv_tile_kernel<CK, CN, TA, TB, SI, OS, REV, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-        attr_set = true;
-    }
+    max_dyn_lds_once<&conv_tile_kernel<CK, CN, TA, TB, SI, OS, REV, NWV>>(160 * 1024 - 64);
     const int items = p.FPB > 1 ? (p.Nf + p.FPB - 1) / p.FPB : p.Nf * p.nbands;
     const int grid = items < 256 ? items : 256;
     hipLaunchKernelGGL((conv_tile_kernel<CK, CN, TA, TB, SI, OS, REV, NWV>), dim3(grid), dim3(NWV * 64), lds, st, p);
@@ -718,21 +714,18 @@ static inline void launch_conv1_fwd(hipStream_t st, const Conv1Src& X, const h16
     const int nbands = (OH + R - 1) / R;
     R = (OH + nbands - 1) / nbands;
     // OCC = 4: min waves per SIMD the register allocation targets: 128 VGPRs (5 spilled) lets all 4 workgroups of a CU be resident
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute((const void*)conv1_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
     const int items = Nf * nbands;
     if (X.u8 && !regconv && (IW * 3) % 4 == 0 && ((uintptr_t)X.X & 3) == 0) {
-        static bool a2 = false;
-        if (!a2) { hipFuncSetAttribute((const void*)conv1_fwd_u8dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a2 = true; }
+        max_dyn_lds_once<&conv1_fwd_u8dma_kernel>(160 * 1024);
         hipLaunchKernelGGL(conv1_fwd_u8dma_kernel, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, maskbits, zero8a, zero8b);
         return;
     }
     if (regconv) {       // uint8 cross-check path (tests, tools/time_conv1_u8reg.py): its own instance, so that the window code does not weigh on the fp32 kernel's registers
-        static bool a3 = false;
-        if (!a3) { hipFuncSetAttribute((const void*)conv1_fwd_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a3 = true; }
+        max_dyn_lds_once<&conv1_fwd_kernel<4, true>>(160 * 1024);
         hipLaunchKernelGGL((conv1_fwd_kernel<4, true>), dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, maskbits, zero8a, zero8b);
         return;
     }
+    max_dyn_lds_once<&conv1_fwd_kernel<4>>(160 * 1024);
     hipLaunchKernelGGL(conv1_fwd_kernel<4>, dim3(items < max_wg ? items : max_wg), dim3(256), lds_of(R), st, X, W, bias, out, Nf, IH, IW, OH, OW, R, nbands, maskbits, zero8a, zero8b);
 }
 

@@ -10,7 +10,7 @@
 // needs f1, f2 and the LayerNorm statistics), the two K-halves of fc2 meet in LDS, wave w normalises rows 2w, 2w + 1 (lane = feature).
 #pragma once
 #include "common.h"
-#include "conv_wgrad.h"   // lds_char
+#include "lds_types.h"   // lds_char, lds_u32x4
 
 namespace HULC_NS {
 

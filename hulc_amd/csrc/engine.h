@@ -15,6 +15,10 @@
 #include "kernels.h"
 #include "plan_ln_launch.h"
 #include "conv_wgrad.h"
+#include "conv1_stage.h"
+#include "window_rows.h"
+#include "conv1_wgrad.h"
+#include "lin_bwd.h"
 #include "conv_tile.h"
 #include "conv_reg.h"
 #include "tr_fused.h"

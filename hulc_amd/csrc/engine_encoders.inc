@@ -1,8 +1,9 @@
 // hulc_amd/csrc/engine_encoders.inc — a section of `template <typename T> struct Engine` (engine.h), included INSIDE the class body; not a standalone header.
 // The perceptual encoders (SURVEY 8 a3-a6): where conv1 reads its frames (conv1_src: fp32 / uint8 / frame store / variable-length windows), then the driver of the
 // forward and backward pass.  The driver is a list of stages (enc_fwd_stages, enc_bwd_stages).  Each stage has a single-camera function (conv1_fwd, conv_fwd, head_fwd;
-// head_bwd, conv_wgrad, conv_dgrad, conv1_wgrad) and, where the 16-bit engines run both cameras as jobs of one launch, a *_both function that returns false when it
-// launched nothing; the list then calls the single-camera function once per camera.  Weight-gradient slabs are queued (queue_unpack) and reduced by one launch
+// head_bwd, conv_dgrad) and, where the 16-bit engines run both cameras as jobs of one launch, a *_both function that returns false when it
+// launched nothing; the list then calls the single-camera function once per camera.  The weight-gradient stages (conv_wgrad, conv1_wgrad) are one function each over
+// the camera range: the joint launch when the range holds both cameras, else per camera.  Weight-gradient slabs are queued (queue_unpack) and reduced by one launch
 // (flush_unpacks).  The rest of the engine calls conv1_src / conv1_src_f32, window_tables (+ enc_frames, ragged: the ragged encoder pass), store_args_bad, actions_of, enc_fwd_both, enc_tail_fusable,
 // enc_tail_fwd_both, enc_tail_bwd_both, enc_bwd_both and flush_unpacks.
     ConvGeom geom(int Nf, int IH, int C, int K, int S) const {
@@ -15,7 +16,7 @@
         s.u8 = b.frames_u8 != 0;
         s.shift = s.u8 ? (gripper ? b.shift_gripper : b.shift_static) : nullptr;
         s.pad = gripper ? b.pad_gripper : b.pad_static;
-        // 16-bit engines: the dataloader's affine is folded out of the uint8 data path (conv_wgrad.h Conv1Src::fold); the fp32 (parity) engine converts
+        // 16-bit engines: the dataloader's affine is folded out of the uint8 data path (conv1_stage.h Conv1Src::fold); the fp32 (parity) engine converts
         // exactly like the reference (ingest_u8_kernel)
         s.fold = (s.u8 && std::is_same<T, h16_t>::value && u8_fold_mode) ? 1 : 0;
         if (s.u8 && b.window_start) { s.wstart = reinterpret_cast<const long long*>(b.window_start); s.S = b.S; s.nstore = b.store_frames; }      // windows gathered from the frame store
@@ -28,7 +29,7 @@
     }
     // fp32 NCHW frames read as they are (the rollout's observations): no dataloader transform, no frame store
     static Conv1Src conv1_src_f32(const void* x) { return Conv1Src{x, nullptr, 0, 0}; }
-    // hulc_batch::window_len, expanded once per forward / validation (conv_wgrad.h window_expand_kernel); set 0 = the batch of the pass, 1 = the paired pass's lang batch (cur2)
+    // hulc_batch::window_len, expanded once per forward / validation (window_rows.h window_expand_kernel); set 0 = the batch of the pass, 1 = the paired pass's lang batch (cur2)
     long long* wl_frame[2] = {nullptr, nullptr};
     int* wl_shift[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     int wl_alloc(int set) {
@@ -371,134 +372,124 @@
         launch_gemm<T, TM, 64>(st, la, lb, dense_out(Kc), ep, c.O, Kc, (int)npix, 1, nsplit);
         return nsplit;
     }
-    // the nsplit slabs a single-camera launch left at part + part_cur -> the layer's gradient: 64 slabs or more of a 16-bit engine join the batched unpack, the rest
-    // is one launch here.  bias_done: the kernel added the bias gradient itself (the tr kernels, atomics)
-    void wgrad_unpack(const ConvW& c, const T* dy, long long npix, int nsplit, bool bias_done) {
+    // The slab hand-off and the bias gradient behind every weight-gradient launch.  nsplit slabs at part + part_cur -> the layer's gradient: a joint (two-camera) launch
+    // always queues them for the batched unpack (its room was checked first; the gripper job has fewer than 64), a single launch queues 64 slabs or more of a 16-bit
+    // engine, the rest is one launch here.  tr: a raw-tile kernel ran — outside reproducible mode it added the bias gradient itself (atomics); else the column sum of dy
+    void wgrad_finish(const ConvW& c, const T* dy, long long npix, int nsplit, bool tr, bool joint) {
         const bool many = std::is_same<T, h16_t>::value && nsplit >= 64;
         const int yparts = many && !repro ? 16 : 1;
         // slab parts over grid.y, each landing with one fp32 atomic per element.  16 parts: more (21 / 24 / 64 for conv3 / conv2 / conv1) made
         // every launch slower (23 / 11.3 / 10.9 us against 18.6 / 9.5 / 9.6: the scattered atomics, not the slab stream, are the cost)
-        if (!(many && queue_unpack(c.dW, c.O, c.I, c.KH, c.KW, c.nhwc, nsplit, 0))) {
+        if (!((joint || many) && queue_unpack(c.dW, c.O, c.I, c.KH, c.KW, c.nhwc, nsplit, 0))) {
             if (yparts > 1) nd(ND_CONV_UNPACK_SPLIT);
             hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3(cdiv(c.O * c.I * c.KH * c.KW, 1024), yparts), dim3(256), 0, st, this->part + part_cur, nsplit,   // fp32 (parity) mode: one deterministic pass, no atomics
                                (long long)c.O * c.I * c.KH * c.KW, c.dW, c.O, c.I, c.KH, c.KW, c.nhwc);
         }
-        if (!bias_done) colsum(dy, c.O, (int)npix, c.O, c.db);
+        if (!tr || repro) colsum(dy, c.O, (int)npix, c.O, c.db);      // reproducible mode: no bias atomics, the two-stage column sum
+        else if (nsplit > 1) nd(ND_CONV_BIAS);
     }
-    // conv2's / conv3's weight gradient of one camera.  16-bit engines: raw-tile + transposing-LDS-read kernel (conv_wgrad.h); slabs = persistent workgroups
-    void conv_wgrad(int k, int sn, int Nf) {
-        const Stage s = stage(k, sn, Nf);
-        const ConvW& c = s.c; const ConvGeom& g = s.g;
-        const long long npix = (long long)g.Nf * g.OH * g.OW;
-        int nsplit = 0;
+    // conv3's / conv2's raw-tile + transposing-LDS-read launch (conv_wgrad.h; 16-bit engines) of camera s alone, or of s and g — both cameras — as ONE launch
+    // (launch_conv_wgrad_pair).  ns = slabs (= persistent workgroups) per camera; false = nothing launched (the fp32 engine, a shape the launchers do not take, no room)
+    bool conv_wgrad_launch(const Stage& s, const Stage* g, int* ns) {
         if constexpr (std::is_same<T, h16_t>::value) {
-            TimerScope ts(this, "conv_wgrad_tr", "mfma", conv_wgrad_flops(c, g), conv_wgrad_bytes(c, g, 2));
-            // reproducible mode: strided items (no claim counter) and no bias atomics — the bias gradient is the two-stage column sum of wgrad_unpack
-            float* const kb = repro ? nullptr : c.db;
-            if (c.I == 64 && c.KH == 3) nsplit = launch_conv_wgrad_tr<64, 64, 3, 3, 1>(st, s.x, s.dy, this->part + part_cur, kb, g.Nf, g.IH, g.IW, g.OH, g.OW, 512, claim_ctr(g.Nf > 1), wgrad_zero_page());
-            else if (c.I == 32 && c.KH == 4) nsplit = launch_conv_wgrad_tr<32, 64, 4, 4, 2>(st, s.x, s.dy, this->part + part_cur, kb, g.Nf, g.IH, g.IW, g.OH, g.OW, 512, claim_ctr(g.Nf > 1), wgrad_zero_page());
-            if (nsplit > 1 && !repro) nd(ND_CONV_BIAS);
-        }
-        const bool tr = nsplit > 0;
-        if (!tr) nsplit = wgrad_gemm<64>(c, s.dy, ConvNHWCLoaderT<T>{s.x, g}, npix);
-        wgrad_unpack(c, s.dy, npix, nsplit, tr && !repro);
-    }
-    // conv1's weight gradient of one camera, once per frame source (paired pass: two, as conv1_fwd).  The fp32 engine reads the frames the forward materialised (conv1_f32)
-    void conv1_wgrad(int k, const Conv1Src& src, int Nf, const Conv1Src* src2) {
-        const EncW& e = encw(k); EncA& a = enca(k);
-        const ConvW& c = e.c1;
-        for (int h = 0; h < (src2 ? 2 : 1); ++h) {
-            const int nf = src2 ? src_frames(Nf, h) : Nf;
-            const ConvGeom g = geom(nf, e.IH, 3, 8, 4);
-            const long long npix = (long long)nf * g.OH * g.OW;
-            const Conv1Src& sh = h ? *src2 : src;
-            const long long foff = h ? src_frames(Nf, 0) : 0;
-            const T* dy = a.dact1 + foff * g.OH * g.OW * 32;
-            const float* x = nullptr;
-            if constexpr (std::is_same<T, float>::value) x = sh.u8 ? x32[k] + foff * 3 * e.IH * e.IH : reinterpret_cast<const float*>(sh.X);
-            int nsplit = 0;
-            if constexpr (std::is_same<T, h16_t>::value) {
-                TimerScope ts(this, "conv1_wgrad", "hbm", conv_wgrad_flops(c, g), conv_wgrad_bytes(c, g, sh.u8 ? 1 : 4));
-                nsplit = launch_conv1_wgrad_tr(st, sh, dy, this->part + part_cur, repro ? (float*)nullptr : c.db, nf, g.IH, g.IW, g.OH, g.OW, 1024, claim_ctr(nf > 1));
-                if (nsplit > 1 && !repro) nd(ND_CONV_BIAS);
-            }
-            const bool tr = nsplit > 0;
-            if (!tr) nsplit = wgrad_gemm<32>(c, dy, Conv1LoaderT<T>{x, g}, npix);
-            wgrad_unpack(c, dy, npix, nsplit, tr && !repro);
-        }
-    }
-    // conv3's or conv2's weight gradient for BOTH cameras as one launch (conv_wgrad.h launch_conv_wgrad_pair); both jobs' slabs go into the one batched
-    // unpack launch whatever their number (the gripper job has fewer than the 64 that send a single launch's slabs there).  false = nothing launched
-    bool conv_wgrad_both(int sn, int Nf) {
-        if constexpr (std::is_same<T, h16_t>::value) {
-            const Stage S = stage(0, sn, Nf), G = stage(1, sn, Nf);
-            const ConvW &cS = S.c, &cG = G.c;
-            const int64_t slab = (int64_t)cS.O * cS.I * cS.KH * cS.KW;
-            if (cG.I != cS.I || cG.KH != cS.KH || cG.O != cS.O || cS.O != 64 || !unpack_room(2, 256 * slab)) return false;
-            auto job = [&](const Stage& s) {
-                WgradJob J{}; J.X = s.x; J.dY = s.dy; J.bias_part = repro ? nullptr : s.c.db; J.zeros = wgrad_zero_page(); J.Nf = s.g.Nf; J.IH = s.g.IH; J.IW = s.g.IW; J.OH = s.g.OH; J.OW = s.g.OW; J.work_ctr = claim_ctr(s.g.Nf > 1); J.FPB = 1;
+            const ConvW& c = s.c;
+            const bool is3 = c.I == 64 && c.KH == 3, is2 = c.I == 32 && c.KH == 4;
+            if (!is3 && !is2) return false;
+            if (g && (g->c.I != c.I || g->c.KH != c.KH || g->c.O != c.O || c.O != 64 || !unpack_room(2, 256 * (int64_t)c.O * c.I * c.KH * c.KW))) return false;
+            // reproducible mode: strided items (no claim counter) and no bias atomics
+            auto job = [&](const Stage& q) {
+                WgradJob J{}; J.X = q.x; J.dY = q.dy; J.part = this->part + part_cur; J.bias_part = repro ? nullptr : q.c.db; J.zeros = wgrad_zero_page(); J.Nf = q.g.Nf; J.IH = q.g.IH; J.IW = q.g.IW; J.OH = q.g.OH; J.OW = q.g.OW; J.work_ctr = claim_ctr(q.g.Nf > 1); J.FPB = 1;
                 return J;
             };
-            WgradJob A = job(S), B = job(G);
-            A.part = this->part + part_cur;
-            int ns[2] = {0, 0};
-            bool ok = false;
-            {
-                TimerScope ts(this, "conv_wgrad_tr", "mfma", 0, 0, 0);
-                if (cS.I == 64 && cS.KH == 3) ok = launch_conv_wgrad_pair<64, 64, 3, 3, 1>(st, A, B, 512, nullptr, ns);
-                else if (cS.I == 32 && cS.KH == 4) ok = launch_conv_wgrad_pair<32, 64, 4, 4, 2>(st, A, B, 512, nullptr, ns);
-                if (ok) ts.add(conv_wgrad_flops(cS, S.g) + conv_wgrad_flops(cG, G.g), conv_wgrad_bytes(cS, S.g, 2) + conv_wgrad_bytes(cG, G.g, 2));
-            }
-            if (!ok) return false;
-            queue_unpack(cS.dW, cS.O, cS.I, cS.KH, cS.KW, cS.nhwc, ns[0], 0);
-            queue_unpack(cG.dW, cS.O, cS.I, cS.KH, cS.KW, cG.nhwc, ns[1], 0);
-            if (repro) { colsum(S.dy, cS.O, S.g.Nf * S.g.OH * S.g.OW, cS.O, cS.db); colsum(G.dy, cG.O, G.g.Nf * G.g.OH * G.g.OW, cG.O, cG.db); }
-            else if (ns[0] > 1 || ns[1] > 1) nd(ND_CONV_BIAS);
-            return true;
+            const WgradJob A = job(s), B = g ? job(*g) : WgradJob{};
+            TimerScope ts(this, "conv_wgrad_tr", "mfma", 0, 0, 0);
+            bool ok;
+            if (g) ok = is3 ? launch_conv_wgrad_pair<64, 64, 3, 3, 1>(st, A, B, 512, nullptr, ns) : launch_conv_wgrad_pair<32, 64, 4, 4, 2>(st, A, B, 512, nullptr, ns);
+            else ok = (ns[0] = is3 ? launch_conv_wgrad_tr<64, 64, 3, 3, 1>(st, A, 512) : launch_conv_wgrad_tr<32, 64, 4, 4, 2>(st, A, 512)) > 0;
+            if (ok) ts.add(conv_wgrad_flops(c, s.g) + (g ? conv_wgrad_flops(g->c, g->g) : 0), conv_wgrad_bytes(c, s.g, 2) + (g ? conv_wgrad_bytes(g->c, g->g, 2) : 0));
+            return ok;
         }
         return false;
     }
-    // conv1's weight gradient for BOTH cameras (and, in the paired pass, both frame sources of each) as one launch (conv_wgrad.h launch_conv1_wgrad_jobs):
-    // the jobs are [static: source, second source | gripper: source, second source], so a camera's slabs lie together and are one job of the batched unpack.
-    // false = nothing launched (the cameras' frames take different kernel forms, or no room for the slabs)
-    bool conv1_wgrad_both(const Conv1Src* src, const Conv1Src* src2, int Nf) {
+    // conv3's / conv2's weight gradient of cameras [k0, k1): the joint launch when the range holds both cameras, else per camera the single launch, or the implicit
+    // GEMM (the fp32 engine's form, the 16-bit engines' last resort)
+    void conv_wgrad(int k0, int k1, int sn, int Nf) {
+        auto npix = [](const Stage& s) { return (long long)s.g.Nf * s.g.OH * s.g.OW; };
+        if (k1 - k0 == 2) {
+            const Stage S = stage(k0, sn, Nf), G = stage(k0 + 1, sn, Nf);
+            int ns[2] = {0, 0};
+            if (conv_wgrad_launch(S, &G, ns)) {
+                wgrad_finish(S.c, S.dy, npix(S), ns[0], true, true);
+                wgrad_finish(G.c, G.dy, npix(G), ns[1], true, true);
+                return;
+            }
+        }
+        for (int k = k0; k < k1; ++k) {
+            const Stage s = stage(k, sn, Nf);
+            int nsplit = 0;
+            const bool tr = conv_wgrad_launch(s, nullptr, &nsplit);
+            if (!tr) nsplit = wgrad_gemm<64>(s.c, s.dy, ConvNHWCLoaderT<T>{s.x, s.g}, npix(s));
+            wgrad_finish(s.c, s.dy, npix(s), nsplit, tr, false);
+        }
+    }
+    // conv1's launch (conv1_wgrad.h launch_conv1_wgrad_jobs; 16-bit engines) of the jobs [cameras ka, kb) x [frame sources ha, hb) in that order, so a camera's slabs lie
+    // together.  Paired pass: two sources per camera, as conv1_fwd.  ns = slabs per job; false = nothing launched (the fp32 engine, or the jobs take different kernel forms)
+    bool conv1_wgrad_launch(int ka, int kb, int ha, int hb, const Conv1Src* src, const Conv1Src* src2, int Nf, int* ns) {
         if constexpr (std::is_same<T, h16_t>::value) {
-            const ConvW &cS = encS.c1, &cG = encG.c1;
-            const int Kc = cS.I * cS.KH * cS.KW;
-            if (cS.O != 32 || cG.O != 32 || Kc != 192 || cG.I * cG.KH * cG.KW != 192) return false;
-            if (!unpack_room(2, 1024 * (int64_t)cS.O * Kc)) return false;      // (at most max_blocks = 1024 slabs)
-            const int ns_src = src2 ? 2 : 1;
             Wgrad1Job J[4]; int nj = 0;
             double fl = 0, by = 0;
-            for (int k = 0; k < 2; ++k) {
-                for (int h = 0; h < ns_src; ++h) {
+            for (int k = ka; k < kb; ++k) {
+                for (int h = ha; h < hb; ++h) {
                     const int nf = src2 ? src_frames(Nf, h) : Nf;
                     const ConvGeom g = geom(nf, encw(k).IH, 3, 8, 4);
                     Wgrad1Job q{}; q.S = h ? src2[k] : src[k]; q.work_ctr = claim_ctr(nf > 1); q.dY = enca(k).dact1 + (long long)(h ? src_frames(Nf, 0) : 0) * g.OH * g.OW * 32; q.bias_part = repro ? nullptr : encw(k).c1.db;
                     q.Nf = nf; q.IH = g.IH; q.IW = g.IW; q.OH = g.OH; q.OW = g.OW;
                     J[nj++] = q;
-                    fl += conv_wgrad_flops(cS, g); by += conv_wgrad_bytes(cS, g, q.S.u8 ? 1 : 4);
+                    fl += conv_wgrad_flops(encw(k).c1, g); by += conv_wgrad_bytes(encw(k).c1, g, q.S.u8 ? 1 : 4);
                 }
             }
             J[0].part = this->part + part_cur;
-            int ns[4] = {0, 0, 0, 0};
-            {
-                TimerScope ts(this, "conv1_wgrad", "hbm", 0, 0, 0);
-                if (!launch_conv1_wgrad_jobs(st, J, nj, 1024, nullptr, ns)) return false;
-                ts.add(fl, by);
-            }
-            for (int k = 0; k < 2; ++k) {
-                const ConvW& c = encw(k).c1;
-                int nsl = 0;
-                for (int h = 0; h < ns_src; ++h) nsl += ns[k * ns_src + h];
-                queue_unpack(c.dW, c.O, c.I, c.KH, c.KW, c.nhwc, nsl, 0);
-                if (nsl > 1 && !repro) nd(ND_CONV_BIAS);
-                // reproducible mode: the bias gradient over all frames of the camera (both sources' rows of dact1 lie back to back)
-                if (repro) { const ConvGeom g = geom(Nf, encw(k).IH, 3, 8, 4); colsum(enca(k).dact1, c.O, Nf * g.OH * g.OW, c.O, c.db); }
-            }
+            TimerScope ts(this, "conv1_wgrad", "hbm", 0, 0, 0);
+            if (!launch_conv1_wgrad_jobs(st, J, nj, 1024, nullptr, ns)) return false;
+            ts.add(fl, by);
             return true;
         }
         return false;
+    }
+    // conv1's weight gradient of cameras [k0, k1): both cameras (and both frame sources of each) as one launch when the range holds both, else once per camera and
+    // frame source.  The fp32 engine reads the frames the forward materialised (conv1_f32)
+    void conv1_wgrad(int k0, int k1, const Conv1Src* src, const Conv1Src* src2, int Nf) {
+        const int ns_src = src2 ? 2 : 1;
+        if (k1 - k0 == 2) {
+            const ConvW &cS = encw(k0).c1, &cG = encw(k0 + 1).c1;
+            int ns[4] = {0, 0, 0, 0};
+            if (cS.O == 32 && cG.O == 32 && cS.I * cS.KH * cS.KW == 192 && cG.I * cG.KH * cG.KW == 192 && unpack_room(2, 1024 * (int64_t)32 * 192) &&      // (at most max_blocks = 1024 slabs)
+                conv1_wgrad_launch(k0, k1, 0, ns_src, src, src2, Nf, ns)) {
+                for (int k = k0; k < k1; ++k) {      // a camera's slabs are one job of the batched unpack; its bias gradient runs over all its frames (both sources' rows of dact1 lie back to back)
+                    const ConvGeom g = geom(Nf, encw(k).IH, 3, 8, 4);
+                    wgrad_finish(encw(k).c1, enca(k).dact1, (long long)Nf * g.OH * g.OW, ns[(k - k0) * ns_src] + (src2 ? ns[(k - k0) * ns_src + 1] : 0), true, true);
+                }
+                return;
+            }
+        }
+        for (int k = k0; k < k1; ++k) {
+            const EncW& e = encw(k);
+            for (int h = 0; h < ns_src; ++h) {
+                const int nf = src2 ? src_frames(Nf, h) : Nf;
+                const ConvGeom g = geom(nf, e.IH, 3, 8, 4);
+                const long long npix = (long long)nf * g.OH * g.OW, foff = h ? src_frames(Nf, 0) : 0;
+                const T* dy = enca(k).dact1 + foff * g.OH * g.OW * 32;
+                int nsplit = 0;
+                const bool tr = conv1_wgrad_launch(k, k + 1, h, h + 1, src, src2, Nf, &nsplit) && nsplit > 0;
+                if (!tr) {
+                    const Conv1Src& sh = h ? src2[k] : src[k];
+                    const float* x = nullptr;
+                    if constexpr (std::is_same<T, float>::value) x = sh.u8 ? x32[k] + foff * 3 * e.IH * e.IH : reinterpret_cast<const float*>(sh.X);
+                    nsplit = wgrad_gemm<32>(e.c1, dy, Conv1LoaderT<T>{x, g}, npix);
+                }
+                wgrad_finish(e.c1, dy, npix, nsplit, tr, false);
+            }
+        }
     }
     ConvTileP conv_dgrad_job(const Stage& s, bool bits) {
         ConvTileP p{};
@@ -615,10 +606,10 @@
         const bool both = k1 - k0 == 2;
         for (int k = k0; k < k1; ++k) head_bwd(k, Nf, tail_done);
         for (int sn = 3; sn >= 2; --sn) {
-            if (!(both && conv_wgrad_both(sn, Nf))) for (int k = k0; k < k1; ++k) conv_wgrad(k, sn, Nf);
+            conv_wgrad(k0, k1, sn, Nf);
             if (!(both && conv_dgrad_both(sn, Nf))) for (int k = k0; k < k1; ++k) conv_dgrad(k, sn, Nf);
         }
-        if (!(both && conv1_wgrad_both(src, src2, Nf))) for (int k = k0; k < k1; ++k) conv1_wgrad(k, src[k], Nf, src2 ? &src2[k] : nullptr);
+        conv1_wgrad(k0, k1, src, src2, Nf);
     }
     void enc_bwd_both(const Conv1Src* src, const Conv1Src* src2, int Nf, bool tail_done) {
         if constexpr (std::is_same<T, h16_t>::value) enc_bwd_stages(0, 2, src, src2, Nf, tail_done);

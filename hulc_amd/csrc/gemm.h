@@ -779,8 +779,7 @@ static inline bool gemm_glds_ok(const DenseLoader<h16_t>& a, const DenseLoader<h
     return K >= 64 && (K % 32) == 0 && ep.z_stride == 0 && row_ok(a) && row_ok(b);
 }
 static inline void launch_gemm_glds(hipStream_t st, const DenseLoader<h16_t>& a, const DenseLoader<h16_t>& b, const DenseOut& om, const EpiP& ep, int M, int N, int K) {
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute((const void*)gemm_glds_kernel<3, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr_set = true; }
+    max_dyn_lds_once<&gemm_glds_kernel<3, 8>>(96 * 1024);
     const int tiles_m = (M + 127) / 128, tiles_n = (N + 127) / 128;
     // a three-stage ring, eight waves (a four-stage ring measured no faster: the operand stream of a tile is not latency-bound)
     hipLaunchKernelGGL((gemm_glds_kernel<3, 8>), dim3(tiles_m * tiles_n), dim3(512), 96 * 1024, st, a, b, om, ep, M, N, K, tiles_m, tiles_n);
@@ -1135,8 +1134,7 @@ __global__ void __launch_bounds__(NW * 64) gru_step_lds_kernel(GruStepP q0, GruS
 static inline bool launch_gru_step(hipStream_t st, const GruStepP* q, int nprob, int M, int H, bool wfrag = false) {
     for (int k = 0; k < nprob; ++k)
         if (H != 2048 || M < 1 || ((uintptr_t)q[k].A % 128) != 0 || ((uintptr_t)q[k].W % 16) != 0) return false;
-    static bool attr = false;
-    if (!attr) { hipFuncSetAttribute((const void*)gru_step_lds_kernel<2, 4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+    max_dyn_lds_once<&gru_step_lds_kernel<2, 4, 16>>(160 * 1024);
     dim3 grid(H / 16, (M + 31) / 32, nprob);
     // LDS: the A region (16 waves x 2 x 2 x 2 KB = 128 KB) is reused for the 16 x 2 x 3 K-partials (96 KB)
     hipLaunchKernelGGL((gru_step_lds_kernel<2, 4, 16>), grid, dim3(1024), (size_t)16 * 2 * 2 * 2 * 1024, st, q[0], q[nprob - 1], (long long)H, wfrag ? 0ll : (long long)H, M, H);
@@ -1271,8 +1269,7 @@ static inline bool skinny_lds_kchunk_ok(const h16_t* A, long long lda, int M, in
 static inline bool launch_skinny_lds_kchunk(hipStream_t st, const h16_t* A, long long lda, const h16_t* W, long long ldw, int M, int N, int K, const DenseOut& om,
                                             const EpiP& ep, const GruBwdP& gb = GruBwdP{}, const KChunk2* p2 = nullptr) {
     if (!skinny_lds_kchunk_ok(A, lda, M, N, K, p2 ? p2->A : nullptr)) return false;
-    static bool attr = false;
-    if (!attr) { hipFuncSetAttribute((const void*)skinny_lds_kchunk_kernel<2, 4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+    max_dyn_lds_once<&skinny_lds_kchunk_kernel<2, 4, 16>>(160 * 1024);
     hipLaunchKernelGGL((skinny_lds_kchunk_kernel<2, 4, 16>), dim3(N / 16, (M + 31) / 32, p2 ? 2 : 1), dim3(1024), (size_t)16 * 2 * 2 * 2 * 1024, st, A, lda, W, ldw, M, N, K, om, ep, gb,
                        p2 ? *p2 : KChunk2{});
     return true;
@@ -1282,11 +1279,7 @@ template <int MT, int KQ32>
 static inline void launch_skinny_lds_t(hipStream_t st, dim3 grid, const h16_t* A, long long lda, const h16_t* W, long long ldw, int M, int N, int K,
                                        const DenseOut& om, const EpiP& ep) {
     const size_t lds = (size_t)8 * MT * 2 * (KQ32 / 2) * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)skinny_lds_kernel<MT, KQ32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    max_dyn_lds_once<&skinny_lds_kernel<MT, KQ32>>(160 * 1024);
     hipLaunchKernelGGL((skinny_lds_kernel<MT, KQ32>), grid, dim3(512), lds, st, A, lda, W, ldw, M, N, K, om, ep);
 }
 // returns false when the shape is not covered (caller uses the register-fragment kernel)
@@ -1298,14 +1291,12 @@ static inline bool launch_skinny_lds(hipStream_t st, const h16_t* A, long long l
     const int kq32 = K / 256;
 #define SKL(mt, kq) launch_skinny_lds_t<mt, kq>(st, grid, A, lda, W, ldw, M, N, K, om, ep)
     if (MT == 1) {                                  // M <= 32 recurrent step (32 + 32 windows per GPU): 16-row blocks so that 2 x 128 workgroups fill the chip
-        static bool attr1 = false;
-        if (!attr1) { hipFuncSetAttribute((const void*)skinny_lds_kernel<1, 4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr1 = true; }
+        max_dyn_lds_once<&skinny_lds_kernel<1, 4, 16>>(160 * 1024);
         hipLaunchKernelGGL((skinny_lds_kernel<1, 4, 16>), grid, dim3(1024), (size_t)16 * 1 * 2 * 2 * 1024, st, A, lda, W, ldw, M, N, K, om, ep);
         return true;
     }
     if (MT == 2 && kq32 == 8) {            // K = 2048 (the recurrent step): 16 waves x 4 k-steps, 4 waves per SIMD overlap DMA issue and MFMAs
-        static bool attr16 = false;
-        if (!attr16) { hipFuncSetAttribute((const void*)skinny_lds_kernel<2, 4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr16 = true; }
+        max_dyn_lds_once<&skinny_lds_kernel<2, 4, 16>>(160 * 1024);
         hipLaunchKernelGGL((skinny_lds_kernel<2, 4, 16>), grid, dim3(1024), (size_t)16 * 2 * 2 * 2 * 1024, st, A, lda, W, ldw, M, N, K, om, ep);
         return true;
     }
@@ -1322,8 +1313,7 @@ static inline bool skinny_lds_dual_ok(const h16_t* A0, const h16_t* W0, const h1
 static inline bool launch_skinny_lds_dual(hipStream_t st, const h16_t* A0, const h16_t* W0, const EpiP& ep0, const h16_t* A1, const h16_t* W1, const EpiP& ep1, long long lda,
                                           long long ldw, int M, int N, int K, const DenseOut& om) {
     if (!skinny_lds_dual_ok(A0, W0, A1, W1, lda, ldw, M, N, K)) return false;
-    static bool attr16 = false;
-    if (!attr16) { hipFuncSetAttribute((const void*)skinny_lds_kernel<2, 4, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr16 = true; }
+    max_dyn_lds_once<&skinny_lds_kernel<2, 4, 16, true>>(160 * 1024);
     Skinny2 p2; p2.A = A1; p2.W = W1; p2.ep = ep1;
     hipLaunchKernelGGL((skinny_lds_kernel<2, 4, 16, true>), dim3(N / 16, (M + 31) / 32, 2), dim3(1024), (size_t)16 * 2 * 2 * 2 * 1024, st, A0, lda, W0, ldw, M, N, K, om, ep0, p2);
     return true;

@@ -3,8 +3,8 @@
 // the LayerNorm family (hulc_k_layernorm_*) and of the fused transformer layer kernels
 // (hulc_k_tr_layer_fwd, hulc_k_tr_ffn_bwd, hulc_k_tr_attn_bwd; launched through tr_fused.h's helpers), and of the GEMM core with its runtime epilogue
 // (hulc_k_gemm_epi, hulc_k_gemm_dual, hulc_k_gemm_pick, hulc_k_gemm_wgrad_nsplit; launched through gemm.h's launchers and routing), and of the encoder's convolution family
-// (hulc_k_conv_tile, hulc_k_conv_pair, hulc_k_conv_wgrad, hulc_k_conv1_wgrad_u8 and their per-type forms; launched through the launchers of conv_tile.h, conv_reg.h and
-// conv_wgrad.h).  Included by engine.h inside each translation unit, so every entry exists once per
+// (hulc_k_conv_tile, hulc_k_conv_pair, hulc_k_conv_wgrad, hulc_k_conv1_wgrad_u8 and their per-type forms; launched through the launchers of conv_tile.h, conv_reg.h,
+// conv_wgrad.h and conv1_wgrad.h).  Included by engine.h inside each translation unit, so every entry exists once per
 // 16-bit type (hulc_bf16 / hulc_f16; iengine.h declares them).  Nothing here restates a kernel or a launch: every entry checks its arguments, then launches
 // through the helper the engine calls (plan_ln_launch.h for the kernels.h families, enc_tail.h, det_head.h, tr_fused.h, gemm.h, the conv launchers).
 #pragma once
@@ -593,7 +593,7 @@ int k_gemm_wgrad_nsplit(int t16, int M, int N, int K, int* nsplit, int* big) {
     return 0;
 }
 
-// hulc_k_lin_bwd_stream: lin_bwd_stream_kernel (conv_wgrad.h) on one job, rows split into nsplit ranges; the four forms the engine launches.  slabs == null, nsplit = 1: the
+// hulc_k_lin_bwd_stream: lin_bwd_stream_kernel (lin_bwd.h) on one job, rows split into nsplit ranges; the four forms the engine launches.  slabs == null, nsplit = 1: the
 // tile is stored to (store != 0) or added to dW by the kernel itself; slabs == null, nsplit > 1: the ranges add to dW with fp32 atomics (store != 0: dW is cleared first).
 // slabs given (any nsplit, 1 included: the decoder heads' form): every range stores its slab ([nsplit][N][K], never read before it is written) and slab_sum_kernel
 // adds them to dW in index order (store != 0: dW is cleared first).  nsplit > 1: the bias sums of the ranges land in db with atomics.  db (may be null) is always added to.
@@ -617,7 +617,7 @@ int k_lin_bwd_stream(const void* dY, const void* X, long long ldx, int M, int N,
     return k_launched(who);
 }
 
-// ---------------------------------------------------------------------------------------------------- the encoder's convolution family (conv_tile.h, conv_reg.h, conv_wgrad.h)
+// ---------------------------------------------------------------------------------------------------- the encoder's convolution family (conv_tile.h, conv_reg.h, conv_wgrad.h, conv1_wgrad.h)
 // hulc_k_conv_wgrad, hulc_k_conv1_wgrad_u8, hulc_k_conv_tile, hulc_k_conv_pair (the bf16 wrappers: typed == 0) and their per-type forms hulc_k_*_t (typed == 1), launched
 // through the launchers engine_encoders.inc calls.  who = the C entry's name (error messages).  typed: the bench-only forms no launch site of engine_encoders.inc names
 // are refused — the 8-wave data-gradient forms (modes 12 / 13 / 18 / 19), the register-staged uint8 conv1 forward (relu bit 256) and the uint8 conv1 weight-gradient
@@ -644,8 +644,9 @@ int k_conv_wgrad(const char* who, int typed, int which, const void* X, const voi
     static h16_t* zp = nullptr;                   // zero page of the LDS-DMA kernel (pad slots, columns / rows beyond the frame)
     if (!zp) { if (hipMalloc(&zp, 256) != hipSuccess) { hulc_set_error("%s: hipMalloc failed", who); return 1; } hipMemset(zp, 0, 256); }
     if (db_out) hipMemsetAsync(bias_tmp, 0, sizeof(float) * 64, st);      // the kernels add their bias partials to bias_tmp[0 .. CO)
-    if (which == 3) { const int OH = IH - 2; ns = launch_conv_wgrad_tr<64, 64, 3, 3, 1>(st, (const h16_t*)X, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512, nullptr, zp); }
-    else if (which == 2) { const int OH = (IH - 4) / 2 + 1; ns = launch_conv_wgrad_tr<32, 64, 4, 4, 2>(st, (const h16_t*)X, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512, nullptr, zp); }
+    WgradJob J{}; J.X = (const h16_t*)X; J.dY = (const h16_t*)dY; J.part = part; J.bias_part = bias_tmp; J.zeros = zp; J.Nf = Nf; J.IH = J.IW = IH; J.FPB = 1;
+    if (which == 3) { J.OH = J.OW = IH - 2; ns = launch_conv_wgrad_tr<64, 64, 3, 3, 1>(st, J, 512); }
+    else if (which == 2) { J.OH = J.OW = (IH - 4) / 2 + 1; ns = launch_conv_wgrad_tr<32, 64, 4, 4, 2>(st, J, 512); }
     else if (which == 1) { const int OH = (IH - 8) / 4 + 1; ns = launch_conv1_wgrad_tr(st, Conv1Src{X, nullptr, 0, 0}, (const h16_t*)dY, part, bias_tmp, Nf, IH, IH, OH, OH, 512); }
     else { hipFree(part); hulc_set_error("%s: which must be 1, 2 or 3", who); return 1; }
     hipMemsetAsync(out, 0, sizeof(float) * CO * KC, st);
@@ -674,10 +675,7 @@ int k_conv1_wgrad_u8(const char* who, int typed, const void* X, const int* shift
     hipMemsetAsync(bias, 0, sizeof(float) * 64, st);
     Conv1Src src{}; src.X = X; src.shift = shifts; src.u8 = 1; src.pad = pad; src.fold = fold != 0;
     const int OH = (IH - 8) / 4 + 1;
-    const int keep = g_conv1_wgrad_u8reg;
-    g_conv1_wgrad_u8reg = form;
-    const int ns = launch_conv1_wgrad_tr(st, src, (const h16_t*)dY, part, bias, Nf, IH, IH, OH, OH, 512);
-    g_conv1_wgrad_u8reg = keep;
+    const int ns = launch_conv1_wgrad_tr(st, src, (const h16_t*)dY, part, bias, Nf, IH, IH, OH, OH, 512, nullptr, form);
     hipMemsetAsync(dw_out, 0, sizeof(float) * 32 * 192, st);
     hipLaunchKernelGGL(unpack_conv_wgrad_kernel, dim3((32 * 192 + 1023) / 1024), dim3(256), 0, st, part, ns, (long long)32 * 192, dw_out, 32, 192, 1, 1, 0);
     hipMemcpyAsync(db_out, bias, sizeof(float) * 32, hipMemcpyDeviceToDevice, st);
@@ -771,7 +769,7 @@ int k_conv_tile(const char* who, int typed, int mode, const void* img, const voi
 }
 
 // One stage of both encoders as ONE launch (conv_reg.h launch_conv_reg_jobs, conv_wgrad.h launch_conv_wgrad_pair /
-// launch_conv1_wgrad_jobs) in the forms the engine runs, dynamic claiming on (one zeroed counter per job, as the engine's next_ctr()); b == NULL: job a alone through the same entry
+// conv1_wgrad.h launch_conv1_wgrad_jobs) in the forms the engine runs, dynamic claiming on (one zeroed counter per job, as the engine's next_ctr()); b == NULL: job a alone through the same entry
 int k_conv_pair(const char* who, int typed, int stage, const hulc_conv_job* a, const hulc_conv_job* b, int wg_a, int wg_b, int* slabs, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const bool fwd = stage == HULC_PAIR_CONV2_FWD || stage == HULC_PAIR_CONV3_FWD, dgr = stage == HULC_PAIR_CONV3_DGRAD || stage == HULC_PAIR_CONV2_DGRAD;

@@ -137,8 +137,7 @@ inline void launch_attention_bwd(hipStream_t st, bool s64, const T* qkv, const f
     if constexpr (WIDE) {
         if (!s64) hipLaunchKernelGGL((attention_bwd32_kernel<T>), grid, dim3(64), 0, st, qkv, P, dao, B, S, D, NH, dqkv, drop_p, seed);
         else {      // ATT_BWD64_LDS (99.5 KB, dynamic) is past the default limit: raised once per instantiation
-            static bool attr = false;
-            if (!attr) { hipFuncSetAttribute((const void*)attention_bwd64_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_BWD64_LDS); attr = true; }
+            max_dyn_lds_once<&attention_bwd64_kernel<T>>((int)ATT_BWD64_LDS);
             hipLaunchKernelGGL((attention_bwd64_kernel<T>), grid, dim3(256), ATT_BWD64_LDS, st, qkv, P, dao, B, S, D, NH, dqkv, drop_p, seed);
         }
     } else if (!s64) hipLaunchKernelGGL((attention_bwd_kernel<T, 32>), grid, dim3(64), 0, st, qkv, P, dao, B, S, D, NH, dqkv, drop_p, seed);

@@ -13,7 +13,7 @@ enum ReproSite : unsigned {
     ND_TR_FFN_FWD = 1u << 7,         // tr_fused.h forward: y2 accumulated by the four hidden quarters
     ND_TR_LN_BWD = 1u << 8,          // tr_fused.h backward: norm1 / norm2 gamma / beta gradients (more than one window)
     ND_ENC_TAIL_LN = 1u << 9,        // enc_tail.h enc_tail_bwd_kernel: LayerNorm gamma / beta gradients (more than 16 frames)
-    ND_CONV_BIAS = 1u << 10,         // conv_wgrad.h: conv bias gradients of the weight-gradient kernels (more than one workgroup)
-    ND_LIN_BWD_ROWS = 1u << 11,      // conv_wgrad.h lin_bwd_smallm_body: row-split bias (and slab-less weight) gradients
-    ND_CONV_CLAIM = 1u << 12,        // conv_wgrad.h work_ctr: items claimed dynamically under a per-workgroup slab accumulator
+    ND_CONV_BIAS = 1u << 10,         // conv_wgrad.h, conv1_wgrad.h: conv bias gradients of the weight-gradient kernels (more than one workgroup)
+    ND_LIN_BWD_ROWS = 1u << 11,      // lin_bwd.h lin_bwd_smallm_body: row-split bias (and slab-less weight) gradients
+    ND_CONV_CLAIM = 1u << 12,        // conv_wgrad.h, conv1_wgrad.h work_ctr: items claimed dynamically under a per-workgroup slab accumulator
 };

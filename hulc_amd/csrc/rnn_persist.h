@@ -335,8 +335,7 @@ static inline size_t rnn_persist_lds(int tok) { return (size_t)2 * RP_NW * (tok 
 // false: shape not covered (the caller keeps the launch-per-step path).  X must lie below 2 GB from its base (buffer offsets are 32 bit).
 template <int TOK, int MODE, bool RES>
 static inline void rnn_persist_go(hipStream_t st, const RnnPersistP& p) {
-    static bool attr = false;
-    if (!attr) { hipFuncSetAttribute((const void*)rnn_persist_kernel<TOK, MODE, RES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rnn_persist_lds(TOK)); attr = true; }
+    max_dyn_lds_once<&rnn_persist_kernel<TOK, MODE, RES>>((int)rnn_persist_lds(TOK));
     hipLaunchKernelGGL((rnn_persist_kernel<TOK, MODE, RES>), dim3(RP_NG * RP_SLOTS), dim3(RP_NW * 64), rnn_persist_lds(TOK), st, p);
 }
 static inline bool launch_rnn_persist(hipStream_t st, RnnPersistP p) {

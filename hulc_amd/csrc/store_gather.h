@@ -1,5 +1,5 @@
 // hulc_amd/csrc/store_gather.h — hulc_store_gather (include/hulc_hip.h): the non-image half of a frame-store batch, assembled on the device from
-// per-frame tables that live next to the store.  Same window arithmetic as the frames (conv_wgrad.h window_expand_kernel): L = clamp(window_len[b], 1, S),
+// per-frame tables that live next to the store.  Same window arithmetic as the frames (window_rows.h window_expand_kernel): L = clamp(window_len[b], 1, S),
 // s0 = clamp(window_start[b], 0, F - L), row (b, t) = table row s0 + min(t, L - 1).  Padding (t >= L) restates calvin_agent's _pad_sequence:
 // robot_obs repeats the last real row; RELATIVE actions pad dims 0..5 with zeros and repeat dim 6 (the gripper); ABSOLUTE actions repeat all seven.
 // Copies and zeros only: the result is exact.  Included by capi.hip alone.

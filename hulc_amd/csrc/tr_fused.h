@@ -26,7 +26,7 @@
 // (engine.h) re-derives them and is unchanged.
 #pragma once
 #include "common.h"
-#include "conv_wgrad.h"   // lds_char
+#include "lds_types.h"   // lds_char, lds_u32x4
 
 namespace HULC_NS {
 
@@ -830,26 +830,23 @@ __global__ void __launch_bounds__(512) tr_attn_bwd_kernel(TrAttnBwdP p) {
     }
 }
 static inline void launch_tr_attn_bwd(hipStream_t st, const TrAttnBwdP& p) {
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute((const void*)tr_attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRA_LDS); attr_set = true; }
+    max_dyn_lds_once<&tr_attn_bwd_kernel>((int)TRA_LDS);
     hipLaunchKernelGGL(tr_attn_bwd_kernel, dim3(p.B), dim3(512), TRA_LDS, st, p);
 }
 
 static inline void launch_tr_ffn_bwd(hipStream_t st, const TrFfnBwdP& p) {
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute((const void*)tr_ffn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRB_LDS); attr_set = true; }
+    max_dyn_lds_once<&tr_ffn_bwd_kernel>((int)TRB_LDS);
     hipLaunchKernelGGL(tr_ffn_bwd_kernel, dim3(p.B * ((p.S + 31) / 32) * TRF_NQ), dim3(512), TRB_LDS, st, p);
 }
 
 static inline void launch_tr_layer_fwd(hipStream_t st, const TrLayerP& p) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)tr_layer_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRF_LDS);
-        hipFuncSetAttribute((const void*)tr_layer_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRF_LDS_WIDE);
-        attr_set = true;
+    if (p.S > 32) {      // 32 < S <= 64: (window, half, quarter)
+        max_dyn_lds_once<&tr_layer_fwd_kernel<true>>((int)TRF_LDS_WIDE);
+        hipLaunchKernelGGL(tr_layer_fwd_kernel<true>, dim3(p.B * 2 * TRF_NQ), dim3(512), TRF_LDS_WIDE, st, p);
+    } else {
+        max_dyn_lds_once<&tr_layer_fwd_kernel<false>>((int)TRF_LDS);
+        hipLaunchKernelGGL(tr_layer_fwd_kernel<false>, dim3(p.B * TRF_NQ), dim3(512), TRF_LDS, st, p);
     }
-    if (p.S > 32) hipLaunchKernelGGL(tr_layer_fwd_kernel<true>, dim3(p.B * 2 * TRF_NQ), dim3(512), TRF_LDS_WIDE, st, p);      // 32 < S <= 64: (window, half, quarter)
-    else hipLaunchKernelGGL(tr_layer_fwd_kernel<false>, dim3(p.B * TRF_NQ), dim3(512), TRF_LDS, st, p);
 }
 
 }  // namespace HULC_NS

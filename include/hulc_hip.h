@@ -769,7 +769,7 @@ int hulc_k_layernorm_bwd(int32_t dtype, const float* dy, int64_t lddy, const flo
 /* layernorm_mean_kernel: x [B][S][n] fp32 -> yout [B][S][n] = LayerNorm(x), stats [B*S][2], out [B][n] T = mean over S of yout. */
 int hulc_k_layernorm_mean(int32_t dtype, const float* x, int32_t B, int32_t S, int32_t n, const float* g, const float* b, float* stats, void* out, float* yout,
                           void* hip_stream);
-/* ---- the row kernels of the ragged encoder pass (hulc_batch::window_len_host; csrc/conv_wgrad.h), launched with the engine's grid and block.  lens (B) int32
+/* ---- the row kernels of the ragged encoder pass (hulc_batch::window_len_host; csrc/window_rows.h), launched with the engine's grid and block.  lens (B) int32
  * holds CLAMPED lengths 1 <= lens[b] <= min(S, store_frames), off (B + 1) int32 their exclusive prefix sum; both on the device.  N' = off[B].
  * hulc_k_window_compact: window_compact_kernel.  frame_out [N'] int64: frame_out[off[b] - off_base + t] = clamp(window_start[b], 0, store_frames - lens[b]) + t for
  *   t < lens[b]; shift_*_out [N'][2] = shift_*[b * S + t] (each pair optional). */
@@ -870,7 +870,7 @@ int hulc_k_gemm_dual(int32_t dtype, const hulc_gemm_epi_job* jobs, int32_t* ran,
  * the skinny and LDS-DMA kernels).  hulc_k_gemm_wgrad_nsplit: Engine::gemm_wgrad's split-K factor (1 = none), *big = 1: the 128x128 tile. */
 int hulc_k_gemm_pick(int32_t dtype, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int32_t* pick, int32_t* bk);
 int hulc_k_gemm_wgrad_nsplit(int32_t dtype, int32_t M, int32_t N, int32_t K, int32_t* nsplit, int32_t* big);
-/* The streaming weight / bias gradient of a Linear layer (conv_wgrad.h lin_bwd_stream_kernel; 16-bit types): dW[N][K] (pitch lddw) = or += dY[M][N]^T X[M][K] (pitch ldx)
+/* The streaming weight / bias gradient of a Linear layer (lin_bwd.h lin_bwd_stream_kernel; 16-bit types): dW[N][K] (pitch lddw) = or += dY[M][N]^T X[M][K] (pitch ldx)
  * and db[N] += column sums of dY (db may be NULL).  The M rows are walked in nsplit ranges.  slabs == NULL: nsplit = 1, the kernel stores (store != 0: what dW held is
  * not read) or adds; nsplit > 1, the ranges add with fp32 atomics (store != 0: to a cleared dW).  slabs given ([nsplit][N][K], 16-byte aligned, never read before it is
  * written; nsplit = 1 allowed): every range stores its own fp32 slab and the slabs are summed into dW in index order (store != 0: into a cleared dW).  With nsplit > 1 the

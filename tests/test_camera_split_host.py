@@ -1,5 +1,5 @@
 """CPU (-m "not gpu"): the host arithmetic that divides a launch's persistent workgroups between the two cameras' jobs of one encoder stage
-(conv_wgrad.h::camera_split through hulc_k_camera_split).  No device needed."""
+(common.h::camera_split through hulc_k_camera_split).  No device needed."""
 import ctypes as C
 
 

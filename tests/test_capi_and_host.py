@@ -166,7 +166,7 @@ def test_frame_store_samples_windows_inside_one_episode_and_builds_reference_bat
 
 
 def test_conv1_interior_groups_never_touch_a_row_end():
-    """The uint8 conv1 kernels convert `interior` 4-pixel groups without clamps (conv_wgrad.h::conv1_interior_groups, round 6): for every column shift |dx| <= pad a group's four
+    """The uint8 conv1 kernels convert `interior` 4-pixel groups without clamps (conv1_stage.h::conv1_interior_groups, round 6): for every column shift |dx| <= pad a group's four
     source pixels 4 c + dx .. + 3 must lie inside the row and its aligned 16-byte window (3 (4 c + dx)) & ~3 .. + 15 inside the row's 3 IW bytes — otherwise the kernel would read
     past the row (past the buffer, for the last row of the last frame).  Host arithmetic of the library, no GPU needed."""
     import ctypes as C

@@ -1,6 +1,6 @@
 """GPU (-m gpu): one encoder stage for BOTH cameras as one launch (conv_reg.h launch_conv_reg_jobs through hulc_k_conv_pair) — conv2 / conv3 forward and
 the conv3 / conv2 data gradients in the production ReLU-bitmask forms, and the conv3 / conv2 / conv1 weight gradients (conv_wgrad.h launch_conv_wgrad_pair,
-launch_conv1_wgrad_jobs).  Job A has the static camera's maps (49 -> 23, 23 -> 21; conv1 200 -> 49), job B the gripper camera's (20 -> 9, 9 -> 7; 84 -> 20); the
+conv1_wgrad.h launch_conv1_wgrad_jobs).  Job A has the static camera's maps (49 -> 23, 23 -> 21; conv1 200 -> 49), job B the gripper camera's (20 -> 9, 9 -> 7; 84 -> 20); the
 weights differ per job; frame counts are small, unequal and odd; the workgroup split is given explicitly, and the entry gives every job a zeroed claim counter of
 its own, so the weight-gradient kernels (the ones that claim) walk their items by dynamic claiming inside the two-job launch.
 
@@ -279,3 +279,42 @@ def test_bf16_step_is_repeatable_and_its_encoder_gradients_follow_the_fp32_engin
         a = np.concatenate([g[n].reshape(-1) for n in gref if n != cancels])
         b = np.concatenate([gref[n].reshape(-1) for n in gref if n != cancels])
         assert float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b))) > 0.995
+
+
+def test_conv1_weight_gradient_entry_form_does_not_reach_the_engines_routing():
+    """The uint8 form of conv1's weight gradient is an argument of the launcher (conv1_wgrad.h conv1_wgrad_plan), not library state: a bf16 engine's backward at
+    B = 2, S = 2 from uint8 frames in reproducible mode, then hulc_k_conv1_wgrad_u8 with form = 1 on 3 frames of 84 x 84, then the same backward again — the conv1
+    weight and bias gradients of both cameras must have the same bits before and after the entry ran the other form."""
+    from bench import synth_batch
+    from hulc_amd import spec
+    from hulc_amd.engine import StepEngine
+    L, lib = _lib()
+    Bt, St = 2, 2
+    dims = spec.ModelDims(kind="hulc", max_window=32, use_clip=False)
+    eng = StepEngine(dims, Bt, St, dtype="bf16", device="cuda:0", dropout_p=0.0, seed=3)
+    eng.load_numpy(spec.init_all(dims, seed=21, ln_jitter=True))
+    eng.set_option("reproducible", 1)
+    mb = synth_batch(Bt, St, torch.device("cuda:0"), 11, False, "u8")
+
+    def conv1_grads():
+        eng.zero_grads()
+        eng.forward_loss(mb, False, 1.0, 3.0, step=0)
+        eng.backward()
+        torch.cuda.synchronize()
+        return {n: t.detach().cpu().numpy().copy() for n, t in eng.views(eng.flat_grads).items() if n.startswith("perceptual_encoder.") and ".conv_model.0." in n}
+
+    before = conv1_grads()
+    assert len(before) == 4 and all(np.abs(g).max() > 0 for g in before.values()), sorted(before)
+    Nf, IH, pad = 3, 84, 4
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.randint(0, 256, (Nf, IH, IH, 3), device="cuda", generator=g, dtype=torch.int32).to(torch.uint8)
+    sh = torch.randint(0, 2 * pad + 1, (Nf, 2), device="cuda", generator=g, dtype=torch.int32)
+    dY = torch.randn(Nf, 20, 20, 32, device="cuda", generator=g).to(torch.bfloat16)
+    gw = torch.zeros(32, 192, device="cuda"); gb = torch.zeros(32, device="cuda")
+    L.check(lib.hulc_k_conv1_wgrad_u8(x.data_ptr(), sh.data_ptr(), pad, dY.data_ptr(), gw.data_ptr(), gb.data_ptr(), Nf, IH, 1, 1, None))
+    torch.cuda.synchronize()
+    assert float(gw.abs().max()) > 0
+    after = conv1_grads()
+    eng.close()
+    for n in before:
+        assert np.array_equal(before[n].view(np.uint32), after[n].view(np.uint32)), n

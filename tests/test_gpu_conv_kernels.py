@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the encoder's convolution kernels (conv_tile.h, conv_reg.h, conv_wgrad.h) alone, through the per-type test entries hulc_k_conv_tile_t, hulc_k_conv_pair_t,
+"""GPU (-m gpu): the encoder's convolution kernels (conv_tile.h, conv_reg.h, conv_wgrad.h, conv1_wgrad.h) alone, through the per-type test entries hulc_k_conv_tile_t, hulc_k_conv_pair_t,
 hulc_k_conv_wgrad_t and hulc_k_conv1_wgrad_u8_t, in bf16 and in fp16, against the float64 reference of tests/conv_ref.py on the inputs of tests/conv_inputs.py.
 
 Every element is compared, none is left out: |got - ref| <= bound + max(ulp |ref|, smallest subnormal) for the 16-bit outputs (conv_inputs.tol16), bound alone for the fp32

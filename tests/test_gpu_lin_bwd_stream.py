@@ -1,4 +1,4 @@
-"""The streaming weight / bias gradient of the Linear layers (csrc/conv_wgrad.h lin_bwd_stream_kernel) and the backward's weight-gradient queue
+"""The streaming weight / bias gradient of the Linear layers (csrc/lin_bwd.h lin_bwd_stream_kernel) and the backward's weight-gradient queue
 (csrc/engine.h wq_add / wq_flush).
 
 Kernel level, through hulc_k_lin_bwd_stream, against fp64 of the SAME device inputs.  16-bit products are exact in fp32, so the only error is the fp32
